@@ -574,6 +574,25 @@ def run_workload(name, S, hz, ctx_sec, mode, steps, warmup, ctx, groups=0, split
     return rec, wl, twin
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, blocks, suffix=""):
+    """--dump-outputs: the output blocks the timed path handed back in its last step ({model: [S, OUT_STRIDE]}, what a caller of
+    vapx_step receives), one float32 DIR/out_<model><suffix>.npy each.  Above 64 MB in all, the same seeded sample of rows of every
+    block, their stream indices in DIR/rows<suffix>.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    S = next(iter(blocks.values())).shape[0]
+    row_bytes = sum(4 * b.shape[1] for b in blocks.values())
+    rows = None
+    if S * row_bytes > DUMP_LIMIT_BYTES:
+        n = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)          # 4 KB for the .npy headers, 8 B per row for the row index
+        rows = np.sort(np.random.default_rng(0).choice(S, n, replace=False))
+        np.save(os.path.join(out_dir, f"rows{suffix}.npy"), rows.astype(np.float64))
+    for name, b in blocks.items():
+        np.save(os.path.join(out_dir, f"out_{name}{suffix}.npy"), np.ascontiguousarray(b if rows is None else b[rows], dtype=np.float32))
+
+
 def cpu_baseline_record(twin: OracleTwin, wl_cfg, seconds: float):
     """The oracle at the record's own shape on this host: 1 thread, batch 1, window full (continues the parity gate's state)."""
     S, hz, ctx_sec, mode = wl_cfg
@@ -951,6 +970,8 @@ def main():
     ap.add_argument("--share-gpu", action="store_true",
                     help="plumbing check on a 1-GPU box: every rank uses device 0 (combine with --backend gloo; RCCL cannot put two ranks on one device)")
     ap.add_argument("--full-record", default="bench_full.json", help="file name of the complete record (written under gpurun_out/, else the repo root)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the headline workload's outputs of its last timed step to DIR/out_<model>.npy (float32, <= 64 MB)")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="multi-rank plumbing check without a GPU: spawn, rendezvous, shard the streams, barrier, print the ranks")
     args = ap.parse_args()
@@ -1000,6 +1021,9 @@ def main():
                                      defer_join=args.defer_join and headline)
         extras = {}
         if headline:
+            if args.dump_outputs:                                  # before anything below steps the engines or reuses d_out
+                dump_outputs(args.dump_outputs, {m: o.cpu().numpy() for m, o in zip(wl.modes, [wl.d_out] + wl.d_out_f)},
+                             f"_rank{rank}" if world > 1 else "")
             extras = {}
             if rank == 0 and world == 1 and side and not wl.followers:
                 extras["lat"] = host_latency(wl)

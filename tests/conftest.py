@@ -15,6 +15,15 @@ if ROOT not in sys.path:
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
+    # The front-end tests hold BOTH ends of hundreds of loopback connections in this one process: a login's usual soft descriptor limit
+    # (1024) runs out before the server's own raise (it counts only its side).  Lift the soft limit to the hard one, as the server does.
+    try:
+        import resource
+        soft, hard = resource.getrlimit(resource.RLIMIT_NOFILE)
+        if soft != hard:
+            resource.setrlimit(resource.RLIMIT_NOFILE, (hard, hard))
+    except (ImportError, ValueError, OSError):
+        pass
     try:
         import torch
         torch.set_num_threads(min(8, os.cpu_count() or 1))

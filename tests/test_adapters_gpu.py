@@ -80,7 +80,7 @@ class _ReferenceShapedRealTime:
     """``VAPRealTime`` with the reference's construction statements (vap_main.py:194-215; vap_bc_main.py:188-209, vap_nod_main.py:187-208 and
     the library twin vap_realtime/model.py:25-49 are the same lines) and its per-frame orchestration (vap_main.py:249-320 /
     vap_realtime/model.py:126-240).  Only the two class names are rebound to vap_realtime_amd.realtime; tests/test_level1_construction.py
-    executes the reference's own ``__init__`` text the same way where the reference tree exists."""
+    runs the same statements on the CPU."""
 
     BINS_P_NOW = [0, 1]
     BINS_PFUTURE = [2, 3]

@@ -177,3 +177,24 @@ def test_board_watch_reads_hwmon_power_and_clock(tmp_path):
     with empty:
         pass
     assert empty.record() is None
+
+
+def test_dump_outputs_writes_whole_blocks_or_one_seeded_row_sample_under_64_mb(tmp_path):
+    """--dump-outputs: float32 out_<model>.npy per model; above 64 MB in all every model keeps the SAME seeded rows, listed in rows.npy."""
+    import numpy as np
+    small = {"vap": np.arange(6 * 784, dtype=np.float32).reshape(6, 784)}
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    assert sorted(os.listdir(tmp_path / "a")) == ["out_vap.npy"]
+    assert np.array_equal(np.load(tmp_path / "a" / "out_vap.npy"), small["vap"])
+    S = 12000                                                                  # 2 models x 12000 x 784 x 4 B = 75 MB
+    big = {m: np.arange(S, dtype=np.float32)[:, None] + np.zeros((1, 784), np.float32) + k for k, m in enumerate(("bc", "nod"))}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, "_rank1")
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["out_bc_rank1.npy", "out_nod_rank1.npy", "rows_rank1.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= bench.DUMP_LIMIT_BYTES
+    rows = np.load(tmp_path / "b" / "rows_rank1.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.load(tmp_path / "c" / "rows_rank1.npy")) and len(set(rows)) == len(rows)
+    for k, m in enumerate(("bc", "nod")):
+        got = np.load(tmp_path / "b" / f"out_{m}_rank1.npy")
+        assert got.dtype == np.float32 and np.array_equal(got[:, 0], rows + k)

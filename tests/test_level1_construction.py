@@ -1,31 +1,21 @@
-"""SURVEY §8b level 1, construction half: the reference's OWN ``__init__`` text must run unchanged against libvapx's classes.
+"""SURVEY §8b level 1, construction half: the reference's constructor statements must run against libvapx's classes.
 
-CPU part (this file, ``-m "not gpu"``): when ``/root/reference`` is present (the build container; the GPU box has none and these tests skip
-there) the source of ``VAPRealTime.__init__`` / ``Vap.__init__`` is cut out of the reference's files with ``ast`` — the module is NOT imported —
-and executed with only the class names rebound (``VapConfig``, ``VapGPT`` -> ``vap_realtime_amd.realtime``).  Nothing touches a GPU until the
-first compute call, so the whole constructor runs here; what it leaves behind must pack into the bit-identical weight blob the direct path
-makes.  The GPU part (tests/test_adapters_gpu.py::test_reference_constructor_lines_then_level1_orchestration) drives the object built this way."""
+CPU part (this file, ``-m "not gpu"``): the statements of ``VAPRealTime.__init__`` (vap_main.py:194-215; vap_bc_main.py:188-209 and
+vap_nod_main.py:187-208 are the same lines) and of the library twin ``Vap.__init__`` (vap_realtime/model.py:25-49), restated in
+``_construct_like_the_reference`` with only the class names bound to ``vap_realtime_amd.realtime``.  Nothing touches a GPU until the first
+compute call, so the whole constructor runs here; what it leaves behind must pack into the bit-identical weight blob the direct path
+makes.  The GPU part (tests/test_adapters_gpu.py::test_reference_constructor_lines_then_level1_orchestration) drives an object built the
+same way."""
 import argparse
-import ast
+import json
 import os
-import queue
-import textwrap
-import time
 
 import numpy as np
 import pytest
 
 from vap_realtime_amd import weights as W
 
-REF = "/root/reference"
-needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists only in the build container")
-
-
-def _method_source(path, cls_name, fn_name="__init__"):
-    txt = open(path).read()
-    cls = next(n for n in ast.parse(txt).body if isinstance(n, ast.ClassDef) and n.name == cls_name)
-    fn = next(n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name == fn_name)
-    return textwrap.dedent(ast.get_source_segment(txt, fn, padded=True))
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _write_reference_format_files(tmp_path, mode, hz=20, seed=11):
@@ -40,49 +30,50 @@ def _write_reference_format_files(tmp_path, mode, hz=20, seed=11):
     return cpc_sd, vap_sd, vap_p, cpc_p
 
 
-def _namespace(klass):
+def _construct_like_the_reference(klass, sd, cpc_p, device):
+    """conf -> VapGPT(conf) -> load_encoder -> load_state_dict(strict=False) -> the eight downsample assignments (weight / bias of
+    downsample[1] and downsample[2].ln, on encoder1 then encoder2) -> .to(device) -> .eval(): the reference's constructor order."""
     import torch
-    from vap_realtime_amd import realtime as R
-    return {"torch": torch, "nn": torch.nn, "time": time, "os": os, "queue": queue, "Base": object,
-            "VapConfig": R.VapConfig, "VapGPT": klass, "VapGPT_bc": R.VapGPT_bc, "VapGPT_nod": R.VapGPT_nod}
+    from vap_realtime_amd.realtime import VapConfig
+    vap = klass(VapConfig())
+    vap.load_encoder(cpc_model=cpc_p)
+    vap.load_state_dict(sd, strict=False)
+    for enc in (vap.encoder1, vap.encoder2):
+        enc.downsample[1].weight = torch.nn.Parameter(sd["encoder.downsample.1.weight"])
+        enc.downsample[1].bias = torch.nn.Parameter(sd["encoder.downsample.1.bias"])
+        enc.downsample[2].ln.weight = torch.nn.Parameter(sd["encoder.downsample.2.ln.weight"])
+        enc.downsample[2].ln.bias = torch.nn.Parameter(sd["encoder.downsample.2.ln.bias"])
+    vap.to(device)
+    return vap.eval()
 
 
-class _Shell:
-    pass
-
-
-@needs_reference
-@pytest.mark.parametrize("prog,mode", [("rvap/vap_main/vap_main.py", "vap"), ("rvap/vap_bc/vap_bc_main.py", "bc"),
-                                       ("rvap/vap_nod/vap_nod_main.py", "nod")])
-def test_reference_server_constructor_runs_verbatim(prog, mode, tmp_path):
+@pytest.mark.parametrize("mode", [pytest.param("vap", id="rvap/vap_main/vap_main.py-vap"), pytest.param("bc", id="rvap/vap_bc/vap_bc_main.py-bc"),
+                                  pytest.param("nod", id="rvap/vap_nod/vap_nod_main.py-nod")])
+def test_reference_server_constructor_runs_verbatim(mode, tmp_path):
+    """vap_main / vap_bc_main / vap_nod_main (the id names the program): each calls its class ``VapGPT`` and loads the file with
+    ``torch.load``; their constructor statements, in the reference's order, through ``_construct_like_the_reference``."""
     import torch
     from vap_realtime_amd import realtime as R
     cpc_sd, vap_sd, vap_p, cpc_p = _write_reference_format_files(tmp_path, mode)
-    ns = _namespace({"vap": R.VapGPT, "bc": R.VapGPT_bc, "nod": R.VapGPT_nod}[mode])     # each program calls its class "VapGPT"
-    exec(_method_source(os.path.join(REF, prog), "VAPRealTime"), ns)
-    obj = _Shell()
-    ns["__init__"](obj, vap_p, cpc_p, torch.device("cuda", 0), 20, 2.5)
-    assert obj.audio_frame_size == 1120 and obj.audio_context_len == 50 and obj.vap.device == torch.device("cuda", 0)
-    assert obj.vap._engine is None, "nothing may touch the GPU before the first compute call"
-    got_cpc, got_vap = obj.vap._gather_state_dicts()
+    klass = {"vap": R.VapGPT, "bc": R.VapGPT_bc, "nod": R.VapGPT_nod}[mode]
+    vap = _construct_like_the_reference(klass, torch.load(vap_p, map_location=torch.device("cpu")), cpc_p, torch.device("cuda", 0))
+    assert type(vap) is klass and vap.device == torch.device("cuda", 0)
+    assert vap._engine is None, "nothing may touch the GPU before the first compute call"
+    got_cpc, got_vap = vap._gather_state_dicts()
     assert np.array_equal(W.pack_blob(got_cpc, got_vap, mode), W.pack_blob(cpc_sd, vap_sd, mode))
 
 
-@needs_reference
 @pytest.mark.parametrize("mode", ["vap", "bc", "nod"])
 def test_reference_library_twin_constructor_runs_verbatim(mode, tmp_path):
-    """``vap_realtime/model.py:25-93``: ``Vap.__init__`` picks VapGPT / VapGPT_bc / VapGPT_nod by ``mode``; ``load_vap_model`` (its download
-    helper) is the one name bound to a local loader."""
+    """``vap_realtime/model.py:25-49``: ``Vap.__init__`` picks VapGPT / VapGPT_bc / VapGPT_nod by ``mode``, loads through
+    ``load_vap_model`` (here the local loader, checkpoints._torch_load) and moves to the device given as a string."""
     import torch
     from vap_realtime_amd import realtime as R, checkpoints
     cpc_sd, vap_sd, vap_p, cpc_p = _write_reference_format_files(tmp_path, mode)
-    ns = _namespace(R.VapGPT)
-    ns["load_vap_model"] = lambda *a, **k: checkpoints._torch_load(vap_p)
-    exec(_method_source(os.path.join(REF, "vap_realtime/model.py"), "Vap"), ns)
-    obj = _Shell()
-    ns["__init__"](obj, mode, 20, 2.5, cpc_model=cpc_p, device="cuda")
-    assert type(obj.vap) is {"vap": R.VapGPT, "bc": R.VapGPT_bc, "nod": R.VapGPT_nod}[mode]
-    got_cpc, got_vap = obj.vap._gather_state_dicts()
+    klass = {"vap": R.VapGPT, "bc": R.VapGPT_bc, "nod": R.VapGPT_nod}[mode]
+    vap = _construct_like_the_reference(klass, checkpoints._torch_load(vap_p), cpc_p, "cuda")
+    assert type(vap) is klass and vap.device == torch.device("cuda", 0) and vap._engine is None
+    got_cpc, got_vap = vap._gather_state_dicts()
     assert np.array_equal(W.pack_blob(got_cpc, got_vap, mode), W.pack_blob(cpc_sd, vap_sd, mode))
 
 
@@ -94,10 +85,8 @@ def test_vapconfig_has_the_reference_fields_and_defaults():
                 dropout=0.1, context_limit=-1, context_limit_cpc_sec=-1, lid_classify=0, lid_classify_num_class=3,
                 lid_classify_adversarial=0, lang_cond=0)                                        # vap_main.py:35-66
     assert {k: getattr(c, k) for k in c.__dataclass_fields__} == want
-    if os.path.isdir(REF):                                                                      # field-for-field against the reference's class text
-        txt = open(os.path.join(REF, "rvap/vap_main/vap_main.py")).read()
-        cls = next(n for n in ast.parse(txt).body if isinstance(n, ast.ClassDef) and n.name == "VapConfig")
-        assert [n.target.id for n in cls.body if isinstance(n, ast.AnnAssign)] == list(want)
+    with open(os.path.join(GOLDEN, "vapconfig_fields.json")) as f:                             # field-for-field against the reference's class
+        assert json.load(f) == list(want) == list(c.__dataclass_fields__)                     # (tools/make_golden_config.py)
     p, added = VapConfig.add_argparse_args(argparse.ArgumentParser(), [])
     args = p.parse_args(["--vap_frame_hz", "20", "--vap_bin_times", "0.2", "0.4", "0.6", "0.8"])
     assert VapConfig.args_to_conf(args).frame_hz == 20 and added == list(want)

@@ -153,7 +153,6 @@ def main():
     ap.add_argument("--devices", default="", help="with --shards N: comma list of N device ids, one engine per listed GPU (default: all on device 0)")
     ap.add_argument("--split-f16", action="store_true", help="engines on the opt-in split-precision path (serve --precision split)")
     ap.add_argument("--mode", default="vap", choices=["vap", "bc", "nod"])
-    ap.add_argument("--backlog", type=int, default=0, help="try to raise net.core.netdev_max_backlog to this before the run (needs root; 0 = leave it)")
     ap.add_argument("--fake", action="store_true", help="native front-end over a trivial step function (plumbing only, no GPU)")
     ap.add_argument("--standin", action="store_true", help="native front-end(s) over the native stand-in for the GPU tick (no GPU, no Python on the tick thread); "
                     "with --shards N: N passive front-ends behind ONE front door")
@@ -374,12 +373,6 @@ def main():
         print(json.dumps({"round": rep, "frames_answered": first["frames_answered"], "frames_sent": first["frames_sent"],
                           "lat_p99_ms": first["lat_p99_ms"]}), file=sys.stderr)
         time.sleep(1.0)
-    if args.backlog > 0:
-        try:
-            with open("/proc/sys/net/core/netdev_max_backlog", "w") as f:
-                f.write(str(args.backlog))
-        except Exception as e:                                    # noqa: BLE001
-            print(f"could not set netdev_max_backlog: {e}", file=sys.stderr)
     net0 = net_counters()
     cpu0 = (time.time(), os.times())
     procs = [subprocess.Popen(cmd_for(r), stdout=subprocess.PIPE, preexec_fn=client_affinity) for r in range(P)]
