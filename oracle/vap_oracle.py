@@ -191,6 +191,25 @@ class VapOracle:
             collect["comb"] = h
         return o1, o2, a, b, h
 
+    # ---- window only (per-layer row tests) ----------------------------------------------------
+    def advance(self, audio, st: OracleState) -> None:
+        """The encoder half of ``step``: encode one frame and append it to the window ring, without the
+        transformer, so that a test can slide a window over hundreds of frames and run ``layers`` where it looks."""
+        audio = _t(audio, self.dtype)
+        with torch.no_grad():
+            st.ring.append(self.encode(audio, st))
+            if len(st.ring) > self.T:
+                st.ring = st.ring[-self.T:]
+
+    def layers(self, st: OracleState) -> Dict[str, np.ndarray]:
+        """Every row of every transformer layer on the current window: ``o`` (ar_channel layer 0) and
+        ``stereo0..2`` (the three GPTStereo layers), each [S, 2, n, 256] with rows in chronological order."""
+        with torch.no_grad():
+            X = torch.stack(st.ring, dim=2)
+            collect: dict = {}
+            self.transformer(X[:, 0], X[:, 1], collect)
+        return {k: collect[k].numpy() for k in ("o", "stereo0", "stereo1", "stereo2")}
+
     # ---- full step ----------------------------------------------------------------------------
     def step(self, audio, st: OracleState, collect: Optional[dict] = None) -> Dict[str, np.ndarray]:
         """One VAP frame for S streams.  audio: float [S,2,L] (carry + new samples, exactly what

@@ -624,7 +624,12 @@ def test_windows_beyond_256_frames_against_the_oracle(hz, ctx, split):
 
 def test_xl_attention_kernel_equals_the_long_window_kernel(monkeypatch):
     """attention_xl_kernel on a window the tuned kernel also takes (T = 250): the same outputs to rounding (the key tiles are visited in the
-    same order with the same arithmetic; only where K / V come from differs)."""
+    same order with the same arithmetic; only where K / V come from differs).  vapx_create reads VAPX_FORCE_ATTENTION_XL per engine; the
+    forced leg's layer rows are also held against the float64 oracle, so the test means something even where the two kernels agree bit
+    for bit."""
+    import torch
+    from layer_rows import check_rows
+    from oracle.vap_oracle import ServerFramer, VapOracle
     from vap_realtime_amd import engine, synth, weights as W
     hz, ctx = 50, 5.0
     cpc, vap = W.synthetic_weights(23, hz, "vap")
@@ -639,10 +644,22 @@ def test_xl_attention_kernel_equals_the_long_window_kernel(monkeypatch):
         eng = engine.Engine(blob, hz, ctx, max_streams=S)
         got = [eng.step(audio[:, :, f * hop:(f + 1) * hop]).copy() for f in range(F_)]
         outs.append(np.stack(got))
+        if force:
+            rows = {b: eng.peek(b, (S, 2, T, 256)) for b in ("o", "stereo0", "stereo1")}
         eng.close()
     worst = float(np.abs(outs[0][:, :, :272] - outs[1][:, :, :272]).max())
     print("attention_xl vs attention_long2: worst |diff| =", worst)
     assert worst <= 2e-5
+    o64, o32 = VapOracle(cpc, vap, hz, ctx, dtype=torch.float64), VapOracle(cpc, vap, hz, ctx)
+    s64, s32, fr = o64.new_state(S), o32.new_state(S), ServerFramer(S, hop)
+    for f in range(F_):
+        frame = fr.frame(audio[:, :, f * hop:(f + 1) * hop])
+        o64.advance(frame, s64)
+        o32.advance(frame, s32)
+    ref64, ref32 = o64.layers(s64), o32.layers(s32)
+    for b, got in rows.items():
+        r = check_rows(b, got, [T] * S, ref64[b], ref32[b], what="forced attention_xl")
+        print(f"forced attention_xl {b}: worst err/E32 = {r:.2f}")
 
 
 @pytest.mark.parametrize("mode,hz,ctx", [("nod", 10, 10.0), ("bc", 20, 5.0)])

@@ -96,6 +96,9 @@ struct vapx_engine {
   // debug knob (env VAPX_POISON_SCRATCH): every scratch buffer is refilled with NaN bit patterns before each step and the rings start as
   // NaNs, so a kernel that consumes anything it (or an earlier kernel of the same tick) did not write shows up as a non-finite output
   std::vector<std::pair<void*, size_t>> poison;
+  // debug knob (env VAPX_FORCE_ATTENTION_XL, read once per engine in vapx_create): every long window of the fp32 path runs
+  // attention_xl_kernel, so tests can hold it against attention_long2_kernel on windows both kernels take
+  bool force_xl = false;
 #ifdef VAPX_TRACE   // debug build only (make trace -> libvapx_trace.so): per-workgroup phase stamps, tools/ffn_trace.py / tools/attn_trace.py
   unsigned long long* ffn_trace = nullptr;   // env VAPX_FFN_TRACE=<file>: phase stamps of the layer-0 FFN block's workgroups
   unsigned long long* attn_trace = nullptr;  // env VAPX_ATTN_TRACE=<file>: phase stamps of the layer-1 self-attention block's workgroups
@@ -423,7 +426,7 @@ int run_layers(vapx_engine* h, const Scratch& sc, int B, hipStream_t st, int l_b
         HIPCHK(h, launch_attention_proj_f16x3(ap, B, st));
       } else {
         ProfScope ps(h, CLS_ATTN, st);
-        HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(aa, B, st) : launch_attention(aa, B, st));
+        HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(aa, B, st) : launch_attention(aa, B, st, h->force_xl));
       }
       pre_att = sc.att; pre_w = split ? Lw.wproj8 : Lw.wprojf; pre_resid = ring0 ? rv->ring : xin;
       pre_ring = ring0;
@@ -435,13 +438,13 @@ int run_layers(vapx_engine* h, const Scratch& sc, int B, hipStream_t st, int l_b
         fp.ln_g = Lw.ln_src_g; fp.ln_b = Lw.ln_src_b; fp.wqkvf = split ? Lw.wqx8 : Lw.wqxf; fp.n_qkv_chunks = 1; fp.qkv = sc.qx;
         { ProfScope ps(h, CLS_FFN_PROJ, st); HIPCHK(h, split ? launch_ffn_block_f16x3(fp, st) : launch_ffn_block(fp, st)); }
         AttnArgs ax{sc.qx, sc.kvx, sc.kvx + 256, sc.att, sc.bn, T, 256, 512, 1};
-        { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(ax, B, st) : launch_attention(ax, B, st)); }
+        { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(ax, B, st) : launch_attention(ax, B, st, h->force_xl)); }
         pre_w = split ? Lw.wprojx8 : Lw.wprojxf; pre_resid = sc.xmid;
       }
     } else {
     // self attention
       AttnArgs aa{sc.qkv, sc.qkv + 256, sc.qkv + 512, sc.att, sc.bn, T, 768, 768, 0};
-      { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(aa, B, st) : launch_attention(aa, B, st)); }
+      { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(aa, B, st) : launch_attention(aa, B, st, h->force_xl)); }
       g = gemm_args(sc.att, r256, Lw.wproj, M, 256, 256, sc.xmid, r256);
       g.resid = xin; g.C2 = sc.xn;
       if (l == 0) { g.gamma = Lw.ln_ffn_g; g.beta = Lw.ln_ffn_b; }
@@ -452,7 +455,7 @@ int run_layers(vapx_engine* h, const Scratch& sc, int B, hipStream_t st, int l_b
         g = gemm_args(sc.xn, r256, Lw.wq_x, M, 256, 256, sc.qx, r256);
         HIPCHK(h, gemm(h, g, EPI_STORE, st));
         AttnArgs ax{sc.qx, sc.kvx, sc.kvx + 256, sc.att, sc.bn, T, 256, 512, 1};
-        { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(ax, B, st) : launch_attention(ax, B, st)); }
+        { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(ax, B, st) : launch_attention(ax, B, st, h->force_xl)); }
         g = gemm_args(sc.att, r256, Lw.wproj_x, M, 256, 256, sc.xmid, r256);
         g.resid = sc.xmid; g.C2 = sc.xn; g.gamma = Lw.ln_ffn_g; g.beta = Lw.ln_ffn_b;
         HIPCHK(h, gemm(h, g, EPI_RESID_LN, st, /*bounded_A=*/false));
@@ -985,6 +988,7 @@ int vapx_create(const vapx_config* cfg, const float* blob, size_t n_floats, vapx
   CR(hipHostMalloc((void**)&h->ids_pinned, B * sizeof(int), hipHostMallocDefault));
   CR(hipHostMalloc((void**)&h->audio_pinned, B * 2 * h->L * sizeof(float), hipHostMallocDefault));
   h->id_stamp.assign(S, 0u);
+  h->force_xl = getenv("VAPX_FORCE_ATTENTION_XL") != nullptr;
   if (getenv("VAPX_POISON_SCRATCH")) {
     CR(hipMemset(h->ring, 0xFF, S * 2 * T * 256 * sizeof(float)));          // rows beyond frames_seen are never read: prove it
     CR(hipMemset(h->ring_qkv, 0xFF, S * 2 * T * 768 * sizeof(float)));
