@@ -5,26 +5,30 @@ One "step" = one VAP frame (one tick) for every stream of this rank: frame assem
 context ring -> 1+3 transformer layers -> heads, through the C ABI (vapx_step) with audio and outputs resident in HBM.
 
 Headline workload (`value`) = BASELINE.json configs[2] ("c3"): 4096 concurrent synthetic stereo streams, 50 Hz frames, 5 s
-context (T = 250) per GPU — the LARGEST single-GPU configuration.  The same command measures the other single-GPU
-configurations as sub-records under "configs", each with its own `roofline`, `cpu_baseline`, `parity_gate`, `split_f16` side
-record and `paced_latency`:
-  c2          256 streams x 20 Hz / T = 50    (configs[1])
-  s4096_20hz  4096 streams x 20 Hz / T = 50   (the per-GPU shard of configs[3]: 32768 streams over 8 GPUs)
-  c5          bc + nod on one shared CPC trunk, 4096 streams (configs[4])
+context (T = 250) per GPU — the LARGEST single-GPU configuration.
 `--gpus N` with N > 1 (and no WORLD_SIZE in the environment) re-executes itself under torch.distributed.run with N ranks,
 one per GPU; streams are sharded over the ranks with NO data-path collective (they are independent), every record is then
 the whole-job aggregate (units of all ranks / max-over-ranks time), so "s4096_20hz" at N = 8 IS configs[3].
 
-Every record passes a PARITY GATE before anything is timed: ticks 0, 1 (window warm-up), T-1 (first full window) and T (first
-slide) of the first and the last stream of the rank are compared with the oracle (CPU restatement of the reference step, pinned
-to the unmodified reference by tests/golden) at 1e-4 abs; a miss aborts the run without a number.
+A plain run measures the headline and nothing else: it fills the context window (T + 1 ticks: the timed region is the steady
+state), runs NP ticks with every kernel class HIP-event timed to find the dominant one, warms up, times the K steps, writes
+`--dump-outputs` and prints ONE JSON line on rank 0: metric / value / unit / ms_per_step / ... plus "roofline" (the dominant kernel
+class, HIP-event timed inside the timed region on the launch stream).  Its ticks are exactly those of a --full run's headline.
 
-Prints ONE JSON line on rank 0 (contract in the task prompt): metric / value / unit / ... plus per record
-  "roofline":      dominant kernel (by summed time), HIP-event timed inside the timed region on the launch stream
+`--full` adds everything else.  Every record then passes a PARITY GATE before anything is timed: ticks 0, 1 (window warm-up), T-1
+(first full window) and T (first slide) of the first and the last stream of the rank are compared with the oracle (CPU restatement
+of the reference step, pinned to the unmodified reference by tests/golden) at 1e-4 abs; a miss aborts the run without a number.
+The line then carries per record
+  "parity_gate":   that comparison
   "cpu_baseline":  the oracle timed on this host at the record's own shape (1 thread, batch 1), continuing from the gate's state
   "paced_latency": distinct streams in phase-staggered sub-ticks on a wall-clock schedule (the <= 10 ms p99 target), per rank
   "split_f16":     the same workload on the opt-in split-precision path (never `value`)
-and once: "front_end" (the native TCP front-end under the real-time load generator, reference wire format).
+and once: "front_end" (the native TCP front-end under the real-time load generator, reference wire format), the CPU leg on every
+core, and the other single-GPU configurations as sub-records under "configs", each with all of the above:
+  c2          256 streams x 20 Hz / T = 50    (configs[1])
+  s4096_20hz  4096 streams x 20 Hz / T = 50   (the per-GPU shard of configs[3]: 32768 streams over 8 GPUs)
+  c5          bc + nod on one shared CPC trunk, 4096 streams (configs[4])
+The complete record of a --full run goes to a file (--full-record); stdout carries only the compact line.
 """
 from __future__ import annotations
 
@@ -34,6 +38,7 @@ import os
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -303,20 +308,23 @@ def compare_with_oracle(mode, row, want, n):
     return worst if np.isfinite(worst) else float("inf")
 
 
-def fill_and_gate(wl: Workload, name: str):
-    """Fill the context window (T + 1 ticks: the timed region is the steady state) and hold the engines' outputs of the first and
-    the last stream at ticks 0, 1, T-1, T against the oracle.  Raises SystemExit on a miss: no number without parity."""
-    import torch
+def fill_and_gate(wl: Workload, name: str, gate: bool = True):
+    """Fill the context window (T + 1 ticks: the timed region is the steady state) and, with `gate`, hold the engines' outputs of
+    the first and the last stream at ticks 0, 1, T-1, T against the oracle.  Raises SystemExit on a miss: no number without parity.
+    Returns (gate record, oracle twin), both None without `gate`."""
     T, S = wl.T, wl.S
     gate_idx = [0, S - 1] if S > 1 else [0]
-    check_ticks = sorted({0, 1, T - 1, T})
-    torch.set_num_threads(min(8, os.cpu_count() or 1))
-    twin = OracleTwin(wl.cpc, wl.sets, wl.hz, wl.ctx_sec, wl.audio, gate_idx)
+    check_ticks = sorted({0, 1, T - 1, T}) if gate else []
     got = {}
     for i in range(T + 1):
         wl.step(i)
         if i in check_ticks:
             got[i] = wl.rows(gate_idx)
+    if not gate:
+        return None, None
+    import torch
+    torch.set_num_threads(min(8, os.cpu_count() or 1))
+    twin = OracleTwin(wl.cpc, wl.sets, wl.hz, wl.ctx_sec, wl.audio, gate_idx)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     worst = {}
@@ -438,9 +446,9 @@ class BoardWatch:
                 "source": "amdgpu hwmon power1_input / freq1_input of this rank's card, 20 Hz, during the timed steps"}
 
 
-def run_workload(name, S, hz, ctx_sec, mode, steps, warmup, ctx, groups=0, split_f16=False, defer_join=False):
-    """Parity gate while the window fills, find the dominant kernel class, then time exactly `steps` ticks bracketed by barrier +
-    device synchronise; returns (record, workload, oracle twin) — the caller closes the workload."""
+def run_workload(name, S, hz, ctx_sec, mode, steps, warmup, ctx, groups=0, split_f16=False, defer_join=False, gate=True):
+    """Fill the window (with `gate`: the parity gate), find the dominant kernel class, then time exactly `steps` ticks bracketed by
+    barrier + device synchronise; returns (record, workload, oracle twin or None) — the caller closes the workload."""
     import torch
     from vap_realtime_amd import dist_util, engine
     rank, local_rank, world, dist = ctx
@@ -450,7 +458,7 @@ def run_workload(name, S, hz, ctx_sec, mode, steps, warmup, ctx, groups=0, split
     def barrier():
         dist_util.barrier(dist, torch.cuda.synchronize)
 
-    gate, twin = fill_and_gate(wl, name + ("_split_f16" if split_f16 else ""))
+    gate, twin = fill_and_gate(wl, name + ("_split_f16" if split_f16 else ""), gate)
     wl.profile_enable(range(len(engine.PROF_CLASSES)))
     wl.profile_read()
     NP = 3 if S * T > 100000 else 5
@@ -858,8 +866,6 @@ def compact_line(result: dict, full_path: str = "") -> str:
         "data": "synthetic (seeded dialogue audio + seeded random weights)",
         "config": {"workload": cfg["workload"], "streams_per_gpu": cfg["streams_per_gpu"], "streams_total": cfg["streams_total"],
                    "frame_hz": cfg["frame_hz"], "ctx_frames": cfg["ctx_frames"], "mode": cfg["mode"], "parallelism": cfg["parallelism"]},
-        "parity_gate": {"ok": result["parity_gate"]["ok"], "worst_abs": _r(result["parity_gate"]["worst_abs"], 3),
-                        "tolerance_abs": result["parity_gate"]["tolerance_abs"]},
         "roofline": {"bound": roof["bound"], "kernel": roof["kernel"], "achieved": _r(roof["achieved"]), "peak": _r(roof["peak"]),
                      "unit": roof["unit"], "frac": _r(roof["frac"], 4), "traffic": _r(roof.get("traffic")), "avg_launch_us": _r(roof["avg_launch_us"]),
                      "launches_per_step": _r(roof["launches_per_step"], 3), "traffic_ratio": _r(roof.get("traffic_ratio"), 3),
@@ -868,6 +874,9 @@ def compact_line(result: dict, full_path: str = "") -> str:
                      # whether the kernels timed here are that tree's (content hash of vap-realtime_amd/csrc)
                      "traffic_source": {k: (roof.get("traffic_source") or {}).get(k) for k in ("file", "git", "csrc_sha", "stale")}},
     }
+    pg = result.get("parity_gate")
+    if pg:                                                                   # --full runs only
+        line["parity_gate"] = {"ok": pg["ok"], "worst_abs": _r(pg["worst_abs"], 3), "tolerance_abs": pg["tolerance_abs"]}
     if "executed_frac_of_fp32_mfma_peak" in result:
         line["executed_tflops"] = _r(result["executed_tflops"], 4)
     bd = result.get("board")
@@ -939,28 +948,37 @@ def _jsonable(o):
     return o
 
 
-def main():
+# options that shape only the --full legs, with their defaults there; a plain run refuses them unless they ask for nothing (None, '', 0)
+FULL_ONLY = {"configs": "c2,s4096_20hz,c5", "cpu_baseline_sec": 6.0, "cpu_procs": -1, "paced_sec": 10.0, "front_end_streams": 4096,
+             "front_end_repeat": 3, "full_record": "bench_full.json"}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS), help="headline workload (`value`)")
-    ap.add_argument("--configs", default="c2,s4096_20hz,c5",
-                    help="comma list of further workloads measured as sub-records under \"configs\" ('' = none)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything else too: parity gates, CPU baselines, split-precision side records, latency legs, "
+                         "the front-end record and the other configurations (--configs)")
+    ap.add_argument("--configs", default=None,
+                    help="--full: comma list of further workloads measured as sub-records under \"configs\" (default c2,s4096_20hz,c5; '' = none)")
     ap.add_argument("--streams", type=int, default=None, help="override: concurrent streams per GPU of the headline workload")
     ap.add_argument("--frame-hz", type=int, default=None)
     ap.add_argument("--ctx-sec", type=float, default=None)
     ap.add_argument("--mode", default=None, choices=["vap", "bc", "nod", "bc+nod", "vap+bc+nod"],
                     help="override: model variant; a+b = weight sets served on one shared CPC trunk (one stream-frame = one audio "
                          "frame through the shared encoder and every listed model)")
-    ap.add_argument("--cpu-baseline-sec", type=float, default=6.0, help="timed oracle seconds per distinct record shape")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-procs", type=int, default=-1,
-                    help="processes of the multi-core CPU leg at the headline shape (-1 = every physical core, 0 = skip)")
-    ap.add_argument("--no-latency", action="store_true", help="skip the latency legs, the split-precision side records and the front-end record")
-    ap.add_argument("--paced-sec", type=float, default=10.0, help="duration of each paced many-stream latency run (0 = skip)")
-    ap.add_argument("--front-end-streams", type=int, default=4096, help="real-time TCP clients of the front-end record (0 = skip)")
-    ap.add_argument("--front-end-repeat", type=int, default=3, help="independent runs of the front-end record; the worst (client-side p99) is reported")
+    ap.add_argument("--cpu-baseline-sec", type=float, default=None, help="--full: timed oracle seconds per distinct record shape (default 6)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU legs")
+    ap.add_argument("--cpu-procs", type=int, default=None,
+                    help="--full: processes of the multi-core CPU leg at the headline shape (default -1 = every physical core, 0 = skip)")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the latency legs, the split-precision side records and the front-end record")
+    ap.add_argument("--paced-sec", type=float, default=None, help="--full: duration of each paced many-stream latency run (default 10; 0 = skip)")
+    ap.add_argument("--front-end-streams", type=int, default=None, help="--full: real-time TCP clients of the front-end record (default 4096; 0 = skip)")
+    ap.add_argument("--front-end-repeat", type=int, default=None,
+                    help="--full: independent runs of the front-end record (default 3); the worst (client-side p99) is reported")
     ap.add_argument("--groups", type=int, default=0, help="intra-tick overlap groups (0 = engine default)")
     ap.add_argument("--split-f16", action="store_true",
                     help="opt-in: GEMM-shaped contractions as fp32-accurate 3-term f16 split products (VAPX_FLAG_SPLIT_F16)")
@@ -969,12 +987,24 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--share-gpu", action="store_true",
                     help="plumbing check on a 1-GPU box: every rank uses device 0 (combine with --backend gloo; RCCL cannot put two ranks on one device)")
-    ap.add_argument("--full-record", default="bench_full.json", help="file name of the complete record (written under gpurun_out/, else the repo root)")
+    ap.add_argument("--full-record", default=None,
+                    help="--full: file of the complete record (default bench_full.json; relative to the repository root, else the temp directory)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write the headline workload's outputs of its last timed step to DIR/out_<model>.npy (float32, <= 64 MB)")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="multi-rank plumbing check without a GPU: spawn, rendezvous, shard the streams, barrier, print the ranks")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    asked = [o for o in FULL_ONLY if getattr(args, o)]
+    if asked and not args.full:
+        ap.error(", ".join("--" + o.replace("_", "-") for o in asked) + ": only with --full (a plain run measures the headline alone)")
+    for o, v in FULL_ONLY.items():
+        if getattr(args, o) is None:
+            setattr(args, o, v)
+    return args
+
+
+def main():
+    args = parse_args()
     ENGINE_KW.update({k: True for k in args.engine_flag})
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1012,13 +1042,14 @@ def main():
     torch.cuda.set_device(local_rank)
     dist = dist_util.init(args.backend, torch.device("cuda", local_rank))
     ctx = (rank, local_rank, world, dist)
-    side = not args.no_latency
+    side = args.full and not args.no_latency
+    cpu_legs = args.full and not args.no_cpu_baseline
     cpu_cache = {}      # (hz, ctx_sec, mode) -> cpu_baseline record: c2 and s4096_20hz are the same CPU shape
 
     def full_record(name, S, hz, ctx_sec, mode, steps, warmup, headline=False):
-        """One configuration: fp32 record (gate, timing, roofline) + its CPU baseline + split-precision side record + paced latency."""
+        """One configuration: fp32 record (timing, roofline; --full: gate) + its CPU baseline + split-precision side record + paced latency."""
         rec, wl, twin = run_workload(name, S, hz, ctx_sec, mode, steps, warmup, ctx, groups=args.groups, split_f16=args.split_f16 and headline,
-                                     defer_join=args.defer_join and headline)
+                                     defer_join=args.defer_join and headline, gate=args.full)
         extras = {}
         if headline:
             if args.dump_outputs:                                  # before anything below steps the engines or reuses d_out
@@ -1032,7 +1063,7 @@ def main():
         wl.close()
         del wl
         torch.cuda.empty_cache()
-        if rank == 0 and not args.no_cpu_baseline:
+        if rank == 0 and cpu_legs:
             key = (hz, ctx_sec, mode)
             if key not in cpu_cache:
                 cpu_cache[key] = cpu_baseline_record(twin, (S, hz, ctx_sec, mode), args.cpu_baseline_sec)
@@ -1130,10 +1161,11 @@ def main():
     if hx.get("groups"):
         result["overlap_groups"] = hx["groups"]
 
-    # ---- the other single-GPU configurations of BASELINE.json, each a full record ----
+    # ---- --full: the other single-GPU configurations of BASELINE.json, each a full record ----
     result["configs"] = {}
     overridden = bool(args.streams or args.frame_hz or args.ctx_sec or args.mode)
-    for name in [c for c in args.configs.split(",") if c]:
+    configs = [c for c in args.configs.split(",") if c] if args.full else []
+    for name in configs:
         if name == args.workload and not overridden:
             continue
         cS, chz, cctx, cmode, csteps, cwarm = WORKLOADS[name]
@@ -1157,7 +1189,7 @@ def main():
                 result["front_end"] = front_end_record(args.front_end_streams, 10.0, devices=devs if world > 1 else None, repeat=args.front_end_repeat)
         dist_util.gather_ints(dist, [rank])
 
-    if rank == 0 and not args.no_cpu_baseline and mode == "vap":
+    if rank == 0 and cpu_legs and mode == "vap":
         P = args.cpu_procs if args.cpu_procs >= 0 else physical_cores()
         if P > 1:
             # the reference deployed on every core: P independent single-threaded processes (one stream each), P = the
@@ -1179,13 +1211,13 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        # the complete record goes to a file; stdout carries exactly ONE line: the compact record (< 4 KB, strict JSON)
+        # --full: the complete record goes to a file; stdout carries exactly ONE line: the compact record (< 4 KB, strict JSON)
         result = _jsonable(result)
         full_path = ""
-        for d in (os.path.join(ROOT, "gpurun_out"), ROOT, "/tmp"):
+        for d in (ROOT, tempfile.gettempdir()) if args.full else ():
             try:
-                os.makedirs(d, exist_ok=True)
                 fp = os.path.join(d, args.full_record)
+                os.makedirs(os.path.dirname(fp), exist_ok=True)
                 with open(fp, "w") as f:
                     json.dump(result, f, allow_nan=False)
                 full_path = os.path.relpath(fp, ROOT) if fp.startswith(ROOT) else fp

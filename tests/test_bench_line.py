@@ -198,3 +198,55 @@ def test_dump_outputs_writes_whole_blocks_or_one_seeded_row_sample_under_64_mb(t
     for k, m in enumerate(("bc", "nod")):
         got = np.load(tmp_path / "b" / f"out_{m}_rank1.npy")
         assert got.dtype == np.float32 and np.array_equal(got[:, 0], rows + k)
+
+
+def test_plain_line_carries_the_headline_without_the_full_legs():
+    """A plain run's record (no parity gate, CPU baselines, side records, configurations or front-end): the line keeps the headline's keys
+    with today's meaning and names no full record."""
+    full = canned()
+    plain = {k: copy.deepcopy(v) for k, v in full.items() if k not in ("configs", "split_f16", "paced_latency", "front_end", "cpu_baseline",
+                                                                       "cpu_baseline_multiprocess", "concurrent_streams_at_10ms",
+                                                                       "latency_ms_host_inclusive", "overlap_groups")}
+    plain["parity_gate"] = None
+    line = strict(bench.compact_line(bench._jsonable(plain)))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config", "roofline"):
+        assert k in line, k
+    assert line["value"] == pytest.approx(full["value"], rel=1e-6) and line["ms_per_step"] == pytest.approx(full["ms_per_step"], rel=1e-5)
+    assert line["metric"] == full["metric"] and line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    for k in ("parity_gate", "cpu_baseline", "cpu_all_cores", "split_f16", "configs", "front_end", "concurrent_streams_at_10ms", "full_record"):
+        assert k not in line, k
+
+
+def test_plain_run_refuses_the_options_of_the_full_legs():
+    """Without --full the legs are off: an option that asks for one is an error, one that switches it off is accepted; --full keeps
+    today's defaults."""
+    plain = bench.parse_args(["--steps", "20", "--warmup", "5"])
+    assert not plain.full
+    for argv in (["--configs", "c2"], ["--paced-sec", "5"], ["--cpu-procs", "4"], ["--front-end-streams", "16"], ["--full-record", "x.json"],
+                 ["--cpu-baseline-sec", "2"], ["--front-end-repeat", "1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(argv)
+    off = bench.parse_args(["--configs=", "--no-latency", "--no-cpu-baseline", "--paced-sec", "0", "--front-end-streams", "0"])
+    assert not off.full and off.configs == ""
+    full = bench.parse_args(["--full"])
+    assert full.configs == "c2,s4096_20hz,c5" and full.paced_sec == 10.0 and full.cpu_procs == -1 and full.front_end_streams == 4096
+    assert full.front_end_repeat == 3 and full.cpu_baseline_sec == 6.0 and full.full_record == "bench_full.json"
+    assert bench.parse_args(["--full", "--configs", "c5", "--paced-sec", "0"]).configs == "c5"
+
+
+def test_plain_fill_steps_the_same_ticks_without_the_oracle():
+    """The plain run fills the window with exactly the ticks of a gated fill (0 .. T), and reads no rows back for a comparison."""
+    class Fake:
+        T, S = 7, 3
+
+        def __init__(self):
+            self.ticks = []
+
+        def step(self, i):
+            self.ticks.append(i)
+
+        def rows(self, idx):
+            raise AssertionError("a plain fill reads no rows")
+    wl = Fake()
+    assert bench.fill_and_gate(wl, "c3", gate=False) == (None, None)
+    assert wl.ticks == list(range(Fake.T + 1))

@@ -4,7 +4,7 @@
 args="$1"; shift
 for rep in 1 2; do
 for lib in "$@"; do
-  VAPX_LIBRARY=$lib timeout 600 python bench.py $args --configs= --no-latency --no-cpu-baseline --front-end-streams 0 --full-record /tmp/ab_full.json >/dev/null 2>&1
+  VAPX_LIBRARY=$lib timeout 600 python bench.py $args --full --configs= --no-latency --no-cpu-baseline --front-end-streams 0 --full-record /tmp/ab_full.json >/dev/null 2>&1
   python - "$lib" <<'PY'
 import json, sys
 d = json.load(open('/tmp/ab_full.json'))
