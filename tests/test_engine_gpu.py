@@ -53,18 +53,28 @@ def test_step_matches_reference_golden(name):
 def test_intermediates_match_reference():
     """Per-stage buffers of selected frames (CNN, LSTM, each transformer layer) vs hooks on the
     reference modules."""
+    import torch
+    from oracle.vap_oracle import ServerFramer, VapOracle
     c = Case("vap20")
     eng = make_engine(c, full_last_layer=True)
     z = c.z
+    # the golden's hook sat on encoder1 only, so it holds cnn4 of the first channel; the second channel's z is held against the
+    # oracle (whose cnn4 is pinned to the golden by tests/test_oracle_golden.py) at the same tolerance
+    orc = VapOracle(c.cpc_sd, c.vap_sd, c.frame_hz, c.ctx_sec)
+    ost, ofr = orc.new_state(1), ServerFramer(1, c.hop)
     inter_frames = sorted({int(k.split(".")[1][1:]) for k in z.files if k.startswith("inter.f")})
     for f in range(max(inter_frames) + 1):
         eng.step(c.new_samples(f))
+        col = {}
+        with torch.no_grad():
+            orc.encode(torch.from_numpy(ofr.frame(c.new_samples(f))), ost, col)
         if f not in inter_frames:
             continue
         ncpc = 5
         zbuf = eng.peek("z", (2, ncpc, 256))
         cnn4 = z[f"inter.f{f}.cnn4"]                       # [256, 7] channel-1
         np.testing.assert_allclose(zbuf[0], cnn4[:, 1:-1].T, rtol=0, atol=2e-5)
+        np.testing.assert_allclose(zbuf[1], col["z"].numpy()[0, 1], rtol=0, atol=2e-5, err_msg=f"frame {f} z of the second channel")
         lo = eng.peek("lstm_out", (2, ncpc, 256))
         np.testing.assert_allclose(lo, z[f"inter.f{f}.lstm_out"], rtol=0, atol=2e-5)
         rows = z[f"inter.f{f}.rows"]

@@ -111,6 +111,7 @@ struct vapx_engine {
   int* ids_pinned = nullptr;
   hipEvent_t ids_evt = nullptr;
   int last_B = 0, last_G = 1;
+  bool last_tail_fused = false;           // some overlap group of the latest encoder pass ran conv_tail_kernel: h2 / h3 were not written
   bool deferred_pending = false;          // the latest step left its overlap groups un-joined (VAPX_DEFER_JOIN)
   std::vector<int32_t> pending_resets;    // vapx_reset_stream requests, applied stream-ordered by the next step
   std::vector<uint32_t> id_stamp;         // duplicate-id check: id_stamp[sid] == id_gen <=> sid already in this batch
@@ -301,6 +302,7 @@ int run_encoder(vapx_engine* h, const Scratch& sc, const StateView& sv, int B, c
   // (on the split-precision path the three GEMMs are 2x cheaper and beat the fp32 fused tail even at 256 streams)
   const bool fused_tail = conv_tail_supported(P[1], h->ncpc) && !(h->cfg.flags & VAPX_FLAG_UNFUSED_CONV) &&
                           !(h->cfg.flags & VAPX_FLAG_SPLIT_F16) && B <= 512;
+  if (fused_tail) h->last_tail_fused = true;   // B is this group's batch: vapx_peek must not re-derive the decision from last_B
   char nm[32];
   for (int i = 0; i < (fused_tail ? 1 : 3); ++i) {
     const ConvSpec& c = cs[i];
@@ -1092,6 +1094,7 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     HIPCHK(h, hipEventRecord(h->gstart, st));
     for (int g = 0; g < G; ++g) HIPCHK(h, hipStreamWaitEvent(h->gstream[g], h->gstart, 0));
   }
+  if (!lead) h->last_tail_fused = false;   // run_encoder sets it per group
   for (int g = 0; g < G; ++g) {
     int b0 = (int)((long)n * g / G), b1 = (int)((long)n * (g + 1) / G);
     const int nb = b1 - b0;
@@ -1309,6 +1312,7 @@ int vapx_encode_audio(vapx_handle h, int32_t n, const int32_t* stream_ids, const
   rc = upload_ids(h, n, stream_ids, 0, st, &ids);
   if (rc) return rc;
   const StateView sv{h->ring, h->ring_qkv, h->h_state, h->c_state, h->carry, h->frames_seen};
+  h->last_tail_fused = false;
   rc = run_encoder(h, h->sc, sv, n, ids, frames, h->L, false, st);
   if (rc) return rc;
   HIPCHK(h, hipMemcpyAsync(e, h->sc.e, (size_t)n * 2 * 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1370,7 +1374,9 @@ int64_t vapx_peek(vapx_handle h, const char* name, float* dst, size_t max_floats
   if (!strcmp(name, "h0")) { src = h->sc.h0; n = B * 2 * (P[0] + 4) * 256; }
   else if (!strcmp(name, "h1")) { src = h->sc.h1; n = B * 2 * (P[1] + 2) * 256; }
   else if (!strcmp(name, "h2") || !strcmp(name, "h3")) {
-    if (conv_tail_supported(P[1], h->ncpc) && !(h->cfg.flags & VAPX_FLAG_UNFUSED_CONV) && B <= 512)
+    // what run_encoder ran for the latest step, not a guess from last_B: the 512-stream limit holds per overlap group, so a batch of
+    // 1000 in two groups runs the fused tail twice and leaves h2 / h3 stale
+    if (h->last_tail_fused)
       return fail(h, VAPX_E_INVAL, "\"%s\" stays in LDS in the fused conv tail; create the engine with VAPX_FLAG_UNFUSED_CONV to peek it", name);
     if (name[1] == '2') { src = h->sc.h2; n = B * 2 * (P[2] + 2) * 256; }
     else { src = h->sc.h3; n = B * 2 * (P[3] + 2) * 256; }
@@ -1392,6 +1398,8 @@ int64_t vapx_peek(vapx_handle h, const char* name, float* dst, size_t max_floats
     src = h->sc.xl[4]; n = B * 2 * T * 256;
   }
   else return fail(h, VAPX_E_INVAL, "unknown buffer '%s'", name);
+  if (!src)   // vapx_attach_trunk freed the follower's encoder scratch
+    return fail(h, VAPX_E_INVAL, "\"%s\" is released: this engine is a trunk follower, peek its leader", name);
   if (n > max_floats) n = max_floats;
   HIPCHK(h, hipMemcpy(dst, src, n * sizeof(float), hipMemcpyDeviceToHost));
   return (int64_t)n;
