@@ -116,6 +116,10 @@ __global__ __launch_bounds__(256, MT == 1 ? 2 : 1) void ffn_block_kernel(const F
   __syncthreads();
   STAMP();   // 1: tile staged + normalised
 
+  // The WEIGHT fragment is operand A of the MFMA and the activation fragment operand B (a lane's registers hold W[col 32 ns + l31][k] and
+  // X[row l31][k], either is legal as either operand), so the 32 x 32 result tile comes out transposed: a lane owns ONE row and four groups of
+  // four consecutive columns.  Same products in the same k order as with the roles the other way round, but every hand-off of the tile
+  // (global store, LDS park, residual add) is a 16-byte access with one row index per lane instead of sixteen rows of one column.
   auto mm = [&](f32x16(&acc)[MT][2], const float* A, const float* wfrag, const float* next_wfrag) {
     const float* pa = A + l31 * LDH + kh;
     const f32x4* wf = wbase(wfrag);
@@ -141,8 +145,8 @@ __global__ __launch_bounds__(256, MT == 1 ? 2 : 1) void ffn_block_kernel(const F
         for (int s = 0; s < 4; ++s)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
-            acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[mt][s], ring[k8 * 2][s], acc[mt][0], 0, 0, 0);
-            acc[mt][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[mt][s], ring[k8 * 2 + 1][s], acc[mt][1], 0, 0, 0);
+            acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ring[k8 * 2][s], ac[mt][s], acc[mt][0], 0, 0, 0);
+            acc[mt][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ring[k8 * 2 + 1][s], ac[mt][s], acc[mt][1], 0, 0, 0);
           }
         ring[k8 * 2] = nx[(k8 * 2) * 64 + lane];
         ring[k8 * 2 + 1] = nx[(k8 * 2 + 1) * 64 + lane];
@@ -162,31 +166,33 @@ __global__ __launch_bounds__(256, MT == 1 ? 2 : 1) void ffn_block_kernel(const F
 #pragma unroll
       for (int r = 0; r < 16; ++r) { acc[mt][0][r] = 0.f; acc[mt][1][r] = 0.f; }
   };
-  // accumulator (mt, ns, r) <-> tile row lr = 32mt + (r&3) + 8*(r>>2) + 4*hi, chunk column w*64 + ns*32 + l31
-  const int ccol = w * 64 + l31;
+  // accumulator (mt, ns, r) <-> tile row lr = 32mt + l31, chunk column w*64 + ns*32 + 8*(r>>2) + 4*hi + (r&3): registers 4q .. 4q+3 are the
+  // four consecutive columns ccol + 32ns + 8q ..+3 of the lane's row
+  const int ccol = w * 64 + kh;
+  auto quad = [](const f32x16& a, int q) { return f32x4{a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]}; };
   auto store_global = [&](const f32x16(&acc)[MT][2], float* base, int ld, int col0) {
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
+    for (int mt = 0; mt < MT; ++mt) {
+      const int m = m0 + mt * 32 + l31;
+      if (m < g.M) {   // one bound test per lane and chunk (false only in the ragged last tile of a launch)
+        float* p = base + (long)m * ld + col0 + ccol;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int m = m0 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        if (m < g.M) {
-          float* p = base + (long)m * ld + col0 + ccol;
-          p[0] = acc[mt][0][r];
-          p[32] = acc[mt][1][r];
-        }
+        for (int ns = 0; ns < 2; ++ns)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) *(f32x4*)(p + ns * 32 + q * 8) = quad(acc[mt][ns], q);
       }
+    }
   };
 
   auto to_lds = [&](const f32x16(&acc)[MT][2], float* buf) {
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
+    for (int mt = 0; mt < MT; ++mt) {
+      float* p = buf + (mt * 32 + l31) * LDH + ccol;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int lr = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        buf[lr * LDH + ccol] = acc[mt][0][r];
-        buf[lr * LDH + ccol + 32] = acc[mt][1][r];
-      }
+      for (int ns = 0; ns < 2; ++ns)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *(f32x4*)(p + ns * 32 + q * 8) = quad(acc[mt][ns], q);
+    }
   };
   auto to_sH = [&](const f32x16(&acc)[MT][2]) { to_lds(acc, sH); };
   // LayerNorm of the tile rows, ROW-PER-WAVE and in place on the fp32 tile in the LDS buffer `buf`: wave w owns rows w, w + 4, ..; a lane
@@ -223,17 +229,27 @@ __global__ __launch_bounds__(256, MT == 1 ? 2 : 1) void ffn_block_kernel(const F
     }
     __syncthreads();
   };
-  auto add_rows = [&](f32x16(&v)[MT][2], const float* src) {   // v += src tile (global [M][256] rows)
+  // v[mt] += the lane's row at rp (256 floats wide; rp points at column ccol): all eight 16-byte loads are issued before the first add
+  auto add_row = [&](f32x16(&v)[2], const float* rp) {
+    f32x4 t[2][4];
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
+    for (int ns = 0; ns < 2; ++ns)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int m = m0 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        m = m < g.M ? m : g.M - 1;
-        const float* rp = src + (long)m * 256 + ccol;
-        v[mt][0][r] += rp[0];
-        v[mt][1][r] += rp[32];
-      }
+      for (int q = 0; q < 4; ++q) t[ns][q] = *(const f32x4*)(rp + ns * 32 + q * 8);
+#pragma unroll
+    for (int ns = 0; ns < 2; ++ns)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[ns][4 * q + j] += t[ns][q][j];
+  };
+  auto add_rows = [&](f32x16(&v)[MT][2], const float* src) {   // v += src tile (global [M][256] rows; rows beyond M read row M - 1)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      int m = m0 + mt * 32 + l31;
+      m = m < g.M ? m : g.M - 1;
+      add_row(v[mt], src + (long)m * 256 + ccol);
+    }
   };
 
   const int nq = g.wqkvf ? g.n_qkv_chunks : 0;
@@ -245,28 +261,17 @@ __global__ __launch_bounds__(256, MT == 1 ? 2 : 1) void ffn_block_kernel(const F
     mm(out, sH, g.wprojf, MODE == 1 ? g.w0f : after_ffn);
     if (MODE == 1 && g.resid_rot) {   // layer 0: residual rows straight from the embedding ring
       const int T = g.resid_T;
-      const int bc0 = ring_bc0, bc1 = ring_bc1, slot0 = ring_slot0, slot1 = ring_slot1, rot0 = ring_rot0, rot1 = ring_rot1;   // (loaded at kernel entry)
-      const int split = (bc0 + 1) * T;                           // first row of the second slab
-      const float* rp[MT][16];
+      const int split = (ring_bc0 + 1) * T;                      // first row of the second slab
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          int m = m0 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          m = m < g.M ? m : g.M - 1;
-          const bool second = m >= split;
-          const int bc = second ? bc1 : bc0, i = m - bc * T;
-          int rr = i + (second ? rot1 : rot0);
-          rr = rr >= T ? rr - T : rr;
-          rp[mt][r] = g.resid + (((long)(second ? slot1 : slot0) * 2 + (bc & 1)) * T + rr) * 256 + ccol;
-        }
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          out[mt][0][r] += rp[mt][r][0];
-          out[mt][1][r] += rp[mt][r][32];
-        }
+      for (int mt = 0; mt < MT; ++mt) {                          // one slot / rotation resolution per lane: the lane's row
+        int m = m0 + mt * 32 + l31;
+        m = m < g.M ? m : g.M - 1;
+        const bool second = m >= split;
+        const int bc = second ? ring_bc1 : ring_bc0, i = m - bc * T;
+        int rr = i + (second ? ring_rot1 : ring_rot0);
+        rr = rr >= T ? rr - T : rr;
+        add_row(out[mt], g.resid + (((long)(second ? ring_slot1 : ring_slot0) * 2 + (bc & 1)) * T + rr) * 256 + ccol);
+      }
     } else
     add_rows(out, g.resid);
     // mode 2 hands xmid to the next block through HBM; in mode 1 its only consumer is this workgroup (the residual of the FFN), so it
