@@ -214,6 +214,14 @@ int vapx_encode_audio(vapx_handle h, int32_t n, const int32_t* stream_ids, const
 int vapx_transformer(vapx_handle h, int32_t n, int32_t rows, const float* x, float* o, float* x12, float* comb,
                      int32_t stage, void* hip_stream);
 
+/* vapx_transformer plus the attention weights the reference returns with attention=True (modules.py:82-110,356-423).
+ * attn       [n][2][1][4][rows][rows]  ar_channel(x_c, attention=True)["attn"], channel c on dim 1
+ * self_attn  [n][2][3][4][rows][rows]  ar(..., attention=True)["self_attn"]
+ * cross_attn [n][2][3][4][rows][rows]  ar(..., attention=True)["cross_attn"]
+ * Any pointer may be NULL; attn needs stage 0|1, self_attn / cross_attn need stage 0|2. */
+int vapx_transformer_maps(vapx_handle h, int32_t n, int32_t rows, const float* x, float* o, float* x12, float* comb,
+                          int32_t stage, float* attn, float* self_attn, float* cross_attn, void* hip_stream);
+
 /* The head callables process_vap applies to tensors of any row count (vap_main.py:290-307); device pointers, rows x 256 fp32:
  *   vapx_vap_head       logits = vap_head(x)            Linear(256, 256) + bias   (vap_main.py:131,290)   [rows][256]
  *   vapx_va_classifier  y = va_classifier(x)            Linear(256, 1) + bias, BEFORE the sigmoid (:142,292-293)   [rows]

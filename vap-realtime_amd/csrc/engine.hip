@@ -350,14 +350,28 @@ int run_encoder(vapx_engine* h, const Scratch& sc, const StateView& sv, int B, c
 }
 
 struct RingView { const float* ring; const float* ring_qkv; const int* ids; };   // layer 0 reads the rings directly
+// vapx_transformer_maps: destinations of the attention weights (device, any may be null), each [B][2][layers][4][rows][rows]
+struct MapOut { float *attn, *self_attn, *cross_attn; int rows; };
 
 // ---- 1 self + 3 self/cross layers on x0 = xl[l_begin] (LN_self already in xn) ---------------------
 // Per layer: [QKV (+cross KV) projections] -> self-attention -> proj+residual+LN -> (cross: q GEMM,
 // cross-attention, proj+residual+LN) -> fused FFN block, which also emits the NEXT layer's
 // projections so that only the first executed layer needs stand-alone projection GEMMs.
 int run_layers(vapx_engine* h, const Scratch& sc, int B, hipStream_t st, int l_begin = 0, int l_end = 4,
-               bool prune_last = false, bool qkv0_ready = false, const RingView* rv = nullptr) {
+               bool prune_last = false, bool qkv0_ready = false, const RingView* rv = nullptr, const MapOut* maps = nullptr) {
   const int T = h->T;
+  if (maps && (rv || prune_last)) return fail(h, VAPX_E_INVAL, "attention maps need chronological buffers and every row of every layer");
+  // maps: one attention_map_kernel launch next to an attention launch, on that launch's own Q and K rows (after their producers, before the
+  // layer's FFN block overwrites sc.qkv / sc.kvx with the next layer's); no ProfScope: a diagnostic path outside the class table
+  auto emit_map = [&](int l, bool cross) -> hipError_t {
+    float* dst = !maps ? nullptr : cross ? maps->cross_attn : l == 0 ? maps->attn : maps->self_attn;
+    if (!dst || (cross && l == 0)) return hipSuccess;
+    const long rr = (long)maps->rows * maps->rows;
+    const int n_layers = l == 0 ? 1 : 3, li = l == 0 ? 0 : l - 1;
+    AttnMapArgs ma{cross ? sc.qx : sc.qkv, cross ? sc.kvx : sc.qkv + 256, sc.bn, T, cross ? 256 : 768, cross ? 512 : 768, cross ? 1 : 0,
+                   dst + li * 4 * rr, n_layers * 4 * rr, rr, maps->rows};
+    return launch_attention_map(ma, B, st);
+  };
   const int M = B * 2 * T;
   const RowMap r256 = contiguous_rows(256), r768 = contiguous_rows(768), r512 = contiguous_rows(512);
   if (prune_last && (l_end != 4 || l_begin > 2)) prune_last = false;
@@ -365,7 +379,9 @@ int run_layers(vapx_engine* h, const Scratch& sc, int B, hipStream_t st, int l_b
   // split path, long windows: the self-attention of a layer whose LN_self rows were written by the previous layer's flat-row block projects
   // its own Q|K|V (attention_proj_f16x3_kernel); that block then skips the three contractions and never writes sc.qkv
   // (windows of 257 .. 512 frames: attention_xl_kernel — fp32, Q|K|V from the flat-row blocks — on both paths)
-  const bool qkv_in_attn = (h->cfg.flags & VAPX_FLAG_SPLIT_F16) && !(h->cfg.flags & (VAPX_FLAG_SPLIT_QKV_IN_FFN | VAPX_FLAG_UNFUSED_PROJ)) && T > 64 && T <= 256;
+  // (a call that wants the self-attention maps needs Q and K in HBM: it takes the VAPX_FLAG_SPLIT_QKV_IN_FFN routing for that call)
+  const bool qkv_in_attn = (h->cfg.flags & VAPX_FLAG_SPLIT_F16) && !(h->cfg.flags & (VAPX_FLAG_SPLIT_QKV_IN_FFN | VAPX_FLAG_UNFUSED_PROJ)) && T > 64 && T <= 256 &&
+                           !(maps && maps->self_attn);
   bool xn_ready = false;                   // sc.xn holds LN_self(layer l)(x) of every row, sc.qkv does NOT hold this layer's Q|K|V
   for (int l = l_begin; l < l_full_end; ++l) {
     const Layer& Lw = h->layer[l];
@@ -404,6 +420,7 @@ int run_layers(vapx_engine* h, const Scratch& sc, int B, hipStream_t st, int l_b
 #ifdef VAPX_TRACE
       ab.trace = nullptr;
 #endif
+      if (maps) { HIPCHK(h, emit_map(l, false)); HIPCHK(h, emit_map(l, true)); }   // sc.qx: written by the launch above
       if (l > 0) {
         ab.q = sc.qx; ab.k = sc.kvx; ab.v = sc.kvx + 256; ab.ldq = 256; ab.ldkv = 512; ab.swap_kv = 1;
         ab.wprojf = asplit ? Lw.wprojxh : Lw.wprojxf; ab.resid = sc.xmid; ab.ln_g = Lw.ln_ffn_g; ab.ln_b = Lw.ln_ffn_b;
@@ -430,6 +447,7 @@ int run_layers(vapx_engine* h, const Scratch& sc, int B, hipStream_t st, int l_b
         ProfScope ps(h, CLS_ATTN, st);
         HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(aa, B, st) : launch_attention(aa, B, st, h->force_xl));
       }
+      if (maps) HIPCHK(h, emit_map(l, false));
       pre_att = sc.att; pre_w = split ? Lw.wproj8 : Lw.wprojf; pre_resid = ring0 ? rv->ring : xin;
       pre_ring = ring0;
       if (l > 0) {
@@ -441,12 +459,14 @@ int run_layers(vapx_engine* h, const Scratch& sc, int B, hipStream_t st, int l_b
         { ProfScope ps(h, CLS_FFN_PROJ, st); HIPCHK(h, split ? launch_ffn_block_f16x3(fp, st) : launch_ffn_block(fp, st)); }
         AttnArgs ax{sc.qx, sc.kvx, sc.kvx + 256, sc.att, sc.bn, T, 256, 512, 1};
         { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(ax, B, st) : launch_attention(ax, B, st, h->force_xl)); }
+        if (maps) HIPCHK(h, emit_map(l, true));
         pre_w = split ? Lw.wprojx8 : Lw.wprojxf; pre_resid = sc.xmid;
       }
     } else {
     // self attention
       AttnArgs aa{sc.qkv, sc.qkv + 256, sc.qkv + 512, sc.att, sc.bn, T, 768, 768, 0};
       { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(aa, B, st) : launch_attention(aa, B, st, h->force_xl)); }
+      if (maps) HIPCHK(h, emit_map(l, false));
       g = gemm_args(sc.att, r256, Lw.wproj, M, 256, 256, sc.xmid, r256);
       g.resid = xin; g.C2 = sc.xn;
       if (l == 0) { g.gamma = Lw.ln_ffn_g; g.beta = Lw.ln_ffn_b; }
@@ -458,6 +478,7 @@ int run_layers(vapx_engine* h, const Scratch& sc, int B, hipStream_t st, int l_b
         HIPCHK(h, gemm(h, g, EPI_STORE, st));
         AttnArgs ax{sc.qx, sc.kvx, sc.kvx + 256, sc.att, sc.bn, T, 256, 512, 1};
         { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(ax, B, st) : launch_attention(ax, B, st, h->force_xl)); }
+        if (maps) HIPCHK(h, emit_map(l, true));
         g = gemm_args(sc.att, r256, Lw.wproj_x, M, 256, 256, sc.xmid, r256);
         g.resid = sc.xmid; g.C2 = sc.xn; g.gamma = Lw.ln_ffn_g; g.beta = Lw.ln_ffn_b;
         HIPCHK(h, gemm(h, g, EPI_RESID_LN, st, /*bounded_A=*/false));
@@ -1322,6 +1343,11 @@ int vapx_encode_audio(vapx_handle h, int32_t n, const int32_t* stream_ids, const
 
 int vapx_transformer(vapx_handle h, int32_t n, int32_t rows, const float* x, float* o, float* x12, float* comb,
                      int32_t stage, void* hip_stream) {
+  return vapx_transformer_maps(h, n, rows, x, o, x12, comb, stage, nullptr, nullptr, nullptr, hip_stream);
+}
+
+int vapx_transformer_maps(vapx_handle h, int32_t n, int32_t rows, const float* x, float* o, float* x12, float* comb,
+                          int32_t stage, float* attn, float* self_attn, float* cross_attn, void* hip_stream) {
   if (!h) return VAPX_E_INVAL;
   if (n < 1 || n > h->cfg.max_batch) return fail(h, VAPX_E_RANGE, "n=%d outside [1,%d]", n, h->cfg.max_batch);
   if (rows < 1 || rows > h->T) return fail(h, VAPX_E_RANGE, "rows=%d outside [1,%d]", rows, h->T);
@@ -1329,6 +1355,8 @@ int vapx_transformer(vapx_handle h, int32_t n, int32_t rows, const float* x, flo
   if (stage < 0 || stage > 2) return fail(h, VAPX_E_INVAL, "stage must be 0 (all), 1 (ar_channel) or 2 (ar)");
   if (stage == 1 && (x12 || comb)) return fail(h, VAPX_E_INVAL, "stage 1 produces only o");
   if (stage == 2 && o) return fail(h, VAPX_E_INVAL, "stage 2 does not produce o");
+  if (stage == 2 && attn) return fail(h, VAPX_E_INVAL, "stage 2 does not run ar_channel: no attn map");
+  if (stage == 1 && (self_attn || cross_attn)) return fail(h, VAPX_E_INVAL, "stage 1 does not run ar: no self_attn / cross_attn maps");
   hipStream_t st = (hipStream_t)hip_stream;
   (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -1342,7 +1370,9 @@ int vapx_transformer(vapx_handle h, int32_t n, int32_t rows, const float* x, flo
   ga.x0 = h->sc.xl[l_begin]; ga.xn = h->sc.xn; ga.gamma = h->layer[l_begin].ln_self_g; ga.beta = h->layer[l_begin].ln_self_b;
   ga.B = n; ga.T = T; ga.rows_in = rows;
   { ProfScope ps(h, CLS_GATHER, st); HIPCHK(h, launch_gather_ln(ga, st)); }
-  int rc = run_layers(h, h->sc, n, st, l_begin, l_end);
+  const MapOut maps{attn, self_attn, cross_attn, rows};
+  const bool want_maps = attn || self_attn || cross_attn;
+  int rc = run_layers(h, h->sc, n, st, l_begin, l_end, false, false, nullptr, want_maps ? &maps : nullptr);
   if (rc) return rc;
   const long nro = (long)n * 2 * rows;
   const unsigned cgrid = (unsigned)((nro * 64 + 255) / 256);

@@ -69,6 +69,16 @@ struct AttnArgs {
 #endif
 };
 
+struct AttnMapArgs {    // attention_map.hip: the attention WEIGHTS of one attention launch (diagnostic path, vapx_transformer_maps)
+  const float* q;       // as AttnArgs: row (bc*T + i), stride ldq, head h at column h*64 (chronological buffers only)
+  const float* k;       // rows of channel (bc ^ swap_kv), stride ldkv
+  const int* bn;
+  int T, ldq, ldkv, swap_kv;
+  float* dst;           // map of (stream b, channel c, head h) at dst + (2b + c) * dst_slab + h * dst_head, rows of dst_ld floats
+  long dst_slab, dst_head;
+  int dst_ld;
+};
+
 struct AttnProjArgs {   // attention_proj_f16x3.hip: long-window self-attention with the Q|K|V projection inside (split path, layers >= 1)
   const float* xn;      // [B*2*T][256] LayerNorm(ln_self_attn)(x) rows of the layer (the previous layer's FFN block wrote them)
   const float* wqkvp;   // the layer's per-head weight stream (weights.frag_pack_f16x3_qkv_heads)
@@ -116,6 +126,7 @@ hipError_t launch_gather_ln(const GatherArgs& a, hipStream_t st);
 hipError_t launch_attention(const AttnArgs& a, int B, hipStream_t st, bool force_xl);   // force_xl: attention_xl_kernel for any T (tests)
 hipError_t launch_attention_f16x3(const AttnArgs& a, int B, hipStream_t st);   // split-precision variant (attention_f16x3.hip), same arguments
 hipError_t launch_attention_proj_f16x3(const AttnProjArgs& a, int B, hipStream_t st);   // split path, layers >= 1: Q|K|V projected inside (attention_proj_f16x3.hip)
+hipError_t launch_attention_map(const AttnMapArgs& a, int B, hipStream_t st);   // softmax(Q.K^T / 16 + ALiBi, causal) itself (attention_map.hip)
 hipError_t launch_gather_last_ln(const LastRowArgs& a, hipStream_t st);
 hipError_t launch_ln_rows(const float* x, float* y, const float* gamma, const float* beta, int rows, hipStream_t st);
 hipError_t launch_attention_last(const AttnArgs& a, int B, hipStream_t st);

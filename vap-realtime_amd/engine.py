@@ -26,7 +26,7 @@ MODE = {"vap": 0, "bc": 1, "nod": 2}
 
 EXPORTS = ("vapx_abi_version", "vapx_blob_floats", "vapx_create", "vapx_destroy", "vapx_step",
            "vapx_attach_trunk", "vapx_join", "vapx_reset_stream", "vapx_get_state", "vapx_set_state", "vapx_encode_audio",
-           "vapx_transformer", "vapx_peek", "vapx_gemm", "vapx_last_error", "vapx_profile_enable",
+           "vapx_transformer", "vapx_transformer_maps", "vapx_peek", "vapx_gemm", "vapx_last_error", "vapx_profile_enable",
            "vapx_profile_read", "vapx_bad_slots", "vapx_host_alloc", "vapx_host_free", "vapx_reset_carry", "vapx_get_config",
            "vapx_ingest_open", "vapx_ingest_open_fn", "vapx_ingest_ports", "vapx_ingest_stats_read", "vapx_ingest_late_read", "vapx_ingest_close",
            "vapx_wire_decode_input", "vapx_wire_encode_result", "vapx_vap_head", "vapx_va_classifier", "vapx_softmax256",
@@ -88,6 +88,8 @@ def load_library(path: Optional[str] = None):
     lib.vapx_encode_audio.argtypes = [vp, i32, i32p, f32p, f32p, vp]
     lib.vapx_transformer.restype = i32
     lib.vapx_transformer.argtypes = [vp, i32, i32, f32p, f32p, f32p, f32p, i32, vp]
+    lib.vapx_transformer_maps.restype = i32
+    lib.vapx_transformer_maps.argtypes = [vp, i32, i32, f32p, f32p, f32p, f32p, i32, f32p, f32p, f32p, vp]
     lib.vapx_peek.restype = C.c_int64
     lib.vapx_peek.argtypes = [vp, C.c_char_p, f32p, C.c_size_t]
     lib.vapx_gemm.restype = i32
@@ -343,6 +345,14 @@ class Engine:
                            stage: int = 0, stream: int = 0):
         self._check(self.lib.vapx_transformer(self._h, n, rows, x_ptr, o_ptr or None, x12_ptr or None, comb_ptr or None,
                                               stage, stream or None), "vapx_transformer")
+
+    def transformer_maps_device(self, n: int, rows: int, x_ptr: int, o_ptr: int = 0, x12_ptr: int = 0, comb_ptr: int = 0,
+                                stage: int = 0, attn_ptr: int = 0, self_attn_ptr: int = 0, cross_attn_ptr: int = 0, stream: int = 0):
+        """``transformer_device`` plus the attention weights (vapx.h, vapx_transformer_maps): ``attn`` [n,2,1,4,rows,rows],
+        ``self_attn`` / ``cross_attn`` [n,2,3,4,rows,rows], device pointers, 0 = not wanted."""
+        self._check(self.lib.vapx_transformer_maps(self._h, n, rows, x_ptr, o_ptr or None, x12_ptr or None, comb_ptr or None, stage,
+                                                   attn_ptr or None, self_attn_ptr or None, cross_attn_ptr or None, stream or None),
+                    "vapx_transformer_maps")
 
 
 class TrunkGroup:

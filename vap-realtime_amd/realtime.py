@@ -613,7 +613,7 @@ class VapGPT:
         no input is computed twice."""
         torch = self._torch
         if attention:
-            raise NotImplementedError("attention maps are never materialised by the fused attention block")
+            raise NotImplementedError("the fused attention block never materialises attention maps; call ar_channel_with_attention(x)")
         B, n, _ = x.shape
         x = x.to(self.device).float()
         if B % 2:
@@ -628,7 +628,7 @@ class VapGPT:
         """GPTStereo.forward (3 self+cross layers + Combinator) (vap_main.py:287)."""
         torch = self._torch
         if attention:
-            raise NotImplementedError("attention maps are never materialised by the fused attention block")
+            raise NotImplementedError("the fused attention block never materialises attention maps; call ar_with_attention(x1, x2)")
         B, n, _ = x1.shape
         xin = torch.stack([x1, x2], dim=1).to(self.device).float().contiguous()
         x12 = torch.empty(B, 2, n, 256, device=self.device)
@@ -636,6 +636,38 @@ class VapGPT:
         self._engine_for(B, n).transformer_device(B, n, xin.data_ptr(), x12_ptr=x12.data_ptr(), comb_ptr=comb.data_ptr(), stage=2,
                                        stream=self._stream())
         return {"x": comb, "x1": x12[:, 0].contiguous(), "x2": x12[:, 1].contiguous()}
+
+    def ar_channel_with_attention(self, x):
+        """``GPT.forward(x, attention=True)`` (modules.py:356-372): ``{"x": [B,n,256], "attn": [B,1,4,n,n]}``.  The same
+        pairing of inputs onto (stream, channel) slots as ``ar_channel``; the maps come from a kernel of their own next to
+        the fused attention block (csrc/attention_map.hip), ``x`` is bit-identical to ``ar_channel(x)["x"]``."""
+        torch = self._torch
+        B, n, _ = x.shape
+        x = x.to(self.device).float()
+        if B % 2:
+            x = torch.cat([x, x[-1:]], dim=0)                         # odd batch: one padding row
+        P = x.shape[0] // 2
+        xin = x.reshape(P, 2, n, 256).contiguous()
+        o = torch.empty(P, 2, n, 256, device=self.device)
+        attn = torch.empty(P, 2, 1, 4, n, n, device=self.device)
+        self._engine_for(P, n).transformer_maps_device(P, n, xin.data_ptr(), o_ptr=o.data_ptr(), stage=1, attn_ptr=attn.data_ptr(),
+                                                       stream=self._stream())
+        return {"x": o.reshape(2 * P, n, 256)[:B].contiguous(), "attn": attn.reshape(2 * P, 1, 4, n, n)[:B].contiguous()}
+
+    def ar_with_attention(self, x1, x2):
+        """``GPTStereo.forward(x1, x2, attention=True)`` (modules.py:395-423): ``ar``'s dictionary plus ``"self_attn"`` and
+        ``"cross_attn"``, each [B,2,3,4,n,n] (channel, layer, head, query row, key)."""
+        torch = self._torch
+        B, n, _ = x1.shape
+        xin = torch.stack([x1, x2], dim=1).to(self.device).float().contiguous()
+        x12 = torch.empty(B, 2, n, 256, device=self.device)
+        comb = torch.empty(B, n, 256, device=self.device)
+        self_attn = torch.empty(B, 2, 3, 4, n, n, device=self.device)
+        cross_attn = torch.empty(B, 2, 3, 4, n, n, device=self.device)
+        self._engine_for(B, n).transformer_maps_device(B, n, xin.data_ptr(), x12_ptr=x12.data_ptr(), comb_ptr=comb.data_ptr(), stage=2,
+                                                       self_attn_ptr=self_attn.data_ptr(), cross_attn_ptr=cross_attn.data_ptr(),
+                                                       stream=self._stream())
+        return {"x": comb, "x1": x12[:, 0].contiguous(), "x2": x12[:, 1].contiguous(), "self_attn": self_attn, "cross_attn": cross_attn}
 
     def forward(self, waveform, attention: bool = False, lang_info: list = None):
         """The training module's call signature (train/model.py:292-319): ``waveform [B,2,N] -> {"logits": [B,n,256],
@@ -645,7 +677,8 @@ class VapGPT:
         runs through the whole call and starts from zero, VAD reads the ar_channel output (vap_main.py:292-293).
         n = N // hop.  Attention maps are not materialised by the fused kernels."""
         if attention:
-            raise NotImplementedError("attention maps are never materialised by the fused attention block")
+            raise NotImplementedError("the fused attention block never materialises attention maps; call ar_channel_with_attention(x) / "
+                                      "ar_with_attention(x1, x2) on explicit context tensors")
         torch = self._torch
         B, two, N = waveform.shape
         assert two == 2
