@@ -173,6 +173,38 @@ int vapx_join(vapx_handle h, void* hip_stream);
  * Destroy followers before their leader. */
 int vapx_attach_trunk(vapx_handle follower, vapx_handle leader);
 
+/* The whole trunk group in ONE call, answered with compact wire rows (multi-model serving: vap_main.py, vap_bc_main.py and
+ * vap_nod_main.py side by side on one cpc_model file).
+ *
+ * The wire row of a model is the head of its vapx_step output row — exactly what its result packet is built from (util.py:122-143 vap,
+ * :193-211 bc, :213-237 nod):
+ *   floats [0, 16)   p_now, p_future, vad, aux, n-valid, vad logits, status (VAPX_OUT_P_NOW .. VAPX_OUT_STATUS and two reserved floats)
+ *   nod only         the next T floats (VAPX_OUT_LOGITS + 0 .. T-1): p_bc of every window row (the quirk of vap_nod_main.py:276)
+ * vapx_wire_floats(mode, ctx_frames) is its length: 16 for vap and bc, 16 + T rounded up to a multiple of 4 for nod (rows stay 16-byte
+ * aligned; the padding floats are the output row's next floats); 0 for a bad mode / window.  A wire row being a prefix of an output
+ * row, vapx_wire_encode_result takes it unchanged.  vapx_group_wire_floats(leader) is the sum over the leader and its followers, per
+ * stream (0 for a follower).
+ *
+ * vapx_step_group(leader, ...) steps the leader, then every follower in attach order — all device-resident on hip_stream, the path
+ * vapx_step takes with VAPX_OUT_DEVICE — and gathers the wire rows with one kernel into one block, model-major:
+ *   wire_out [model m][n][wire_floats(m)], model m's rows starting at float n * (wire_floats(0) + .. + wire_floats(m-1));
+ *   model 0 is the leader, model i + 1 the i-th attached follower.
+ * stream_ids / audio / samples_per_ch as in vapx_step; flags: VAPX_AUDIO_* | VAPX_IDS_DEVICE | VAPX_OUT_*.  With VAPX_OUT_HOST the tick
+ * costs ONE linear device-to-host copy and ONE synchronisation (M host-output vapx_step calls copy M x n x 784 floats and synchronise M
+ * times; a bc packet needs 2 of those floats); vapx_host_alloc memory is written directly, pageable memory is staged.  With
+ * VAPX_OUT_DEVICE wire_out is device memory: no copy, no synchronisation.  VAPX_DEFER_JOIN is NOT honoured: the gather consumes every
+ * overlap group's rows.
+ * VAPX_E_NUMERIC (host output only) is per stream and per model as in vapx_step: the block is complete, the offending rows carry
+ * VAPX_OUT_STATUS = 1 in every model that produced non-finite values, and vapx_group_bad lists the (batch slot, model index) pairs
+ * (returns their number, writes at most max; either array may be NULL).  Reset such a stream on the leader.
+ * Refused with VAPX_E_INVAL: on a follower, and on a leader whose followers have not all consumed its latest plain vapx_step.
+ * vapx_peek, vapx_get_state / vapx_set_state and vapx_reset_stream behave after it as after the separate calls. */
+int32_t vapx_wire_floats(int32_t mode, int32_t ctx_frames);
+size_t vapx_group_wire_floats(vapx_handle leader);
+int vapx_step_group(vapx_handle leader, int32_t n, const int32_t* stream_ids, const float* audio, int32_t samples_per_ch,
+                    float* wire_out, int32_t flags, void* hip_stream);
+int32_t vapx_group_bad(vapx_handle leader, int32_t* slots, int32_t* models, int32_t max);
+
 /* Zero one stream's state (context ring fill, LSTM h/c, carry).  The reference never resets
  * model state on reconnect (vap_main.py:368-369 re-zeroes only the carry); this is the explicit
  * equivalent of constructing a fresh VAPRealTime for that stream.
@@ -346,6 +378,35 @@ typedef void (*vapx_ingest_reset_fn)(void* user, int32_t stream_id);
 int vapx_ingest_open_fn(vapx_ingest_step_fn step, vapx_ingest_reset_fn reset, void* user, int32_t n_streams, int32_t max_batch,
                         int32_t frame_hz, int32_t mode, const vapx_ingest_config* cfg, vapx_ingest_handle* out);
 int vapx_ingest_ports(vapx_ingest_handle g, int32_t* port_in, int32_t* port_out);   /* (0, 0) for a passive shard */
+/* One front-end for a trunk group (vapx_attach_trunk): the reference's deployment of vap_main.py, vap_bc_main.py and vap_nod_main.py
+ * side by side on one cpc_model file, with ONE input port and the audio encoded once.
+ *   - input: cfg->port_in; every accepted connection is a dialogue exactly as with vapx_ingest_open (lowest free slot, carry re-zeroed,
+ *     reset_on_connect, gain, overrun pause);
+ *   - output: one port per model — the leader's is cfg->port_out, follower i's is follower_ports_out[i] (0 = ephemeral; NULL = all
+ *     ephemeral).  A connection on model m's port hears model m's packets only, in that model's framing (vap util.py:122-143, bc
+ *     :193-211, nod :213-237 with p_bc of every window row); fewest-listeners / lowest-slot placement and broadcast hold per port;
+ *   - a tick is one vapx_step_group (host in, host out, page-locked wire block); batching, max_wait_us, pacing and min_batch are
+ *     unchanged, and a stream's packets leave through one sender thread, so they stay in frame order on every port;
+ *   - a stream with a non-zero status in ANY model is reset through the leader (which resets the followers) and gets no packet on any
+ *     port that tick; numeric_resets counts it once;
+ *   - stats: frames_done counts stream-frames (not packets), the latency of a stream-frame is taken once, after the LAST model's packets
+ *     were handed to the kernel; tx_bytes, out_connections and dropped_listeners sum over the ports.
+ * `followers` must be the leader's attached followers in attach order (modes pairwise distinct).  A group cannot be a passive shard:
+ * port_in = -1 is refused (VAPX_E_INVAL, message in vapx_ingest_last_open_error); the front door stays single-model.
+ * vapx_ingest_group_ports: the input port and up to max_ports output ports in model order; returns the number of models.
+ * vapx_ingest_ports reports the leader's output port. */
+int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int32_t n_followers, const vapx_ingest_config* cfg,
+                           const int32_t* follower_ports_out, vapx_ingest_handle* out);
+int vapx_ingest_group_ports(vapx_ingest_handle g, int32_t* port_in, int32_t* ports_out, int32_t max_ports);
+/* The same over a caller-supplied step function (host-logic tests without a GPU): step(user, n, stream_ids, audio[n][2][hop], wire_out)
+ * fills wire_out in the layout of vapx_step_group for that tick's n and modes[0 .. n_models); ctx_frames sizes nod's wire rows. .
+ * vapx_ingest_last_open_error: why the calling thread's latest vapx_ingest_open_group* call was refused ("" if it was not). */
+typedef int (*vapx_ingest_group_step_fn)(void* user, int32_t n, const int32_t* stream_ids, const float* audio,
+                                         float* wire_out /* layout of vapx_step_group */);
+int vapx_ingest_open_group_fn(vapx_ingest_group_step_fn step, vapx_ingest_reset_fn reset, void* user, int32_t n_streams, int32_t max_batch,
+                              int32_t frame_hz, int32_t ctx_frames, const int32_t* modes, int32_t n_models, const vapx_ingest_config* cfg,
+                              const int32_t* follower_ports_out, vapx_ingest_handle* out);
+const char* vapx_ingest_last_open_error(void);
 int vapx_ingest_stats_read(vapx_ingest_handle g, vapx_ingest_stats* out, int32_t reset_latency_window);
 /* Exact server-side count of late answers in the current latency window (since the last stats_read(.., 1)): result packets handed to the
  * kernel more than 10 ms after their frame was complete on the host — the north-star bound — and the packets of the window. */

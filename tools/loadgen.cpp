@@ -14,6 +14,9 @@
 //   --procs P --rank r --sync-dir D    P processes, rank r plays dialogues r, r + P, ... of --total-streams (phases spread over the GLOBAL
 //                     population); all dial their inputs, meet (files in D), dial their outputs, meet, and start at a common CLOCK_MONOTONIC time
 //   --src-ips N       dial from 127.0.0.2 .. 127.0.0.(1+N) in turn (one (src ip, dst ip, dst port) triple has ~28 k ephemeral ports)
+//   --ports-out a,b,...   a server that serves several models on one shared trunk (serve --mode a+b[+c]) has one output port per model: every
+//                     dialogue opens one listener per port; a frame counts as answered when EVERY port has answered it and its latency is that
+//                     of the last packet.  With a single port this is --port-out.  (Not with --inband: one process, sender-side stamps.)
 //   --hist-out F      latency histogram (50 us bins up to 400 ms) as JSON, for merging the processes' percentiles
 // Build: make -C vap-realtime_amd/csrc loadgen   (plain C++17, no dependencies)
 #include <arpa/inet.h>
@@ -78,10 +81,12 @@ static int dial(const char* host, int port) {
 }
 
 struct Stream {
-  int fd_in = -1, fd_out = -1;
+  int fd_in = -1;
+  std::vector<int> fd_out;          // one listener per output port (--ports-out)
+  std::vector<std::vector<uint8_t>> rbufs;
+  std::vector<long> got;            // result packets read per port; frame k is answered when every port has delivered k + 1 of them
   std::mutex mu;
   std::deque<double> sent;          // send-completion time of each frame not yet answered
-  std::vector<uint8_t> rbuf;
   long answered = 0, frames = 0;
   int heard = -1;                   // --inband: the dialogue this output socket hears (must never change)
   double t_first_sent = 0, t_first_answer = 0;
@@ -89,7 +94,8 @@ struct Stream {
 
 int main(int argc, char** argv) {
   const char* host = "127.0.0.1";
-  int port_in = 50007, port_out = 50008, S = 256, hz = 20, packet_ms = 10, threads = 4;
+  std::vector<int> ports_out{50008};
+  int port_in = 50007, S = 256, hz = 20, packet_ms = 10, threads = 4;
   double seconds = 10.0, late_ms = 10.0, warm = 3.0;
   int inband = 0, procs = 1, rank = 0, total_streams = 0;
   const char* sync_dir = nullptr;
@@ -99,7 +105,11 @@ int main(int argc, char** argv) {
     const char* v = argv[i + 1];
     if (k == "--host") host = v;
     else if (k == "--port-in") port_in = atoi(v);
-    else if (k == "--port-out") port_out = atoi(v);
+    else if (k == "--port-out") ports_out.assign(1, atoi(v));
+    else if (k == "--ports-out") {
+      ports_out.clear();
+      for (const char* q = v; *q;) { ports_out.push_back(atoi(q)); q = strchr(q, ','); if (!q) break; ++q; }
+    }
     else if (k == "--streams") S = atoi(v);
     else if (k == "--hz") hz = atoi(v);
     else if (k == "--seconds") seconds = atof(v);
@@ -117,6 +127,8 @@ int main(int argc, char** argv) {
     else { fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
   }
   if (total_streams <= 0) total_streams = S * procs;
+  const int P = (int)ports_out.size();
+  if (P < 1 || (P > 1 && inband)) { fprintf(stderr, "--ports-out takes one or more ports; several ports do not combine with --inband\n"); return 2; }
   if (procs > 1 && (!sync_dir || !inband)) { fprintf(stderr, "--procs > 1 needs --sync-dir and --inband 1\n"); return 2; }
   // meet the other loadgen processes: touch <dir>/<tag>.<rank>, wait until every rank's file is there
   auto meet = [&](const char* tag) {
@@ -143,7 +155,7 @@ int main(int argc, char** argv) {
   }
   {   // two sockets per stream: raise the soft descriptor limit if it is short
     rlimit rl;
-    const rlim_t need = (rlim_t)2 * S + 256;
+    const rlim_t need = (rlim_t)(1 + P) * S + 256;
     if (getrlimit(RLIMIT_NOFILE, &rl) == 0 && rl.rlim_cur < need) {
       rl.rlim_cur = rl.rlim_max == RLIM_INFINITY ? need : std::min<rlim_t>(rl.rlim_max, need);
       setrlimit(RLIMIT_NOFILE, &rl);
@@ -158,7 +170,11 @@ int main(int argc, char** argv) {
   meet("inputs");
 
   const double td2 = now_s();
-  for (int i = 0; i < S; ++i) st[i].fd_out = dial(host, port_out);
+  for (int p = 0; p < P; ++p) {                      // port by port: on every port the k-th connection hears the k-th dialogue
+    for (int i = 0; i < S; ++i) st[i].fd_out.push_back(dial(host, ports_out[p]));
+    if (p + 1 < P) usleep((useconds_t)(300000 + 100 * S));
+  }
+  for (auto& s : st) { s.rbufs.resize(P); s.got.assign(P, 0); }
   const double td3 = now_s();
   usleep((useconds_t)(300000 + 100 * S));
   meet("outputs");
@@ -256,8 +272,10 @@ int main(int argc, char** argv) {
       epoll_event ev;
       memset(&ev, 0, sizeof ev);
       ev.events = EPOLLIN;
-      ev.data.u32 = (uint32_t)i;
-      epoll_ctl(ep, EPOLL_CTL_ADD, st[i].fd_out, &ev);
+      for (int p = 0; p < P; ++p) {                  // every port of a dialogue on the same thread: its counters need no lock
+        ev.data.u64 = (uint64_t)(uint32_t)i | ((uint64_t)p << 32);
+        epoll_ctl(ep, EPOLL_CTL_ADD, st[i].fd_out[p], &ev);
+      }
     }
     std::vector<uint8_t> buf(1 << 18);
     epoll_event evs[128];
@@ -266,21 +284,27 @@ int main(int argc, char** argv) {
       int n = epoll_wait(ep, evs, 128, 50);
       if (n > 0 && t_busy > 0.0) amax(max_recv_gap_us, (long)((now_s() - t_busy) * 1e6));
       for (int k = 0; k < n; ++k) {
-        Stream& s = st[evs[k].data.u32];
-        ssize_t r = recv(s.fd_out, buf.data(), buf.size(), MSG_DONTWAIT);
+        const int si = (int)(evs[k].data.u64 & 0xffffffffu), port = (int)(evs[k].data.u64 >> 32);
+        Stream& s = st[si];
+        std::vector<uint8_t>& rbuf = s.rbufs[port];
+        ssize_t r = recv(s.fd_out[port], buf.data(), buf.size(), MSG_DONTWAIT);
         if (r <= 0) continue;
         const double t = now_s();
-        s.rbuf.insert(s.rbuf.end(), buf.begin(), buf.begin() + r);
+        rbuf.insert(rbuf.end(), buf.begin(), buf.begin() + r);
         size_t off = 0;
-        while (s.rbuf.size() - off >= 4) {
+        while (rbuf.size() - off >= 4) {
           uint32_t len;
-          memcpy(&len, s.rbuf.data() + off, 4);
-          if (s.rbuf.size() - off < 4 + (size_t)len) break;
+          memcpy(&len, rbuf.data() + off, 4);
+          if (rbuf.size() - off < 4 + (size_t)len) break;
+          if (P > 1) {   // answered only when the LAST port's packet of the frame is in: this packet completes a frame iff its port was the one behind
+            ++s.got[port];
+            if (*std::min_element(s.got.begin(), s.got.end()) <= s.answered) { off += 4 + len; continue; }
+          }
           double t_sent = 0;
           if (inband) {   // payload: f64 t | u32 n | x1[n] | u32 n | x2[n] | ...; the stamps sit at sample k0 = hop - pk_samples of x1 / x2
             const size_t k0 = (size_t)(hop - pk_samples), o1 = off + 4 + 8 + 4 + 8 * k0, o2 = off + 4 + 8 + 4 + 8 * (size_t)hop + 4 + 8 * k0;
             double v1 = 0, v2 = 0;
-            if (len >= 8 + 4 + 8 * (size_t)hop + 4 + 8 * (size_t)hop) { memcpy(&v1, s.rbuf.data() + o1, 8); memcpy(&v2, s.rbuf.data() + o2, 8); }
+            if (len >= 8 + 4 + 8 * (size_t)hop + 4 + 8 * (size_t)hop) { memcpy(&v1, rbuf.data() + o1, 8); memcpy(&v2, rbuf.data() + o2, 8); }
             const long id = lround(v2 * 1073741824.0) - 1;
             if (id < 0 || v1 <= 0) inband_bad.fetch_add(1);
             else {
@@ -302,10 +326,10 @@ int main(int argc, char** argv) {
             if (ms > late_ms) late.fetch_add(1);
             std::lock_guard<std::mutex> lk(lat_mu);
             lats.push_back((float)ms);
-            if (ms > 50.0 && stalls.size() < 4096) stalls.push_back({t - t_measure, (int)evs[k].data.u32, (float)ms});
+            if (ms > 50.0 && stalls.size() < 4096) stalls.push_back({t - t_measure, si, (float)ms});
           }
         }
-        if (off) s.rbuf.erase(s.rbuf.begin(), s.rbuf.begin() + off);
+        if (off) rbuf.erase(rbuf.begin(), rbuf.begin() + off);
       }
       t_busy = n > 0 ? now_s() : 0.0;
     }
@@ -363,12 +387,13 @@ int main(int argc, char** argv) {
     printf("\"streams_with_unanswered_frames\": %s], ", u.c_str());
   }
   printf("\"inband\": %d, \"procs\": %d, \"rank\": %d, \"route_changes\": %ld, \"inband_unreadable\": %ld, ", inband, procs, rank, route_changes.load(), inband_bad.load());
+  printf("\"output_ports\": %d, ", P);
   printf("\"streams\": %d, \"frame_hz\": %d, \"packet_ms\": %d, \"seconds_measured\": %.1f, \"frames_sent\": %ld, \"frames_answered\": %ld, "
          "\"unanswered_at_end\": %ld, \"latency_samples\": %zu, \"lat_p50_ms\": %.3f, \"lat_p99_ms\": %.3f, \"lat_p999_ms\": %.3f, \"lat_max_ms\": %.3f, "
          "\"late_over_%.0fms\": %ld, \"schedule_slips\": %ld, \"client_max_send_lag_ms\": %.2f, \"client_max_send_call_ms\": %.2f, \"client_max_recv_pass_ms\": %.2f, \"stream_frames_per_s\": %.1f}\n",
          S, hz, packet_ms, seconds, frames_sent.load(), frames_answered.load(), unanswered, lats.size(), pct(0.50), pct(0.99), pct(0.999),
          lats.empty() ? 0.0 : (double)lats.back(), late_ms, late.load(), slipped.load(), max_send_lag_us.load() * 1e-3, max_send_call_us.load() * 1e-3,
          max_recv_gap_us.load() * 1e-3, lats.size() / seconds);
-  for (auto& s : st) { close(s.fd_in); close(s.fd_out); }
+  for (auto& s : st) { close(s.fd_in); for (int fd : s.fd_out) close(fd); }
   return 0;
 }

@@ -152,7 +152,8 @@ def main():
                     "--streams / N slots each: what `python -m vap_realtime_amd.serve --gpus N --share-gpu` runs")
     ap.add_argument("--devices", default="", help="with --shards N: comma list of N device ids, one engine per listed GPU (default: all on device 0)")
     ap.add_argument("--split-f16", action="store_true", help="engines on the opt-in split-precision path (serve --precision split)")
-    ap.add_argument("--mode", default="vap", choices=["vap", "bc", "nod"])
+    ap.add_argument("--mode", default="vap", help="vap, bc or nod; a+b[+c] (e.g. bc+nod): several models on one shared CPC trunk behind the group "
+                    "front-end (vapx_ingest_open_group), one output port per model, the load generator listens on all of them")
     ap.add_argument("--fake", action="store_true", help="native front-end over a trivial step function (plumbing only, no GPU)")
     ap.add_argument("--standin", action="store_true", help="native front-end(s) over the native stand-in for the GPU tick (no GPU, no Python on the tick thread); "
                     "with --shards N: N passive front-ends behind ONE front door")
@@ -297,6 +298,19 @@ def main():
                                                 min_batch=args.min_batch, rx_threads=args.rx_threads, tx_threads=args.tx_threads)
         cores = client_cores = None                       # (over_function has no placement argument)
         kind = "native front-end over a trivial step function"
+    elif "+" in args.mode:
+        from vap_realtime_amd import weights as W
+        names = args.mode.split("+")
+        assert len(set(names)) == len(names) and all(m in ("vap", "bc", "nod") for m in names), "--mode a+b[+c]: distinct names from vap, bc, nod"
+        assert args.shards == 1 and not args.python and not args.inband and args.loadgen_procs <= 1, \
+            "a + mode is served by one group front-end: no --shards, --python, --inband or --loadgen-procs"
+        blobs = {m: W.pack_blob(*W.synthetic_weights(0, args.hz, m), m) for m in names}      # one seed: the same CPC tensors in every model
+        grp = engine.TrunkGroup(blobs, args.hz, args.ctx_sec, max_streams=S, max_batch=args.max_batch or None, groups=args.groups,
+                                split_f16=args.split_f16)
+        srv = ingest.NativeServer.for_group(grp, port_in=0, ports_out=[0] * len(names), max_wait_s=args.max_wait_ms * 1e-3, min_batch=args.min_batch,
+                                            rx_threads=args.rx_threads, tx_threads=args.tx_threads, target_util=args.target_util, cores=cores,
+                                            core_set=(args.pin_mode == "set"))
+        kind = f"group front-end (vapx_ingest_open_group) + {'+'.join(names)} on one CPC trunk (vapx_step_group)"
     else:
         from vap_realtime_amd import realtime, weights as W
         cpc, vap_sd = W.synthetic_weights(0, args.hz, args.mode)
@@ -351,7 +365,9 @@ def main():
     sync_dir = tempfile.mkdtemp(prefix="loadgen_sync_")
 
     def cmd_for(r):
-        c = [loadgen, "--port-in", str(srv.port_in), "--port-out", str(srv.port_out), "--streams", str(per_proc[r]), "--hz", str(args.hz),
+        ports = getattr(srv, "ports_out", None)         # a group front-end: one output port per model
+        c = [loadgen, "--port-in", str(srv.port_in)] + (["--ports-out", ",".join(str(p) for p in ports.values())] if ports else
+                                                        ["--port-out", str(srv.port_out)]) + ["--streams", str(per_proc[r]), "--hz", str(args.hz),
              "--seconds", str(args.seconds), "--warm", str(args.warm), "--packet-ms", str(args.packet_ms), "--threads", str(args.client_threads)]
         if inband:
             c += ["--inband", "1", "--hist-out", os.path.join(sync_dir, f"hist.{r}.json")]

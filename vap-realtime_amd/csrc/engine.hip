@@ -124,6 +124,10 @@ struct vapx_engine {
   bool orphaned = false;                  // follower whose leader was destroyed
   uint64_t tick = 0, followed_tick = 0;
   const int* last_ids = nullptr;          // device ids of the latest step (null = identity)
+  // vapx_step_group (leader only): the tick's wire rows, model-major, on the device and in page-locked host memory
+  float *gw_dev = nullptr, *gw_pinned = nullptr;
+  size_t gw_cap = 0;                      // floats either block holds
+  std::vector<std::pair<int32_t, int32_t>> group_bad;   // (batch slot, model index) pairs of the latest host-output vapx_step_group
 
   // optional per-kernel-class HIP-event timing (vapx_profile_*): events are recorded on the launch
   // stream around the launches whose class bit is set in prof_mask
@@ -858,6 +862,8 @@ void vapx_destroy(vapx_handle h) {
   for (float* p : fp) dfree(p);
   int* ip[] = {h->frames_seen, h->ids_dev, h->sc.bn, h->sc.bhead, h->sc.rot};
   for (int* p : ip) dfree(p);
+  dfree(h->gw_dev);
+  if (h->gw_pinned) (void)hipHostFree(h->gw_pinned);
   if (h->out_pinned) (void)hipHostFree(h->out_pinned);
   if (h->ids_pinned) (void)hipHostFree(h->ids_pinned);
   if (h->audio_pinned) (void)hipHostFree(h->audio_pinned);
@@ -1165,6 +1171,98 @@ int32_t vapx_bad_slots(vapx_handle h, int32_t* slots, int32_t max_slots) {
   if (!h) return VAPX_E_INVAL;
   const int32_t n = (int32_t)h->bad_slots.size();
   for (int32_t i = 0; i < n && i < max_slots && slots; ++i) slots[i] = h->bad_slots[i];
+  return n;
+}
+
+size_t vapx_group_wire_floats(vapx_handle h) {
+  if (!h || h->trunk || h->orphaned) return 0;
+  size_t per = (size_t)vapx_wire_floats(h->cfg.mode, h->T);
+  for (vapx_engine* f : h->followers) per += (size_t)vapx_wire_floats(f->cfg.mode, f->T);
+  return per;
+}
+
+int vapx_step_group(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* audio, int32_t spc, float* wire_out,
+                    int32_t flags, void* hip_stream) {
+  if (!h) return VAPX_E_INVAL;
+  if (h->trunk || h->orphaned) return fail(h, VAPX_E_INVAL, "vapx_step_group takes the trunk leader; this engine is a follower");
+  if (n < 1 || n > h->cfg.max_batch) return fail(h, VAPX_E_RANGE, "n=%d outside [1,%d]", n, h->cfg.max_batch);
+  if (!wire_out) return fail(h, VAPX_E_INVAL, "null wire_out");
+  for (size_t i = 0; i < h->followers.size(); ++i)
+    if (h->followers[i]->followed_tick != h->tick)
+      return fail(h, VAPX_E_INVAL, "follower %zu has not consumed the leader's latest vapx_step yet: step it first (or step the whole group "
+                  "with vapx_step_group every tick)", i);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const bool to_host = !(flags & VAPX_OUT_DEVICE);
+  const size_t per = vapx_group_wire_floats(h);
+  (void)hipGetLastError();
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (to_host && h->gw_cap < per * (size_t)h->cfg.max_batch) {   // first group step (the follower set is fixed once anyone has stepped)
+    dfree(h->gw_dev); h->gw_dev = nullptr;
+    if (h->gw_pinned) (void)hipHostFree(h->gw_pinned);
+    h->gw_pinned = nullptr; h->gw_cap = 0;
+    HIPCHK(h, dalloc(&h->gw_dev, per * (size_t)h->cfg.max_batch));
+    HIPCHK(h, hipHostMalloc((void**)&h->gw_pinned, per * (size_t)h->cfg.max_batch * sizeof(float), hipHostMallocDefault));
+    h->gw_cap = per * (size_t)h->cfg.max_batch;
+  }
+  // every model device-resident, on the one stream: exactly the vapx_step(.., VAPX_OUT_DEVICE, ..) path (VAPX_DEFER_JOIN is dropped:
+  // the pack kernel below consumes every overlap group's rows)
+  int rc = vapx_step(h, n, stream_ids, audio, spc, h->out_dev, (flags & (VAPX_AUDIO_DEVICE | VAPX_IDS_DEVICE)) | VAPX_OUT_DEVICE, hip_stream);
+  if (rc) return rc;
+  for (size_t i = 0; i < h->followers.size(); ++i) {
+    vapx_engine* f = h->followers[i];
+    rc = vapx_step(f, n, nullptr, nullptr, 0, f->out_dev, VAPX_OUT_DEVICE, hip_stream);
+    if (rc) return fail(h, rc, "follower %zu: %s", i, f->err.c_str());
+  }
+  float* wd = to_host ? h->gw_dev : wire_out;
+  const int M = 1 + (int)h->followers.size();
+  std::vector<int> wf(M);
+  std::vector<size_t> off(M);
+  size_t acc = 0;
+  for (int m = 0; m < M; ++m) {
+    const vapx_engine* e = m ? h->followers[m - 1] : h;
+    wf[m] = vapx_wire_floats(e->cfg.mode, e->T);
+    off[m] = (size_t)n * acc;
+    acc += (size_t)wf[m];
+  }
+  for (int m0 = 0; m0 < M; m0 += 4) {   // one launch for up to four models
+    WirePackArgs a;
+    memset(&a, 0, sizeof a);
+    a.dst = wd; a.n = n; a.src_stride = VAPX_OUT_STRIDE; a.n_models = std::min(4, M - m0);
+    for (int k = 0; k < a.n_models; ++k) {
+      a.src[k] = (m0 + k) ? h->followers[m0 + k - 1]->out_dev : h->out_dev;
+      a.dst_off[k] = (long)off[m0 + k];
+      a.wf4[k] = wf[m0 + k] / 4;
+    }
+    HIPCHK(h, launch_wire_pack(a, st));
+  }
+  h->group_bad.clear();
+  if (!to_host) return VAPX_OK;
+  const size_t bytes = (size_t)n * per * sizeof(float);
+  const bool direct = is_pinned_host(wire_out);   // vapx_host_alloc memory: the one D2H copy of the tick lands in the caller's block
+  HIPCHK(h, hipMemcpyAsync(direct ? wire_out : h->gw_pinned, h->gw_dev, bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  if (!direct) memcpy(wire_out, h->gw_pinned, bytes);
+  // per stream and per model, as vapx_step: the block is complete, the offending rows carry VAPX_OUT_STATUS = 1
+  for (int m = 0; m < M; ++m) {
+    vapx_engine* e = m ? h->followers[m - 1] : h;
+    e->bad_slots.clear();
+    for (int i = 0; i < n; ++i)
+      if (wire_out[off[m] + (size_t)i * wf[m] + VAPX_OUT_STATUS] != 0.f) { e->bad_slots.push_back(i); h->group_bad.push_back({i, m}); }
+  }
+  if (!h->group_bad.empty())
+    return fail(h, VAPX_E_NUMERIC, "non-finite outputs for batch slot %d in model %d and %zu more (slot, model) pairs; the other rows are valid; "
+                "reset those streams on the leader (vapx_group_bad lists the pairs)", h->group_bad[0].first, h->group_bad[0].second,
+                h->group_bad.size() - 1);
+  return VAPX_OK;
+}
+
+int32_t vapx_group_bad(vapx_handle h, int32_t* slots, int32_t* models, int32_t max) {
+  if (!h) return VAPX_E_INVAL;
+  const int32_t n = (int32_t)h->group_bad.size();
+  for (int32_t i = 0; i < n && i < max; ++i) {
+    if (slots) slots[i] = h->group_bad[i].first;
+    if (models) models[i] = h->group_bad[i].second;
+  }
   return n;
 }
 

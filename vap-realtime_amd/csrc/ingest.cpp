@@ -44,9 +44,15 @@
 
 #include "../../include/vapx.h"
 
+// the engine's group entry points: weak here, so the front-end still links into a program that stubs only the single-model
+// engine calls (tests/native); vapx_ingest_open_group says so if they are missing
+#pragma weak vapx_step_group
+#pragma weak vapx_group_wire_floats
+
 namespace {
 
 constexpr int NBUF = 5;   // frame buffers per stream: filling + waiting + in flight + two of slack for a client that bursts after a stall
+constexpr int MAX_MODELS = 3;                 // output ports of one front-end: a trunk group serves up to vap + bc + nod
 constexpr int PAIR_BYTES = 16;                 // one sample of both channels: f64 ch1, f64 ch2 (util.py:52-62)
 enum BufState : int { B_FREE = 0, B_FILLING = 1, B_READY = 2, B_INFLIGHT = 3 };
 
@@ -89,7 +95,7 @@ int tail_bytes(int mode, int n_rows_pbc) {
 }
 
 // heads of one out row -> tail of the packet (after "u32 n | x2"); returns bytes written
-int encode_tail(int mode, const float* row, uint8_t* dst) {
+int encode_tail(int mode, const float* row, uint8_t* dst, int max_rows = 256) {
   uint8_t* p = dst;
   if (mode == VAPX_MODE_VAP) {            // u32 2 | p_now | u32 2 | p_future | u32 2 | vad   (util.py:134-141)
     for (int blk = 0; blk < 3; ++blk) {
@@ -104,7 +110,7 @@ int encode_tail(int mode, const float* row, uint8_t* dst) {
     // clamped to the tail buffer's 256 rows: a step function of vapx_ingest_open_fn that leaves the column unset must not
     // turn into an out-of-bounds write here (vapx_wire_encode_result validates the same range)
     int n = (int)row[VAPX_OUT_NVALID];
-    n = n < 0 ? 0 : (n > 256 ? 256 : n);
+    n = n < 0 ? 0 : (n > max_rows ? max_rows : n);   // (max_rows: a wire row holds ctx_frames of them, an output row 256)
     put_u32(p, (uint32_t)n);
     for (int i = 0; i < n; ++i) put_f64(p, (double)row[VAPX_OUT_LOGITS + i]);
     for (int k = 1; k <= 3; ++k) { put_u32(p, 1); put_f64(p, (double)row[VAPX_OUT_AUX + k]); }
@@ -154,7 +160,7 @@ struct Slot {
   int lowat = 0;                          // rx thread only: SO_RCVLOWAT currently set on fd_in (0 = the kernel default)
   std::atomic<bool> paused{false};        // written by the slot's rx / accept thread, read by whoever frees a buffer
   std::mutex lmu;                         // guards listeners
-  std::vector<int> listeners;
+  std::vector<int> listeners[MAX_MODELS]; // per output port (model); a single-model front-end uses [0] only
   // VAPX_INGEST_DEBUG bookkeeping (relaxed counters, printed at close): where do a stream's frames go?
   std::atomic<int64_t> dbg_ready{0}, dbg_sent{0}, dbg_nolistener{0};
   double dbg_t_first_ready = 0, dbg_t_attach = 0, dbg_t_first_sent = 0;
@@ -166,11 +172,23 @@ struct Ready { int slot; int buf; uint32_t gen; double t; };
 struct Job {                               // one tick's rows on their way out
   int n = 0;
   std::vector<Ready> rows;
-  float* out = nullptr;                    // [max_batch][VAPX_OUT_STRIDE] pinned
+  float* out = nullptr;                    // pinned; [max_batch][VAPX_OUT_STRIDE], or a trunk group's wire block [model][n][wire floats]
+  std::vector<uint8_t> bad;                // per row: some model's status is non-zero (no packet on any port)
   double t_unix = 0;
   std::vector<std::vector<int>> part;      // row indices per sender thread: slot % X — a stream is always sent by the same thread
   int senders_done = 0;                    // sender threads that are through with this job (under job_mu)
   bool busy = false;
+};
+
+// one output port: a model's listen socket, its framing and its listener placement (fewest listeners, lowest slot first)
+struct OutPort {
+  int mode = 0;
+  int wf = VAPX_OUT_STRIDE;                // floats per row of this model in a job's block
+  size_t off = 0;                          // floats per stream in front of this model's rows (the block is model-major)
+  int lsock = -1, port = 0;
+  std::vector<int> out_all;                // broadcast listeners (under slots_mu)
+  std::vector<int> lcount;                 // listeners per slot (under slots_mu)
+  int lmin = 0, lcursor = 0;               // fewest listeners on any slot; lowest slot that may still have that few
 };
 
 }  // namespace
@@ -181,7 +199,11 @@ struct vapx_ingest {
   vapx_ingest_reset_fn reset = nullptr;
   void* user = nullptr;
   vapx_handle engine = nullptr;
-  int S = 0, max_batch = 0, hop = 0, mode = 0, hz = 0;
+  int S = 0, max_batch = 0, hop = 0, hz = 0;
+  int M = 1;                               // models = output ports (> 1: a trunk group, `step` fills wire blocks)
+  OutPort ports[MAX_MODELS];
+  size_t row_floats = VAPX_OUT_STRIDE;     // floats per stream in a job's block, all models
+  int cfg_ports_out[MAX_MODELS] = {0, 0, 0};   // requested ports of the followers ([0] unused: cfg.port_out)
   bool broadcast = false;
   int R = 2, X = 2;
 
@@ -192,18 +214,15 @@ struct vapx_ingest {
   std::vector<int32_t> batch_ids;
   Job jobs[2];
 
-  int lin = -1, lout = -1;
-  int port_in = 0, port_out = 0;
+  int lin = -1;
+  int port_in = 0;
   std::vector<int> ep;                     // epoll fd per rx thread
   std::vector<int> wake;                   // eventfd per rx thread (resume / stop)
   std::vector<std::thread> rx_threads, tx_threads;
   std::thread tick_thread;
   std::atomic<bool> stop{false};
 
-  std::mutex slots_mu;                     // slot allocation, out_all, listener bookkeeping
-  std::vector<int> out_all;                // broadcast listeners
-  std::vector<int> lcount;                 // listeners per slot (under slots_mu)
-  int lmin = 0, lcursor = 0;               // fewest listeners on any slot; lowest slot that may still have that few
+  std::mutex slots_mu;                     // slot allocation, the ports' out_all and listener bookkeeping
   int free_hint = 0;                       // no input slot below this one is free (under slots_mu): adoption is O(1) amortised, not a scan of S slots
   int ep_accept = -1;                      // the accept thread's epoll (listen sockets only)
   std::thread accept_thread;
@@ -591,46 +610,49 @@ void accept_in(vapx_ingest* g) {
 
 // the (listener count, slot) an output connection attached now would get: fewest listeners, lowest index first
 // (amortised O(1): a cursor walks the slots that still have `lmin` listeners and wraps with lmin + 1)
-std::pair<int, int> next_listener_slot(vapx_ingest* g) {
+std::pair<int, int> next_listener_slot(vapx_ingest* g, int m = 0) {
   std::lock_guard<std::mutex> lk(g->slots_mu);
+  OutPort& o = g->ports[m];
   for (int pass = 0; pass < 2; ++pass) {
-    for (int i = g->lcursor; i < g->S; ++i)
-      if (g->lcount[i] == g->lmin) { g->lcursor = i; return {g->lmin, i}; }
-    ++g->lmin; g->lcursor = 0;
+    for (int i = o.lcursor; i < g->S; ++i)
+      if (o.lcount[i] == o.lmin) { o.lcursor = i; return {o.lmin, i}; }
+    ++o.lmin; o.lcursor = 0;
   }
-  return {g->lmin, 0};
+  return {o.lmin, 0};
 }
 
 // take over an accepted output connection (non-blocking like vap_main.py:346-347): the k-th output connection hears the k-th stream
-void adopt_out(vapx_ingest* g, int fd) {
+void adopt_out(vapx_ingest* g, int fd, int m = 0) {
+  OutPort& o = g->ports[m];
   int one = 1;
   setsockopt(fd, IPPROTO_TCP, TCP_NODELAY, &one, sizeof one);
   g->out_conns.fetch_add(1);
   { const double t = mono_now(); if (g->dbg_t_out_first == 0) g->dbg_t_out_first = t; g->dbg_t_out_last = t; }
-  if (g->broadcast) { std::lock_guard<std::mutex> lk(g->slots_mu); g->out_all.push_back(fd); return; }
-  const int best = next_listener_slot(g).second;
+  if (g->broadcast) { std::lock_guard<std::mutex> lk(g->slots_mu); o.out_all.push_back(fd); return; }
+  const int best = next_listener_slot(g, m).second;
   std::lock_guard<std::mutex> lk(g->slots_mu);
-  g->lcursor = best + 1;
-  ++g->lcount[best];
+  o.lcursor = best + 1;
+  ++o.lcount[best];
   std::lock_guard<std::mutex> l2(g->slots[best].lmu);
-  g->slots[best].listeners.push_back(fd);
+  g->slots[best].listeners[m].push_back(fd);
   if (g->slots[best].dbg_t_attach == 0) g->slots[best].dbg_t_attach = mono_now();
 }
 
-void accept_out(vapx_ingest* g) {
+void accept_out(vapx_ingest* g, int m) {
   for (;;) {
-    int fd = accept4(g->lout, nullptr, nullptr, SOCK_NONBLOCK);
+    int fd = accept4(g->ports[m].lsock, nullptr, nullptr, SOCK_NONBLOCK);
     if (fd < 0) { accept_failed_for_fds(g); return; }
-    adopt_out(g, fd);
+    adopt_out(g, fd, m);
   }
 }
 
 // a dropped listener lowers its slot's count: the next output connection goes there first
-void listener_dropped(vapx_ingest* g, int slot) {
+void listener_dropped(vapx_ingest* g, int slot, int m = 0) {
   {
     std::lock_guard<std::mutex> lk(g->slots_mu);
-    if (--g->lcount[slot] < g->lmin) { g->lmin = g->lcount[slot]; g->lcursor = slot; }
-    else if (g->lcount[slot] == g->lmin && slot < g->lcursor) g->lcursor = slot;
+    OutPort& o = g->ports[m];
+    if (--o.lcount[slot] < o.lmin) { o.lmin = o.lcount[slot]; o.lcursor = slot; }
+    else if (o.lcount[slot] == o.lmin && slot < o.lcursor) o.lcursor = slot;
   }
   link_event(g, LK_OUT_CLOSED, slot);
 }
@@ -664,12 +686,12 @@ void adopt_out_at(vapx_ingest* g, int fd, int slot) {
   const int fl = fcntl(fd, F_GETFL, 0);
   if (fl >= 0) fcntl(fd, F_SETFL, fl | O_NONBLOCK);
   g->out_conns.fetch_add(1);
-  if (g->broadcast) { std::lock_guard<std::mutex> lk(g->slots_mu); g->out_all.push_back(fd); return; }
+  if (g->broadcast) { std::lock_guard<std::mutex> lk(g->slots_mu); g->ports[0].out_all.push_back(fd); return; }
   if (slot < 0 || slot >= g->S) slot = 0;
   std::lock_guard<std::mutex> lk(g->slots_mu);
-  ++g->lcount[slot];
+  ++g->ports[0].lcount[slot];
   std::lock_guard<std::mutex> l2(g->slots[slot].lmu);
-  g->slots[slot].listeners.push_back(fd);
+  g->slots[slot].listeners[0].push_back(fd);
 }
 
 void link_main(vapx_ingest* g) {
@@ -694,7 +716,7 @@ void accept_main(vapx_ingest* g) {
     for (int i = 0; i < n; ++i) {
       const uint64_t kind = evs[i].data.u64 & ~0xffffffffull;
       if (kind == K_LISTEN_IN) accept_in(g);
-      else if (kind == K_LISTEN_OUT) accept_out(g);
+      else if (kind == K_LISTEN_OUT) accept_out(g, (int)(evs[i].data.u64 & 0xffffffffu));
     }
   }
 }
@@ -760,42 +782,48 @@ void tx_main(vapx_ingest* g, int x) {
     Job& job = g->jobs[j];
     for (int k : job.part[x]) {
       const Ready& rd = job.rows[k];
-      const float* row = job.out + (size_t)k * VAPX_OUT_STRIDE;
       Slot& s = g->slots[rd.slot];
-      if (row[VAPX_OUT_STATUS] == 0.f) {
-        // u32 len | f64 t | u32 n | x1 | u32 n | x2 | tail   (util.py:122-143; length prefix vap_main.py:446-448)
-        uint8_t head[16], mid[4];
-        const int tb = encode_tail(g->mode, row, tail.data());
-        const uint32_t plen = 8 + 2 * (4 + 8 * (uint32_t)hop) + (uint32_t)tb;
-        uint8_t* p = head;
-        put_u32(p, plen); put_f64(p, job.t_unix); put_u32(p, (uint32_t)hop);
-        p = mid; put_u32(p, (uint32_t)hop);
-        double* e = g->f64buf(rd.slot, rd.buf);
-        iovec iov[5] = {{head, 16}, {e, (size_t)hop * 8}, {mid, 4}, {e + hop, (size_t)hop * 8}, {tail.data(), (size_t)tb}};
-        const size_t total = 4 + plen;
-        auto send_to = [&](std::vector<int>& fds) {
-          for (size_t i = 0; i < fds.size();) {
-            const double ts0 = g->debug ? mono_now() : 0.0;
-            const bool sent = send_packet(fds[i], iov, 5, total);
-            if (g->debug) atomic_max(g->dbg_send_us, (int64_t)((mono_now() - ts0) * 1e6));   // longest sendmsg() call (the socket is non-blocking)
-            if (sent) { g->tx_bytes.fetch_add((int64_t)total, std::memory_order_relaxed); ++i; }
-            else { close(fds[i]); fds.erase(fds.begin() + i); g->dropped.fetch_add(1); g->out_conns.fetch_sub(1); if (g->broadcast) link_event(g, LK_OUT_CLOSED, -1); }
+      if (!job.bad[k]) {
+        // u32 len | f64 t | u32 n | x1 | u32 n | x2 | tail   (util.py:122-143; length prefix vap_main.py:446-448); a trunk group sends one
+        // packet per model, each to its own port's listeners, tail in that model's framing (bc util.py:193-211, nod :213-237)
+        for (int m = 0; m < g->M; ++m) {
+          OutPort& o = g->ports[m];
+          const float* row = job.out + (size_t)job.n * o.off + (size_t)k * o.wf;
+          uint8_t head[16], mid[4];
+          const int tb = encode_tail(o.mode, row, tail.data(), std::min(256, o.wf - VAPX_OUT_LOGITS));
+          const uint32_t plen = 8 + 2 * (4 + 8 * (uint32_t)hop) + (uint32_t)tb;
+          uint8_t* p = head;
+          put_u32(p, plen); put_f64(p, job.t_unix); put_u32(p, (uint32_t)hop);
+          p = mid; put_u32(p, (uint32_t)hop);
+          double* e = g->f64buf(rd.slot, rd.buf);
+          iovec iov[5] = {{head, 16}, {e, (size_t)hop * 8}, {mid, 4}, {e + hop, (size_t)hop * 8}, {tail.data(), (size_t)tb}};
+          const size_t total = 4 + plen;
+          auto send_to = [&](std::vector<int>& fds) {
+            for (size_t i = 0; i < fds.size();) {
+              const double ts0 = g->debug ? mono_now() : 0.0;
+              const bool sent = send_packet(fds[i], iov, 5, total);
+              if (g->debug) atomic_max(g->dbg_send_us, (int64_t)((mono_now() - ts0) * 1e6));   // longest sendmsg() call (the socket is non-blocking)
+              if (sent) { g->tx_bytes.fetch_add((int64_t)total, std::memory_order_relaxed); ++i; }
+              else { close(fds[i]); fds.erase(fds.begin() + i); g->dropped.fetch_add(1); g->out_conns.fetch_sub(1); if (g->broadcast) link_event(g, LK_OUT_CLOSED, -1); }
+            }
+          };
+          if (g->broadcast) { std::lock_guard<std::mutex> lk(g->slots_mu); send_to(o.out_all); }
+          else {
+            size_t gone = 0;
+            {
+              std::lock_guard<std::mutex> lk(s.lmu);
+              const size_t before = s.listeners[m].size();
+              if (m == 0) {
+                if (before == 0) s.dbg_nolistener.fetch_add(1, std::memory_order_relaxed);
+                else if (s.dbg_sent.fetch_add(1, std::memory_order_relaxed) == 0) s.dbg_t_first_sent = mono_now();
+              }
+              send_to(s.listeners[m]);
+              gone = before - s.listeners[m].size();
+            }
+            for (size_t d = 0; d < gone; ++d) listener_dropped(g, rd.slot, m);   // (slots_mu is never taken under a slot's lmu here)
           }
-        };
-        if (g->broadcast) { std::lock_guard<std::mutex> lk(g->slots_mu); send_to(g->out_all); }
-        else {
-          size_t gone = 0;
-          {
-            std::lock_guard<std::mutex> lk(s.lmu);
-            const size_t before = s.listeners.size();
-            if (before == 0) s.dbg_nolistener.fetch_add(1, std::memory_order_relaxed);
-            else if (s.dbg_sent.fetch_add(1, std::memory_order_relaxed) == 0) s.dbg_t_first_sent = mono_now();
-            send_to(s.listeners);
-            gone = before - s.listeners.size();
-          }
-          for (size_t d = 0; d < gone; ++d) listener_dropped(g, rd.slot);   // (slots_mu is never taken under a slot's lmu here)
         }
-        const double lat = mono_now() - rd.t;
+        const double lat = mono_now() - rd.t;   // once per stream-frame: the last model's packets are with the kernel
         g->lat.add(lat);
         if (lat > 0.010) g->late10.fetch_add(1, std::memory_order_relaxed);
       }
@@ -900,11 +928,15 @@ void tick_main(vapx_ingest* g) {
       for (int k = 0; k < n; ++k) release_buf(g, job.rows[k].slot, job.rows[k].buf);
       continue;
     }
-    for (int k = 0; k < n; ++k)
-      if (job.out[(size_t)k * VAPX_OUT_STRIDE + VAPX_OUT_STATUS] != 0.f) {   // poisoned stream: fresh state, no packet
+    job.bad.assign(n, 0);
+    for (int k = 0; k < n; ++k) {
+      for (int m = 0; m < g->M; ++m)
+        if (job.out[(size_t)n * g->ports[m].off + (size_t)k * g->ports[m].wf + VAPX_OUT_STATUS] != 0.f) job.bad[k] = 1;
+      if (job.bad[k]) {   // poisoned stream (in any model): fresh state, no packet on any port; counted once
         if (g->reset) g->reset(g->user, job.rows[k].slot);
         g->numeric_resets.fetch_add(1);
       }
+    }
     g->frames_done.fetch_add(n);
     job.t_unix = unix_now();
     for (auto& pt : job.part) pt.clear();
@@ -968,7 +1000,7 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in) {
   g->slots.reset(new Slot[g->S]);
   const size_t per = (size_t)g->S * NBUF * 2 * g->hop;
   const size_t ba = (size_t)g->max_batch * 2 * g->hop;
-  const size_t ob = (size_t)g->max_batch * VAPX_OUT_STRIDE;
+  const size_t ob = (size_t)g->max_batch * g->row_floats;
   // page-locked staging so vapx_step DMAs straight out of / into it; without a HIP device (host-logic tests over a step
   // function) plain memory does
   g->stage = (float*)vapx_host_alloc(per * sizeof(float));
@@ -1005,8 +1037,11 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in) {
   if (passive != (cfg->port_out < 0)) return VAPX_E_INVAL;   // a shard is passive on BOTH ports or on none (-1 / >= 0 mixed is a configuration error)
   if (!passive) {
     g->lin = listen_on(cfg->port_in, cfg->bind_any != 0, &g->port_in);
-    g->lout = listen_on(cfg->port_out, cfg->bind_any != 0, &g->port_out);
-    if (g->lin < 0 || g->lout < 0) return VAPX_E_INVAL;
+    for (int m = 0; m < g->M; ++m) {
+      g->ports[m].lsock = listen_on(m ? g->cfg_ports_out[m] : cfg->port_out, cfg->bind_any != 0, &g->ports[m].port);
+      if (g->ports[m].lsock < 0) return VAPX_E_INVAL;
+    }
+    if (g->lin < 0) return VAPX_E_INVAL;
   }
   g->resume_mu = std::vector<std::mutex>(g->R);
   g->resume.assign(g->R, {});
@@ -1015,11 +1050,11 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in) {
     g->wake.push_back(eventfd(0, EFD_NONBLOCK));
     ep_add(g->ep[r], g->wake[r], K_WAKE);
   }
-  g->lcount.assign(g->S, 0);
+  for (int m = 0; m < g->M; ++m) g->ports[m].lcount.assign(g->S, 0);
   if (!passive) {
     g->ep_accept = epoll_create1(0);          // own thread: a connect storm must not starve the streams of a receive thread
     ep_add(g->ep_accept, g->lin, K_LISTEN_IN);
-    ep_add(g->ep_accept, g->lout, K_LISTEN_OUT);
+    for (int m = 0; m < g->M; ++m) ep_add(g->ep_accept, g->ports[m].lsock, K_LISTEN_OUT | (uint32_t)m);
     g->accept_thread = std::thread(accept_main, g);
   }
   for (int r = 0; r < g->R; ++r) g->rx_threads.emplace_back(rx_main, g, r);
@@ -1030,6 +1065,38 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in) {
   pin_to(g->accept_thread, g->cfg, 0);
   for (int r = 0; r < g->R; ++r) pin_to(g->rx_threads[r], g->cfg, 1 + r);
   for (int x = 0; x < g->X; ++x) pin_to(g->tx_threads[x], g->cfg, 1 + g->R + x);
+  return VAPX_OK;
+}
+
+int engine_group_step(void* user, int32_t n, const int32_t* ids, const float* audio, float* wire_out) {
+  vapx_ingest* g = (vapx_ingest*)user;
+  return vapx_step_group(g->engine, n, ids, audio, g->hop, wire_out, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
+}
+
+thread_local std::string g_open_error;   // vapx_ingest_last_open_error
+int open_refused(const char* why) { g_open_error = why; return VAPX_E_INVAL; }
+
+// a trunk group's ports: model m's framing, the geometry of its rows in the tick's wire block (vapx_step_group) and its requested port
+int setup_group(vapx_ingest* g, const int32_t* modes, int n_models, int ctx_frames, const vapx_ingest_config& cfg,
+                const int32_t* follower_ports_out) {
+  if (n_models < 1 || n_models > MAX_MODELS) return open_refused("a group serves one to three models");
+  if (cfg.port_in < 0 || cfg.port_out < 0)
+    return open_refused("a trunk group cannot be a passive shard (port_in = -1): the front door is single-model");
+  size_t acc = 0;
+  for (int m = 0; m < n_models; ++m) {
+    const int wf = vapx_wire_floats(modes[m], ctx_frames);
+    if (wf <= 0) return open_refused("bad mode or ctx_frames");
+    for (int j = 0; j < m; ++j)
+      if (modes[j] == modes[m]) return open_refused("the models of a group must have pairwise distinct modes (vap, bc, nod)");
+    if (m && follower_ports_out && follower_ports_out[m - 1] < 0) return open_refused("a follower's output port must be >= 0 (0 = ephemeral)");
+    g->ports[m].mode = modes[m];
+    g->ports[m].wf = wf;
+    g->ports[m].off = acc;
+    g->cfg_ports_out[m] = (m && follower_ports_out) ? follower_ports_out[m - 1] : 0;
+    acc += (size_t)wf;
+  }
+  g->M = n_models;
+  g->row_floats = acc;
   return VAPX_OK;
 }
 
@@ -1046,7 +1113,7 @@ int vapx_ingest_open_fn(vapx_ingest_step_fn step, vapx_ingest_reset_fn reset, vo
   if (mode < 0 || mode > 2) return VAPX_E_INVAL;
   vapx_ingest* g = new vapx_ingest();
   g->step = step; g->reset = reset; g->user = user;
-  g->S = n_streams; g->max_batch = max_batch; g->hz = frame_hz; g->mode = mode;
+  g->S = n_streams; g->max_batch = max_batch; g->hz = frame_hz; g->ports[0].mode = mode;
   int rc = open_common(g, cfg);
   if (rc != VAPX_OK) { vapx_ingest_close(g); return rc; }
   *out = g;
@@ -1062,7 +1129,7 @@ int vapx_ingest_open(vapx_handle engine, const vapx_ingest_config* cfg, vapx_ing
   vapx_ingest* g = new vapx_ingest();
   g->engine = engine;
   g->step = engine_step; g->reset = engine_reset; g->user = g;
-  g->S = ec.max_streams; g->max_batch = ec.max_batch; g->hz = ec.frame_hz; g->mode = ec.mode;
+  g->S = ec.max_streams; g->max_batch = ec.max_batch; g->hz = ec.frame_hz; g->ports[0].mode = ec.mode;
   {  // warm the engine up before the first client connects: the first vapx_step of a process loads the code objects and sizes
      // the runtime's pools (hundreds of ms) — paid here on silence, then every touched stream is reset
     const int nw = ec.max_batch, hop = 16000 / ec.frame_hz;
@@ -1085,7 +1152,84 @@ int vapx_ingest_open(vapx_handle engine, const vapx_ingest_config* cfg, vapx_ing
 int vapx_ingest_ports(vapx_ingest_handle g, int32_t* port_in, int32_t* port_out) {
   if (!g) return VAPX_E_INVAL;
   if (port_in) *port_in = g->port_in;
-  if (port_out) *port_out = g->port_out;
+  if (port_out) *port_out = g->ports[0].port;
+  return VAPX_OK;
+}
+
+int vapx_ingest_group_ports(vapx_ingest_handle g, int32_t* port_in, int32_t* ports_out, int32_t max_ports) {
+  if (!g) return VAPX_E_INVAL;
+  if (port_in) *port_in = g->port_in;
+  for (int m = 0; m < g->M && m < max_ports && ports_out; ++m) ports_out[m] = g->ports[m].port;
+  return g->M;
+}
+
+const char* vapx_ingest_last_open_error(void) { return g_open_error.c_str(); }
+
+int32_t vapx_wire_floats(int32_t mode, int32_t ctx_frames) {
+  if (mode < VAPX_MODE_VAP || mode > VAPX_MODE_NOD || ctx_frames < 1 || ctx_frames > 512) return 0;
+  return mode == VAPX_MODE_NOD ? ((VAPX_OUT_LOGITS + ctx_frames + 3) & ~3) : VAPX_OUT_LOGITS;
+}
+
+int vapx_ingest_open_group_fn(vapx_ingest_group_step_fn step, vapx_ingest_reset_fn reset, void* user, int32_t n_streams, int32_t max_batch,
+                              int32_t frame_hz, int32_t ctx_frames, const int32_t* modes, int32_t n_models, const vapx_ingest_config* cfg,
+                              const int32_t* follower_ports_out, vapx_ingest_handle* out) {
+  g_open_error.clear();
+  vapx_ingest_config probe;
+  if (!step || !out || !modes || !read_config(cfg, &probe)) return open_refused("null argument or a vapx_ingest_config of unknown size");
+  if (n_streams < 1 || max_batch < 1 || max_batch > n_streams) return open_refused("need 1 <= max_batch <= n_streams");
+  if (frame_hz != 5 && frame_hz != 10 && frame_hz != 20 && frame_hz != 50) return open_refused("frame_hz must be 5, 10, 20 or 50");
+  vapx_ingest* g = new vapx_ingest();
+  int rc = setup_group(g, modes, n_models, ctx_frames, probe, follower_ports_out);
+  if (rc != VAPX_OK) { delete g; return rc; }
+  g->step = step; g->reset = reset; g->user = user;
+  g->S = n_streams; g->max_batch = max_batch; g->hz = frame_hz;
+  rc = open_common(g, cfg);
+  if (rc != VAPX_OK) { vapx_ingest_close(g); return open_refused("could not allocate the staging blocks or bind the ports"); }
+  *out = g;
+  return VAPX_OK;
+}
+
+int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int32_t n_followers, const vapx_ingest_config* cfg,
+                           const int32_t* follower_ports_out, vapx_ingest_handle* out) {
+  g_open_error.clear();
+  vapx_ingest_config probe;
+  if (!leader || !out || n_followers < 0 || (n_followers && !followers) || !read_config(cfg, &probe))
+    return open_refused("null argument or a vapx_ingest_config of unknown size");
+  if (!vapx_step_group || !vapx_group_wire_floats) return open_refused("this build has no vapx_step_group");
+  if (n_followers + 1 > MAX_MODELS) return open_refused("a group serves at most three models (vap, bc, nod)");
+  vapx_config ec;
+  int rc = vapx_get_config(leader, &ec);
+  if (rc != VAPX_OK) return rc;
+  int32_t modes[MAX_MODELS] = {ec.mode, 0, 0};
+  for (int i = 0; i < n_followers; ++i) {
+    vapx_config fc;
+    if (!followers[i] || vapx_get_config(followers[i], &fc) != VAPX_OK) return open_refused("null follower");
+    modes[i + 1] = fc.mode;
+  }
+  vapx_ingest* g = new vapx_ingest();
+  rc = setup_group(g, modes, n_followers + 1, ec.ctx_frames, probe, follower_ports_out);
+  if (rc == VAPX_OK && g->row_floats != vapx_group_wire_floats(leader)) {
+    rc = open_refused("`followers` are not the leader's attached followers (vapx_attach_trunk) in attach order");
+  }
+  if (rc != VAPX_OK) { delete g; return rc; }
+  g->engine = leader;
+  g->step = engine_group_step; g->reset = engine_reset; g->user = g;
+  g->S = ec.max_streams; g->max_batch = ec.max_batch; g->hz = ec.frame_hz;
+  {  // warm-up on silence as in vapx_ingest_open, the whole group per tick; every touched stream is reset (the leader cascades)
+    const int nw = ec.max_batch, hop = 16000 / ec.frame_hz;
+    float* a = (float*)vapx_host_alloc((size_t)nw * 2 * hop * sizeof(float));
+    float* o = (float*)vapx_host_alloc((size_t)nw * g->row_floats * sizeof(float));
+    if (a && o) {
+      memset(a, 0, (size_t)nw * 2 * hop * sizeof(float));
+      for (int k = 0; k < 3; ++k) (void)vapx_step_group(leader, nw, nullptr, a, hop, o, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
+      for (int i = 0; i < nw; ++i) (void)vapx_reset_stream(leader, i);
+    }
+    vapx_host_free(a);
+    vapx_host_free(o);
+  }
+  rc = open_common(g, cfg);
+  if (rc != VAPX_OK) { vapx_ingest_close(g); return open_refused("could not allocate the staging blocks or bind the ports"); }
+  *out = g;
   return VAPX_OK;
 }
 
@@ -1159,12 +1303,11 @@ void vapx_ingest_close(vapx_ingest_handle g) {
   if (g->slots) {
     for (int i = 0; i < g->S; ++i) {
       if (g->slots[i].fd_in >= 0) close(g->slots[i].fd_in);
-      for (int fd : g->slots[i].listeners) close(fd);
+      for (auto& l : g->slots[i].listeners) for (int fd : l) close(fd);
     }
   }
-  for (int fd : g->out_all) close(fd);
+  for (auto& o : g->ports) { for (int fd : o.out_all) close(fd); if (o.lsock >= 0) close(o.lsock); }
   if (g->lin >= 0) close(g->lin);
-  if (g->lout >= 0) close(g->lout);
   for (int fd : g->ep) close(fd);
   for (int fd : g->wake) close(fd);
   auto drop = [&](void* p) {
@@ -1256,7 +1399,7 @@ void frontdoor_main(vapx_frontdoor* d) {
             // a broadcast shard (one dialogue slot: serve.py's default --streams 1) is ONE candidate: (its listener count, slot 0) — so the
             // k-th output connection hears GPU k mod N's dialogue instead of every listener piling up on shard 0
             std::pair<int, int> c;
-            if (d->shards[k]->broadcast) { std::lock_guard<std::mutex> lk(d->shards[k]->slots_mu); c = {(int)d->shards[k]->out_all.size(), 0}; }
+            if (d->shards[k]->broadcast) { std::lock_guard<std::mutex> lk(d->shards[k]->slots_mu); c = {(int)d->shards[k]->ports[0].out_all.size(), 0}; }
             else c = next_listener_slot(d->shards[k]);
             const long gslot = (long)c.second * N + k;
             if (bestc < 0 || c.first < bestc || (c.first == bestc && gslot < bestg)) { bestc = c.first; bestg = gslot; who = k; }
@@ -1343,9 +1486,9 @@ extern "C" {
 
 int vapx_ingest_attach_link(vapx_ingest_handle g, int32_t link_fd) {
   if (!g || link_fd < 0 || g->link_fd >= 0) return VAPX_E_INVAL;
-  if (g->lin >= 0 || g->lout >= 0) return VAPX_E_INVAL;           // only a passive shard takes its connections from a door
+  if (g->lin >= 0 || g->ports[0].lsock >= 0) return VAPX_E_INVAL;           // only a passive shard takes its connections from a door
   g->link_fd = link_fd;
-  if (!link_send(link_fd, &g->link_mu, LinkMsg{LK_HELLO, g->S, g->hz, g->mode | (g->broadcast ? 256 : 0)})) { g->link_fd = -1; return VAPX_E_INVAL; }
+  if (!link_send(link_fd, &g->link_mu, LinkMsg{LK_HELLO, g->S, g->hz, g->ports[0].mode | (g->broadcast ? 256 : 0)})) { g->link_fd = -1; return VAPX_E_INVAL; }
   g->link_thread = std::thread(link_main, g);
   return VAPX_OK;
 }
@@ -1381,8 +1524,8 @@ int vapx_frontdoor_open(vapx_ingest_handle* shards, int32_t n_shards, int32_t po
                         vapx_frontdoor_handle* out) {
   if (!shards || n_shards < 1 || !out || port_in < 0 || port_out < 0) return VAPX_E_INVAL;
   for (int k = 0; k < n_shards; ++k) {
-    if (!shards[k] || shards[k]->lin >= 0 || shards[k]->lout >= 0) return VAPX_E_INVAL;   // shards must be passive (port_in = port_out = -1)
-    if (shards[k]->hz != shards[0]->hz || shards[k]->mode != shards[0]->mode) return VAPX_E_INVAL;
+    if (!shards[k] || shards[k]->lin >= 0 || shards[k]->ports[0].lsock >= 0 || shards[k]->M != 1) return VAPX_E_INVAL;   // shards must be passive (port_in = port_out = -1)
+    if (shards[k]->hz != shards[0]->hz || shards[k]->ports[0].mode != shards[0]->ports[0].mode) return VAPX_E_INVAL;
   }
   vapx_frontdoor* d = new vapx_frontdoor();
   d->shards.assign(shards, shards + n_shards);

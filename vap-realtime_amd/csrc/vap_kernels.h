@@ -119,6 +119,14 @@ struct HeadArgs {
   int B, T, mode, out_stride, x_last_only;
 };
 
+struct WirePackArgs {   // wire_pack_kernel: up to 4 models per launch
+  const float* src[4];  // [n][src_stride] output rows of model m
+  float* dst;           // model-major wire block
+  long dst_off[4];      // floats before model m's rows in dst
+  int wf4[4];           // wire floats of model m / 4
+  int n_models, n, src_stride;
+};
+
 hipError_t launch_conv0(const Conv0Args& a, int B, hipStream_t st);
 hipError_t launch_lstm(const LstmArgs& a, hipStream_t st);
 hipError_t launch_ring_append(const GatherArgs& a, hipStream_t st);
@@ -131,3 +139,4 @@ hipError_t launch_gather_last_ln(const LastRowArgs& a, hipStream_t st);
 hipError_t launch_ln_rows(const float* x, float* y, const float* gamma, const float* beta, int rows, hipStream_t st);
 hipError_t launch_attention_last(const AttnArgs& a, int B, hipStream_t st);
 hipError_t launch_head(const HeadArgs& a, hipStream_t st);
+hipError_t launch_wire_pack(const WirePackArgs& a, hipStream_t st);

@@ -1046,6 +1046,20 @@ __global__ __launch_bounds__(256) void head_kernel(HeadArgs a) {
   }
 }
 
+// Wire rows of a trunk group's tick (vapx_step_group): the first wf floats of every model's [n][VAPX_OUT_STRIDE] output rows, packed
+// model-major into one block [model m][n][wf(m)] that a single linear copy takes to the host.  One 16-byte load and one 16-byte
+// store per lane; blockIdx.y = model.  Rows are 16-byte aligned on both sides (784 and every wf are multiples of 4 floats).
+__global__ __launch_bounds__(256) void wire_pack_kernel(WirePackArgs a) {
+  const int m = blockIdx.y;
+  const int wf4 = a.wf4[m];
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)a.n * wf4) return;
+  const long row = idx / wf4;
+  const int q = (int)(idx - row * wf4);
+  const f32x4 v = *(const f32x4*)(a.src[m] + row * a.src_stride + q * 4);
+  *(f32x4*)(a.dst + a.dst_off[m] + idx * 4) = v;
+}
+
 }  // namespace
 
 hipError_t launch_conv0(const Conv0Args& a, int B, hipStream_t st) {
@@ -1094,5 +1108,12 @@ hipError_t launch_head(const HeadArgs& a, hipStream_t st) {
   // batch over more CUs (2: 30 us at 256 streams vs 56 us with 8), more amortise the stream at large batches
   if (a.B <= 1024) hipLaunchKernelGGL(head_kernel<2>, dim3((a.B + 1) / 2), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(head_kernel<4>, dim3((a.B + 3) / 4), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_wire_pack(const WirePackArgs& a, hipStream_t st) {
+  int wmax = 0;
+  for (int m = 0; m < a.n_models; ++m) wmax = a.wf4[m] > wmax ? a.wf4[m] : wmax;
+  const long items = (long)a.n * wmax;
+  hipLaunchKernelGGL(wire_pack_kernel, dim3((unsigned)((items + 255) / 256), a.n_models), dim3(256), 0, st, a);
   return hipGetLastError();
 }

@@ -30,7 +30,9 @@ EXPORTS = ("vapx_abi_version", "vapx_blob_floats", "vapx_create", "vapx_destroy"
            "vapx_profile_read", "vapx_bad_slots", "vapx_host_alloc", "vapx_host_free", "vapx_reset_carry", "vapx_get_config",
            "vapx_ingest_open", "vapx_ingest_open_fn", "vapx_ingest_ports", "vapx_ingest_stats_read", "vapx_ingest_late_read", "vapx_ingest_close",
            "vapx_wire_decode_input", "vapx_wire_encode_result", "vapx_vap_head", "vapx_va_classifier", "vapx_softmax256",
-           "vapx_aggregate", "vapx_aux_head", "vapx_frontdoor_open", "vapx_frontdoor_open_links", "vapx_ingest_attach_link", "vapx_frontdoor_ports", "vapx_frontdoor_counts", "vapx_frontdoor_close")
+           "vapx_aggregate", "vapx_aux_head", "vapx_frontdoor_open", "vapx_frontdoor_open_links", "vapx_ingest_attach_link", "vapx_frontdoor_ports", "vapx_frontdoor_counts", "vapx_frontdoor_close",
+           "vapx_wire_floats", "vapx_group_wire_floats", "vapx_step_group", "vapx_group_bad", "vapx_ingest_open_group",
+           "vapx_ingest_open_group_fn", "vapx_ingest_group_ports", "vapx_ingest_last_open_error")
 PROF_CLASSES = {0: "gemm_store", 1: "gemm_gelu", 2: "gemm_resid", 3: "gemm_resid_ln", 4: "gemm_cn_relu",
                 5: "conv_tail", 6: "ffn_block", 7: "last_row", 8: "conv0", 9: "lstm", 10: "gather_ln", 11: "attention", 12: "head",
                 13: "gemm_bias_ln_gelu", 14: "ffn_proj"}
@@ -144,6 +146,22 @@ def load_library(path: Optional[str] = None):
     lib.vapx_softmax256.argtypes = [C.c_int64, f32p, f32p, vp]
     lib.vapx_aggregate.restype = i32
     lib.vapx_aggregate.argtypes = [C.c_int64, f32p, i32, i32, f32p, vp]
+    lib.vapx_wire_floats.restype = i32
+    lib.vapx_wire_floats.argtypes = [i32, i32]
+    lib.vapx_group_wire_floats.restype = C.c_size_t
+    lib.vapx_group_wire_floats.argtypes = [vp]
+    lib.vapx_step_group.restype = i32
+    lib.vapx_step_group.argtypes = [vp, i32, i32p, f32p, i32, f32p, i32, vp]
+    lib.vapx_group_bad.restype = i32
+    lib.vapx_group_bad.argtypes = [vp, i32p, i32p, i32]
+    lib.vapx_ingest_open_group.restype = i32
+    lib.vapx_ingest_open_group.argtypes = [vp, C.POINTER(vp), i32, vp, C.POINTER(i32), C.POINTER(vp)]
+    lib.vapx_ingest_open_group_fn.restype = i32
+    lib.vapx_ingest_open_group_fn.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), i32, vp, C.POINTER(i32), C.POINTER(vp)]
+    lib.vapx_ingest_group_ports.restype = i32
+    lib.vapx_ingest_group_ports.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), i32]
+    lib.vapx_ingest_last_open_error.restype = C.c_char_p
+    lib.vapx_ingest_last_open_error.argtypes = []
     lib.vapx_wire_decode_input.restype = C.c_int64
     lib.vapx_wire_decode_input.argtypes = [vp, C.c_size_t, C.c_double, vp, vp, vp, vp]
     lib.vapx_wire_encode_result.restype = C.c_int64
@@ -293,6 +311,45 @@ class Engine:
         flags = AUDIO_DEVICE | OUT_DEVICE | (IDS_DEVICE if ids_ptr else 0) | (8 if defer_join else 0)
         self._check(self.lib.vapx_step(self._h, n, ids_ptr or None, audio_ptr, spc, out_ptr, flags, stream or None), "vapx_step")
 
+    # -- the whole trunk group in one call (this engine leads) -----------------------------------------
+    def group_wire_floats(self) -> int:
+        """Wire floats per stream of this leader and its followers together (vapx.h, vapx_group_wire_floats)."""
+        return int(self.lib.vapx_group_wire_floats(self._h))
+
+    def step_group(self, audio: np.ndarray, stream_ids: Optional[Sequence[int]] = None, out: Optional[np.ndarray] = None,
+                   on_numeric: str = "raise") -> np.ndarray:
+        """Host path of ``vapx_step_group``: steps this leader and every follower and returns the tick's wire block, flat float32
+        [n * group_wire_floats()], model-major (``TrunkGroup.step_wire`` slices it).  ``out``: e.g. a ``pinned_empty`` block.
+        ``on_numeric`` as in ``step``; ``group_bad()`` lists the (slot, model) pairs."""
+        audio = np.ascontiguousarray(audio, dtype=np.float32)
+        n, two, spc = audio.shape
+        assert two == 2
+        ids = None if stream_ids is None else np.ascontiguousarray(stream_ids, dtype=np.int32)
+        if ids is not None:
+            assert ids.shape == (n,)
+        need = n * self.group_wire_floats()
+        if out is None:
+            out = np.empty(max(need, 1), dtype=np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size >= need
+        rc = self.lib.vapx_step_group(self._h, n, _np_ptr(ids), _np_ptr(audio), spc, _np_ptr(out), 0, None)
+        if not (rc == E_NUMERIC and on_numeric == "status"):
+            self._check(rc, "vapx_step_group")
+        return out.reshape(-1)[:need]
+
+    def step_group_device(self, n: int, audio_ptr: int, spc: int, wire_ptr: int, ids_ptr: int = 0, stream: int = 0):
+        """Device path of ``vapx_step_group``: raw device pointers, no copy and no synchronisation; ``wire_ptr`` receives the block."""
+        flags = AUDIO_DEVICE | OUT_DEVICE | (IDS_DEVICE if ids_ptr else 0)
+        self._check(self.lib.vapx_step_group(self._h, n, ids_ptr or None, audio_ptr, spc, wire_ptr, flags, stream or None), "vapx_step_group")
+
+    def group_bad(self) -> list:
+        """(batch slot, model index) pairs of the latest host-path ``step_group`` whose results were not finite."""
+        n = self.lib.vapx_group_bad(self._h, None, None, 0)
+        if n <= 0:
+            return []
+        slots, models = np.empty(n, np.int32), np.empty(n, np.int32)
+        self.lib.vapx_group_bad(self._h, _np_ptr(slots), _np_ptr(models), n)
+        return list(zip(slots.tolist(), models.tolist()))
+
     def reset_stream(self, sid: int):
         self._check(self.lib.vapx_reset_stream(self._h, sid), "vapx_reset_stream")
 
@@ -379,6 +436,23 @@ class TrunkGroup:
             res[m] = self.engines[m].step_follow(len(audio))
         return res
 
+    def wire_floats(self, mode: str) -> int:
+        return wire_floats(mode, self.T)
+
+    def step_wire(self, audio: np.ndarray, stream_ids: Optional[Sequence[int]] = None, out: Optional[np.ndarray] = None,
+                  on_numeric: str = "raise") -> dict:
+        """One ``vapx_step_group`` call for the whole group: ``{mode: wire rows [n, wire_floats(mode)]}`` (views of one block; name
+        the columns with ``split_wire``).  One compact device-to-host copy and one synchronisation per tick, where ``step`` pays a
+        full [n, OUT_STRIDE] copy and a synchronisation per model."""
+        n = len(audio)
+        block = self.leader.step_group(audio, stream_ids, out, on_numeric)
+        res, at = {}, 0
+        for m in self.modes:
+            wf = self.wire_floats(m)
+            res[m] = block[at:at + n * wf].reshape(n, wf)
+            at += n * wf
+        return res
+
     def step_device(self, n: int, audio_ptr: int, spc: int, out_ptrs: dict, ids_ptr: int = 0, stream: int = 0):
         self.leader.step_device(n, audio_ptr, spc, out_ptrs[self.modes[0]], ids_ptr, stream)
         for m in self.modes[1:]:
@@ -402,3 +476,25 @@ def split_outputs(out: np.ndarray) -> dict:
         "status": out[:, OUT_STATUS].astype(np.int32),
         "e": out[:, OUT_E:OUT_E + 512].reshape(-1, 2, 256),
     }
+
+
+def wire_floats(mode: str, ctx_frames: int) -> int:
+    """Length of a model's wire row (vapx.h, vapx_wire_floats): 16, or for nod 16 + ctx_frames rounded up to a multiple of 4."""
+    got = int(load_library().vapx_wire_floats(MODE[mode], int(ctx_frames)))
+    if got <= 0:
+        raise VapxError(f"vapx_wire_floats({mode}, {ctx_frames}): bad mode or window")
+    return got
+
+
+def split_wire(mode: str, rows: np.ndarray) -> dict:
+    """Name the columns of wire rows [n, wire_floats] (``TrunkGroup.step_wire``): the head of ``split_outputs``' columns; for nod,
+    ``p_bc_rows`` [n, ctx_frames] is p_bc of every window row (valid up to each row's ``n``, vap_nod_main.py:276)."""
+    d = {
+        "p_now": rows[:, OUT_P_NOW:OUT_P_NOW + 2], "p_future": rows[:, OUT_P_FUTURE:OUT_P_FUTURE + 2],
+        "vad": rows[:, OUT_VAD:OUT_VAD + 2], "aux": rows[:, OUT_AUX:OUT_AUX + 4],
+        "n": rows[:, OUT_NVALID].astype(np.int32), "vad_logit": rows[:, OUT_VAD_LOGIT:OUT_VAD_LOGIT + 2],
+        "status": rows[:, OUT_STATUS].astype(np.int32),
+    }
+    if mode == "nod":
+        d["p_bc_rows"] = rows[:, OUT_LOGITS:]
+    return d

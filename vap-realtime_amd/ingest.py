@@ -104,6 +104,91 @@ class NativeServer:
         return self
 
     @classmethod
+    def for_group(cls, trunk_group: "_engine.TrunkGroup", port_in: int = 50007, ports_out=None, gain: float = 1.0, max_wait_s: float = 0.002,
+                  min_batch: int = 0, reset_on_connect: bool = True, broadcast: Optional[bool] = None, rx_threads: int = 0,
+                  tx_threads: int = 0, bind_any: bool = False, target_util: float = 0.9, cores: Optional[tuple] = None,
+                  keep_nofile: bool = False, core_set: bool = False):
+        """One front-end for a whole ``engine.TrunkGroup`` (``vapx_ingest_open_group``): one input port, the audio encoded once, one
+        output port per model in ``trunk_group.modes`` order (``ports_out``: one per model, default 50008, 50009, ...; 0 = ephemeral),
+        each with its model's reference framing.  ``.ports_out`` is the bound ``{mode: port}``."""
+        self = cls.__new__(cls)
+        self.lib = _engine.load_library()
+        modes = list(trunk_group.modes)
+        ports = list(ports_out) if ports_out is not None else [50008 + i for i in range(len(modes))]
+        if len(ports) != len(modes):
+            raise ValueError(f"{len(modes)} models need {len(modes)} output ports, got {len(ports)}")
+        self._keep = [trunk_group]
+        cfg = cls._cfg(port_in, ports[0], gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, bind_any, target_util,
+                       cores, keep_nofile, core_set)
+        fol = (C.c_void_p * max(len(modes) - 1, 1))(*[trunk_group.engines[m]._h.value for m in modes[1:]])
+        fports = (C.c_int32 * max(len(modes) - 1, 1))(*ports[1:])
+        h = C.c_void_p()
+        rc = self.lib.vapx_ingest_open_group(trunk_group.leader._h, fol, len(modes) - 1, C.byref(cfg), fports, C.byref(h))
+        if rc != 0:
+            raise _engine.VapxError(f"vapx_ingest_open_group failed ({rc}): {self.lib.vapx_ingest_last_open_error().decode()}")
+        self._h = h
+        self._group_ports(modes)
+        return self
+
+    @classmethod
+    def over_group_function(cls, step: Callable, modes, n_streams: int, frame_hz: int = 20, ctx_frames: int = 50,
+                            max_batch: Optional[int] = None, reset: Optional[Callable] = None, port_in: int = 0, ports_out=None,
+                            gain: float = 1.0, max_wait_s: float = 0.002, min_batch: int = 0, reset_on_connect: bool = True,
+                            broadcast: Optional[bool] = None, rx_threads: int = 0, tx_threads: int = 0, target_util: float = 1.0):
+        """The group front-end over a Python step function (``vapx_ingest_open_group_fn``; host-logic tests without a GPU):
+        ``step(ids int32[n], audio float32[n,2,hop], wire {mode: float32[n, wire_floats]}) -> int`` fills the views of that tick's wire
+        block in place (status columns start at 0); ``reset`` as in ``over_function``."""
+        self = cls.__new__(cls)
+        self.lib = _engine.load_library()
+        modes = list(modes)
+        hop = 16000 // frame_hz
+        wf = [int(self.lib.vapx_wire_floats(MODE[m], ctx_frames)) for m in modes]
+        ports = list(ports_out) if ports_out is not None else [0] * len(modes)
+        if len(ports) != len(modes):
+            raise ValueError(f"{len(modes)} models need {len(modes)} output ports, got {len(ports)}")
+
+        def _step(_user, n, ids, audio, out):
+            try:
+                i = np.ctypeslib.as_array(ids, shape=(n,))
+                a = np.ctypeslib.as_array(audio, shape=(n, 2, hop))
+                block = np.ctypeslib.as_array(out, shape=(n * sum(wf),))
+                wire, at = {}, 0
+                for m, w in zip(modes, wf):
+                    wire[m] = block[at:at + n * w].reshape(n, w)
+                    wire[m][:, _engine.OUT_STATUS] = 0.0
+                    at += n * w
+                return int(step(i, a, wire) or 0)
+            except Exception:          # noqa: BLE001 — never unwind through the C caller
+                import traceback
+                traceback.print_exc()
+                return -1
+
+        def _reset(_user, sid):
+            if reset is not None:
+                reset(int(sid))
+
+        self._keep = [_STEP_FN(_step), _RESET_FN(_reset)]
+        cfg = cls._cfg(port_in, ports[0], gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, False, target_util)
+        marr = (C.c_int32 * len(modes))(*[MODE[m] for m in modes])
+        fports = (C.c_int32 * max(len(modes) - 1, 1))(*ports[1:])
+        h = C.c_void_p()
+        rc = self.lib.vapx_ingest_open_group_fn(C.cast(self._keep[0], C.c_void_p), C.cast(self._keep[1], C.c_void_p), None, n_streams,
+                                                max_batch or n_streams, frame_hz, ctx_frames, marr, len(modes), C.byref(cfg), fports,
+                                                C.byref(h))
+        if rc != 0:
+            raise _engine.VapxError(f"vapx_ingest_open_group_fn failed ({rc}): {self.lib.vapx_ingest_last_open_error().decode()}")
+        self._h = h
+        self._group_ports(modes)
+        return self
+
+    def _group_ports(self, modes):
+        a = C.c_int32(0)
+        arr = (C.c_int32 * len(modes))()
+        self.lib.vapx_ingest_group_ports(self._h, C.byref(a), arr, len(modes))
+        self.port_in, self.port_out = a.value, arr[0]
+        self.ports_out = {m: int(arr[i]) for i, m in enumerate(modes)}
+
+    @classmethod
     def over_native_function(cls, step_ptr: int, user_ptr: int, n_streams: int, frame_hz: int = 20, mode: str = "vap", max_batch: Optional[int] = None,
                              keep=(), port_in: int = 0, port_out: int = 0, gain: float = 1.0, max_wait_s: float = 0.002, min_batch: int = 0,
                              rx_threads: int = 0, tx_threads: int = 0, target_util: float = 0.9, cores: Optional[tuple] = None):

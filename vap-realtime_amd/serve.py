@@ -17,6 +17,11 @@ front door becomes a process of its own that only accepts and routes, and every 
 to which accepted connections are passed (``vapx_frontdoor_open_links`` / ``vapx_ingest_attach_link``, include/vapx.h).  Same ports, same
 placement, same packets; 8 x 4096 dialogues need it in a container whose descriptor limit is 20 000.
 
+``--mode a+b[+c]`` (distinct names from vap / bc / nod, the first leads) serves SEVERAL models on one shared CPC trunk — the reference's
+``vap_main.py``, ``vap_bc_main.py`` and ``vap_nod_main.py`` side by side on one ``cpc_model`` file, with the audio encoded once: one input port, one
+output port per model (``--port_num_out`` comma-separated, default 50008, 50009, ...), ``--vap_model`` one path per model, comma-separated in the
+same order.  One GPU, one process: the front door and ``--worker-procs`` are single-model.
+
 ``--synthetic-weights SEED`` serves seeded random weights (no checkpoint files: load tests, demos).  SIGTERM / SIGINT stop every GPU's
 front-end and engine in order; a failure while one GPU comes up tears the others down and exits non-zero.
 """
@@ -36,6 +41,92 @@ def load_blob(args):
         return W.pack_blob(cpc, vap, args.mode or "vap"), args.mode or "vap"
     blob, hz, mode = checkpoints.import_checkpoints(args.vap_model, args.cpc_model, frame_rate=args.vap_process_rate, mode=args.mode)
     return blob, mode
+
+
+def group_modes(mode):
+    """``"bc+nod"`` -> ``["bc", "nod"]``; None for a single mode (or none).  Raises ValueError for unknown / repeated names."""
+    if not mode or "+" not in mode:
+        if mode and mode not in ("vap", "bc", "nod"):
+            raise ValueError(f"--mode {mode}: choose from vap, bc, nod, or a+b[+c] of distinct ones")
+        return None
+    names = mode.split("+")
+    if any(m not in ("vap", "bc", "nod") for m in names) or len(set(names)) != len(names):
+        raise ValueError(f"--mode {mode}: a+b[+c] takes distinct names from vap, bc, nod")
+    return names
+
+
+def out_ports(args, n_models: int):
+    """``--port_num_out``: one port per model, comma-separated (default 50008, 50009, ...)."""
+    ports = [int(p) for p in str(args.port_num_out).split(",")]
+    if len(ports) == 1 and n_models > 1 and args.port_num_out_default:
+        ports = [ports[0] + i for i in range(n_models)]
+    if len(ports) != n_models:
+        raise ValueError(f"--port_num_out names {len(ports)} port(s) for {n_models} model(s)")
+    return ports
+
+
+def load_group_blobs(args, names):
+    """{mode: blob} of a ``+`` mode, first = leader; every model on the SAME CPC weights (vapx_attach_trunk refuses otherwise)."""
+    from . import checkpoints, weights as W
+    blobs = {}
+    if args.synthetic_weights is not None:
+        for m in names:                              # one seed -> identical CPC tensors in every mode, only the heads differ
+            cpc, vap = W.synthetic_weights(args.synthetic_weights, args.vap_process_rate, m)
+            blobs[m] = W.pack_blob(cpc, vap, m)
+        return blobs
+    paths = args.vap_model.split(",")
+    if len(paths) != len(names):
+        raise ValueError(f"--vap_model names {len(paths)} file(s) for --mode {'+'.join(names)}: one per model, comma-separated, in that order")
+    for m, path in zip(names, paths):
+        blobs[m] = checkpoints.import_checkpoints(path, args.cpc_model, frame_rate=args.vap_process_rate, mode=m)[0]
+    return blobs
+
+
+def build_group(args, names):
+    """One trunk group + one group front-end on GPU 0: (group, server)."""
+    from . import dist_util, engine, ingest
+    blobs = load_group_blobs(args, names)
+    ports = out_ports(args, len(names))
+    args.precision_plan = None
+    choose_precision(args, "+".join(names))          # capacity.plan sums the weight sets of a + mode
+    grp = srv = None
+    try:
+        grp = engine.TrunkGroup(blobs, args.vap_process_rate, args.context_len_sec, max_streams=args.streams,
+                                max_batch=min(args.streams, args.max_batch), device_id=0, groups=2, split_f16=(args.precision == "split"))
+        cores = None
+        if args.pin:
+            cores, _ = dist_util.front_end_placement(0, 1 + args.rx_threads + args.tx_threads)
+        srv = ingest.NativeServer.for_group(grp, port_in=args.port_num_in, ports_out=ports, gain=args.audio_gain,
+                                            max_wait_s=args.max_wait_ms * 1e-3, bind_any=args.bind_any, rx_threads=args.rx_threads,
+                                            tx_threads=args.tx_threads, cores=cores)
+    except Exception:
+        if srv is not None:
+            srv.close()
+        if grp is not None:
+            grp.close()
+        raise
+    return grp, srv
+
+
+def run_group(args, names, stop) -> int:
+    try:
+        grp, srv = build_group(args, names)
+    except Exception as e:                                      # noqa: BLE001
+        print(f"[vapx] start-up failed: {e}", file=sys.stderr, flush=True)
+        return 1
+    outs = ", ".join(f"{m} :{srv.ports_out[m]}" for m in names)
+    print(f"[vapx] 1 GPU(s) x {args.streams} dialogue slots, modes {'+'.join(names)} on one CPC trunk, {args.precision} arithmetic, "
+          f"{args.vap_process_rate} Hz / {args.context_len_sec} s — input :{srv.port_in}, output {outs}", flush=True)
+    last = time.time()
+    while not stop["now"]:
+        time.sleep(0.2)
+        if args.stats_sec > 0 and time.time() - last >= args.stats_sec:
+            last = time.time()
+            st = srv.stats(reset_latency_window=True)
+            print("[vapx] GPU 0: " + json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in st.items()}), flush=True)
+    srv.close()
+    grp.close()
+    return 0
 
 
 def choose_precision(args, mode):
@@ -208,12 +299,14 @@ def main(argv=None) -> int:
     ap.add_argument("--vap_model", type=str, default="../../asset/vap/vap_state_dict_jp_20hz_2500msec.pt")
     ap.add_argument("--cpc_model", type=str, default="../../asset/cpc/60k_epoch4-d0f474de.pt")
     ap.add_argument("--port_num_in", type=int, default=50007)
-    ap.add_argument("--port_num_out", type=int, default=50008)
+    ap.add_argument("--port_num_out", type=str, default=None, help="50008; with --mode a+b[+c] one port per model, comma-separated (default 50008, 50009, ...)")
     ap.add_argument("--vap_process_rate", type=int, default=20)
     ap.add_argument("--context_len_sec", type=float, default=2.5)
     ap.add_argument("--gpu", action="store_true", help="accepted for compatibility: this engine has no CPU path")
     ap.add_argument("--audio_gain", type=float, default=1.0)
-    ap.add_argument("--mode", choices=["vap", "bc", "nod"], default=None, help="head set (default: inferred from the state dict)")
+    ap.add_argument("--mode", type=str, default=None,
+                    help="head set: vap, bc or nod (default: inferred from the state dict), or a+b[+c] of distinct ones: several models on one shared "
+                         "CPC trunk, the first leads (then --vap_model takes one path per model, comma-separated)")
     ap.add_argument("--streams", type=int, default=1, help="dialogue slots per GPU (the reference serves exactly one)")
     ap.add_argument("--max_batch", type=int, default=1024)
     ap.add_argument("--gpus", type=int, default=1)
@@ -241,6 +334,24 @@ def main(argv=None) -> int:
     ap.add_argument("--worker-link", dest="worker_link", type=int, default=None, help=argparse.SUPPRESS)     # set by the door process
     ap.add_argument("--worker-rank", dest="worker_rank", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
+    args.port_num_out_default = args.port_num_out is None
+    if args.port_num_out is None:
+        args.port_num_out = "50008"
+    try:
+        names = group_modes(args.mode)
+        if names is None:
+            args.port_num_out = int(args.port_num_out)
+    except ValueError as e:
+        ap.error(str(e))
+    if names is not None:
+        if args.gpus > 1 or args.worker_procs == "on" or args.worker_link is not None:
+            print(f"[vapx] --mode {args.mode} serves one GPU from one process: the front door (--gpus > 1, --worker-procs on) is single-model",
+                  file=sys.stderr, flush=True)
+            return 2
+        stop = {"now": False}
+        signal.signal(signal.SIGTERM, lambda *_: stop.__setitem__("now", True))
+        signal.signal(signal.SIGINT, lambda *_: stop.__setitem__("now", True))
+        return run_group(args, names, stop)
     if args.worker_link is not None:
         return run_worker(args)
     if wants_worker_procs(args):
