@@ -228,6 +228,63 @@ int vapx_get_state(vapx_handle h, int32_t stream_id, float* ring, int32_t* n_fra
 int vapx_set_state(vapx_handle h, int32_t stream_id, const float* ring, int32_t n_frames, const float* lstm,
                    const float* carry);
 
+/* Bulk state export / import: snapshot, restore and migrate MANY streams in one stream-ordered call (a rolling restart, an upgrade, a
+ * GPU drain: INTEGRATION.md "Snapshots and migration").  The reference keeps the LSTM (h, c) of a dialogue for good and needs 2.5 - 10 s to
+ * refill its context window (vap_main.py:274-283), so a stream restarted from zeros never again matches the uninterrupted one.
+ *
+ * One fixed-size RECORD per stream, vapx_state_floats(h, flags) floats long (a multiple of 4: records stay 16-byte aligned), in order:
+ *   header  8 x int32 (32 bytes, stored in the float slots bit for bit):
+ *             [0] VAPX_STATE_MAGIC   [1] ctx_frames   [2] frame_hz
+ *             [3] content bits: VAPX_STATE_HAS_LSTM (LSTM + carry follow), VAPX_STATE_HAS_CACHE (the Q|K|V cache follows the ring),
+ *                 VAPX_STATE_CACHE_SPLIT (that cache was made by an engine created with VAPX_FLAG_SPLIT_F16)
+ *             [4] n_frames, 0 .. T: valid ring rows   [5] the exporting engine's mode (informational)   [6], [7] zero
+ *   lstm    [2 ch][2 (h, c)][256] and carry [2][320] (1664 floats) - a stand-alone engine or a trunk leader only.  A trunk follower's
+ *           records omit them: that state lives in its leader
+ *   ring    [2][T][256] chronological, oldest -> newest; rows t >= n_frames are written as ZEROS, so a blob is deterministic and never
+ *           carries uninitialised (or VAPX_POISON_SCRATCH) memory
+ *   cache   only with VAPX_STATE_CACHE: the layer-0 Q|K|V cache [2][T][768], same order, same zero fill
+ * Record k of a call belongs to stream_ids[k] and starts at float k * vapx_state_floats(h, flags).
+ *
+ *   n          : 1 .. max_streams (NOT limited by max_batch)
+ *   stream_ids : n distinct ids, host (checked as in vapx_step) or device (VAPX_IDS_DEVICE, unchecked); NULL means 0..n-1
+ *   dst / src  : the records; host memory (VAPX_OUT_HOST) or device memory (VAPX_OUT_DEVICE) - the bit names the space for both calls
+ *   flags      : VAPX_STATE_CACHE | VAPX_OUT_HOST / VAPX_OUT_DEVICE | VAPX_IDS_DEVICE
+ *
+ * Ordering: like a step.  The call makes hip_stream wait for overlap groups a VAPX_DEFER_JOIN step left running, applies queued
+ * vapx_reset_stream / vapx_reset_carry requests, then enqueues its work on hip_stream.  No device-wide synchronisation anywhere.  With a
+ * device buffer: no synchronisation at all, ONE gather (scatter) kernel for the whole call; work enqueued later on that stream sees the
+ * records (the imported state).  With a host buffer the records travel through a bounded device
+ * staging block (at most 32 MiB, or one record), one kernel and one copy per block: vapx_host_alloc memory is the DMA target / source itself
+ * and the call synchronises hip_stream ONCE, at its end; pageable memory is staged block by block through a pinned buffer of the same
+ * bounded size (one event wait per block) - never a second full-size pinned copy.  Host buffers are valid / reusable on return.
+ *
+ * Import: ring rows land in slots 0 .. n_frames-1, the window fill becomes n_frames, LSTM and carry go to the stream's slots.
+ *   - with VAPX_STATE_CACHE the cache rows are scattered as they are: no LayerNorm, no GEMM is launched, and the continuation consumes
+ *     exactly the cached values the source engine had - on the same checkpoint and flags it is BIT-IDENTICAL to the uninterrupted stream
+ *     (tests/test_state_bulk_gpu.py asserts equality, not a tolerance).  Such records go only into an engine of the same precision path
+ *     (VAPX_FLAG_SPLIT_F16 set or clear on both sides: the cached values differ); a mismatch is VAPX_E_INVAL;
+ *   - without it the cache is rebuilt as vapx_set_state does, LN(ring rows) . Wqkv^T on the fp32 path, batched over the streams of the
+ *     call in chunks of max_batch through the engine's scratch: three launches per chunk however many streams it holds.  Such records are
+ *     portable between the two precision paths; the continuation is then close to the uninterrupted one (1e-5), not equal.
+ * Validation happens on the host before anything is enqueued - a refused call modifies NO stream: n (VAPX_E_RANGE), host ids (VAPX_E_RANGE
+ * out of range, VAPX_E_INVAL duplicate), and for a host src every record's header: magic, ctx_frames, frame_hz, content bits (VAPX_E_INVAL:
+ * a leader / stand-alone record has VAPX_STATE_HAS_LSTM and is refused by a follower, and the reverse; VAPX_STATE_HAS_CACHE must agree
+ * with the flag; VAPX_STATE_CACHE_SPLIT with the engine) and n_frames in [0, T] (VAPX_E_RANGE); vapx_last_error names the record index
+ * and the field.  A DEVICE src cannot be read without a synchronisation: the kernel clamps n_frames into [0, T] and trusts the rest - the
+ * caller vouches for records it keeps on the device (they came from vapx_export_streams of a matching engine).
+ * Trunk groups: export / import on the leader moves LSTM + carry + the leader's ring, on a follower that follower's ring (+ cache);
+ * after importing a stream into the leader AND every follower, vapx_step_group and the plain leader / follower steps continue as if the
+ * stream had been stepped there. */
+#define VAPX_STATE_CACHE 16         /* flags bit of vapx_state_floats / vapx_export_streams / vapx_import_streams */
+#define VAPX_STATE_MAGIC 0x31535056 /* "VPS1" */
+#define VAPX_STATE_HAS_LSTM 1
+#define VAPX_STATE_HAS_CACHE 2
+#define VAPX_STATE_CACHE_SPLIT 4
+#define VAPX_STATE_HEADER_FLOATS 8
+size_t vapx_state_floats(vapx_handle h, int32_t flags);
+int vapx_export_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, float* dst, int32_t flags, void* hip_stream);
+int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* src, int32_t flags, void* hip_stream);
+
 /* Stage-level entry points: the model-attribute surface process_vap calls (SURVEY.md §8b level 1).
  * All pointers are DEVICE memory, fp32, contiguous.  They use the handle's weights and scratch
  * but touch no stream state except vapx_encode_audio (LSTM h/c of the given stream ids). */
@@ -351,6 +408,10 @@ typedef struct vapx_ingest_config {
 #define VAPX_INGEST_CORE_SET 2      /* with cpu_count > 0: every front-end thread may run on ANY core of the range (one affinity set) instead of
                                        one core each: keeps other processes' work off the range without nailing a thread to a core that the
                                        kernel then borrows for softirq work */
+#define VAPX_INGEST_KEEP_STATE 4    /* the engine's streams hold imported state (vapx_import_streams): vapx_ingest_open / _open_group skip their warm-up, which
+                                       steps the first max_batch streams on silence and then resets them.  Step the engine once BEFORE importing
+                                       instead (the first vapx_step of a process loads the code objects: hundreds of ms).  Combine with
+                                       reset_on_connect = 0, or the first connection on a slot clears what was imported */
 #define VAPX_INGEST_KEEP_NOFILE 1   /* never touch RLIMIT_NOFILE.  Default (flag clear): vapx_ingest_open* needs one descriptor per dialogue
                                        and one per listener; if the process's SOFT limit is below 2 x streams + 256 it is raised towards the
                                        hard limit with setrlimit() — a process-wide change the host should know about (select()-based code

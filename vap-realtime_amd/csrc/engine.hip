@@ -128,6 +128,12 @@ struct vapx_engine {
   float *gw_dev = nullptr, *gw_pinned = nullptr;
   size_t gw_cap = 0;                      // floats either block holds
   std::vector<std::pair<int32_t, int32_t>> group_bad;   // (batch slot, model index) pairs of the latest host-output vapx_step_group
+  // vapx_export_streams / vapx_import_streams: ids of up to max_streams streams; bounded staging blocks for host records (allocated
+  // on the first host-buffer call; the pinned one only for pageable memory)
+  int *sio_ids_dev = nullptr, *sio_ids_pinned = nullptr;
+  hipEvent_t sio_ids_evt = nullptr, sio_evt = nullptr;   // the copy out of sio_ids_pinned / the copy out of (into) sio_pin has completed
+  float *sio_dev = nullptr, *sio_pin = nullptr;
+  size_t sio_dev_cap = 0, sio_pin_cap = 0;               // floats
 
   // optional per-kernel-class HIP-event timing (vapx_profile_*): events are recorded on the launch
   // stream around the launches whose class bit is set in prof_mask
@@ -671,16 +677,22 @@ __global__ void compact_rows_kernel(float* dst, const float* src, int T, int row
   ((f32x4*)dst)[i] = ((const f32x4*)src)[(bc * T + t) * 64 + q];
 }
 
-int upload_ids(vapx_engine* h, int n, const int32_t* ids, int flags, hipStream_t st, const int** out) {
-  if (!ids) { *out = nullptr; return VAPX_OK; }
-  if (flags & VAPX_IDS_DEVICE) { *out = ids; return VAPX_OK; }
+// host stream ids of one call: in range and distinct
+int check_ids(vapx_engine* h, int n, const int32_t* ids) {
   if (++h->id_gen == 0) { std::fill(h->id_stamp.begin(), h->id_stamp.end(), 0u); h->id_gen = 1; }
   for (int i = 0; i < n; ++i) {
     if (ids[i] < 0 || ids[i] >= h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "stream id %d out of range [0,%d)", ids[i], h->cfg.max_streams);
     // two batch slots on one stream would race on its ring slot, LSTM state, carry and frame counter
-    if (h->id_stamp[ids[i]] == h->id_gen) return fail(h, VAPX_E_INVAL, "stream id %d appears twice in one step (batch slot %d)", ids[i], i);
+    if (h->id_stamp[ids[i]] == h->id_gen) return fail(h, VAPX_E_INVAL, "stream id %d appears twice in one call (batch slot %d)", ids[i], i);
     h->id_stamp[ids[i]] = h->id_gen;
   }
+  return VAPX_OK;
+}
+
+int upload_ids(vapx_engine* h, int n, const int32_t* ids, int flags, hipStream_t st, const int** out) {
+  if (!ids) { *out = nullptr; return VAPX_OK; }
+  if (flags & VAPX_IDS_DEVICE) { *out = ids; return VAPX_OK; }
+  { int rc = check_ids(h, n, ids); if (rc) return rc; }
   HIPCHK(h, hipEventSynchronize(h->ids_evt));  // previous async copy out of the pinned buffer is done
   memcpy(h->ids_pinned, ids, n * sizeof(int));
   HIPCHK(h, hipMemcpyAsync(h->ids_dev, h->ids_pinned, n * sizeof(int), hipMemcpyHostToDevice, st));
@@ -863,6 +875,12 @@ void vapx_destroy(vapx_handle h) {
   int* ip[] = {h->frames_seen, h->ids_dev, h->sc.bn, h->sc.bhead, h->sc.rot};
   for (int* p : ip) dfree(p);
   dfree(h->gw_dev);
+  dfree(h->sio_dev);
+  dfree(h->sio_ids_dev);
+  if (h->sio_pin) (void)hipHostFree(h->sio_pin);
+  if (h->sio_ids_pinned) (void)hipHostFree(h->sio_ids_pinned);
+  if (h->sio_ids_evt) (void)hipEventDestroy(h->sio_ids_evt);
+  if (h->sio_evt) (void)hipEventDestroy(h->sio_evt);
   if (h->gw_pinned) (void)hipHostFree(h->gw_pinned);
   if (h->out_pinned) (void)hipHostFree(h->out_pinned);
   if (h->ids_pinned) (void)hipHostFree(h->ids_pinned);
@@ -1016,6 +1034,8 @@ int vapx_create(const vapx_config* cfg, const float* blob, size_t n_floats, vapx
   CR(hipHostMalloc((void**)&h->out_pinned, B * VAPX_OUT_STRIDE * sizeof(float), hipHostMallocDefault));
   CR(hipHostMalloc((void**)&h->ids_pinned, B * sizeof(int), hipHostMallocDefault));
   CR(hipHostMalloc((void**)&h->audio_pinned, B * 2 * h->L * sizeof(float), hipHostMallocDefault));
+  CR(dalloc(&h->sio_ids_dev, S));
+  CR(hipHostMalloc((void**)&h->sio_ids_pinned, S * sizeof(int), hipHostMallocDefault));
   h->id_stamp.assign(S, 0u);
   h->force_xl = getenv("VAPX_FORCE_ATTENTION_XL") != nullptr;
   if (getenv("VAPX_POISON_SCRATCH")) {
@@ -1051,6 +1071,10 @@ int vapx_create(const vapx_config* cfg, const float* blob, size_t n_floats, vapx
   CR(hipEventRecord(h->ids_evt, nullptr));
   CR(hipEventCreateWithFlags(&h->audio_evt, hipEventDisableTiming));
   CR(hipEventRecord(h->audio_evt, nullptr));
+  CR(hipEventCreateWithFlags(&h->sio_ids_evt, hipEventDisableTiming));
+  CR(hipEventRecord(h->sio_ids_evt, nullptr));
+  CR(hipEventCreateWithFlags(&h->sio_evt, hipEventDisableTiming));
+  CR(hipEventRecord(h->sio_evt, nullptr));
   CR(hipDeviceSynchronize());
 #undef CR
   *out = h;
@@ -1412,6 +1436,214 @@ int vapx_set_state(vapx_handle h, int32_t sid, const float* ring, int32_t n_fram
     }
   }
   if (carry) HIPCHK(h, hipMemcpy(h->carry + (size_t)sid * 2 * VAPX_PAD, carry, 2 * VAPX_PAD * sizeof(float), hipMemcpyHostToDevice));
+  return VAPX_OK;
+}
+
+// ---- bulk state export / import (vapx.h "Bulk state export / import"; kernels in state_io.hip) ----------------------------------------
+namespace {
+
+constexpr size_t kStateStageFloats = (size_t)8 << 20;   // 32 MiB: host records travel through device / pinned blocks of at most this size
+
+bool sio_follower(const vapx_engine* h) { return h->trunk != nullptr || h->orphaned; }
+
+size_t state_floats(const vapx_engine* h, int flags) {
+  return VAPX_STATE_HEADER_FLOATS + (sio_follower(h) ? 0 : (size_t)(1024 + 2 * VAPX_PAD)) + (size_t)2 * h->T * 256 +
+         ((flags & VAPX_STATE_CACHE) ? (size_t)2 * h->T * 768 : 0);
+}
+
+// what every state call does first: order `st` behind un-joined overlap groups and apply the queued resets (they live in the leader and
+// touch every engine of its trunk group, so with resets pending every engine's groups are joined first)
+int sio_begin(vapx_engine* h, hipStream_t st) {
+  (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  int rc = join_deferred(h, st);
+  if (rc) return rc;
+  vapx_engine* lead = h->trunk ? h->trunk : h;
+  if (!lead->pending_resets.empty()) {
+    if ((rc = join_deferred(lead, st))) return rc;
+    for (vapx_engine* f : lead->followers)
+      if ((rc = join_deferred(f, st))) return rc;
+    rc = flush_resets(lead, st);
+    if (rc) return h == lead ? rc : fail(h, rc, "trunk leader: %s", lead->err.c_str());
+  }
+  return VAPX_OK;
+}
+
+// common argument checks; host ids are validated here, before anything is enqueued
+int sio_check(vapx_engine* h, const char* what, int n, const int32_t* ids, const void* buf, int flags) {
+  if (n < 1 || n > h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "%s: n=%d outside [1,%d] (max_streams)", what, n, h->cfg.max_streams);
+  if (!buf) return fail(h, VAPX_E_INVAL, "%s: null record buffer", what);
+  if ((uintptr_t)buf & 15) return fail(h, VAPX_E_INVAL, "%s: the record buffer must be 16-byte aligned", what);
+  if (flags & ~(VAPX_STATE_CACHE | VAPX_OUT_DEVICE | VAPX_IDS_DEVICE)) return fail(h, VAPX_E_INVAL, "%s: unknown flag bits 0x%x", what, flags);
+  if (ids && !(flags & VAPX_IDS_DEVICE)) return check_ids(h, n, ids);
+  return VAPX_OK;
+}
+
+// device copy of host ids (up to max_streams of them: the step's id buffers hold max_batch)
+int sio_ids(vapx_engine* h, int n, const int32_t* ids, int flags, hipStream_t st, const int** out) {
+  if (!ids || (flags & VAPX_IDS_DEVICE)) { *out = ids; return VAPX_OK; }
+  HIPCHK(h, hipEventSynchronize(h->sio_ids_evt));   // the previous copy out of the pinned buffer is done
+  memcpy(h->sio_ids_pinned, ids, (size_t)n * sizeof(int));
+  HIPCHK(h, hipMemcpyAsync(h->sio_ids_dev, h->sio_ids_pinned, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipEventRecord(h->sio_ids_evt, st));
+  *out = h->sio_ids_dev;
+  return VAPX_OK;
+}
+
+// staging blocks for host records: streams per block (>= 1).  Every host-buffer call ends with the stream synchronised, so a block that
+// has to grow is idle.
+int sio_stage(vapx_engine* h, size_t rec, int n, bool need_pinned, int* per_block) {
+  size_t cap = kStateStageFloats;
+  if (const char* ev = getenv("VAPX_STATE_STAGE_FLOATS")) {   // debug knob: small blocks, so that a test with a handful of streams takes the multi-block path
+    const long v = atol(ev);
+    if (v > 0) cap = (size_t)v;
+  }
+  size_t per = cap / rec;
+  if (per < 1) per = 1;
+  if (per > (size_t)n) per = (size_t)n;
+  const size_t want = per * rec;
+  if (h->sio_dev_cap < want) {
+    dfree(h->sio_dev); h->sio_dev = nullptr; h->sio_dev_cap = 0;
+    hipError_t e = dalloc(&h->sio_dev, want, false);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, VAPX_E_NOMEM, "state staging block (%zu bytes, device): %s", want * 4, hipGetErrorString(e)); }
+    h->sio_dev_cap = want;
+  }
+  if (need_pinned && h->sio_pin_cap < want) {
+    if (h->sio_pin) (void)hipHostFree(h->sio_pin);
+    h->sio_pin = nullptr; h->sio_pin_cap = 0;
+    hipError_t e = hipHostMalloc((void**)&h->sio_pin, want * sizeof(float), hipHostMallocDefault);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, VAPX_E_NOMEM, "state staging block (%zu bytes, pinned): %s", want * 4, hipGetErrorString(e)); }
+    h->sio_pin_cap = want;
+  }
+  *per_block = (int)per;
+  return VAPX_OK;
+}
+
+StateIoArgs sio_args(vapx_engine* h, int flags, float* rec, const int* ids, int n) {
+  StateIoArgs a;
+  memset(&a, 0, sizeof a);
+  a.rec = rec; a.rec_floats = (long)state_floats(h, flags); a.ids = ids; a.id0 = 0;
+  a.ring = h->ring; a.ring_qkv = h->ring_qkv; a.h_state = h->h_state; a.c_state = h->c_state; a.carry = h->carry;
+  a.frames_seen = h->frames_seen; a.T = h->T; a.n = n;
+  a.with_state = sio_follower(h) ? 0 : 1; a.with_cache = (flags & VAPX_STATE_CACHE) ? 1 : 0;
+  a.hdr[0] = VAPX_STATE_MAGIC; a.hdr[1] = h->T; a.hdr[2] = h->cfg.frame_hz;
+  a.hdr[3] = (a.with_state ? VAPX_STATE_HAS_LSTM : 0) |
+             (a.with_cache ? VAPX_STATE_HAS_CACHE | ((h->cfg.flags & VAPX_FLAG_SPLIT_F16) ? VAPX_STATE_CACHE_SPLIT : 0) : 0);
+  a.hdr[5] = h->cfg.mode;
+  return a;
+}
+
+}  // namespace
+
+size_t vapx_state_floats(vapx_handle h, int32_t flags) { return h ? state_floats(h, flags) : 0; }
+
+int vapx_export_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, float* dst, int32_t flags, void* hip_stream) {
+  if (!h) return VAPX_E_INVAL;
+  { int rc = sio_check(h, "vapx_export_streams", n, stream_ids, dst, flags); if (rc) return rc; }
+  hipStream_t st = (hipStream_t)hip_stream;
+  int rc = sio_begin(h, st);
+  if (rc) return rc;
+  const int* ids = nullptr;
+  if ((rc = sio_ids(h, n, stream_ids, flags, st, &ids))) return rc;
+  if (flags & VAPX_OUT_DEVICE) {   // one gather kernel, no synchronisation
+    HIPCHK(h, launch_state_export(sio_args(h, flags, dst, ids, n), st));
+    return VAPX_OK;
+  }
+  const size_t rec = state_floats(h, flags);
+  const bool direct = is_pinned_host(dst);   // vapx_host_alloc memory: the copies land in the caller's block
+  int per = 1;
+  if ((rc = sio_stage(h, rec, n, !direct, &per))) return rc;
+  for (int k0 = 0; k0 < n; k0 += per) {
+    const int nb = std::min(per, n - k0);
+    StateIoArgs a = sio_args(h, flags, h->sio_dev, ids ? ids + k0 : nullptr, nb);
+    a.id0 = k0;
+    HIPCHK(h, launch_state_export(a, st));
+    const size_t bytes = (size_t)nb * rec * sizeof(float);
+    float* to = dst + (size_t)k0 * rec;
+    if (direct) {
+      HIPCHK(h, hipMemcpyAsync(to, h->sio_dev, bytes, hipMemcpyDeviceToHost, st));
+    } else {   // pageable: block by block through the pinned buffer
+      HIPCHK(h, hipMemcpyAsync(h->sio_pin, h->sio_dev, bytes, hipMemcpyDeviceToHost, st));
+      HIPCHK(h, hipEventRecord(h->sio_evt, st));
+      HIPCHK(h, hipEventSynchronize(h->sio_evt));
+      memcpy(to, h->sio_pin, bytes);
+    }
+  }
+  HIPCHK(h, hipStreamSynchronize(st));
+  return VAPX_OK;
+}
+
+int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* src, int32_t flags, void* hip_stream) {
+  if (!h) return VAPX_E_INVAL;
+  { int rc = sio_check(h, "vapx_import_streams", n, stream_ids, src, flags); if (rc) return rc; }
+  const size_t rec = state_floats(h, flags);
+  const bool with_cache = (flags & VAPX_STATE_CACHE) != 0, on_host = !(flags & VAPX_OUT_DEVICE);
+  const int T = h->T;
+  if (on_host) {   // every header, before any stream is touched
+    const int want_bits = (sio_follower(h) ? 0 : VAPX_STATE_HAS_LSTM) | (with_cache ? VAPX_STATE_HAS_CACHE : 0);
+    const int split_bit = (h->cfg.flags & VAPX_FLAG_SPLIT_F16) ? VAPX_STATE_CACHE_SPLIT : 0;
+    for (int k = 0; k < n; ++k) {
+      int32_t hd[8];
+      memcpy(hd, src + (size_t)k * rec, sizeof hd);
+      if (hd[0] != VAPX_STATE_MAGIC) return fail(h, VAPX_E_INVAL, "record %d: magic 0x%08x is not a state record (0x%08x)", k, hd[0], VAPX_STATE_MAGIC);
+      if (hd[1] != T) return fail(h, VAPX_E_INVAL, "record %d: ctx_frames %d differs from this engine's %d", k, hd[1], T);
+      if (hd[2] != h->cfg.frame_hz) return fail(h, VAPX_E_INVAL, "record %d: frame_hz %d differs from this engine's %d", k, hd[2], h->cfg.frame_hz);
+      if ((hd[3] & VAPX_STATE_HAS_LSTM) != (want_bits & VAPX_STATE_HAS_LSTM))
+        return fail(h, VAPX_E_INVAL, "record %d: content bits 0x%x: %s", k, hd[3],
+                    sio_follower(h) ? "a leader / stand-alone record (LSTM + carry) offered to a trunk follower"
+                                    : "a trunk follower's record (no LSTM + carry) offered to a leader / stand-alone engine");
+      if ((hd[3] & VAPX_STATE_HAS_CACHE) != (want_bits & VAPX_STATE_HAS_CACHE))
+        return fail(h, VAPX_E_INVAL, "record %d: content bits 0x%x: the record %s a Q|K|V cache, the call's flags say it %s", k, hd[3],
+                    (hd[3] & VAPX_STATE_HAS_CACHE) ? "carries" : "carries no", with_cache ? "does" : "does not");
+      if (with_cache && (hd[3] & VAPX_STATE_CACHE_SPLIT) != split_bit)
+        return fail(h, VAPX_E_INVAL, "record %d: content bits 0x%x: the Q|K|V cache was made on the %s path, this engine runs the %s path "
+                    "(import without VAPX_STATE_CACHE: records without a cache are portable)", k, hd[3],
+                    (hd[3] & VAPX_STATE_CACHE_SPLIT) ? "split-precision" : "fp32", split_bit ? "split-precision" : "fp32");
+      if (hd[4] < 0 || hd[4] > T) return fail(h, VAPX_E_RANGE, "record %d: n_frames %d outside [0,%d]", k, hd[4], T);
+    }
+  }
+  hipStream_t st = (hipStream_t)hip_stream;
+  int rc = sio_begin(h, st);
+  if (rc) return rc;
+  const int* ids = nullptr;
+  if ((rc = sio_ids(h, n, stream_ids, flags, st, &ids))) return rc;
+  if (!on_host) {   // one scatter kernel, no synchronisation
+    HIPCHK(h, launch_state_import(sio_args(h, flags, const_cast<float*>(src), ids, n), st));
+  } else {
+    const bool direct = is_pinned_host(src);
+    int per = 1;
+    if ((rc = sio_stage(h, rec, n, !direct, &per))) return rc;
+    for (int k0 = 0; k0 < n; k0 += per) {
+      const int nb = std::min(per, n - k0);
+      const size_t bytes = (size_t)nb * rec * sizeof(float);
+      const float* from = src + (size_t)k0 * rec;
+      if (!direct) {
+        HIPCHK(h, hipEventSynchronize(h->sio_evt));   // the previous block has left the pinned buffer
+        memcpy(h->sio_pin, from, bytes);
+        from = h->sio_pin;
+      }
+      HIPCHK(h, hipMemcpyAsync(h->sio_dev, from, bytes, hipMemcpyHostToDevice, st));
+      if (!direct) HIPCHK(h, hipEventRecord(h->sio_evt, st));
+      StateIoArgs a = sio_args(h, flags, h->sio_dev, ids ? ids + k0 : nullptr, nb);
+      a.id0 = k0;
+      HIPCHK(h, launch_state_import(a, st));
+    }
+  }
+  if (!with_cache) {
+    // rebuild the layer-0 Q|K|V cache of the imported rows as vapx_set_state does, LN(ring rows) . Wqkv^T (fp32 path), for up to
+    // max_batch streams per pass through the step's scratch: LN, one GEMM, one scatter - whatever the number of streams in the pass
+    const int B = h->cfg.max_batch;
+    for (int k0 = 0; k0 < n; k0 += B) {
+      const int nb = std::min(B, n - k0);
+      const int* cids = ids ? ids + k0 : nullptr;
+      { ProfScope ps(h, CLS_GATHER, st);
+        HIPCHK(h, launch_state_ln(h->ring, cids, k0, h->sc.xn, h->layer[0].ln_self_g, h->layer[0].ln_self_b, T, nb, st)); }
+      GemmArgs g = gemm_args(h->sc.xn, contiguous_rows(256), h->layer[0].wqkv, nb * 2 * T, 768, 256, h->sc.qkv, contiguous_rows(768));
+      { ProfScope ps(h, gemm_class(EPI_STORE), st); HIPCHK(h, launch_gemm_f32(g, EPI_STORE, 0, st)); }
+      HIPCHK(h, launch_state_cache_scatter(h->sc.qkv, cids, k0, h->ring_qkv, h->frames_seen, T, nb, st));
+    }
+  }
+  if (on_host) HIPCHK(h, hipStreamSynchronize(st));
   return VAPX_OK;
 }
 

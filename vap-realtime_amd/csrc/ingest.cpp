@@ -1130,8 +1130,10 @@ int vapx_ingest_open(vapx_handle engine, const vapx_ingest_config* cfg, vapx_ing
   g->engine = engine;
   g->step = engine_step; g->reset = engine_reset; g->user = g;
   g->S = ec.max_streams; g->max_batch = ec.max_batch; g->hz = ec.frame_hz; g->ports[0].mode = ec.mode;
-  {  // warm the engine up before the first client connects: the first vapx_step of a process loads the code objects and sizes
-     // the runtime's pools (hundreds of ms) — paid here on silence, then every touched stream is reset
+  if (!(probe.flags & VAPX_INGEST_KEEP_STATE)) {
+     // warm the engine up before the first client connects: the first vapx_step of a process loads the code objects and sizes
+     // the runtime's pools (hundreds of ms) — paid here on silence, then every touched stream is reset (VAPX_INGEST_KEEP_STATE: the
+     // streams hold imported state and the caller has warmed the engine up before importing)
     const int nw = ec.max_batch, hop = 16000 / ec.frame_hz;
     float* a = (float*)vapx_host_alloc((size_t)nw * 2 * hop * sizeof(float));
     float* o = (float*)vapx_host_alloc((size_t)nw * VAPX_OUT_STRIDE * sizeof(float));
@@ -1215,7 +1217,7 @@ int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int
   g->engine = leader;
   g->step = engine_group_step; g->reset = engine_reset; g->user = g;
   g->S = ec.max_streams; g->max_batch = ec.max_batch; g->hz = ec.frame_hz;
-  {  // warm-up on silence as in vapx_ingest_open, the whole group per tick; every touched stream is reset (the leader cascades)
+  if (!(probe.flags & VAPX_INGEST_KEEP_STATE)) {  // warm-up on silence as in vapx_ingest_open, the whole group per tick; every touched stream is reset (the leader cascades)
     const int nw = ec.max_batch, hop = 16000 / ec.frame_hz;
     float* a = (float*)vapx_host_alloc((size_t)nw * 2 * hop * sizeof(float));
     float* o = (float*)vapx_host_alloc((size_t)nw * g->row_floats * sizeof(float));

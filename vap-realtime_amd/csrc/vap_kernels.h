@@ -127,6 +127,23 @@ struct WirePackArgs {   // wire_pack_kernel: up to 4 models per launch
   int n_models, n, src_stride;
 };
 
+struct StateIoArgs {    // state_io.hip: bulk stream-state export / import (vapx_export_streams / vapx_import_streams)
+  float* rec;           // [n][rec_floats] records (device): header | lstm + carry (with_state) | ring [2][T][256] | cache [2][T][768] (with_cache)
+  long rec_floats;
+  const int* ids;       // [n] stream slots (device) or null: slot = id0 + k
+  int id0;
+  float *ring, *ring_qkv, *h_state, *c_state, *carry;   // per-stream state bases (h_state / c_state / carry unused without with_state)
+  int* frames_seen;
+  int T, n, with_state, with_cache;
+  int hdr[8];           // export: the header words as they are written, [4] (n_frames) filled in per stream
+};
+
+hipError_t launch_state_export(const StateIoArgs& a, hipStream_t st);
+hipError_t launch_state_import(const StateIoArgs& a, hipStream_t st);
+// cache rebuild of an import without cache: xn[(k*2+c)*T + t] = LayerNorm(ring row (slot ids[k], c, t)); after the GEMM, rows t < window fill
+// of qkv [n][2][T][768] go to the streams' cache slots
+hipError_t launch_state_ln(const float* ring, const int* ids, int id0, float* xn, const float* gamma, const float* beta, int T, int n, hipStream_t st);
+hipError_t launch_state_cache_scatter(const float* qkv, const int* ids, int id0, float* ring_qkv, const int* frames_seen, int T, int n, hipStream_t st);
 hipError_t launch_conv0(const Conv0Args& a, int B, hipStream_t st);
 hipError_t launch_lstm(const LstmArgs& a, hipStream_t st);
 hipError_t launch_ring_append(const GatherArgs& a, hipStream_t st);

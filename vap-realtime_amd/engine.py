@@ -22,6 +22,12 @@ OUT_STATUS = 13
 E_NUMERIC = -6
 ABI_VERSION = 2
 AUDIO_DEVICE, OUT_DEVICE, IDS_DEVICE = 1, 2, 4
+# bulk state records (vapx.h "Bulk state export / import")
+STATE_CACHE = 16
+STATE_MAGIC = 0x31535056
+STATE_HAS_LSTM, STATE_HAS_CACHE, STATE_CACHE_SPLIT = 1, 2, 4
+STATE_HEADER_FLOATS = 8
+STATE_LSTM_FLOATS, STATE_CARRY_FLOATS = 2 * 2 * 256, 2 * 320
 MODE = {"vap": 0, "bc": 1, "nod": 2}
 
 EXPORTS = ("vapx_abi_version", "vapx_blob_floats", "vapx_create", "vapx_destroy", "vapx_step",
@@ -32,7 +38,8 @@ EXPORTS = ("vapx_abi_version", "vapx_blob_floats", "vapx_create", "vapx_destroy"
            "vapx_wire_decode_input", "vapx_wire_encode_result", "vapx_vap_head", "vapx_va_classifier", "vapx_softmax256",
            "vapx_aggregate", "vapx_aux_head", "vapx_frontdoor_open", "vapx_frontdoor_open_links", "vapx_ingest_attach_link", "vapx_frontdoor_ports", "vapx_frontdoor_counts", "vapx_frontdoor_close",
            "vapx_wire_floats", "vapx_group_wire_floats", "vapx_step_group", "vapx_group_bad", "vapx_ingest_open_group",
-           "vapx_ingest_open_group_fn", "vapx_ingest_group_ports", "vapx_ingest_last_open_error")
+           "vapx_ingest_open_group_fn", "vapx_ingest_group_ports", "vapx_ingest_last_open_error",
+           "vapx_state_floats", "vapx_export_streams", "vapx_import_streams")
 PROF_CLASSES = {0: "gemm_store", 1: "gemm_gelu", 2: "gemm_resid", 3: "gemm_resid_ln", 4: "gemm_cn_relu",
                 5: "conv_tail", 6: "ffn_block", 7: "last_row", 8: "conv0", 9: "lstm", 10: "gather_ln", 11: "attention", 12: "head",
                 13: "gemm_bias_ln_gelu", 14: "ffn_proj"}
@@ -86,6 +93,12 @@ def load_library(path: Optional[str] = None):
     lib.vapx_get_state.argtypes = [vp, i32, f32p, C.POINTER(i32), f32p, f32p]
     lib.vapx_set_state.restype = i32
     lib.vapx_set_state.argtypes = [vp, i32, f32p, i32, f32p, f32p]
+    lib.vapx_state_floats.restype = C.c_size_t
+    lib.vapx_state_floats.argtypes = [vp, i32]
+    lib.vapx_export_streams.restype = i32
+    lib.vapx_export_streams.argtypes = [vp, i32, i32p, f32p, i32, vp]
+    lib.vapx_import_streams.restype = i32
+    lib.vapx_import_streams.argtypes = [vp, i32, i32p, f32p, i32, vp]
     lib.vapx_encode_audio.restype = i32
     lib.vapx_encode_audio.argtypes = [vp, i32, i32p, f32p, f32p, vp]
     lib.vapx_transformer.restype = i32
@@ -228,6 +241,7 @@ class Engine:
         flags = ((groups & 0xF) | (16 if full_last_layer else 0) | (32 if unfused_conv else 0)
                  | (64 if materialize_x0 else 0) | (256 if unfused_last_row else 0) | (512 if split_f16 else 0) | (1024 if unfused_proj else 0)
                  | (2048 if split_qkv_in_ffn else 0))
+        self.split_f16 = bool(split_f16)
         cfg = _Config(C.sizeof(_Config), device_id, frame_hz, self.T, max_streams, self.max_batch, MODE[mode], flags)
         h = C.c_void_p()
         rc = self.lib.vapx_create(C.byref(cfg), _np_ptr(blob), blob.size, C.byref(h))
@@ -373,6 +387,58 @@ class Engine:
         carry = None if state.get("carry") is None else np.ascontiguousarray(state["carry"], np.float32)
         self._check(self.lib.vapx_set_state(self._h, sid, _np_ptr(ring), int(state["n_frames"]), _np_ptr(lstm), _np_ptr(carry)), "vapx_set_state")
 
+    # -- bulk state export / import (snapshot, restore, migrate) -----------------------------------------
+    def state_floats(self, cache: bool = False) -> int:
+        """Floats of one state record of this engine (vapx.h, vapx_state_floats): ``state_record_floats`` for its window and role."""
+        return int(self.lib.vapx_state_floats(self._h, STATE_CACHE if cache else 0))
+
+    def _state_ids(self, ids):
+        if ids is None:
+            ids = np.arange(self.max_streams, dtype=np.int32)
+        return np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+
+    def export_streams(self, ids: Optional[Sequence[int]] = None, cache: bool = False, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """State records of streams ``ids`` (None: every slot) as float32 [n, state_floats(cache)], in ONE stream-ordered call
+        (vapx_export_streams; ``split_state`` names the fields).  ``out``: e.g. a ``pinned_empty`` block, filled by DMA directly."""
+        ids = self._state_ids(ids)
+        n, fl = ids.size, self.state_floats(cache)
+        if out is None:
+            out = np.empty((n, fl), dtype=np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size >= n * fl
+        self._check(self.lib.vapx_export_streams(self._h, n, _np_ptr(ids), _np_ptr(out), STATE_CACHE if cache else 0, None),
+                    "vapx_export_streams")
+        return out.reshape(-1)[:n * fl].reshape(n, fl)
+
+    def import_streams(self, ids: Optional[Sequence[int]], records: np.ndarray, cache: Optional[bool] = None):
+        """Put state records [n, floats] into streams ``ids`` (None: slots 0..n-1).  ``cache``: the records carry the layer-0 Q|K|V
+        cache (None: told from their length).  Every header is validated before any stream changes (vapx_import_streams)."""
+        records = np.asarray(records)
+        if records.dtype != np.float32 or not records.flags.c_contiguous:
+            records = np.ascontiguousarray(records, dtype=np.float32)
+        if records.ndim != 2:
+            raise VapxError(f"records must be [n, floats], got shape {records.shape}")
+        if cache is None:
+            cache = records.shape[1] == self.state_floats(True)
+        if records.shape[1] != self.state_floats(cache):
+            raise VapxError(f"record length {records.shape[1]} floats: this engine's records have {self.state_floats(False)} "
+                            f"(without cache) or {self.state_floats(True)} (with cache)")
+        n = records.shape[0]
+        ids = np.arange(n, dtype=np.int32) if ids is None else self._state_ids(ids)
+        if ids.size != n:
+            raise VapxError(f"{ids.size} stream ids for {n} records")
+        self._check(self.lib.vapx_import_streams(self._h, n, _np_ptr(ids), _np_ptr(records), STATE_CACHE if cache else 0, None),
+                    "vapx_import_streams")
+
+    def export_streams_device(self, n: int, dst_ptr: int, ids_ptr: int = 0, cache: bool = False, stream: int = 0):
+        """Device twin of ``export_streams``: raw device pointers, one gather kernel enqueued on ``stream``, no synchronisation."""
+        flags = OUT_DEVICE | (IDS_DEVICE if ids_ptr else 0) | (STATE_CACHE if cache else 0)
+        self._check(self.lib.vapx_export_streams(self._h, n, ids_ptr or None, dst_ptr, flags, stream or None), "vapx_export_streams")
+
+    def import_streams_device(self, n: int, src_ptr: int, ids_ptr: int = 0, cache: bool = False, stream: int = 0):
+        """Device twin of ``import_streams``: the records are trusted (only n_frames is clamped), no synchronisation."""
+        flags = OUT_DEVICE | (IDS_DEVICE if ids_ptr else 0) | (STATE_CACHE if cache else 0)
+        self._check(self.lib.vapx_import_streams(self._h, n, ids_ptr or None, src_ptr, flags, stream or None), "vapx_import_streams")
+
     def profile_enable(self, classes=()):
         mask = 0
         for c in classes:
@@ -461,6 +527,17 @@ class TrunkGroup:
     def reset_stream(self, sid: int):
         self.leader.reset_stream(sid)                      # cascades to the followers
 
+    def export_streams(self, ids: Optional[Sequence[int]] = None, cache: bool = False) -> dict:
+        """``{mode: records}``, leader first: the leader's records carry LSTM + carry, a follower's only its ring (+ cache)."""
+        return {m: self.engines[m].export_streams(ids, cache) for m in self.modes}
+
+    def import_streams(self, ids: Optional[Sequence[int]], records: dict, cache: Optional[bool] = None):
+        """Inverse of ``export_streams``; ``records`` must name exactly this group's modes."""
+        if set(records) != set(self.modes):
+            raise VapxError(f"records for modes {sorted(records)}, this group serves {self.modes}")
+        for m in self.modes:
+            self.engines[m].import_streams(ids, records[m], cache)
+
     def close(self):
         for m in reversed(self.modes):                     # followers before their leader
             self.engines[m].close()
@@ -476,6 +553,38 @@ def split_outputs(out: np.ndarray) -> dict:
         "status": out[:, OUT_STATUS].astype(np.int32),
         "e": out[:, OUT_E:OUT_E + 512].reshape(-1, 2, 256),
     }
+
+
+def state_record_floats(ctx_frames: int, cache: bool = False, follower: bool = False) -> int:
+    """Length of a state record (the layout in vapx.h): header, LSTM + carry unless ``follower``, ring, optional Q|K|V cache."""
+    T = int(ctx_frames)
+    return (STATE_HEADER_FLOATS + (0 if follower else STATE_LSTM_FLOATS + STATE_CARRY_FLOATS) + 2 * T * 256
+            + (2 * T * 768 if cache else 0))
+
+
+def split_state(records: np.ndarray, T: int, follower: bool = False) -> dict:
+    """Name the fields of state records [n, floats] (views, as ``split_outputs`` does for output rows): the header words
+    ``magic`` / ``ctx_frames`` / ``frame_hz`` / ``bits`` / ``n_frames`` / ``mode``, ``lstm`` [n,2,2,256] and ``carry`` [n,2,320] (None
+    for a follower's records), ``ring`` [n,2,T,256] oldest -> newest (zero beyond ``n_frames``) and ``cache`` [n,2,T,768] or None."""
+    records = np.asarray(records)
+    n, fl = records.shape
+    cache = fl == state_record_floats(T, True, follower)
+    if fl != state_record_floats(T, cache, follower):
+        raise VapxError(f"record length {fl} fits no layout of a {'follower' if follower else 'leader / stand-alone'} engine with T={T}")
+    hdr = records[:, :STATE_HEADER_FLOATS].view(np.int32)
+    d = {"magic": hdr[:, 0], "ctx_frames": hdr[:, 1], "frame_hz": hdr[:, 2], "bits": hdr[:, 3], "n_frames": hdr[:, 4], "mode": hdr[:, 5],
+         "lstm": None, "carry": None, "cache": None}
+    at = STATE_HEADER_FLOATS
+    if not follower:
+        d["lstm"] = records[:, at:at + STATE_LSTM_FLOATS].reshape(n, 2, 2, 256)
+        at += STATE_LSTM_FLOATS
+        d["carry"] = records[:, at:at + STATE_CARRY_FLOATS].reshape(n, 2, 320)
+        at += STATE_CARRY_FLOATS
+    d["ring"] = records[:, at:at + 2 * T * 256].reshape(n, 2, T, 256)
+    at += 2 * T * 256
+    if cache:
+        d["cache"] = records[:, at:at + 2 * T * 768].reshape(n, 2, T, 768)
+    return d
 
 
 def wire_floats(mode: str, ctx_frames: int) -> int:

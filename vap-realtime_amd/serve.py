@@ -22,6 +22,14 @@ placement, same packets; 8 x 4096 dialogues need it in a container whose descrip
 output port per model (``--port_num_out`` comma-separated, default 50008, 50009, ...), ``--vap_model`` one path per model, comma-separated in the
 same order.  One GPU, one process: the front door and ``--worker-procs`` are single-model.
 
+``--load_state PATH`` / ``--save_state PATH`` keep the dialogues' state (LSTM, carry, context window, Q|K|V cache) across a restart: the
+snapshot (``snapshot.py``) is imported after the engines are built and before the front-end opens, and written after the front-end has closed on
+SIGTERM / SIGINT.  With ``--gpus N`` or worker processes every engine uses ``PATH.<rank>``; ``--mode a+b`` saves and loads the whole group.  A
+missing ``--load_state`` file is a warning and a cold start; a file that does not fit the engines is refused at start-up (exit 1), never half-loaded.
+An engine that loaded a snapshot opens its front-end without the warm-up on silence (done before the import instead) and WITHOUT reset-on-connect: a dialogue that (re)connects finds its slot's state — as in the
+reference, which never resets the model on a reconnect and re-zeroes only the carry (vap_main.py:368-369) — where a cold engine starts every new
+connection from a fresh stream.
+
 ``--synthetic-weights SEED`` serves seeded random weights (no checkpoint files: load tests, demos).  SIGTERM / SIGINT stop every GPU's
 front-end and engine in order; a failure while one GPU comes up tears the others down and exits non-zero.
 """
@@ -41,6 +49,61 @@ def load_blob(args):
         return W.pack_blob(cpc, vap, args.mode or "vap"), args.mode or "vap"
     blob, hz, mode = checkpoints.import_checkpoints(args.vap_model, args.cpc_model, frame_rate=args.vap_process_rate, mode=args.mode)
     return blob, mode
+
+
+def state_path(path, rank: int, n_engines: int, worker: bool = False):
+    """The snapshot file of engine ``rank``: ``PATH`` for the one engine of a one-process service, ``PATH.<rank>`` with ``--gpus N`` or
+    worker processes."""
+    if not path:
+        return None
+    return f"{path}.{rank}" if (n_engines > 1 or worker) else path
+
+
+def _warm_up(target):
+    """What the front-end's open does for a cold engine (the first step of a process loads the code objects: hundreds of ms), done here
+    because it must happen BEFORE a snapshot is imported: one tick of silence on max_batch streams, then those streams reset."""
+    import numpy as np
+    lead = target.leader if hasattr(target, "leader") else target
+    if not hasattr(lead, "reset_stream"):
+        return
+    silence = np.zeros((lead.max_batch, 2, lead.hop), np.float32)
+    if hasattr(target, "step_wire"):
+        target.step_wire(silence)
+    else:
+        target.step(silence)
+    for i in range(lead.max_batch):
+        lead.reset_stream(i)
+
+
+def load_state(path, target, tag: str = "") -> bool:
+    """``--load_state``: False (and a warning) when there is no file — a cold start; True after an import; raises when the file does not
+    fit ``target`` (nothing was imported then: snapshot.load validates first)."""
+    import os
+    from . import snapshot
+    if not path:
+        return False
+    if not os.path.exists(path):
+        print(f"[vapx] {tag}WARNING: --load_state {path}: no such file, cold start", file=sys.stderr, flush=True)
+        return False
+    _warm_up(target)                                             # before the import: the front-end will not step on silence over loaded state
+    ids = snapshot.load(path, target)
+    print(f"[vapx] {tag}state of {len(ids)} dialogue slot(s) loaded from {path}: connections keep their slot's state (no reset on connect)", flush=True)
+    return True
+
+
+def save_state(path, target, tag: str = "") -> bool:
+    """``--save_state``: every slot, with the Q|K|V cache; call it once the front-end is closed (its tick thread is then stopped, so calls on
+    the handle stay serialised).  A failure is reported, not raised: the shutdown goes on."""
+    from . import snapshot
+    if not path:
+        return False
+    try:
+        hdr = snapshot.save(path, target)
+    except Exception as e:                                      # noqa: BLE001
+        print(f"[vapx] {tag}--save_state {path} failed: {e}", file=sys.stderr, flush=True)
+        return False
+    print(f"[vapx] {tag}state of {len(hdr['ids'])} dialogue slot(s) saved to {path}", flush=True)
+    return True
 
 
 def group_modes(mode):
@@ -93,12 +156,13 @@ def build_group(args, names):
     try:
         grp = engine.TrunkGroup(blobs, args.vap_process_rate, args.context_len_sec, max_streams=args.streams,
                                 max_batch=min(args.streams, args.max_batch), device_id=0, groups=2, split_f16=(args.precision == "split"))
+        warm = load_state(state_path(args.load_state, 0, 1), grp)
         cores = None
         if args.pin:
             cores, _ = dist_util.front_end_placement(0, 1 + args.rx_threads + args.tx_threads)
         srv = ingest.NativeServer.for_group(grp, port_in=args.port_num_in, ports_out=ports, gain=args.audio_gain,
                                             max_wait_s=args.max_wait_ms * 1e-3, bind_any=args.bind_any, rx_threads=args.rx_threads,
-                                            tx_threads=args.tx_threads, cores=cores)
+                                            tx_threads=args.tx_threads, cores=cores, reset_on_connect=not warm, keep_state=warm)
     except Exception:
         if srv is not None:
             srv.close()
@@ -125,6 +189,7 @@ def run_group(args, names, stop) -> int:
             st = srv.stats(reset_latency_window=True)
             print("[vapx] GPU 0: " + json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in st.items()}), flush=True)
     srv.close()
+    save_state(state_path(args.save_state, 0, 1), grp)
     grp.close()
     return 0
 
@@ -169,6 +234,7 @@ def build(args):
                                 groups=2,   # two intra-tick overlap groups: ragged ticks of a few hundred streams get 20 % shorter
                                 split_f16=(args.precision == "split"))
             engines.append(eng)
+            warm = load_state(state_path(args.load_state, r, n), eng, f"GPU {r}: ")
             passive = n > 1
             cores = None
             if args.pin:                  # tick / receive / sender threads next to their GPU, every shard on cores of its own
@@ -178,7 +244,7 @@ def build(args):
                 taken[node_key] = taken.get(node_key, 0) + nthr
             shards.append(ingest.NativeServer(eng, port_in=-1 if passive else args.port_num_in, port_out=-1 if passive else args.port_num_out,
                                               gain=args.audio_gain, max_wait_s=args.max_wait_ms * 1e-3, bind_any=args.bind_any,
-                                              rx_threads=args.rx_threads, tx_threads=args.tx_threads, cores=cores))
+                                              rx_threads=args.rx_threads, tx_threads=args.tx_threads, cores=cores, reset_on_connect=not warm, keep_state=warm))
         if n > 1:
             door = ingest.FrontDoor(shards, args.port_num_in, args.port_num_out, bind_any=args.bind_any)
     except Exception:
@@ -200,12 +266,13 @@ def run_worker(args) -> int:
         dev = 0 if args.share_gpu else r
         eng = engine.Engine(blob, args.vap_process_rate, args.context_len_sec, max_streams=args.streams, max_batch=min(args.streams, args.max_batch),
                             mode=mode, device_id=dev, groups=2, split_f16=(args.precision == "split"))
+        warm = load_state(state_path(args.load_state, r, max(1, args.gpus), worker=True), eng, f"GPU {r}: ")
         cores = None
         if args.pin:
             nthr = 1 + args.rx_threads + args.tx_threads
             cores, _ = dist_util.front_end_placement(dev, nthr, skip=(r * nthr if args.share_gpu else 0))
         shard = ingest.NativeServer(eng, port_in=-1, port_out=-1, gain=args.audio_gain, max_wait_s=args.max_wait_ms * 1e-3,
-                                    rx_threads=args.rx_threads, tx_threads=args.tx_threads, cores=cores)
+                                    rx_threads=args.rx_threads, tx_threads=args.tx_threads, cores=cores, reset_on_connect=not warm, keep_state=warm)
         shard.attach_link(args.worker_link)
     except Exception as e:                                      # noqa: BLE001
         print(f"[vapx] GPU {r}: worker start-up failed: {e}", file=sys.stderr, flush=True)
@@ -219,6 +286,7 @@ def run_worker(args) -> int:
             st = shard.stats(reset_latency_window=True)
             print(f"[vapx] GPU {r}: " + json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in st.items()}), flush=True)
     shard.close()
+    save_state(state_path(args.save_state, r, max(1, args.gpus), worker=True), eng, f"GPU {r}: ")
     eng.close()
     return 0
 
@@ -277,7 +345,7 @@ def run_door(args, argv) -> int:
             w.terminate()
     for w in workers:
         try:
-            w.wait(timeout=30)
+            w.wait(timeout=300 if args.save_state else 30)         # a worker writes its snapshot before it exits
         except Exception:                                        # noqa: BLE001
             w.kill()
     for l in links:
@@ -285,12 +353,14 @@ def run_door(args, argv) -> int:
     return rc
 
 
-def teardown(engines, shards, door):
+def teardown(engines, shards, door, save_path=None):
     if door is not None:
         door.close(close_shards=False)
     for s in shards:
         s.close()
-    for e in engines:
+    for r, e in enumerate(engines):
+        if save_path:                                            # every front-end is closed: nobody else steps the engines now
+            save_state(state_path(save_path, r, len(engines)), e, f"GPU {r}: ")
         e.close()
 
 
@@ -328,6 +398,11 @@ def main(argv=None) -> int:
                          "no better than floating threads (profiles/r05_frontend/README.md)")
     ap.add_argument("--stats_sec", type=float, default=10.0)
     ap.add_argument("--synthetic-weights", dest="synthetic_weights", type=int, default=None)
+    ap.add_argument("--load_state", type=str, default=None,
+                    help="snapshot to import before the front-end opens (PATH.<rank> per engine with --gpus N / worker processes); a missing file is a "
+                         "warning and a cold start, a file that does not fit the engines is refused")
+    ap.add_argument("--save_state", type=str, default=None,
+                    help="snapshot of every dialogue slot, written after the front-end has closed on SIGTERM / SIGINT (same naming)")
     ap.add_argument("--worker-procs", dest="worker_procs", choices=["auto", "on", "off"], default="auto",
                     help="one worker PROCESS per GPU behind a front-door process that passes accepted connections on (auto: when one process could not "
                          "hold 2 sockets per dialogue under RLIMIT_NOFILE; --gpus 8 x --streams 4096 needs 65 792 descriptors)")
@@ -375,7 +450,7 @@ def main(argv=None) -> int:
             for r, s in enumerate(shards):
                 st = s.stats(reset_latency_window=True)
                 print(f"[vapx] GPU {r}: " + json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in st.items()}), flush=True)
-    teardown(engines, shards, door)
+    teardown(engines, shards, door, args.save_state)
     return 0
 
 
