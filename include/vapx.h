@@ -100,7 +100,8 @@ extern "C" {
 #define VAPX_OUT_STATUS 13   /* [1]  0 = ok, 1 = this row's probabilities are not finite (see VAPX_E_NUMERIC); written on device,
                                       so the device-output path carries it too */
 #define VAPX_OUT_LOGITS 16   /* [256] vap_head logits of the newest row  vap_main.py:290;
-                                      nod mode: p_bc of rows 0..n-1 instead (vap_nod_main.py:276 quirk) */
+                                      nod mode: p_bc of rows 0..n-1 instead (vap_nod_main.py:276 quirk), 0 in slots n..ctx_frames-1;
+                                      one slot per window row, so vapx_create refuses nod mode with ctx_frames > 256 */
 #define VAPX_OUT_E 272       /* [2*256] this frame's embeddings e1,e2   vap_main.py:272 */
 #define VAPX_OUT_STRIDE 784
 
@@ -110,7 +111,8 @@ typedef struct vapx_config {
   int32_t struct_size;  /* sizeof(vapx_config), for ABI evolution */
   int32_t device_id;    /* HIP device ordinal */
   int32_t frame_hz;     /* 5, 10, 20 or 50: VAPRealTime frame_rate   vap_main.py:192,219 */
-  int32_t ctx_frames;   /* T = int(context_len_sec*frame_rate)        vap_main.py:221.  1 <= T <= 512 (vapx_create returns VAPX_E_INVAL beyond).
+  int32_t ctx_frames;   /* T = int(context_len_sec*frame_rate)        vap_main.py:221.  1 <= T <= 512 (vapx_create returns VAPX_E_INVAL beyond;
+                         * nod mode: T <= 256, the p_bc slots of an output row).
                          * Every published checkpoint fits in 256 (largest: 20 Hz x 10 s = 200 rows, README.md; BASELINE configs[2]: 50 Hz x 5 s = 250)
                          * and that is what the long-window attention kernels are tuned for; the reference's ALiBi transformer itself takes any T
                          * (modules.py:303-308), so windows of 257 .. 512 rows run too — through a plain fp32 attention kernel (K / V from L2, no
@@ -328,10 +330,15 @@ int vapx_softmax256(int64_t rows, const float* x, float* y, void* hip_stream);
 int vapx_aggregate(int64_t rows, const float* probs, int32_t from_bin, int32_t to_bin, float* out, void* hip_stream);
 
 /* Copy an internal scratch buffer of the LAST vapx_step to the host (per-layer parity tests).
- * name: "h0".."h3","z","lstm_out","e","x0","o","stereo0".."stereo2"; returns the number of
+ * name: "h0".."h3","z","lstm_out","e","x0","o","stereo0".."stereo2","last","comb"; returns the number of
  * floats written (<= max_floats) or a negative error.  "h2"/"h3" are refused when any overlap group of that step ran the
  * fused conv tail (VAPX_FLAG_UNFUSED_CONV always materialises them), "stereo2" needs VAPX_FLAG_FULL_LAST_LAYER, and a trunk
  * follower refuses the encoder buffers it released (peek its leader).
+ * "last": [n*2][256], the last layer's output for the newest row of every (stream, channel), where that layer runs on the newest
+ * row alone (the default fused block and VAPX_FLAG_UNFUSED_LAST_ROW; one peek spans the overlap groups); with
+ * VAPX_FLAG_FULL_LAST_LAYER or in nod mode it is refused: take row n - 1 of "stereo2".
+ * "comb": nod mode only, [n][ctx_frames][256], the combinator of every window row (rows >= a stream's n undefined); refused in
+ * the other modes and when the latest step ran in more than one overlap group (the groups' blocks are not contiguous).
  * Debug: "guard_violations" writes one float, the number of canary bytes overwritten around the process's engine allocations (-1 unless
  * the library was started with VAPX_GUARD_ZONES=1; INTEGRATION.md "Debug and experiment knobs"). */
 int64_t vapx_peek(vapx_handle h, const char* name, float* dst, size_t max_floats);

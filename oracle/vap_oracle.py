@@ -224,10 +224,11 @@ class VapOracle:
             o1, o2, a, b, h = self.transformer(X[:, 0], X[:, 1], collect)
             v = self.v
             out: Dict[str, np.ndarray] = {}
-            out["vad"] = torch.stack([
-                torch.sigmoid(o1[:, -1] @ v["va_classifier.weight"].T + v["va_classifier.bias"])[:, 0],
-                torch.sigmoid(o2[:, -1] @ v["va_classifier.weight"].T + v["va_classifier.bias"])[:, 0],
-            ], dim=1).numpy()                                     # vap_main.py:292-293,313-314
+            vad_logit = torch.stack([(o1[:, -1] @ v["va_classifier.weight"].T + v["va_classifier.bias"])[:, 0],
+                                     (o2[:, -1] @ v["va_classifier.weight"].T + v["va_classifier.bias"])[:, 0]], dim=1)
+            out["vad"] = torch.sigmoid(vad_logit).numpy()         # vap_main.py:292-293,313-314
+            if collect is not None:
+                collect["vad_logit"] = vad_logit                  # [S,2], before the sigmoid
             if "vap_head.weight" in v:
                 logits = h[:, -1] @ v["vap_head.weight"].T + v["vap_head.bias"]
                 probs = logits.softmax(dim=-1)
@@ -239,16 +240,21 @@ class VapOracle:
                 out["p_now"] = pn.numpy()
                 out["p_future"] = pf.numpy()
             if self.mode == "bc":                                 # vap_bc_main.py:272-277
-                bc = (h[:, -1] @ v["bc_head.weight"].T + v["bc_head.bias"]).softmax(-1)
+                aux = h[:, -1] @ v["bc_head.weight"].T + v["bc_head.bias"]
+                bc = aux.softmax(-1)
                 out["p_bc_react"] = bc[:, 1].numpy()
                 out["p_bc_emo"] = bc[:, 2].numpy()
             elif self.mode == "nod":                              # vap_nod_main.py:273-279
-                nod = (h[:, -1] @ v["nod_head.weight"].T + v["nod_head.bias"]).softmax(-1)
+                aux = h[:, -1] @ v["nod_head.weight"].T + v["nod_head.bias"]
+                nod = aux.softmax(-1)
                 out["p_nod_short"] = nod[:, 1].numpy()
                 out["p_nod_long"] = nod[:, 2].numpy()
                 out["p_nod_long_p"] = nod[:, 3].numpy()
                 # quirk: `p_bc.sigmoid()[-1]` indexes the batch dim -> all n rows are emitted
                 out["p_bc"] = torch.sigmoid(h @ v["bc_head.weight"].T + v["bc_head.bias"])[..., 0].numpy()  # [S,n]
+            if collect is not None and self.mode in ("bc", "nod"):
+                collect["aux_logit"] = aux                        # [S,3] / [S,4], before the softmax
+                collect["aux"] = aux.softmax(-1)                  # every column, also the one the reference drops
             out["e"] = e.numpy()
         return out
 

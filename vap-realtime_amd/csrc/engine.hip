@@ -905,6 +905,9 @@ int vapx_create(const vapx_config* cfg, const float* blob, size_t n_floats, vapx
   if (cfg->max_streams < 1 || cfg->max_batch < 1 || cfg->max_batch > cfg->max_streams)
     return fail(nullptr, VAPX_E_INVAL, "need 1 <= max_batch <= max_streams");
   if (cfg->mode < 0 || cfg->mode > 2) return fail(nullptr, VAPX_E_INVAL, "bad mode");
+  if (cfg->mode == VAPX_MODE_NOD && cfg->ctx_frames > 256)   // pbc_rows_kernel writes p_bc of window row t into logits slot t
+    return fail(nullptr, VAPX_E_INVAL, "nod mode needs ctx_frames <= 256 (got %d): the output row holds 256 p_bc slots, one per window row",
+                cfg->ctx_frames);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(nullptr, VAPX_E_NODEVICE, "no HIP device visible");
   if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(nullptr, VAPX_E_INVAL, "device_id out of range");
@@ -1756,6 +1759,19 @@ int64_t vapx_peek(vapx_handle h, const char* name, float* dst, size_t max_floats
     if (!(h->cfg.flags & VAPX_FLAG_FULL_LAST_LAYER) && h->cfg.mode != VAPX_MODE_NOD)
       return fail(h, VAPX_E_INVAL, "\"stereo2\" is only materialised with VAPX_FLAG_FULL_LAST_LAYER (default: last layer runs on the newest row only)");
     src = h->sc.xl[4]; n = B * 2 * T * 256;
+  }
+  else if (!strcmp(name, "last")) {   // the last layer's newest row of every (stream, channel): fused block and the ten-launch path alike
+    if ((h->cfg.flags & VAPX_FLAG_FULL_LAST_LAYER) || h->cfg.mode == VAPX_MODE_NOD)
+      return fail(h, VAPX_E_INVAL, "\"last\" exists only where the last layer runs on the newest row alone; this engine (VAPX_FLAG_FULL_LAST_LAYER "
+                  "or nod mode) computes every row: peek \"stereo2\" and take row n - 1");
+    src = h->sc.last[5]; n = B * 2 * 256;   // overlap groups slice it by batch row, so one copy spans them
+  }
+  else if (!strcmp(name, "comb")) {   // the all-rows combinator of the nod variant, [n][T][256]
+    if (h->cfg.mode != VAPX_MODE_NOD)
+      return fail(h, VAPX_E_INVAL, "\"comb\" is only materialised in nod mode (vap / bc: the combinator of the newest row stays inside head_kernel)");
+    if (h->last_G > 1)   // a group's block starts at its first row of the [B*2*T]-row scratch, twice the stride of the [nb*T] rows it holds
+      return fail(h, VAPX_E_INVAL, "\"comb\" is not contiguous when the latest step ran in %d overlap groups; step with groups = 1 to peek it", h->last_G);
+    src = h->sc.xmid; n = B * T * 256;
   }
   else return fail(h, VAPX_E_INVAL, "unknown buffer '%s'", name);
   if (!src)   // vapx_attach_trunk freed the follower's encoder scratch

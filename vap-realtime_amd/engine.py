@@ -454,6 +454,8 @@ class Engine:
         return {PROF_CLASSES[i]: (ms[i], cnt[i]) for i in PROF_CLASSES if cnt[i]}
 
     def peek(self, name: str, shape) -> np.ndarray:
+        """A scratch buffer of the latest step (vapx.h, vapx_peek): the encoder stages, ``x0``, ``o``, ``stereo0`` .. ``stereo2`` [n,2,T,256],
+        ``last`` [n,2,256] (the last layer's newest row where that layer runs on the newest row alone) and, nod only, ``comb`` [n,T,256]."""
         buf = np.empty(int(np.prod(shape)), np.float32)
         got = self._check(self.lib.vapx_peek(self._h, name.encode(), _np_ptr(buf), buf.size), "vapx_peek")
         assert got == buf.size, (name, got, buf.size)
