@@ -98,7 +98,10 @@ extern "C" {
 #define VAPX_OUT_NVALID 10   /* [1]  n = rows in the context window this frame (as float) */
 #define VAPX_OUT_VAD_LOGIT 11 /* [2] va_classifier outputs before the sigmoid (what the training-style forward() returns) */
 #define VAPX_OUT_STATUS 13   /* [1]  0 = ok, 1 = this row's probabilities are not finite (see VAPX_E_NUMERIC); written on device,
-                                      so the device-output path carries it too */
+                                      so the device-output path carries it too; 2 = VAPX_STATUS_NO_FRAME */
+#define VAPX_STATUS_NO_FRAME 2 /* a trunk follower slower than its leader (vapx_attach_trunk) had no frame due for this stream on this
+                                      leader tick: the rest of the row is zero.  No fault: vapx_bad_slots, VAPX_E_NUMERIC and
+                                      vapx_group_bad count status 1 only */
 #define VAPX_OUT_LOGITS 16   /* [256] vap_head logits of the newest row  vap_main.py:290;
                                       nod mode: p_bc of rows 0..n-1 instead (vap_nod_main.py:276 quirk), 0 in slots n..ctx_frames-1;
                                       one slot per window row, so vapx_create refuses nod mode with ctx_frames > 256 */
@@ -169,10 +172,29 @@ int vapx_join(vapx_handle h, void* hip_stream);
  * encoder: each tick, step the leader with the audio, then step every follower with audio == NULL (same n, same
  * hip_stream; stream_ids is ignored, the leader's are used).  The follower applies its own downsample to the
  * leader's LSTM outputs and runs its own rings / transformer / heads.  Requirements: both engines freshly created
- * (no step yet), same device, frame_hz, ctx_frames, max_streams, max_batch, and bit-identical CPC weights in the two
- * blobs.  A leader can have several followers; vapx_reset_stream on the leader resets them too (and is refused on
- * a follower); LSTM / carry state import / export goes through the leader, ring state through each engine.
- * Destroy followers before their leader. */
+ * (no step yet), same device, max_streams, max_batch, and bit-identical CPC weights in the two blobs.  A leader can
+ * have several followers; vapx_reset_stream on the leader resets them too (and is refused on a follower); LSTM /
+ * carry state import / export goes through the leader, ring state through each engine.  Destroy followers before
+ * their leader.
+ *
+ * Mixed groups (the reference deploys vap at 20 Hz / 2.5 s next to bc at 20 Hz / 5 s and nod at 10 Hz / 10 s, README.md).
+ * ctx_frames may differ from the leader's: the follower then fills and slides its own window (a follower with the leader's rate
+ * and window runs exactly the path it ran before, bit for bit).  frame_hz may differ when the leader's rate is an integer
+ * multiple R of the follower's (50 -> 10, 50 -> 5, 20 -> 10, 20 -> 5, 10 -> 5; 50 -> 20 and a leader slower than its follower are
+ * refused): the group's fastest model leads.  A CPC frame is a function of real samples only and the LSTM carries (h, c) from frame
+ * to frame, so the R * n_cpc LSTM rows of a follower's frame are those of R consecutive leader ticks.  Such a follower
+ *   - is still stepped every leader tick, with the leader's n.  Per stream it collects the leader's rows (trunk_collect_kernel, keyed
+ *     by stream id: batches may be ragged and reorder) and runs its own chain on every R-th tick OF THAT STREAM, counted from the
+ *     stream's reset.  out[n][VAPX_OUT_STRIDE] keeps the leader's batch order; a row without a frame is all zero with
+ *     VAPX_OUT_STATUS = VAPX_STATUS_NO_FRAME.  In vapx_step_group the wire row being a prefix of the output row, a slower model's
+ *     wire rows carry status 2 on ticks without a frame.
+ *   - needs the leader's stream ids on the host: after a leader step with VAPX_IDS_DEVICE its step returns VAPX_E_INVAL.
+ *   - does not honour VAPX_DEFER_JOIN (it joins its overlap groups, which split the due streams, before it returns).
+ *   - vapx_reset_stream on the leader restarts the stream's frame as well; vapx_reset_carry leaves it alone, as the reference's
+ *     reconnect leaves its model state.
+ *   - vapx_get_state / vapx_set_state move its ring as on any follower; vapx_export_streams / vapx_import_streams are REFUSED
+ *     (VAPX_E_INVAL): a state record does not carry the half-collected frame and the phase yet.  Same-rate followers with a window
+ *     of their own export and import as before (their records carry ctx_frames). */
 int vapx_attach_trunk(vapx_handle follower, vapx_handle leader);
 
 /* The whole trunk group in ONE call, answered with compact wire rows (multi-model serving: vap_main.py, vap_bc_main.py and
@@ -356,10 +378,10 @@ int vapx_gemm(void* hip_stream, int32_t M, int32_t N, int32_t K, const float* A,
  * 7 last-row path of the final layer, 8 conv0, 9 lstm,
  * 10 ring gather+LN, 11 attention, 12 heads, 13 the GEMM with epilogue 5 (bias + LayerNorm + GELU: a trunk follower's
  * downsample, nod's Combinator on all rows), 14 the long-window mode-2 flat-row block (attention output projection + ln_src_attn + cross-attention
- * query projection; the FFN block proper stays class 6).  enable(mask) selects classes (0 = off);
+ * query projection; the FFN block proper stays class 6), 15 a slower trunk follower's collect and output scatter (pure copies).  enable(mask) selects classes (0 = off);
  * read() synchronises the device, sums the elapsed time and launch count per class since the
  * last read into total_ms[n_classes] / launches[n_classes], and recycles the events. */
-#define VAPX_PROF_CLASSES 15
+#define VAPX_PROF_CLASSES 16
 int vapx_profile_enable(vapx_handle h, uint32_t class_mask);
 int vapx_profile_read(vapx_handle h, double* total_ms, int64_t* launches, int32_t n_classes);
 
@@ -455,8 +477,15 @@ int vapx_ingest_ports(vapx_ingest_handle g, int32_t* port_in, int32_t* port_out)
  *     :193-211, nod :213-237 with p_bc of every window row); fewest-listeners / lowest-slot placement and broadcast hold per port;
  *   - a tick is one vapx_step_group (host in, host out, page-locked wire block); batching, max_wait_us, pacing and min_batch are
  *     unchanged, and a stream's packets leave through one sender thread, so they stay in frame order on every port;
- *   - a stream with a non-zero status in ANY model is reset through the leader (which resets the followers) and gets no packet on any
- *     port that tick; numeric_resets counts it once;
+ *   - a stream with status 1 (not finite) in ANY model is reset through the leader (which resets the followers) and gets no packet on
+ *     any port that tick; numeric_resets counts it once;
+ *   - a mixed group (models with windows / rates of their own, read from each engine's vapx_get_config): input framing, ticks and
+ *     batching stay the leader's.  A model at 1/R of the leader's rate sends ONE packet per R leader hops of a dialogue, echoing
+ *     n = R * hop samples per channel as its reference program does (10 Hz: 1600, util.py:213-237): the front-end keeps an f64 echo
+ *     history of R - 1 leader hops per dialogue, appended when the model's wire row carries VAPX_STATUS_NO_FRAME — which sends no
+ *     packet on that model's port, resets nothing and is not a numeric_reset.  The history is cleared with the slot's carry on a new
+ *     connection; without reset_on_connect the engine's phase runs on across the reconnect (as the reference's model state does), so
+ *     a connection that starts in the middle of a slower model's frame gets no packet for that one frame;
  *   - stats: frames_done counts stream-frames (not packets), the latency of a stream-frame is taken once, after the LAST model's packets
  *     were handed to the kernel; tx_bytes, out_connections and dropped_listeners sum over the ports.
  * `followers` must be the leader's attached followers in attach order (modes pairwise distinct).  A group cannot be a passive shard:
@@ -467,13 +496,19 @@ int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int
                            const int32_t* follower_ports_out, vapx_ingest_handle* out);
 int vapx_ingest_group_ports(vapx_ingest_handle g, int32_t* port_in, int32_t* ports_out, int32_t max_ports);
 /* The same over a caller-supplied step function (host-logic tests without a GPU): step(user, n, stream_ids, audio[n][2][hop], wire_out)
- * fills wire_out in the layout of vapx_step_group for that tick's n and modes[0 .. n_models); ctx_frames sizes nod's wire rows. .
+ * fills wire_out in the layout of vapx_step_group for that tick's n and modes[0 .. n_models); ctx_frames sizes nod's wire rows.
+ * vapx_ingest_open_group_fn2 takes every model's rate and window (frame_hzs[n_models], ctx_frames[n_models]; model 0 leads and is the
+ * fastest, its rate an integer multiple of the others'): the step function then marks a slower model's rows without a frame with
+ * VAPX_STATUS_NO_FRAME.  vapx_ingest_open_group_fn is fn2 with equal rates and windows.
  * vapx_ingest_last_open_error: why the calling thread's latest vapx_ingest_open_group* call was refused ("" if it was not). */
 typedef int (*vapx_ingest_group_step_fn)(void* user, int32_t n, const int32_t* stream_ids, const float* audio,
                                          float* wire_out /* layout of vapx_step_group */);
 int vapx_ingest_open_group_fn(vapx_ingest_group_step_fn step, vapx_ingest_reset_fn reset, void* user, int32_t n_streams, int32_t max_batch,
                               int32_t frame_hz, int32_t ctx_frames, const int32_t* modes, int32_t n_models, const vapx_ingest_config* cfg,
                               const int32_t* follower_ports_out, vapx_ingest_handle* out);
+int vapx_ingest_open_group_fn2(vapx_ingest_group_step_fn step, vapx_ingest_reset_fn reset, void* user, int32_t n_streams, int32_t max_batch,
+                               const int32_t* frame_hzs, const int32_t* ctx_frames, const int32_t* modes, int32_t n_models,
+                               const vapx_ingest_config* cfg, const int32_t* follower_ports_out, vapx_ingest_handle* out);
 const char* vapx_ingest_last_open_error(void);
 int vapx_ingest_stats_read(vapx_ingest_handle g, vapx_ingest_stats* out, int32_t reset_latency_window);
 /* Exact server-side count of late answers in the current latency window (since the last stats_read(.., 1)): result packets handed to the

@@ -17,6 +17,10 @@
 //   --ports-out a,b,...   a server that serves several models on one shared trunk (serve --mode a+b[+c]) has one output port per model: every
 //                     dialogue opens one listener per port; a frame counts as answered when EVERY port has answered it and its latency is that
 //                     of the last packet.  With a single port this is --port-out.  (Not with --inband: one process, sender-side stamps.)
+//   --port-samples a,b,...   with --ports-out: the samples per channel each port's packets echo (default: one hop, 16000 / hz).  A model at
+//                     1/R of the input rate (a mixed trunk group: serve --vap_process_rate 20,20,10) answers every R-th frame of a dialogue with
+//                     one packet of R hops: frame k expects a packet on that port only when (k + 1) % R == 0.  Every packet's sample count
+//                     is checked, and the latency percentiles are also reported per port (last byte of the packet's LAST frame sent -> packet read).
 //   --hist-out F      latency histogram (50 us bins up to 400 ms) as JSON, for merging the processes' percentiles
 // Build: make -C vap-realtime_amd/csrc loadgen   (plain C++17, no dependencies)
 #include <arpa/inet.h>
@@ -84,7 +88,7 @@ struct Stream {
   int fd_in = -1;
   std::vector<int> fd_out;          // one listener per output port (--ports-out)
   std::vector<std::vector<uint8_t>> rbufs;
-  std::vector<long> got;            // result packets read per port; frame k is answered when every port has delivered k + 1 of them
+  std::vector<long> got;            // result packets read per port; frame k is answered when every port has delivered the packets due up to it
   std::mutex mu;
   std::deque<double> sent;          // send-completion time of each frame not yet answered
   long answered = 0, frames = 0;
@@ -95,6 +99,7 @@ struct Stream {
 int main(int argc, char** argv) {
   const char* host = "127.0.0.1";
   std::vector<int> ports_out{50008};
+  std::vector<int> port_samples;
   int port_in = 50007, S = 256, hz = 20, packet_ms = 10, threads = 4;
   double seconds = 10.0, late_ms = 10.0, warm = 3.0;
   int inband = 0, procs = 1, rank = 0, total_streams = 0;
@@ -109,6 +114,9 @@ int main(int argc, char** argv) {
     else if (k == "--ports-out") {
       ports_out.clear();
       for (const char* q = v; *q;) { ports_out.push_back(atoi(q)); q = strchr(q, ','); if (!q) break; ++q; }
+    }
+    else if (k == "--port-samples") {
+      for (const char* q = v; *q;) { port_samples.push_back(atoi(q)); q = strchr(q, ','); if (!q) break; ++q; }
     }
     else if (k == "--streams") S = atoi(v);
     else if (k == "--hz") hz = atoi(v);
@@ -142,6 +150,18 @@ int main(int argc, char** argv) {
     }
   };
   const int hop = 16000 / hz;
+  std::vector<int> ratio(P, 1);                      // frames per packet of each port
+  if (!port_samples.empty()) {
+    if ((int)port_samples.size() != P) { fprintf(stderr, "--port-samples needs one value per output port\n"); return 2; }
+    for (int p = 0; p < P; ++p) {
+      if (port_samples[p] < hop || port_samples[p] % hop) { fprintf(stderr, "--port-samples: %d is no multiple of the hop (%d)\n", port_samples[p], hop); return 2; }
+      ratio[p] = port_samples[p] / hop;
+    }
+  }
+  bool mixed = false;
+  for (int r : ratio) mixed |= r > 1;
+  std::vector<std::vector<float>> lats_port(P);
+  std::atomic<long> size_mismatch{0};
   const double period = 1.0 / hz;
   const int packets_per_frame = (int)lround(period * 1000.0 / packet_ms);
   const int pk_samples = hop / packets_per_frame;
@@ -296,7 +316,23 @@ int main(int argc, char** argv) {
           uint32_t len;
           memcpy(&len, rbuf.data() + off, 4);
           if (rbuf.size() - off < 4 + (size_t)len) break;
-          if (P > 1) {   // answered only when the LAST port's packet of the frame is in: this packet completes a frame iff its port was the one behind
+          if (mixed) {   // ports at rates of their own: check the echoed sample count, book the port's latency, then see whether a frame is complete
+            uint32_t ns = 0;
+            if (len >= 12) memcpy(&ns, rbuf.data() + off + 4 + 8, 4);
+            if ((int)ns != ratio[port] * hop) size_mismatch.fetch_add(1);
+            ++s.got[port];
+            const long last_frame = s.got[port] * ratio[port] - 1;   // the frame whose last byte completed this packet's input
+            double tp = 0;
+            {
+              std::lock_guard<std::mutex> lk(s.mu);
+              const long k = last_frame - s.answered;
+              if (k >= 0 && k < (long)s.sent.size()) tp = s.sent[(size_t)k];
+            }
+            if (tp >= t_measure && tp > 0) { std::lock_guard<std::mutex> lk(lat_mu); lats_port[port].push_back((float)((t - tp) * 1e3)); }
+            bool complete = true;                     // frame s.answered is answered when every port delivered the packets due up to it
+            for (int p = 0; p < P; ++p) complete &= s.got[p] >= (s.answered + 1) / ratio[p];
+            if (!complete) { off += 4 + len; continue; }
+          } else if (P > 1) {   // answered only when the LAST port's packet of the frame is in: this packet completes a frame iff its port was the one behind
             ++s.got[port];
             if (*std::min_element(s.got.begin(), s.got.end()) <= s.answered) { off += 4 + len; continue; }
           }
@@ -388,6 +424,19 @@ int main(int argc, char** argv) {
   }
   printf("\"inband\": %d, \"procs\": %d, \"rank\": %d, \"route_changes\": %ld, \"inband_unreadable\": %ld, ", inband, procs, rank, route_changes.load(), inband_bad.load());
   printf("\"output_ports\": %d, ", P);
+  if (mixed) {
+    printf("\"port_size_mismatches\": %ld, \"per_port\": [", size_mismatch.load());
+    for (int p = 0; p < P; ++p) {
+      std::vector<float>& lp = lats_port[p];
+      std::sort(lp.begin(), lp.end());
+      auto pq = [&](double q) { return lp.empty() ? 0.0 : (double)lp[std::min(lp.size() - 1, (size_t)(q * lp.size()))]; };
+      long got = 0;
+      for (auto& s : st) got += s.got[p];
+      printf("%s{\"samples_per_packet\": %d, \"packets\": %ld, \"latency_samples\": %zu, \"lat_p50_ms\": %.3f, \"lat_p99_ms\": %.3f, \"lat_max_ms\": %.3f}",
+             p ? ", " : "", ratio[p] * hop, got, lp.size(), pq(0.50), pq(0.99), lp.empty() ? 0.0 : (double)lp.back());
+    }
+    printf("], ");
+  }
   printf("\"streams\": %d, \"frame_hz\": %d, \"packet_ms\": %d, \"seconds_measured\": %.1f, \"frames_sent\": %ld, \"frames_answered\": %ld, "
          "\"unanswered_at_end\": %ld, \"latency_samples\": %zu, \"lat_p50_ms\": %.3f, \"lat_p99_ms\": %.3f, \"lat_p999_ms\": %.3f, \"lat_max_ms\": %.3f, "
          "\"late_over_%.0fms\": %ld, \"schedule_slips\": %ld, \"client_max_send_lag_ms\": %.2f, \"client_max_send_call_ms\": %.2f, \"client_max_recv_pass_ms\": %.2f, \"stream_frames_per_s\": %.1f}\n",

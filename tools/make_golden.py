@@ -51,6 +51,11 @@ CASES = {
     # T = 200: the longest published window (20 Hz x 10 s, README.md:381 vap-nod_state_dict_erica_20hz_10000msec) for vap and nod
     "vap20_10s": dict(mode="vap", frame_hz=20, ctx=10.0, streams=[70], n_frames=204, framing="server", seed=25, inter=[0, 202], e_stride=17),
     "nod20_10s": dict(mode="nod", frame_hz=20, ctx=10.0, streams=[71], n_frames=203, framing="server", seed=26, inter=[], e_stride=29),
+    # a MIXED trunk group: three programs on one cpc_model file and the same 64 320 samples, each at its own rate and window (bc and
+    # nod at their published 3 s window, nod at the 10 Hz of its program): every window fills and slides (30, 20 and 10 slides)
+    "mix_vap20": dict(mode="vap", frame_hz=20, ctx=2.5, streams=[80, 81], n_frames=80, framing="server", seed=30, cpc_seed=33, inter=[], e_stride=8),
+    "mix_bc20_3s": dict(mode="bc", frame_hz=20, ctx=3.0, streams=[80, 81], n_frames=80, framing="server", seed=31, cpc_seed=33, inter=[], e_stride=8),
+    "mix_nod10_3s": dict(mode="nod", frame_hz=10, ctx=3.0, streams=[80, 81], n_frames=40, framing="server", seed=32, cpc_seed=33, inter=[], e_stride=4),
 }
 ROW_SUBSET_AT = 8  # intermediates with more rows than this keep rows [0, n//3, n-1] only
 

@@ -154,6 +154,9 @@ def main():
     ap.add_argument("--split-f16", action="store_true", help="engines on the opt-in split-precision path (serve --precision split)")
     ap.add_argument("--mode", default="vap", help="vap, bc or nod; a+b[+c] (e.g. bc+nod): several models on one shared CPC trunk behind the group "
                     "front-end (vapx_ingest_open_group), one output port per model, the load generator listens on all of them")
+    ap.add_argument("--hzs", default="", help="with --mode a+b[+c]: one frame rate per model, comma-separated in model order (a mixed trunk group: "
+                    "20,20,10); the fastest model leads and sets the input framing.  Default: --hz for every model")
+    ap.add_argument("--ctx-secs", default="", help="with --mode a+b[+c]: one window per model, comma-separated (2.5,5,10).  Default: --ctx-sec for every model")
     ap.add_argument("--fake", action="store_true", help="native front-end over a trivial step function (plumbing only, no GPU)")
     ap.add_argument("--standin", action="store_true", help="native front-end(s) over the native stand-in for the GPU tick (no GPU, no Python on the tick thread); "
                     "with --shards N: N passive front-ends behind ONE front door")
@@ -304,9 +307,14 @@ def main():
         assert len(set(names)) == len(names) and all(m in ("vap", "bc", "nod") for m in names), "--mode a+b[+c]: distinct names from vap, bc, nod"
         assert args.shards == 1 and not args.python and not args.inband and args.loadgen_procs <= 1, \
             "a + mode is served by one group front-end: no --shards, --python, --inband or --loadgen-procs"
-        blobs = {m: W.pack_blob(*W.synthetic_weights(0, args.hz, m), m) for m in names}      # one seed: the same CPC tensors in every model
-        grp = engine.TrunkGroup(blobs, args.hz, args.ctx_sec, max_streams=S, max_batch=args.max_batch or None, groups=args.groups,
+        hzs = [int(v) for v in args.hzs.split(",")] if args.hzs else [args.hz] * len(names)
+        ctxs = [float(v) for v in args.ctx_secs.split(",")] if args.ctx_secs else [args.ctx_sec] * len(names)
+        assert len(hzs) == len(names) and len(ctxs) == len(names), "--hzs / --ctx-secs: one value per model"
+        args.hz = max(hzs)                                # input framing and ticks are the leader's, the fastest model
+        blobs = {m: W.pack_blob(*W.synthetic_weights(0, hz, m), m) for m, hz in zip(names, hzs)}   # one seed: the same CPC tensors in every model
+        grp = engine.TrunkGroup(blobs, hzs, ctxs, max_streams=S, max_batch=args.max_batch or None, groups=args.groups,
                                 split_f16=args.split_f16)
+        port_samples = {m: grp.hop_of[m] for m in names} if any(r > 1 for r in grp.R.values()) else None
         srv = ingest.NativeServer.for_group(grp, port_in=0, ports_out=[0] * len(names), max_wait_s=args.max_wait_ms * 1e-3, min_batch=args.min_batch,
                                             rx_threads=args.rx_threads, tx_threads=args.tx_threads, target_util=args.target_util, cores=cores,
                                             core_set=(args.pin_mode == "set"))
@@ -358,6 +366,8 @@ def main():
                                       rx_threads=args.rx_threads, tx_threads=args.tx_threads, target_util=args.target_util, cores=cores,
                                       core_set=(args.pin_mode == "set"))
             kind = "native front-end (vapx_ingest_*) + engine"
+    if "+" not in args.mode:
+        port_samples = None
     P = max(1, args.loadgen_procs)
     inband = args.inband or P > 1
     per_proc = [len(range(r, S, P)) for r in range(P)]
@@ -367,7 +377,10 @@ def main():
     def cmd_for(r):
         ports = getattr(srv, "ports_out", None)         # a group front-end: one output port per model
         c = [loadgen, "--port-in", str(srv.port_in)] + (["--ports-out", ",".join(str(p) for p in ports.values())] if ports else
-                                                        ["--port-out", str(srv.port_out)]) + ["--streams", str(per_proc[r]), "--hz", str(args.hz),
+                                                        ["--port-out", str(srv.port_out)])
+        if ports and port_samples:                      # a model slower than the leader answers every R-th frame with one packet of R hops
+            c += ["--port-samples", ",".join(str(port_samples[m]) for m in ports)]
+        c += ["--streams", str(per_proc[r]), "--hz", str(args.hz),
              "--seconds", str(args.seconds), "--warm", str(args.warm), "--packet-ms", str(args.packet_ms), "--threads", str(args.client_threads)]
         if inband:
             c += ["--inband", "1", "--hist-out", os.path.join(sync_dir, f"hist.{r}.json")]

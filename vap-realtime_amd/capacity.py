@@ -119,3 +119,44 @@ def plan(streams: int, hz: int, ctx_sec: float, mode: str = "vap", dedicated: Op
                           f"{out['fp32']['max_streams']}), split {100 * out['split']['busy']:.0f} % busy (holds {out['split']['max_streams']}); "
                           f"spread the dialogues over more GPUs (--gpus) or lower --streams")
     return out
+
+
+def plan_mixed(streams: int, models, dedicated: Optional[bool] = None) -> Dict:
+    """``plan`` for a MIXED trunk group: ``models`` is ``[(mode, frame_hz, ctx_sec), ...]``, the first leads (runs the CPC encoder at its
+    rate), the others are followers with rates and windows of their own.  Every model is priced at ITS rate and window:
+
+        busy(path) = sum over models of  streams x hz_m x executed GFLOP_m / sustained TFLOP/s of the path for m's window class
+
+    (a follower at 1/R of the leader's rate runs its transformer on every R-th leader tick of a stream; the collect kernel is a copy
+    of ~20 KB per due stream and is not priced).  Same keys as ``plan``; ``frame_hz`` / ``ctx_frames`` are the leader's, ``models``
+    lists each model's ``busy`` share per path."""
+    models = [(m, int(hz), float(ctx)) for m, hz, ctx in models]
+    lead_hz = models[0][1]
+    out = {"streams": streams, "frame_hz": lead_hz, "ctx_frames": int(models[0][2] * lead_hz), "mode": "+".join(m for m, _, _ in models),
+           "max_busy": MAX_BUSY, "models": []}
+    per_stream = {"fp32": 0.0, "split": 0.0}       # GPU-seconds per second of audio of ONE dialogue
+    for k, (m, hz, ctx) in enumerate(models):
+        T = int(ctx * hz)
+        row = {"mode": m, "frame_hz": hz, "ctx_frames": T}
+        for p in ("fp32", "split"):
+            macs = model_macs(hz, T, m, leader=(k == 0), qkv_in_attention=(p == "split" and T > 64))
+            dense_attn = (7 if m == "nod" else 5) * 2 * 4 * (T * T * 64 * 2)
+            gflop = 2.0 * (sum(macs.values()) - (1.0 - attention_executed_fraction(T)) * dense_attn) / 1e9
+            sec = hz * gflop / (MEASURED_TFLOPS[p]["short" if T <= 64 else "long"] * 1e3)
+            per_stream[p] += sec
+            row[p] = {"busy": streams * sec}
+        out["models"].append(row)
+    for p in ("fp32", "split"):
+        out[p] = {"frames_per_s": lead_hz / per_stream[p], "busy": streams * per_stream[p], "max_streams": int(MAX_BUSY / per_stream[p])}
+    if out["fp32"]["busy"] <= MAX_BUSY:
+        out.update(precision="fp32", ok=True, reason=f"fp32 path {100 * out['fp32']['busy']:.0f} % busy")
+    elif out["split"]["busy"] <= MAX_BUSY:
+        out.update(precision="split", ok=True,
+                   reason=f"fp32 path would be {100 * out['fp32']['busy']:.0f} % busy (> {100 * MAX_BUSY:.0f} %: holds {out['fp32']['max_streams']} streams within "
+                          f"10 ms); split-precision path {100 * out['split']['busy']:.0f} % busy")
+    else:
+        out.update(precision="split", ok=False,
+                   reason=f"NEITHER path holds <= 10 ms per frame at {streams} streams per GPU: fp32 {100 * out['fp32']['busy']:.0f} % busy (holds "
+                          f"{out['fp32']['max_streams']}), split {100 * out['split']['busy']:.0f} % busy (holds {out['split']['max_streams']}); "
+                          f"spread the dialogues over more GPUs or lower --streams")
+    return out

@@ -124,6 +124,15 @@ struct vapx_engine {
   bool orphaned = false;                  // follower whose leader was destroyed
   uint64_t tick = 0, followed_tick = 0;
   const int* last_ids = nullptr;          // device ids of the latest step (null = identity)
+  // a follower at its own window and / or at 1/R of the leader's rate (mixed trunk groups)
+  int R = 1;                              // leader ticks per frame of this follower
+  bool own_window = false;                // R == 1, ctx_frames differs from the leader's: bn / bhead from this engine's frames_seen
+  std::vector<int32_t> last_ids_host;     // leader: host copy of the latest step's ids (identity spelled out) ...
+  bool last_ids_known = false;            // ... unless they were device ids
+  std::vector<int32_t> phase;             // R > 1: leader ticks since the stream's last follower frame, per stream
+  float *acc = nullptr, *mixA = nullptr, *out_c = nullptr;   // R > 1: TrunkCollectArgs acc / A, compact output rows [max_batch][784]
+  int *mix_dev = nullptr, *mix_pinned = nullptr;             // R > 1: [3][max_batch] stream id | leader slot | pos of this tick's entries
+  hipEvent_t mix_evt = nullptr;           // the copy out of mix_pinned has completed
   // vapx_step_group (leader only): the tick's wire rows, model-major, on the device and in page-locked host memory
   float *gw_dev = nullptr, *gw_pinned = nullptr;
   size_t gw_cap = 0;                      // floats either block holds
@@ -248,7 +257,8 @@ enum { CLS_CONVTAIL = 5, CLS_FFN = 6, CLS_LASTROW = 7, CLS_CONV0 = 8, CLS_LSTM =
        CLS_FFN_PROJ = 14,   // long windows: the mode-2 flat-row block (attention output projection + LN_src + cross-attention query): two
                             // contractions per row where the FFN block proper has seven to twelve — its own class so that a class's
                             // FLOPs, time and HBM bytes describe the same launches (bench.py roofline)
-       CLS_COUNT = 15 };
+       CLS_TRUNK_COLLECT = 15,   // a slower trunk follower's collect (trunk_collect_kernel) and its output scatter: pure copies
+       CLS_COUNT = 16 };
 static inline int gemm_class(int epi) { return epi == EPI_BIAS_LN_GELU ? CLS_GEMM_BIAS_LN_GELU : epi; }
 
 struct ProfScope {
@@ -720,6 +730,10 @@ int flush_resets(vapx_engine* h, hipStream_t st) {
         if (r.ids[k] >= 0) hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, st, h->followers[f]->frames_seen + r.ids[k], 0, 1);
   }
   HIPCHK(h, hipGetLastError());
+  for (vapx_engine* f : h->followers)   // a slower follower starts the stream's next frame from its first leader hop (acc needs no clearing)
+    if (f->R > 1)
+      for (int32_t q : h->pending_resets)
+        if (q >= 0) f->phase[q] = 0;
   h->pending_resets.clear();
   return VAPX_OK;
 }
@@ -768,7 +782,8 @@ int run_combinator_all_rows(vapx_engine* h, const Scratch& sc, int n, hipStream_
 int step_group(vapx_engine* h, const Scratch& sc_own, int nb, int b0, const int* ids, const float* audio, int spc,
                float* out, hipStream_t st, const Scratch* lead = nullptr) {
   Scratch sc = sc_own;
-  if (lead) { sc.bn = lead->bn; sc.bhead = lead->bhead; }   // window fill / ring slot: decided by the leader's conv0
+  // window fill / ring slot: decided by the leader's conv0 — unless this follower keeps a window or a rate of its own
+  if (lead && !h->own_window && h->R == 1) { sc.bn = lead->bn; sc.bhead = lead->bhead; }
   // identity ids: kernels index state by batch slot, so advance the state bases by b0 streams
   const size_t s0 = ids ? 0 : (size_t)b0;
   const StateView sv{h->ring + s0 * 2 * h->T * 256, h->ring_qkv + s0 * 2 * h->T * 768, h->h_state + s0 * 512, h->c_state + s0 * 512,
@@ -778,6 +793,7 @@ int step_group(vapx_engine* h, const Scratch& sc_own, int nb, int b0, const int*
     rc = run_encoder(h, sc, sv, nb, ids, audio, spc, true, st);
     if (rc) return rc;
   } else {
+    if (h->own_window) HIPCHK(h, launch_window_meta(ids, sv.frames_seen, h->T, sc.bn, sc.bhead, nb, st));
     // this weight set's own downsample on the shared LSTM outputs: e = gelu(LN(Conv1d_K(lstm_out))), en = LN0(e)
     GemmArgs g = gemm_args(lead->lstm_out, contiguous_rows(h->ncpc * 256), h->W("down.w"), nb * 2, 256, h->ncpc * 256, sc.e,
                            contiguous_rows(256));
@@ -875,6 +891,9 @@ void vapx_destroy(vapx_handle h) {
   int* ip[] = {h->frames_seen, h->ids_dev, h->sc.bn, h->sc.bhead, h->sc.rot};
   for (int* p : ip) dfree(p);
   dfree(h->gw_dev);
+  dfree(h->acc); dfree(h->mixA); dfree(h->out_c); dfree(h->mix_dev);
+  if (h->mix_pinned) (void)hipHostFree(h->mix_pinned);
+  if (h->mix_evt) (void)hipEventDestroy(h->mix_evt);
   dfree(h->sio_dev);
   dfree(h->sio_ids_dev);
   if (h->sio_pin) (void)hipHostFree(h->sio_pin);
@@ -1096,6 +1115,9 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     if (lead->tick == 0 || lead->tick == h->followed_tick)
       return fail(h, VAPX_E_INVAL, "step the trunk leader first: no new encoder output since this follower's last step");
     if (n != lead->last_B) return fail(h, VAPX_E_INVAL, "n=%d differs from the leader's latest step (%d streams)", n, lead->last_B);
+    if (h->R > 1 && !lead->last_ids_known)
+      return fail(h, VAPX_E_INVAL, "the leader's latest step took device stream ids (VAPX_IDS_DEVICE): a follower at 1/%d of the leader's rate "
+                  "needs host ids (or none), the host decides which streams have a frame due", h->R);
   } else {
     if (!audio) return fail(h, VAPX_E_INVAL, "null audio");
     if (spc != h->hop && spc != h->L) return fail(h, VAPX_E_INVAL, "samples_per_ch must be %d (hop) or %d (full frame)", h->hop, h->L);
@@ -1106,12 +1128,19 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   // split the batch into groups on separate HIP streams: streams are independent, and a second
   // group's kernels fill the prologue / epilogue / tail bubbles of the first group's kernels
+  const bool slower = lead && h->R > 1;
+  int n_run = n;   // rows this engine's chain runs on: a slower follower's streams with a frame due this tick
+  if (slower) {
+    const int32_t* lid = lead->last_ids_host.data();
+    n_run = 0;
+    for (int i = 0; i < n; ++i) n_run += h->phase[lid[i]] + 1 == h->R;
+  }
   int G = h->n_groups;
-  while (G > 1 && n / G < 32) --G;
+  while (G > 1 && n_run / G < 32) --G;
   // free-running groups are only safe when nothing of this step is staged through engine-owned buffers on `st`
   // (host audio / host ids would be overwritten under a still-running group of the previous tick)
   const bool all_device = (flags & VAPX_OUT_DEVICE) && (lead || (flags & VAPX_AUDIO_DEVICE)) && (!stream_ids || (flags & VAPX_IDS_DEVICE));
-  const bool defer_join = G > 1 && (flags & VAPX_DEFER_JOIN) && all_device;
+  const bool defer_join = G > 1 && (flags & VAPX_DEFER_JOIN) && all_device && !slower;
   int rc = VAPX_OK;
   // a different batch split re-slices the shared scratch, and a reset touches state a running group may still use:
   // in both cases the previous tick's groups are joined first
@@ -1129,6 +1158,38 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
   if (lead) ids = lead->last_ids;   // same streams, same order as the leader's step (stream_ids is ignored)
   else rc = upload_ids(h, n, stream_ids, flags, st, &ids);
   if (rc) return rc;
+  if (!lead) {   // what a slower follower walks: this step's stream ids on the host
+    h->last_ids_known = !(stream_ids && (flags & VAPX_IDS_DEVICE));
+    if (h->last_ids_known && !h->followers.empty()) {
+      h->last_ids_host.resize(n);
+      for (int i = 0; i < n; ++i) h->last_ids_host[i] = stream_ids ? stream_ids[i] : i;
+    }
+  }
+  if (slower) {
+    // the host advances every stream's phase and sorts the batch into due entries (compact slots 0 .. n_run-1 of this engine's
+    // chain) and collecting ones; trunk_collect_kernel does the rest, keyed by stream id
+    if (lead->deferred_pending)   // the collect reads every overlap group's LSTM rows (the leader's own flag stays: only `st` waits)
+      for (int g = 0; g < lead->last_G; ++g) HIPCHK(h, hipStreamWaitEvent(st, lead->gdone[g], 0));
+    const int32_t* lid = lead->last_ids_host.data();
+    HIPCHK(h, hipEventSynchronize(h->mix_evt));
+    int *e_sid = h->mix_pinned, *e_slot = h->mix_pinned + n, *e_pos = h->mix_pinned + 2 * n;
+    int kd = 0, kn = n_run;
+    for (int i = 0; i < n; ++i) {
+      const int sid = lid[i], ph = h->phase[sid];
+      const bool due = ph + 1 == h->R;
+      const int k = due ? kd++ : kn++;
+      e_sid[k] = sid; e_slot[k] = i; e_pos[k] = ph;
+      h->phase[sid] = due ? 0 : ph + 1;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->mix_dev, h->mix_pinned, (size_t)3 * n * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipEventRecord(h->mix_evt, st));
+    TrunkCollectArgs ca;
+    ca.lstm_out = lead->sc.lstm_out; ca.acc = h->acc; ca.A = h->mixA; ca.sid = h->mix_dev; ca.slot = h->mix_dev + n; ca.pos = h->mix_dev + 2 * n;
+    ca.frames_seen = h->frames_seen; ca.bn = h->sc.bn; ca.bhead = h->sc.bhead;
+    ca.n = n; ca.n_due = n_run; ca.ncpc_l = lead->ncpc; ca.R = h->R; ca.T = h->T;
+    { ProfScope ps(h, CLS_TRUNK_COLLECT, st); HIPCHK(h, launch_trunk_collect(ca, st)); }
+    ids = h->mix_dev;   // the due streams' ids, in compact order
+  }
   const float* ad = audio;
   if (!lead && !(flags & VAPX_AUDIO_DEVICE)) {
     const size_t bytes = (size_t)n * 2 * spc * sizeof(float);
@@ -1144,26 +1205,33 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     ad = h->audio_dev;
   }
   float* od = (flags & VAPX_OUT_DEVICE) ? out : h->out_dev;
+  float* orows = slower ? h->out_c : od;   // a slower follower's kernels write compact rows; one scatter places them in `od`
   if (G > 1) {
     HIPCHK(h, hipEventRecord(h->gstart, st));
     for (int g = 0; g < G; ++g) HIPCHK(h, hipStreamWaitEvent(h->gstream[g], h->gstart, 0));
   }
   if (!lead) h->last_tail_fused = false;   // run_encoder sets it per group
-  for (int g = 0; g < G; ++g) {
-    int b0 = (int)((long)n * g / G), b1 = (int)((long)n * (g + 1) / G);
+  for (int g = 0; g < G && n_run > 0; ++g) {
+    int b0 = (int)((long)n_run * g / G), b1 = (int)((long)n_run * (g + 1) / G);
     const int nb = b1 - b0;
     hipStream_t gs = G > 1 ? h->gstream[g] : st;
     const Scratch sc = h->sc.slice(b0, h->P, h->ncpc, h->T);
     const int* gids = ids ? ids + b0 : nullptr;
     Scratch lsc;
-    if (lead) lsc = lead->sc.slice(b0, h->P, h->ncpc, h->T);
-    rc = step_group(h, sc, nb, b0, gids, lead ? nullptr : ad + (size_t)b0 * 2 * spc, spc, od + (size_t)b0 * VAPX_OUT_STRIDE, gs,
+    if (slower) lsc.lstm_out = h->mixA + (size_t)b0 * 2 * h->ncpc * 256;   // the collected operand: this engine's own n_cpc rows per frame
+    else if (lead) lsc = lead->sc.slice(b0, lead->P, lead->ncpc, lead->T);
+    rc = step_group(h, sc, nb, b0, gids, lead ? nullptr : ad + (size_t)b0 * 2 * spc, spc, orows + (size_t)b0 * VAPX_OUT_STRIDE, gs,
                     lead ? &lsc : nullptr);
     if (rc) return rc;
     if (G > 1) HIPCHK(h, hipEventRecord(h->gdone[g], gs));
   }
   if (G > 1 && !defer_join)
     for (int g = 0; g < G; ++g) HIPCHK(h, hipStreamWaitEvent(st, h->gdone[g], 0));
+  if (slower) {
+    OutScatterArgs oa{h->out_c, od, h->mix_dev + n, n, n_run, VAPX_OUT_STRIDE};
+    ProfScope ps(h, CLS_TRUNK_COLLECT, st);
+    HIPCHK(h, launch_out_scatter(oa, st));
+  }
   h->deferred_pending = defer_join;
   h->last_G = G;
   h->last_B = n;
@@ -1183,7 +1251,7 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     // are valid, the offending batch slots carry VAPX_OUT_STATUS = 1 and are listed by vapx_bad_slots().
     h->bad_slots.clear();
     for (int i = 0; i < n; ++i)
-      if (out[(size_t)i * VAPX_OUT_STRIDE + VAPX_OUT_STATUS] != 0.f) h->bad_slots.push_back(i);
+      if (out[(size_t)i * VAPX_OUT_STRIDE + VAPX_OUT_STATUS] == 1.f) h->bad_slots.push_back(i);   // VAPX_STATUS_NO_FRAME (2) is no fault
     if (!h->bad_slots.empty()) {
       const int i = h->bad_slots[0];
       return fail(h, VAPX_E_NUMERIC, "non-finite outputs for batch slot %d (stream %d) and %zu more; the other rows are valid; these streams' state is "
@@ -1274,7 +1342,7 @@ int vapx_step_group(vapx_handle h, int32_t n, const int32_t* stream_ids, const f
     vapx_engine* e = m ? h->followers[m - 1] : h;
     e->bad_slots.clear();
     for (int i = 0; i < n; ++i)
-      if (wire_out[off[m] + (size_t)i * wf[m] + VAPX_OUT_STATUS] != 0.f) { e->bad_slots.push_back(i); h->group_bad.push_back({i, m}); }
+      if (wire_out[off[m] + (size_t)i * wf[m] + VAPX_OUT_STATUS] == 1.f) { e->bad_slots.push_back(i); h->group_bad.push_back({i, m}); }
   }
   if (!h->group_bad.empty())
     return fail(h, VAPX_E_NUMERIC, "non-finite outputs for batch slot %d in model %d and %zu more (slot, model) pairs; the other rows are valid; "
@@ -1316,9 +1384,17 @@ int vapx_attach_trunk(vapx_handle f, vapx_handle lead) {
   if (f == lead || lead->trunk || f->trunk || !f->followers.empty())
     return fail(f, VAPX_E_INVAL, "attach a stand-alone engine to a leader that is not itself a follower");
   if (f->tick != 0 || lead->tick != 0) return fail(f, VAPX_E_INVAL, "attach before the first step of either engine");
-  if (f->cfg.device_id != lead->cfg.device_id || f->cfg.frame_hz != lead->cfg.frame_hz || f->T != lead->T ||
-      f->cfg.max_streams != lead->cfg.max_streams || f->cfg.max_batch != lead->cfg.max_batch)
-    return fail(f, VAPX_E_INVAL, "device, frame_hz, ctx_frames, max_streams and max_batch must match the leader's");
+  if (f->cfg.device_id != lead->cfg.device_id || f->cfg.max_streams != lead->cfg.max_streams || f->cfg.max_batch != lead->cfg.max_batch)
+    return fail(f, VAPX_E_INVAL, "device, max_streams and max_batch must match the leader's");
+  // window and rate may differ: the follower's frame is R consecutive leader ticks (a CPC frame is a function of real samples only)
+  if (lead->cfg.frame_hz < f->cfg.frame_hz)
+    return fail(f, VAPX_E_INVAL, "the leader (%d Hz) is slower than this follower (%d Hz): the group's fastest model leads, a follower "
+                "cannot make frames its leader never encodes", lead->cfg.frame_hz, f->cfg.frame_hz);
+  if (lead->cfg.frame_hz % f->cfg.frame_hz != 0)
+    return fail(f, VAPX_E_INVAL, "the leader's frame_hz (%d) is not an integer multiple of this follower's (%d): the follower's frames "
+                "would not end on leader ticks", lead->cfg.frame_hz, f->cfg.frame_hz);
+  const int R = lead->cfg.frame_hz / f->cfg.frame_hz;
+  if (f->ncpc != R * lead->ncpc) return fail(f, VAPX_E_INVAL, "internal: n_cpc %d is not %d x the leader's %d", f->ncpc, R, lead->ncpc);
   HIPCHK(f, hipSetDevice(f->cfg.device_id));
   HIPCHK(f, hipDeviceSynchronize());
   {  // the CPC CNN + LSTM weights must be the same tensors (they come from the common cpc_model file, vap_main.py:199-201)
@@ -1331,6 +1407,21 @@ int vapx_attach_trunk(vapx_handle f, vapx_handle lead) {
     if (memcmp(ha.data(), hb.data(), nfl * sizeof(float)) != 0)
       return fail(f, VAPX_E_INVAL, "CPC encoder weights differ from the leader's: nothing to share");
   }
+  if (R > 1) {
+    const size_t S = f->cfg.max_streams, B = f->cfg.max_batch;
+    hipError_t e = dalloc(&f->acc, S * 2 * (size_t)(R - 1) * lead->ncpc * 256);
+    if (e == hipSuccess) e = dalloc(&f->mixA, B * 2 * (size_t)f->ncpc * 256);
+    if (e == hipSuccess) e = dalloc(&f->out_c, B * VAPX_OUT_STRIDE);
+    if (e == hipSuccess) e = dalloc(&f->mix_dev, 3 * B);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&f->mix_pinned, 3 * B * sizeof(int), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->mix_evt, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(f->mix_evt, nullptr);
+    if (e != hipSuccess) {   // nothing of the engine is released yet: it stays a stand-alone engine
+      (void)hipGetLastError();
+      return fail(f, e == hipErrorOutOfMemory ? VAPX_E_NOMEM : VAPX_E_HIP, "state of a 1/%d-rate follower: %s", R, hipGetErrorString(e));
+    }
+    f->phase.assign(S, 0);
+  }
   // a follower never runs the encoder: release its encoder scratch and LSTM / carry state
   float** drop[] = {&f->sc.h0, &f->sc.h1, &f->sc.h2, &f->sc.h3, &f->sc.z, &f->sc.gx, &f->sc.lstm_out, &f->audio_dev,
                     &f->h_state, &f->c_state, &f->carry};
@@ -1342,6 +1433,8 @@ int vapx_attach_trunk(vapx_handle f, vapx_handle lead) {
     }
     *p = nullptr;
   }
+  f->R = R;
+  f->own_window = R == 1 && f->T != lead->T;
   f->trunk = lead;
   lead->followers.push_back(f);
   return VAPX_OK;
@@ -1474,6 +1567,9 @@ int sio_begin(vapx_engine* h, hipStream_t st) {
 
 // common argument checks; host ids are validated here, before anything is enqueued
 int sio_check(vapx_engine* h, const char* what, int n, const int32_t* ids, const void* buf, int flags) {
+  if (h->R > 1)   // the record has no place yet for the leader rows of a frame in the making (acc) and the stream's phase
+    return fail(h, VAPX_E_INVAL, "%s: refused on a trunk follower at 1/%d of its leader's rate: a state record does not carry the stream's "
+                "half-collected frame and phase yet (vapx_get_state / vapx_set_state move its ring)", what, h->R);
   if (n < 1 || n > h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "%s: n=%d outside [1,%d] (max_streams)", what, n, h->cfg.max_streams);
   if (!buf) return fail(h, VAPX_E_INVAL, "%s: null record buffer", what);
   if ((uintptr_t)buf & 15) return fail(h, VAPX_E_INVAL, "%s: the record buffer must be 16-byte aligned", what);

@@ -173,7 +173,7 @@ struct Job {                               // one tick's rows on their way out
   int n = 0;
   std::vector<Ready> rows;
   float* out = nullptr;                    // pinned; [max_batch][VAPX_OUT_STRIDE], or a trunk group's wire block [model][n][wire floats]
-  std::vector<uint8_t> bad;                // per row: some model's status is non-zero (no packet on any port)
+  std::vector<uint8_t> bad;                // per row: some model's status is 1, not finite (no packet on any port)
   double t_unix = 0;
   std::vector<std::vector<int>> part;      // row indices per sender thread: slot % X — a stream is always sent by the same thread
   int senders_done = 0;                    // sender threads that are through with this job (under job_mu)
@@ -185,6 +185,12 @@ struct OutPort {
   int mode = 0;
   int wf = VAPX_OUT_STRIDE;                // floats per row of this model in a job's block
   size_t off = 0;                          // floats per stream in front of this model's rows (the block is model-major)
+  int R = 1;                               // leader hops per frame of this model (a trunk follower slower than its leader: > 1)
+  // R > 1: the f64 echo of the leader hops of each dialogue's frame in the making.  Touched only by the slot's sender thread
+  // (slot % X), which sees a slot's rows in tick order.
+  std::vector<double> hist;                // [S][R-1][2][hop]
+  std::vector<int> hist_n;                 // [S] hops held
+  std::vector<uint32_t> hist_gen;          // [S] the connection they belong to: a new connection starts with an empty history
   int lsock = -1, port = 0;
   std::vector<int> out_all;                // broadcast listeners (under slots_mu)
   std::vector<int> lcount;                 // listeners per slot (under slots_mu)
@@ -766,6 +772,7 @@ bool send_packet(int fd, iovec* iov, int niov, size_t total) {
 void tx_main(vapx_ingest* g, int x) {
   std::vector<uint8_t> tail(64 + 8 * 256);
   const int hop = g->hop;
+  constexpr int MAX_R = 10;                  // 50 Hz -> 5 Hz
   int64_t next = 0;                          // the job this thread sends next: every sender walks over EVERY job, in publication order
   while (true) {
     // Per-stream order without serialising the ticks: the rows of a job are partitioned by slot % X, so a stream's packets always leave
@@ -783,25 +790,56 @@ void tx_main(vapx_ingest* g, int x) {
     for (int k : job.part[x]) {
       const Ready& rd = job.rows[k];
       Slot& s = g->slots[rd.slot];
-      if (!job.bad[k]) {
+      if (job.bad[k]) {   // the stream was reset (status 1 in some model): a slower model's frame in the making starts over with it
+        for (int m = 0; m < g->M; ++m)
+          if (g->ports[m].R > 1) g->ports[m].hist_n[rd.slot] = 0;
+      } else {
         // u32 len | f64 t | u32 n | x1 | u32 n | x2 | tail   (util.py:122-143; length prefix vap_main.py:446-448); a trunk group sends one
         // packet per model, each to its own port's listeners, tail in that model's framing (bc util.py:193-211, nod :213-237)
         for (int m = 0; m < g->M; ++m) {
           OutPort& o = g->ports[m];
           const float* row = job.out + (size_t)job.n * o.off + (size_t)k * o.wf;
           uint8_t head[16], mid[4];
-          const int tb = encode_tail(o.mode, row, tail.data(), std::min(256, o.wf - VAPX_OUT_LOGITS));
-          const uint32_t plen = 8 + 2 * (4 + 8 * (uint32_t)hop) + (uint32_t)tb;
-          uint8_t* p = head;
-          put_u32(p, plen); put_f64(p, job.t_unix); put_u32(p, (uint32_t)hop);
-          p = mid; put_u32(p, (uint32_t)hop);
           double* e = g->f64buf(rd.slot, rd.buf);
-          iovec iov[5] = {{head, 16}, {e, (size_t)hop * 8}, {mid, 4}, {e + hop, (size_t)hop * 8}, {tail.data(), (size_t)tb}};
+          // a model at 1/R of the leader's rate answers every R-th leader hop of a dialogue with ONE packet echoing all R hops, what
+          // its reference program sends (n = R * hop samples per channel); the hops in between (VAPX_STATUS_NO_FRAME) only add to its
+          // echo history: no packet, no reset
+          int held = 0;
+          double* hb = nullptr;
+          if (o.R > 1) {
+            hb = o.hist.data() + (size_t)rd.slot * (o.R - 1) * 2 * hop;
+            int& hn = o.hist_n[rd.slot];
+            if (o.hist_gen[rd.slot] != rd.gen) { hn = 0; o.hist_gen[rd.slot] = rd.gen; }
+            if (row[VAPX_OUT_STATUS] == (float)VAPX_STATUS_NO_FRAME) {
+              if (hn < o.R - 1) { memcpy(hb + (size_t)hn * 2 * hop, e, (size_t)2 * hop * 8); ++hn; }
+              continue;
+            }
+            held = hn;
+            hn = 0;
+            // a connection that began in the middle of this model's frame (carry-only reconnect: the engine's phase runs on) has no
+            // samples to echo for the frame's head: that one frame goes unanswered
+            if (held != o.R - 1) continue;
+          }
+          const uint32_t ns = (uint32_t)(hop * o.R);
+          const int tb = encode_tail(o.mode, row, tail.data(), std::min(256, o.wf - VAPX_OUT_LOGITS));
+          const uint32_t plen = 8 + 2 * (4 + 8 * ns) + (uint32_t)tb;
+          uint8_t* p = head;
+          put_u32(p, plen); put_f64(p, job.t_unix); put_u32(p, ns);
+          p = mid; put_u32(p, ns);
+          iovec iov[2 * MAX_R + 3];
+          int niov = 0;
+          iov[niov++] = {head, 16};
+          for (int c = 0; c < 2; ++c) {
+            if (c) iov[niov++] = {mid, 4};
+            for (int q = 0; q < held; ++q) iov[niov++] = {hb + ((size_t)q * 2 + c) * hop, (size_t)hop * 8};
+            iov[niov++] = {e + (size_t)c * hop, (size_t)hop * 8};
+          }
+          iov[niov++] = {tail.data(), (size_t)tb};
           const size_t total = 4 + plen;
           auto send_to = [&](std::vector<int>& fds) {
             for (size_t i = 0; i < fds.size();) {
               const double ts0 = g->debug ? mono_now() : 0.0;
-              const bool sent = send_packet(fds[i], iov, 5, total);
+              const bool sent = send_packet(fds[i], iov, niov, total);
               if (g->debug) atomic_max(g->dbg_send_us, (int64_t)((mono_now() - ts0) * 1e6));   // longest sendmsg() call (the socket is non-blocking)
               if (sent) { g->tx_bytes.fetch_add((int64_t)total, std::memory_order_relaxed); ++i; }
               else { close(fds[i]); fds.erase(fds.begin() + i); g->dropped.fetch_add(1); g->out_conns.fetch_sub(1); if (g->broadcast) link_event(g, LK_OUT_CLOSED, -1); }
@@ -931,7 +969,7 @@ void tick_main(vapx_ingest* g) {
     job.bad.assign(n, 0);
     for (int k = 0; k < n; ++k) {
       for (int m = 0; m < g->M; ++m)
-        if (job.out[(size_t)n * g->ports[m].off + (size_t)k * g->ports[m].wf + VAPX_OUT_STATUS] != 0.f) job.bad[k] = 1;
+        if (job.out[(size_t)n * g->ports[m].off + (size_t)k * g->ports[m].wf + VAPX_OUT_STATUS] == 1.f) job.bad[k] = 1;   // (2: no frame due, no fault)
       if (job.bad[k]) {   // poisoned stream (in any model): fresh state, no packet on any port; counted once
         if (g->reset) g->reset(g->user, job.rows[k].slot);
         g->numeric_resets.fetch_add(1);
@@ -1077,14 +1115,20 @@ thread_local std::string g_open_error;   // vapx_ingest_last_open_error
 int open_refused(const char* why) { g_open_error = why; return VAPX_E_INVAL; }
 
 // a trunk group's ports: model m's framing, the geometry of its rows in the tick's wire block (vapx_step_group) and its requested port
-int setup_group(vapx_ingest* g, const int32_t* modes, int n_models, int ctx_frames, const vapx_ingest_config& cfg,
-                const int32_t* follower_ports_out) {
+int setup_group(vapx_ingest* g, int n_streams, const int32_t* frame_hzs, const int32_t* ctx_frames, const int32_t* modes, int n_models,
+                const vapx_ingest_config& cfg, const int32_t* follower_ports_out) {
   if (n_models < 1 || n_models > MAX_MODELS) return open_refused("a group serves one to three models");
+  for (int m = 0; m < n_models; ++m) {
+    const int hz = frame_hzs[m];
+    if (hz != 5 && hz != 10 && hz != 20 && hz != 50) return open_refused("frame_hz must be 5, 10, 20 or 50");
+    if (hz > frame_hzs[0]) return open_refused("model 0 leads the group and must be its fastest model: a follower's frame_hz exceeds it");
+    if (frame_hzs[0] % hz) return open_refused("the leader's frame_hz must be an integer multiple of every follower's");
+  }
   if (cfg.port_in < 0 || cfg.port_out < 0)
     return open_refused("a trunk group cannot be a passive shard (port_in = -1): the front door is single-model");
   size_t acc = 0;
   for (int m = 0; m < n_models; ++m) {
-    const int wf = vapx_wire_floats(modes[m], ctx_frames);
+    const int wf = vapx_wire_floats(modes[m], ctx_frames[m]);
     if (wf <= 0) return open_refused("bad mode or ctx_frames");
     for (int j = 0; j < m; ++j)
       if (modes[j] == modes[m]) return open_refused("the models of a group must have pairwise distinct modes (vap, bc, nod)");
@@ -1092,6 +1136,13 @@ int setup_group(vapx_ingest* g, const int32_t* modes, int n_models, int ctx_fram
     g->ports[m].mode = modes[m];
     g->ports[m].wf = wf;
     g->ports[m].off = acc;
+    g->ports[m].R = frame_hzs[0] / frame_hzs[m];
+    if (g->ports[m].R > 1) {   // input framing, ticks and batching stay the leader's; this model's packets echo R leader hops
+      const size_t hop = (size_t)(16000 / frame_hzs[0]);
+      g->ports[m].hist.assign((size_t)n_streams * (g->ports[m].R - 1) * 2 * hop, 0.0);
+      g->ports[m].hist_n.assign(n_streams, 0);
+      g->ports[m].hist_gen.assign(n_streams, 0u);
+    }
     g->cfg_ports_out[m] = (m && follower_ports_out) ? follower_ports_out[m - 1] : 0;
     acc += (size_t)wf;
   }
@@ -1175,13 +1226,24 @@ int32_t vapx_wire_floats(int32_t mode, int32_t ctx_frames) {
 int vapx_ingest_open_group_fn(vapx_ingest_group_step_fn step, vapx_ingest_reset_fn reset, void* user, int32_t n_streams, int32_t max_batch,
                               int32_t frame_hz, int32_t ctx_frames, const int32_t* modes, int32_t n_models, const vapx_ingest_config* cfg,
                               const int32_t* follower_ports_out, vapx_ingest_handle* out) {
+  const int32_t hzs[MAX_MODELS] = {frame_hz, frame_hz, frame_hz}, ctxs[MAX_MODELS] = {ctx_frames, ctx_frames, ctx_frames};
+  if (n_models > MAX_MODELS) { g_open_error.clear(); return open_refused("a group serves one to three models"); }
+  return vapx_ingest_open_group_fn2(step, reset, user, n_streams, max_batch, hzs, ctxs, modes, n_models, cfg, follower_ports_out, out);
+}
+
+int vapx_ingest_open_group_fn2(vapx_ingest_group_step_fn step, vapx_ingest_reset_fn reset, void* user, int32_t n_streams, int32_t max_batch,
+                               const int32_t* frame_hzs, const int32_t* ctx_frames, const int32_t* modes, int32_t n_models,
+                               const vapx_ingest_config* cfg, const int32_t* follower_ports_out, vapx_ingest_handle* out) {
   g_open_error.clear();
   vapx_ingest_config probe;
-  if (!step || !out || !modes || !read_config(cfg, &probe)) return open_refused("null argument or a vapx_ingest_config of unknown size");
+  if (!step || !out || !modes || !frame_hzs || !ctx_frames || !read_config(cfg, &probe))
+    return open_refused("null argument or a vapx_ingest_config of unknown size");
   if (n_streams < 1 || max_batch < 1 || max_batch > n_streams) return open_refused("need 1 <= max_batch <= n_streams");
+  if (n_models < 1 || n_models > MAX_MODELS) return open_refused("a group serves one to three models");
+  const int32_t frame_hz = frame_hzs[0];
   if (frame_hz != 5 && frame_hz != 10 && frame_hz != 20 && frame_hz != 50) return open_refused("frame_hz must be 5, 10, 20 or 50");
   vapx_ingest* g = new vapx_ingest();
-  int rc = setup_group(g, modes, n_models, ctx_frames, probe, follower_ports_out);
+  int rc = setup_group(g, n_streams, frame_hzs, ctx_frames, modes, n_models, probe, follower_ports_out);
   if (rc != VAPX_OK) { delete g; return rc; }
   g->step = step; g->reset = reset; g->user = user;
   g->S = n_streams; g->max_batch = max_batch; g->hz = frame_hz;
@@ -1202,14 +1264,14 @@ int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int
   vapx_config ec;
   int rc = vapx_get_config(leader, &ec);
   if (rc != VAPX_OK) return rc;
-  int32_t modes[MAX_MODELS] = {ec.mode, 0, 0};
-  for (int i = 0; i < n_followers; ++i) {
+  int32_t modes[MAX_MODELS] = {ec.mode, 0, 0}, hzs[MAX_MODELS] = {ec.frame_hz, 0, 0}, ctxs[MAX_MODELS] = {ec.ctx_frames, 0, 0};
+  for (int i = 0; i < n_followers; ++i) {   // each model's own rate and window (a mixed group: vapx.h, vapx_attach_trunk)
     vapx_config fc;
     if (!followers[i] || vapx_get_config(followers[i], &fc) != VAPX_OK) return open_refused("null follower");
-    modes[i + 1] = fc.mode;
+    modes[i + 1] = fc.mode; hzs[i + 1] = fc.frame_hz; ctxs[i + 1] = fc.ctx_frames;
   }
   vapx_ingest* g = new vapx_ingest();
-  rc = setup_group(g, modes, n_followers + 1, ec.ctx_frames, probe, follower_ports_out);
+  rc = setup_group(g, ec.max_streams, hzs, ctxs, modes, n_followers + 1, probe, follower_ports_out);
   if (rc == VAPX_OK && g->row_floats != vapx_group_wire_floats(leader)) {
     rc = open_refused("`followers` are not the leader's attached followers (vapx_attach_trunk) in attach order");
   }
@@ -1223,7 +1285,9 @@ int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int
     float* o = (float*)vapx_host_alloc((size_t)nw * g->row_floats * sizeof(float));
     if (a && o) {
       memset(a, 0, (size_t)nw * 2 * hop * sizeof(float));
-      for (int k = 0; k < 3; ++k) (void)vapx_step_group(leader, nw, nullptr, a, hop, o, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
+      int nwarm = 3;   // every model's chain at least once: a slower follower's runs on every R-th tick
+      for (int m = 0; m <= n_followers; ++m) nwarm = std::max(nwarm, g->ports[m].R);
+      for (int k = 0; k < nwarm; ++k) (void)vapx_step_group(leader, nw, nullptr, a, hop, o, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
       for (int i = 0; i < nw; ++i) (void)vapx_reset_stream(leader, i);
     }
     vapx_host_free(a);

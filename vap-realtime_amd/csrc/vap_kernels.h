@@ -127,6 +127,31 @@ struct WirePackArgs {   // wire_pack_kernel: up to 4 models per launch
   int n_models, n, src_stride;
 };
 
+// A trunk follower at 1/R of its leader's rate (vapx_attach_trunk): entry k < n_due is a stream whose frame completes this leader tick
+// (compact slot k of the follower's chain), the entries after them are streams still collecting.  Keyed by stream id.
+struct TrunkCollectArgs {
+  const float* lstm_out;   // leader's [n][2][ncpc_l][256]
+  float* acc;              // [S][2][(R-1)*ncpc_l][256] leader rows of each stream's frame in the making
+  float* A;                // [n_due][2][R*ncpc_l][256] the follower's downsample operand
+  const int* sid;          // [n] stream id of entry k
+  const int* slot;         // [n] leader batch slot of entry k
+  const int* pos;          // [n] leader hops this stream already holds in acc (not-due entries: where this hop goes)
+  const int* frames_seen;  // [S] the follower's
+  int* bn;                 // [n_due] out: rows in the follower's window this frame
+  int* bhead;              // [n_due] out: ring slot of the new row
+  int n, n_due, ncpc_l, R, T;
+};
+struct OutScatterArgs {    // compact follower rows -> the leader's batch order; a stream without a frame gets a zero row with status 2
+  const float* src;        // [n_due][stride]
+  float* dst;              // [n][stride]
+  const int* slot;         // [n] as in TrunkCollectArgs
+  int n, n_due, stride;
+};
+hipError_t launch_trunk_collect(const TrunkCollectArgs& a, hipStream_t st);
+hipError_t launch_out_scatter(const OutScatterArgs& a, hipStream_t st);
+// bn / bhead of a same-rate follower with a window of its own: bn[i] = min(fs + 1, T), bhead[i] = fs % T, fs = frames_seen[ids ? ids[i] : i]
+hipError_t launch_window_meta(const int* ids, const int* frames_seen, int T, int* bn, int* bhead, int n, hipStream_t st);
+
 struct StateIoArgs {    // state_io.hip: bulk stream-state export / import (vapx_export_streams / vapx_import_streams)
   float* rec;           // [n][rec_floats] records (device): header | lstm + carry (with_state) | ring [2][T][256] | cache [2][T][768] (with_cache)
   long rec_floats;

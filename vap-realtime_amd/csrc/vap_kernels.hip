@@ -1060,6 +1060,51 @@ __global__ __launch_bounds__(256) void wire_pack_kernel(WirePackArgs a) {
   *(f32x4*)(a.dst + a.dst_off[m] + idx * 4) = v;
 }
 
+// Trunk follower at 1/R of its leader's rate: a pure copy keyed by STREAM ID (batches are ragged and reorder between ticks).  One
+// workgroup per (entry, channel); a wave moves a row of 256 floats with one 16-byte load and store per lane.  A due entry k gets the
+// follower's downsample operand A[k][c] = the stream's (R-1) * ncpc_l collected rows followed by this tick's ncpc_l leader rows, and
+// its window fill / ring slot from the follower's own frame counter; a not-due entry parks this tick's rows in the stream's acc.
+__global__ __launch_bounds__(256) void trunk_collect_kernel(TrunkCollectArgs a) {
+  const int k = blockIdx.x, c = blockIdx.y;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int sid = a.sid[k], slot = a.slot[k];
+  const int nl = a.ncpc_l, na = (a.R - 1) * nl;
+  const float* src = a.lstm_out + ((long)slot * 2 + c) * nl * 256 + lane * 4;
+  float* accp = a.acc + ((long)sid * 2 + c) * na * 256 + lane * 4;
+  if (k < a.n_due) {
+    float* dst = a.A + ((long)k * 2 + c) * (na + nl) * 256 + lane * 4;
+    for (int r = w; r < na + nl; r += 4)
+      *(f32x4*)(dst + (long)r * 256) = r < na ? *(const f32x4*)(accp + (long)r * 256) : *(const f32x4*)(src + (long)(r - na) * 256);
+    if (c == 0 && threadIdx.x == 0) {
+      const int fs = a.frames_seen[sid];
+      a.bn[k] = fs + 1 < a.T ? fs + 1 : a.T;
+      a.bhead[k] = fs % a.T;
+    }
+  } else {
+    float* dst = accp + (long)a.pos[k] * nl * 256;
+    for (int r = w; r < nl; r += 4) *(f32x4*)(dst + (long)r * 256) = *(const f32x4*)(src + (long)r * 256);
+  }
+}
+
+// The follower's compact rows back into the leader's batch order; a stream without a frame this tick gets an all-zero row whose
+// VAPX_OUT_STATUS is VAPX_STATUS_NO_FRAME (2).  One workgroup per entry, one 16-byte store per lane.
+__global__ __launch_bounds__(256) void out_scatter_kernel(OutScatterArgs a) {
+  const int k = blockIdx.x, q = threadIdx.x;
+  if (q * 4 >= a.stride) return;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (k < a.n_due) v = *(const f32x4*)(a.src + (long)k * a.stride + q * 4);
+  else if (q == 3) v[1] = 2.f;   // float 13
+  *(f32x4*)(a.dst + (long)a.slot[k] * a.stride + q * 4) = v;
+}
+
+__global__ void window_meta_kernel(const int* ids, const int* frames_seen, int T, int* bn, int* bhead, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int fs = frames_seen[ids ? ids[i] : i];
+  bn[i] = fs + 1 < T ? fs + 1 : T;
+  bhead[i] = fs % T;
+}
+
 }  // namespace
 
 hipError_t launch_conv0(const Conv0Args& a, int B, hipStream_t st) {
@@ -1115,5 +1160,18 @@ hipError_t launch_wire_pack(const WirePackArgs& a, hipStream_t st) {
   for (int m = 0; m < a.n_models; ++m) wmax = a.wf4[m] > wmax ? a.wf4[m] : wmax;
   const long items = (long)a.n * wmax;
   hipLaunchKernelGGL(wire_pack_kernel, dim3((unsigned)((items + 255) / 256), a.n_models), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_trunk_collect(const TrunkCollectArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(trunk_collect_kernel, dim3(a.n, 2), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_out_scatter(const OutScatterArgs& a, hipStream_t st) {
+  if (a.stride > 1024 || a.stride % 4) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(out_scatter_kernel, dim3(a.n), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_window_meta(const int* ids, const int* frames_seen, int T, int* bn, int* bhead, int n, hipStream_t st) {
+  hipLaunchKernelGGL(window_meta_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ids, frames_seen, T, bn, bhead, n);
   return hipGetLastError();
 }

@@ -19,6 +19,7 @@ OUT_STRIDE = 784
 OUT_P_NOW, OUT_P_FUTURE, OUT_VAD, OUT_AUX, OUT_NVALID, OUT_LOGITS, OUT_E = 0, 2, 4, 6, 10, 16, 272
 OUT_VAD_LOGIT = 11
 OUT_STATUS = 13
+STATUS_NO_FRAME = 2     # a slower trunk follower had no frame due for this stream on this leader tick (vapx.h VAPX_STATUS_NO_FRAME)
 E_NUMERIC = -6
 ABI_VERSION = 2
 AUDIO_DEVICE, OUT_DEVICE, IDS_DEVICE = 1, 2, 4
@@ -38,11 +39,11 @@ EXPORTS = ("vapx_abi_version", "vapx_blob_floats", "vapx_create", "vapx_destroy"
            "vapx_wire_decode_input", "vapx_wire_encode_result", "vapx_vap_head", "vapx_va_classifier", "vapx_softmax256",
            "vapx_aggregate", "vapx_aux_head", "vapx_frontdoor_open", "vapx_frontdoor_open_links", "vapx_ingest_attach_link", "vapx_frontdoor_ports", "vapx_frontdoor_counts", "vapx_frontdoor_close",
            "vapx_wire_floats", "vapx_group_wire_floats", "vapx_step_group", "vapx_group_bad", "vapx_ingest_open_group",
-           "vapx_ingest_open_group_fn", "vapx_ingest_group_ports", "vapx_ingest_last_open_error",
+           "vapx_ingest_open_group_fn", "vapx_ingest_open_group_fn2", "vapx_ingest_group_ports", "vapx_ingest_last_open_error",
            "vapx_state_floats", "vapx_export_streams", "vapx_import_streams")
 PROF_CLASSES = {0: "gemm_store", 1: "gemm_gelu", 2: "gemm_resid", 3: "gemm_resid_ln", 4: "gemm_cn_relu",
                 5: "conv_tail", 6: "ffn_block", 7: "last_row", 8: "conv0", 9: "lstm", 10: "gather_ln", 11: "attention", 12: "head",
-                13: "gemm_bias_ln_gelu", 14: "ffn_proj"}
+                13: "gemm_bias_ln_gelu", 14: "ffn_proj", 15: "trunk_collect"}
 
 
 class VapxError(RuntimeError):
@@ -171,6 +172,9 @@ def load_library(path: Optional[str] = None):
     lib.vapx_ingest_open_group.argtypes = [vp, C.POINTER(vp), i32, vp, C.POINTER(i32), C.POINTER(vp)]
     lib.vapx_ingest_open_group_fn.restype = i32
     lib.vapx_ingest_open_group_fn.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), i32, vp, C.POINTER(i32), C.POINTER(vp)]
+    lib.vapx_ingest_open_group_fn2.restype = i32
+    lib.vapx_ingest_open_group_fn2.argtypes = [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, vp, C.POINTER(i32),
+                                               C.POINTER(vp)]
     lib.vapx_ingest_group_ports.restype = i32
     lib.vapx_ingest_group_ports.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), i32]
     lib.vapx_ingest_last_open_error.restype = C.c_char_p
@@ -480,32 +484,85 @@ class Engine:
                     "vapx_transformer_maps")
 
 
+TRUNK_RATIOS = (1, 2, 4, 5, 10)     # leader rate / follower rate (vapx.h, vapx_attach_trunk): 50->10, 50->5, 20->10, 20->5, 10->5
+
+
+def trunk_plan(modes: Sequence[str], frame_hz, context_len_sec) -> dict:
+    """Per-mode geometry of a trunk group, without a device: ``frame_hz`` / ``context_len_sec`` are scalars (every model), ``{mode:
+    value}`` dictionaries or sequences in ``modes`` order.  Returns ``{"leader": mode, "order": [leader, followers ...], "hz" / "ctx" /
+    "hop" / "L" / "T" / "R": {mode: value}}``.  The fastest model leads (ties: the earliest in ``modes``); ``R`` is the leader's
+    rate over the model's.  Raises ``VapxError`` for what ``vapx_attach_trunk`` refuses."""
+    modes = list(modes)
+
+    def per_mode(v, what):
+        if isinstance(v, dict):
+            if set(v) != set(modes):
+                raise VapxError(f"{what} names {sorted(v)}, the group serves {modes}")
+            return {m: v[m] for m in modes}
+        if isinstance(v, (list, tuple, np.ndarray)):
+            if len(v) == 1:
+                return {m: v[0] for m in modes}
+            if len(v) != len(modes):
+                raise VapxError(f"{what} has {len(v)} values for {len(modes)} models ({modes}): give one, or one per model in model order")
+            return dict(zip(modes, v))
+        return {m: v for m in modes}
+    hz = {m: int(v) for m, v in per_mode(frame_hz, "frame_hz").items()}
+    ctx = {m: float(v) for m, v in per_mode(context_len_sec, "context_len_sec").items()}
+    for m in modes:
+        if hz[m] not in (5, 10, 20, 50):
+            raise VapxError(f"{m}: frame_hz must be 5, 10, 20 or 50 (got {hz[m]})")
+    leader = max(modes, key=lambda m: hz[m])                 # max() keeps the first of equals
+    R = {}
+    for m in modes:
+        if hz[leader] % hz[m]:
+            raise VapxError(f"{m} at {hz[m]} Hz cannot follow {leader} at {hz[leader]} Hz: the leader's rate must be an integer "
+                            f"multiple of every model's (its frames would not end on leader ticks)")
+        R[m] = hz[leader] // hz[m]
+    return {"leader": leader, "order": [leader] + [m for m in modes if m != leader], "hz": hz, "ctx": ctx,
+            "hop": {m: 16000 // hz[m] for m in modes}, "L": {m: 16000 // hz[m] + 320 for m in modes},
+            "T": {m: int(ctx[m] * hz[m]) for m in modes}, "R": R}
+
+
 class TrunkGroup:
     """Several weight sets (vap / bc / nod) served from ONE pass of the CPC CNN + LSTM per tick.
 
     The reference runs one process per model, each re-encoding the same audio with the same ``cpc_model``
-    weights (vap_main.py:199-201, vap_bc_main.py, vap_nod_main.py).  Here ``blobs`` is ``{mode: blob}``; the first
-    entry leads (runs the encoder), the others follow.  ``step`` returns ``{mode: out[n, OUT_STRIDE]}``."""
+    weights (vap_main.py:199-201, vap_bc_main.py, vap_nod_main.py).  Here ``blobs`` is ``{mode: blob}``.  ``frame_hz`` and
+    ``context_len_sec`` are scalars (every model, as before) or per model: ``{mode: value}`` or a sequence in ``blobs`` order — the
+    reference's own deployment is vap 20 Hz / 2.5 s, bc 20 Hz / 5 s, nod 10 Hz / 10 s.  The fastest model leads (runs the encoder;
+    ties: the first entry), the others follow; ``hz / hop_of / L_of / T_of / R`` hold each mode's geometry, ``R[mode]`` being the
+    leader ticks per frame of that model.  Input framing (``hop``, ``L``) is the leader's.
 
-    def __init__(self, blobs: dict, frame_hz: int = 20, context_len_sec: float = 2.5, max_streams: int = 1,
+    ``step`` returns ``{mode: out[n, OUT_STRIDE]}``.  A model with ``R > 1`` answers every R-th tick of a stream: its block still has
+    n rows in the batch order, rows without a frame are zero with column OUT_STATUS = STATUS_NO_FRAME (``due`` masks them)."""
+
+    def __init__(self, blobs: dict, frame_hz=20, context_len_sec=2.5, max_streams: int = 1,
                  max_batch: Optional[int] = None, device_id: int = 0, **engine_kw):
         self.modes = list(blobs)
+        plan = trunk_plan(self.modes, frame_hz, context_len_sec)
+        self.hz, self.ctx, self.hop_of, self.L_of, self.T_of, self.R = (plan[k] for k in ("hz", "ctx", "hop", "L", "T", "R"))
+        self.order = plan["order"]                             # model order of vapx_step_group's wire block: leader, then followers
         self.engines = {}
-        for m in self.modes:                                   # engine_kw: groups / split_f16 / ... — the same for every weight set
-            self.engines[m] = Engine(blobs[m], frame_hz, context_len_sec, max_streams, max_batch, m, device_id, **engine_kw)
-        self.leader = self.engines[self.modes[0]]
-        for m in self.modes[1:]:
+        for m in self.order:                                   # engine_kw: groups / split_f16 / ... — the same for every weight set
+            self.engines[m] = Engine(blobs[m], self.hz[m], self.ctx[m], max_streams, max_batch, m, device_id, **engine_kw)
+        self.leader = self.engines[self.order[0]]
+        for m in self.order[1:]:
             self.engines[m].attach_trunk(self.leader)
         self.hop, self.L, self.T = self.leader.hop, self.leader.L, self.leader.T
 
     def step(self, audio: np.ndarray, stream_ids: Optional[Sequence[int]] = None) -> dict:
-        res = {self.modes[0]: self.leader.step(audio, stream_ids)}
-        for m in self.modes[1:]:
+        res = {self.order[0]: self.leader.step(audio, stream_ids)}
+        for m in self.order[1:]:
             res[m] = self.engines[m].step_follow(len(audio))
-        return res
+        return {m: res[m] for m in self.modes}
+
+    @staticmethod
+    def due(mode: str, rows: np.ndarray) -> np.ndarray:
+        """Boolean mask over ``rows`` (a model's block of ``step`` or ``step_wire``): True where the row carries a frame."""
+        return rows[:, OUT_STATUS] != STATUS_NO_FRAME
 
     def wire_floats(self, mode: str) -> int:
-        return wire_floats(mode, self.T)
+        return wire_floats(mode, self.T_of[mode])
 
     def step_wire(self, audio: np.ndarray, stream_ids: Optional[Sequence[int]] = None, out: Optional[np.ndarray] = None,
                   on_numeric: str = "raise") -> dict:
@@ -515,33 +572,34 @@ class TrunkGroup:
         n = len(audio)
         block = self.leader.step_group(audio, stream_ids, out, on_numeric)
         res, at = {}, 0
-        for m in self.modes:
+        for m in self.order:
             wf = self.wire_floats(m)
             res[m] = block[at:at + n * wf].reshape(n, wf)
             at += n * wf
-        return res
+        return {m: res[m] for m in self.modes}
 
     def step_device(self, n: int, audio_ptr: int, spc: int, out_ptrs: dict, ids_ptr: int = 0, stream: int = 0):
-        self.leader.step_device(n, audio_ptr, spc, out_ptrs[self.modes[0]], ids_ptr, stream)
-        for m in self.modes[1:]:
+        self.leader.step_device(n, audio_ptr, spc, out_ptrs[self.order[0]], ids_ptr, stream)
+        for m in self.order[1:]:
             self.engines[m].step_follow_device(n, out_ptrs[m], stream)
 
     def reset_stream(self, sid: int):
         self.leader.reset_stream(sid)                      # cascades to the followers
 
     def export_streams(self, ids: Optional[Sequence[int]] = None, cache: bool = False) -> dict:
-        """``{mode: records}``, leader first: the leader's records carry LSTM + carry, a follower's only its ring (+ cache)."""
-        return {m: self.engines[m].export_streams(ids, cache) for m in self.modes}
+        """``{mode: records}``: the leader's records carry LSTM + carry, a follower's only its ring (+ cache).  A group with a
+        follower slower than its leader raises the engine's refusal (its records do not carry the half-collected frame yet)."""
+        return {m: self.engines[m].export_streams(ids, cache) for m in sorted(self.modes, key=lambda m: -self.R[m])}
 
     def import_streams(self, ids: Optional[Sequence[int]], records: dict, cache: Optional[bool] = None):
         """Inverse of ``export_streams``; ``records`` must name exactly this group's modes."""
         if set(records) != set(self.modes):
             raise VapxError(f"records for modes {sorted(records)}, this group serves {self.modes}")
-        for m in self.modes:
+        for m in sorted(self.modes, key=lambda m: -self.R[m]):     # a refusing (slower) model first: no stream is touched
             self.engines[m].import_streams(ids, records[m], cache)
 
     def close(self):
-        for m in reversed(self.modes):                     # followers before their leader
+        for m in reversed(self.order):                     # followers before their leader
             self.engines[m].close()
 
 

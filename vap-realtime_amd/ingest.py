@@ -112,13 +112,17 @@ class NativeServer:
                   keep_nofile: bool = False, core_set: bool = False, keep_state: bool = False):
         """One front-end for a whole ``engine.TrunkGroup`` (``vapx_ingest_open_group``): one input port, the audio encoded once, one
         output port per model in ``trunk_group.modes`` order (``ports_out``: one per model, default 50008, 50009, ...; 0 = ephemeral),
-        each with its model's reference framing.  ``.ports_out`` is the bound ``{mode: port}``."""
+        each with its model's reference framing.  ``.ports_out`` is the bound ``{mode: port}``.  In a mixed group (models with rates
+        of their own) input framing and ticks are the leader's; a model at 1/R of its rate sends one packet per R leader hops of a
+        dialogue, echoing all R hops (vapx.h, vapx_ingest_open_group)."""
         self = cls.__new__(cls)
         self.lib = _engine.load_library()
-        modes = list(trunk_group.modes)
-        ports = list(ports_out) if ports_out is not None else [50008 + i for i in range(len(modes))]
-        if len(ports) != len(modes):
-            raise ValueError(f"{len(modes)} models need {len(modes)} output ports, got {len(ports)}")
+        ports = list(ports_out) if ports_out is not None else [50008 + i for i in range(len(trunk_group.modes))]
+        if len(ports) != len(trunk_group.modes):
+            raise ValueError(f"{len(trunk_group.modes)} models need {len(trunk_group.modes)} output ports, got {len(ports)}")
+        by_mode = dict(zip(trunk_group.modes, ports))
+        modes = list(trunk_group.order)                        # the engine's model order: the leader (fastest model) first
+        ports = [by_mode[m] for m in modes]
         self._keep = [trunk_group]
         cfg = cls._cfg(port_in, ports[0], gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, bind_any, target_util,
                        cores, keep_nofile, core_set, keep_state)
@@ -133,18 +137,26 @@ class NativeServer:
         return self
 
     @classmethod
-    def over_group_function(cls, step: Callable, modes, n_streams: int, frame_hz: int = 20, ctx_frames: int = 50,
+    def over_group_function(cls, step: Callable, modes, n_streams: int, frame_hz=20, ctx_frames=50,
                             max_batch: Optional[int] = None, reset: Optional[Callable] = None, port_in: int = 0, ports_out=None,
                             gain: float = 1.0, max_wait_s: float = 0.002, min_batch: int = 0, reset_on_connect: bool = True,
                             broadcast: Optional[bool] = None, rx_threads: int = 0, tx_threads: int = 0, target_util: float = 1.0):
         """The group front-end over a Python step function (``vapx_ingest_open_group_fn``; host-logic tests without a GPU):
         ``step(ids int32[n], audio float32[n,2,hop], wire {mode: float32[n, wire_floats]}) -> int`` fills the views of that tick's wire
-        block in place (status columns start at 0); ``reset`` as in ``over_function``."""
+        block in place (status columns start at 0); ``reset`` as in ``over_function``.  ``frame_hz`` / ``ctx_frames`` may be sequences,
+        one value per model (``vapx_ingest_open_group_fn2``): ``modes[0]`` leads, ``hop`` is its hop, and the step function marks a
+        slower model's rows without a frame with ``engine.STATUS_NO_FRAME``."""
         self = cls.__new__(cls)
         self.lib = _engine.load_library()
         modes = list(modes)
+        mixed = not (np.isscalar(frame_hz) and np.isscalar(ctx_frames))
+        hzs = [int(frame_hz)] * len(modes) if np.isscalar(frame_hz) else [int(v) for v in frame_hz]
+        ctxs = [int(ctx_frames)] * len(modes) if np.isscalar(ctx_frames) else [int(v) for v in ctx_frames]
+        if len(hzs) != len(modes) or len(ctxs) != len(modes):
+            raise ValueError(f"{len(modes)} models need {len(modes)} rates and windows")
+        frame_hz = hzs[0]
         hop = 16000 // frame_hz
-        wf = [int(self.lib.vapx_wire_floats(MODE[m], ctx_frames)) for m in modes]
+        wf = [int(self.lib.vapx_wire_floats(MODE[m], c)) for m, c in zip(modes, ctxs)]
         ports = list(ports_out) if ports_out is not None else [0] * len(modes)
         if len(ports) != len(modes):
             raise ValueError(f"{len(modes)} models need {len(modes)} output ports, got {len(ports)}")
@@ -174,9 +186,14 @@ class NativeServer:
         marr = (C.c_int32 * len(modes))(*[MODE[m] for m in modes])
         fports = (C.c_int32 * max(len(modes) - 1, 1))(*ports[1:])
         h = C.c_void_p()
-        rc = self.lib.vapx_ingest_open_group_fn(C.cast(self._keep[0], C.c_void_p), C.cast(self._keep[1], C.c_void_p), None, n_streams,
-                                                max_batch or n_streams, frame_hz, ctx_frames, marr, len(modes), C.byref(cfg), fports,
-                                                C.byref(h))
+        if mixed:
+            harr, carr = (C.c_int32 * len(modes))(*hzs), (C.c_int32 * len(modes))(*ctxs)
+            rc = self.lib.vapx_ingest_open_group_fn2(C.cast(self._keep[0], C.c_void_p), C.cast(self._keep[1], C.c_void_p), None, n_streams,
+                                                     max_batch or n_streams, harr, carr, marr, len(modes), C.byref(cfg), fports, C.byref(h))
+        else:
+            rc = self.lib.vapx_ingest_open_group_fn(C.cast(self._keep[0], C.c_void_p), C.cast(self._keep[1], C.c_void_p), None, n_streams,
+                                                    max_batch or n_streams, frame_hz, ctxs[0], marr, len(modes), C.byref(cfg), fports,
+                                                    C.byref(h))
         if rc != 0:
             raise _engine.VapxError(f"vapx_ingest_open_group_fn failed ({rc}): {self.lib.vapx_ingest_last_open_error().decode()}")
         self._h = h

@@ -20,7 +20,12 @@ placement, same packets; 8 x 4096 dialogues need it in a container whose descrip
 ``--mode a+b[+c]`` (distinct names from vap / bc / nod, the first leads) serves SEVERAL models on one shared CPC trunk — the reference's
 ``vap_main.py``, ``vap_bc_main.py`` and ``vap_nod_main.py`` side by side on one ``cpc_model`` file, with the audio encoded once: one input port, one
 output port per model (``--port_num_out`` comma-separated, default 50008, 50009, ...), ``--vap_model`` one path per model, comma-separated in the
-same order.  One GPU, one process: the front door and ``--worker-procs`` are single-model.
+same order.  One GPU, one process: the front door and ``--worker-procs`` are single-model.  ``--vap_process_rate`` and
+``--context_len_sec`` take one value per model, comma-separated in model order (a single value applies to all): the reference's own deployment
+is ``--mode vap+bc+nod --vap_process_rate 20,20,10 --context_len_sec 2.5,5,10``.  The fastest model leads (ties: the first); a slower model's
+rate must divide the leader's, and it answers every R-th input frame of a dialogue with one packet that echoes all R frames' samples, as its
+reference program does.  ``--save_state`` / ``--load_state`` are refused for a group with a slower model (its half-collected frame is not
+part of a snapshot yet).
 
 ``--load_state PATH`` / ``--save_state PATH`` keep the dialogues' state (LSTM, carry, context window, Q|K|V cache) across a restart: the
 snapshot (``snapshot.py``) is imported after the engines are built and before the front-end opens, and written after the front-end has closed on
@@ -128,20 +133,51 @@ def out_ports(args, n_models: int):
     return ports
 
 
+def per_model(value, n_models: int, cast, flag: str):
+    """``"20,20,10"`` -> ``[20, 20, 10]``; a single value applies to every model.  Raises ValueError for another count."""
+    parts = [cast(p) for p in str(value).split(",")]
+    if len(parts) == 1:
+        return parts * n_models
+    if len(parts) != n_models:
+        raise ValueError(f"{flag} names {len(parts)} value(s) for {n_models} model(s): give one, or one per model in model order")
+    return parts
+
+
+def group_plan(args, names):
+    """Per-model geometry of a ``+`` mode (``engine.trunk_plan``) from ``--vap_process_rate`` / ``--context_len_sec``; raises ValueError for
+    rates a shared trunk cannot serve and for ``--save_state`` / ``--load_state`` with a model slower than its leader."""
+    from . import engine
+    rates = per_model(args.vap_process_rate, len(names), int, "--vap_process_rate")
+    ctxs = per_model(args.context_len_sec, len(names), float, "--context_len_sec")
+    try:
+        plan = engine.trunk_plan(names, rates, ctxs)
+    except engine.VapxError as e:
+        raise ValueError(str(e)) from None
+    slow = [m for m in names if plan["R"][m] > 1]
+    if slow and (args.save_state or args.load_state):
+        raise ValueError(f"--save_state / --load_state with {'+'.join(slow)} at 1/{plan['R'][slow[0]]} of the leader's rate: a snapshot does not carry "
+                         f"a slower model's half-collected frame yet (vapx_export_streams refuses it); serve this group without them")
+    if len({(plan["hz"][m], plan["T"][m]) for m in names}) > 1 and (args.save_state or args.load_state):
+        raise ValueError("--save_state / --load_state with models of different windows: a snapshot file describes ONE rate and window for the "
+                         "whole group (the engines' own vapx_export_streams / vapx_import_streams handle each window)")
+    return plan
+
+
 def load_group_blobs(args, names):
-    """{mode: blob} of a ``+`` mode, first = leader; every model on the SAME CPC weights (vapx_attach_trunk refuses otherwise)."""
+    """{mode: blob} of a ``+`` mode, each model at its own rate; every model on the SAME CPC weights (vapx_attach_trunk refuses otherwise)."""
     from . import checkpoints, weights as W
+    hz = args.group_plan["hz"]
     blobs = {}
     if args.synthetic_weights is not None:
-        for m in names:                              # one seed -> identical CPC tensors in every mode, only the heads differ
-            cpc, vap = W.synthetic_weights(args.synthetic_weights, args.vap_process_rate, m)
+        for m in names:                              # one seed -> identical CPC tensors in every mode and at every rate, only the rest differs
+            cpc, vap = W.synthetic_weights(args.synthetic_weights, hz[m], m)
             blobs[m] = W.pack_blob(cpc, vap, m)
         return blobs
     paths = args.vap_model.split(",")
     if len(paths) != len(names):
         raise ValueError(f"--vap_model names {len(paths)} file(s) for --mode {'+'.join(names)}: one per model, comma-separated, in that order")
     for m, path in zip(names, paths):
-        blobs[m] = checkpoints.import_checkpoints(path, args.cpc_model, frame_rate=args.vap_process_rate, mode=m)[0]
+        blobs[m] = checkpoints.import_checkpoints(path, args.cpc_model, frame_rate=hz[m], mode=m)[0]
     return blobs
 
 
@@ -151,10 +187,11 @@ def build_group(args, names):
     blobs = load_group_blobs(args, names)
     ports = out_ports(args, len(names))
     args.precision_plan = None
-    choose_precision(args, "+".join(names))          # capacity.plan sums the weight sets of a + mode
+    gp = args.group_plan
+    choose_precision(args, "+".join(names), [(m, gp["hz"][m], gp["ctx"][m]) for m in gp["order"]])   # every model at its own rate and window
     grp = srv = None
     try:
-        grp = engine.TrunkGroup(blobs, args.vap_process_rate, args.context_len_sec, max_streams=args.streams,
+        grp = engine.TrunkGroup(blobs, gp["hz"], gp["ctx"], max_streams=args.streams,
                                 max_batch=min(args.streams, args.max_batch), device_id=0, groups=2, split_f16=(args.precision == "split"))
         warm = load_state(state_path(args.load_state, 0, 1), grp)
         cores = None
@@ -179,8 +216,9 @@ def run_group(args, names, stop) -> int:
         print(f"[vapx] start-up failed: {e}", file=sys.stderr, flush=True)
         return 1
     outs = ", ".join(f"{m} :{srv.ports_out[m]}" for m in names)
-    print(f"[vapx] 1 GPU(s) x {args.streams} dialogue slots, modes {'+'.join(names)} on one CPC trunk, {args.precision} arithmetic, "
-          f"{args.vap_process_rate} Hz / {args.context_len_sec} s — input :{srv.port_in}, output {outs}", flush=True)
+    geo = ", ".join(f"{m} {grp.hz[m]} Hz / {grp.ctx[m]:g} s" for m in names)
+    print(f"[vapx] 1 GPU(s) x {args.streams} dialogue slots, modes {'+'.join(names)} on one CPC trunk ({grp.order[0]} leads), {args.precision} "
+          f"arithmetic, {geo} — input :{srv.port_in}, output {outs}", flush=True)
     last = time.time()
     while not stop["now"]:
         time.sleep(0.2)
@@ -194,10 +232,12 @@ def run_group(args, names, stop) -> int:
     return 0
 
 
-def choose_precision(args, mode):
+def choose_precision(args, mode, models=None):
+    """``models``: [(mode, frame_hz, ctx_sec), ...] of a trunk group, leader first — each is priced at its own rate and window."""
     if args.precision == "auto":                 # serve the arithmetic the load needs (capacity.plan: measured sustained rate per path)
         from . import capacity
-        pl = capacity.plan(args.streams, args.vap_process_rate, args.context_len_sec, mode)
+        pl = (capacity.plan_mixed(args.streams, models) if models else
+              capacity.plan(args.streams, args.vap_process_rate, args.context_len_sec, mode))
         args.precision_plan = pl
         print(f"[vapx] --precision auto -> {pl['precision']}: {pl['reason']}", file=sys.stderr, flush=True)
         if not pl["ok"]:
@@ -370,8 +410,8 @@ def main(argv=None) -> int:
     ap.add_argument("--cpc_model", type=str, default="../../asset/cpc/60k_epoch4-d0f474de.pt")
     ap.add_argument("--port_num_in", type=int, default=50007)
     ap.add_argument("--port_num_out", type=str, default=None, help="50008; with --mode a+b[+c] one port per model, comma-separated (default 50008, 50009, ...)")
-    ap.add_argument("--vap_process_rate", type=int, default=20)
-    ap.add_argument("--context_len_sec", type=float, default=2.5)
+    ap.add_argument("--vap_process_rate", type=str, default="20", help="20; with --mode a+b[+c] optionally one rate per model, comma-separated")
+    ap.add_argument("--context_len_sec", type=str, default="2.5", help="2.5; with --mode a+b[+c] optionally one window per model, comma-separated")
     ap.add_argument("--gpu", action="store_true", help="accepted for compatibility: this engine has no CPU path")
     ap.add_argument("--audio_gain", type=float, default=1.0)
     ap.add_argument("--mode", type=str, default=None,
@@ -416,6 +456,10 @@ def main(argv=None) -> int:
         names = group_modes(args.mode)
         if names is None:
             args.port_num_out = int(args.port_num_out)
+            args.vap_process_rate = per_model(args.vap_process_rate, 1, int, "--vap_process_rate")[0]
+            args.context_len_sec = per_model(args.context_len_sec, 1, float, "--context_len_sec")[0]
+        else:
+            args.group_plan = group_plan(args, names)
     except ValueError as e:
         ap.error(str(e))
     if names is not None:
