@@ -153,6 +153,33 @@ void vapx_destroy(vapx_handle h);
 int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* audio,
               int32_t samples_per_ch, float* out, int32_t flags, void* hip_stream);
 
+/* Input rate: audio at 8, 32 or 48 kHz, resampled to the model's 16 kHz on the device (csrc/resample.hip).  Telephone audio is 8 kHz
+ * and WebRTC delivers 48 kHz; the published multilingual checkpoints met their 8 kHz corpora through torchaudio's default resampler
+ * (train/audio.py:65-68), which is the filter used here: sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99, fp32 taps
+ * (vap-realtime_amd/resample.py restates it and writes the tables).  With g = gcd(input_hz, 16000), orig = input_hz / g, new = 16000 / g:
+ *   Y[new*i + p] = sum_k h[p][k] * x[orig*i + k - width]   (x = 0 outside the signal), one fmaf chain over k = 0 .. K-1
+ *   8000: orig 1, new 2, width 7, K 15     32000: 2, 1, 13, 28     48000: 3, 1, 19, 41
+ *
+ * vapx_set_input_rate: allowed once, on a freshly created engine with no step yet (the rule of vapx_attach_trunk); refused on a trunk
+ * follower (the leader owns the audio) and for any rate but 8000, 16000, 32000, 48000 (VAPX_E_INVAL).  16000 is accepted and changes
+ * nothing: such an engine behaves bit for bit as one that never made the call.  Otherwise the engine allocates a zeroed per-stream
+ * history and from then on
+ *   - vapx_step / vapx_step_group take samples_per_ch == hop_in = input_hz / frame_hz and nothing else: a full frame with the caller's
+ *     carry (hop + 320) is defined at 16 kHz only; vapx_encode_audio, whose frames carry their own carry, is refused;
+ *   - DELAY: a dialogue has no future samples, so the 16 kHz stream the model sees is Y delayed by d = ceil(width / orig) = 7 blocks:
+ *     z[m] = Y[m - new*d], zero for m < new*d — 0.875 ms at 8 kHz, 0.4375 ms at 32 and 48 kHz.  Tick t consumes x[t*hop_in, (t+1)*hop_in)
+ *     and emits z[t*hop, (t+1)*hop); the engine keeps the last H = orig*d + width input samples per stream and channel (14, 27, 40).  One
+ *     launch per step, before the overlap groups fork; conv0, the 320-sample carry and everything after them see plain 16 kHz hops;
+ *   - vapx_reset_stream and vapx_reset_carry zero the stream's history together with the carry: a new connection is a new signal;
+ *   - VAPX_DEFER_JOIN is not honoured (the resampled hops of a tick live in one buffer).
+ * vapx_get_input_rate: the rate in Hz (16000 unless another was set); on a follower 16000.
+ * vapx_resample: the whole-signal Y for `rows` independent signals, device pointers, x [rows][n_in] -> y [rows][ceil(new*n_in/orig)];
+ * stateless and without a handle, like vapx_softmax256; the same device function as the engine's kernel, so a stream stepped at
+ * input_hz equals, bit for bit, a 16 kHz engine fed z.  16000 copies. */
+int vapx_set_input_rate(vapx_handle h, int32_t input_hz);
+int32_t vapx_get_input_rate(vapx_handle h);
+int vapx_resample(int32_t input_hz, int64_t rows, int64_t n_in, const float* x, float* y, void* hip_stream);
+
 /* Batch slots (row indices of `out`) of the latest host-output vapx_step whose results were not finite; returns their number
  * (writes at most max_slots of them; slots may be NULL to just count). */
 int32_t vapx_bad_slots(vapx_handle h, int32_t* slots, int32_t max_slots);
@@ -229,7 +256,7 @@ int vapx_step_group(vapx_handle leader, int32_t n, const int32_t* stream_ids, co
                     float* wire_out, int32_t flags, void* hip_stream);
 int32_t vapx_group_bad(vapx_handle leader, int32_t* slots, int32_t* models, int32_t max);
 
-/* Zero one stream's state (context ring fill, LSTM h/c, carry).  The reference never resets
+/* Zero one stream's state (context ring fill, LSTM h/c, carry; with an input rate the resampler history too).  The reference never resets
  * model state on reconnect (vap_main.py:368-369 re-zeroes only the carry); this is the explicit
  * equivalent of constructing a fresh VAPRealTime for that stream.
  * Stream-ordered and free for everybody else: the call only queues the request (no device work, no synchronisation); the
@@ -237,7 +264,7 @@ int32_t vapx_group_bad(vapx_handle leader, int32_t* slots, int32_t* models, int3
  * vapx_set_state / vapx_peek apply it before they look. */
 int vapx_reset_stream(vapx_handle h, int32_t stream_id);
 
-/* Zero only the 320-sample carry of a stream: exactly what the reference does when an input client (re)connects
+/* Zero only the 320-sample carry of a stream (and, with an input rate, its resampler history): exactly what the reference does when an input client (re)connects
  * (vap_main.py:368-369: current_x1 / current_x2 restart from zeros, LSTM and context are kept).  Queued and stream-ordered
  * like vapx_reset_stream. */
 int vapx_reset_carry(vapx_handle h, int32_t stream_id);
@@ -247,7 +274,8 @@ int vapx_get_config(vapx_handle h, vapx_config* out);
 
 /* State export / import for one stream (tests, migration between GPUs).  Host pointers, any may
  * be NULL to skip.  ring: [2][T][256] oldest->newest, rows >= n_frames undefined;
- * lstm: [2 ch][2 (h,c)][256]; carry: [2][320]. */
+ * lstm: [2 ch][2 (h,c)][256]; carry: [2][320].  The resampler history of an engine with an input rate has no place in these calls:
+ * vapx_set_state ZEROES it (the stream's input continues as a new signal); vapx_export_streams / vapx_import_streams carry it. */
 int vapx_get_state(vapx_handle h, int32_t stream_id, float* ring, int32_t* n_frames, float* lstm, float* carry);
 int vapx_set_state(vapx_handle h, int32_t stream_id, const float* ring, int32_t n_frames, const float* lstm,
                    const float* carry);
@@ -261,9 +289,13 @@ int vapx_set_state(vapx_handle h, int32_t stream_id, const float* ring, int32_t 
  *             [0] VAPX_STATE_MAGIC   [1] ctx_frames   [2] frame_hz
  *             [3] content bits: VAPX_STATE_HAS_LSTM (LSTM + carry follow), VAPX_STATE_HAS_CACHE (the Q|K|V cache follows the ring),
  *                 VAPX_STATE_CACHE_SPLIT (that cache was made by an engine created with VAPX_FLAG_SPLIT_F16)
- *             [4] n_frames, 0 .. T: valid ring rows   [5] the exporting engine's mode (informational)   [6], [7] zero
+ *             [4] n_frames, 0 .. T: valid ring rows   [5] the exporting engine's mode (informational)   [6], [7] zero — unless the
+ *                 engine has an input rate (vapx_set_input_rate): then [3] has VAPX_STATE_HAS_RESAMPLE, [6] is input_hz and bits 0 / 1 of [7]
+ *                 say that channel 1 / 2 has consumed a tick since the stream's reset (before that the first d blocks are silent)
  *   lstm    [2 ch][2 (h, c)][256] and carry [2][320] (1664 floats) - a stand-alone engine or a trunk leader only.  A trunk follower's
  *           records omit them: that state lives in its leader
+ *   history only with VAPX_STATE_HAS_RESAMPLE: the resampler's input history [2][H] (H = 14, 27, 40 at 8, 32, 48 kHz), padded with zeros to a
+ *           multiple of 4 floats (28, 56, 80), after the carry.  Records of engines without an input rate are byte for byte what they were
  *   ring    [2][T][256] chronological, oldest -> newest; rows t >= n_frames are written as ZEROS, so a blob is deterministic and never
  *           carries uninitialised (or VAPX_POISON_SCRATCH) memory
  *   cache   only with VAPX_STATE_CACHE: the layer-0 Q|K|V cache [2][T][768], same order, same zero fill
@@ -293,7 +325,7 @@ int vapx_set_state(vapx_handle h, int32_t stream_id, const float* ring, int32_t 
  * Validation happens on the host before anything is enqueued - a refused call modifies NO stream: n (VAPX_E_RANGE), host ids (VAPX_E_RANGE
  * out of range, VAPX_E_INVAL duplicate), and for a host src every record's header: magic, ctx_frames, frame_hz, content bits (VAPX_E_INVAL:
  * a leader / stand-alone record has VAPX_STATE_HAS_LSTM and is refused by a follower, and the reverse; VAPX_STATE_HAS_CACHE must agree
- * with the flag; VAPX_STATE_CACHE_SPLIT with the engine) and n_frames in [0, T] (VAPX_E_RANGE); vapx_last_error names the record index
+ * with the flag; VAPX_STATE_CACHE_SPLIT with the engine; VAPX_STATE_HAS_RESAMPLE and input_hz with the engine's input rate) and n_frames in [0, T] (VAPX_E_RANGE); vapx_last_error names the record index
  * and the field.  A DEVICE src cannot be read without a synchronisation: the kernel clamps n_frames into [0, T] and trusts the rest - the
  * caller vouches for records it keeps on the device (they came from vapx_export_streams of a matching engine).
  * Trunk groups: export / import on the leader moves LSTM + carry + the leader's ring, on a follower that follower's ring (+ cache);
@@ -305,6 +337,8 @@ int vapx_set_state(vapx_handle h, int32_t stream_id, const float* ring, int32_t 
 #define VAPX_STATE_HAS_CACHE 2
 #define VAPX_STATE_CACHE_SPLIT 4
 #define VAPX_STATE_HEADER_FLOATS 8
+enum { VAPX_STATE_HAS_RESAMPLE = 8 }; /* content bit of records with a resampler history; an enumerator: the macros above are the vocabulary
+                                         of records without one */
 size_t vapx_state_floats(vapx_handle h, int32_t flags);
 int vapx_export_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, float* dst, int32_t flags, void* hip_stream);
 int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* src, int32_t flags, void* hip_stream);

@@ -17,10 +17,12 @@
 //   --ports-out a,b,...   a server that serves several models on one shared trunk (serve --mode a+b[+c]) has one output port per model: every
 //                     dialogue opens one listener per port; a frame counts as answered when EVERY port has answered it and its latency is that
 //                     of the last packet.  With a single port this is --port-out.  (Not with --inband: one process, sender-side stamps.)
-//   --port-samples a,b,...   with --ports-out: the samples per channel each port's packets echo (default: one hop, 16000 / hz).  A model at
+//   --port-samples a,b,...   with --ports-out: the samples per channel each port's packets echo (default: one hop, input rate / hz).  A model at
 //                     1/R of the input rate (a mixed trunk group: serve --vap_process_rate 20,20,10) answers every R-th frame of a dialogue with
 //                     one packet of R hops: frame k expects a packet on that port only when (k + 1) % R == 0.  Every packet's sample count
 //                     is checked, and the latency percentiles are also reported per port (last byte of the packet's LAST frame sent -> packet read).
+//   --input-rate R    sample rate of the dialogues' audio (8000, 16000, 32000, 48000; default 16000): a 10 ms packet carries R / 100 sample
+//                     pairs and a frame R / hz; the server's engines resample on the GPU (serve --input_rate R) and echo the samples as received
 //   --hist-out F      latency histogram (50 us bins up to 400 ms) as JSON, for merging the processes' percentiles
 // Build: make -C vap-realtime_amd/csrc loadgen   (plain C++17, no dependencies)
 #include <arpa/inet.h>
@@ -100,7 +102,7 @@ int main(int argc, char** argv) {
   const char* host = "127.0.0.1";
   std::vector<int> ports_out{50008};
   std::vector<int> port_samples;
-  int port_in = 50007, S = 256, hz = 20, packet_ms = 10, threads = 4;
+  int port_in = 50007, S = 256, hz = 20, packet_ms = 10, threads = 4, input_rate = 16000;
   double seconds = 10.0, late_ms = 10.0, warm = 3.0;
   int inband = 0, procs = 1, rank = 0, total_streams = 0;
   const char* sync_dir = nullptr;
@@ -120,6 +122,7 @@ int main(int argc, char** argv) {
     }
     else if (k == "--streams") S = atoi(v);
     else if (k == "--hz") hz = atoi(v);
+    else if (k == "--input-rate") input_rate = atoi(v);
     else if (k == "--seconds") seconds = atof(v);
     else if (k == "--warm") warm = atof(v);
     else if (k == "--packet-ms") packet_ms = atoi(v);
@@ -149,7 +152,8 @@ int main(int argc, char** argv) {
       while (access(p, F_OK) != 0) usleep(2000);
     }
   };
-  const int hop = 16000 / hz;
+  if (input_rate != 8000 && input_rate != 16000 && input_rate != 32000 && input_rate != 48000) { fprintf(stderr, "--input-rate: 8000, 16000, 32000 or 48000\n"); return 2; }
+  const int hop = input_rate / hz;                   // sample pairs per frame on the wire
   std::vector<int> ratio(P, 1);                      // frames per packet of each port
   if (!port_samples.empty()) {
     if ((int)port_samples.size() != P) { fprintf(stderr, "--port-samples needs one value per output port\n"); return 2; }
@@ -169,7 +173,7 @@ int main(int argc, char** argv) {
   const int NF = 8;
   std::vector<double> audio((size_t)NF * hop * 2);
   for (int i = 0; i < NF * hop; ++i) {
-    const double t = i / 16000.0;
+    const double t = i / (double)input_rate;
     audio[2 * i] = 0.2 * sin(2 * M_PI * 140.0 * t) * (0.6 + 0.4 * sin(2 * M_PI * 4.0 * t)) + 1e-3 * ((rand() % 2001) / 1000.0 - 1.0);
     audio[2 * i + 1] = 0.15 * sin(2 * M_PI * 210.0 * t + 1.0) * (i / hop % 2 ? 1.0 : 0.05) + 1e-3 * ((rand() % 2001) / 1000.0 - 1.0);
   }

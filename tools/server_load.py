@@ -138,6 +138,9 @@ def main():
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--warm", type=float, default=4.0)
     ap.add_argument("--packet-ms", type=int, default=10)
+    ap.add_argument("--input-rate", type=int, default=16000, choices=[8000, 16000, 32000, 48000],
+                    help="sample rate of the dialogues' audio: a 10 ms packet carries input_rate / 100 sample pairs and the engines resample on "
+                         "the GPU (serve --input_rate); real engines behind the native front-end only")
     ap.add_argument("--max-wait-ms", type=float, default=2.0)
     ap.add_argument("--min-batch", type=int, default=0)
     ap.add_argument("--max-batch", type=int, default=0)
@@ -180,6 +183,8 @@ def main():
     if not os.path.exists(loadgen):
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "vap-realtime_amd", "csrc"), "../../tools/loadgen"])
     S = args.streams
+    rate_kw = {"input_hz": args.input_rate} if args.input_rate != 16000 else {}
+    assert not rate_kw or not (args.fake or args.standin or args.python), "--input-rate needs real engines behind the native front-end"
     from vap_realtime_amd import dist_util, engine, ingest
     srv = None
     # placement: the front-end's tick / receive / sender threads on consecutive cores of the GPU's NUMA node, the load generator on the
@@ -313,8 +318,8 @@ def main():
         args.hz = max(hzs)                                # input framing and ticks are the leader's, the fastest model
         blobs = {m: W.pack_blob(*W.synthetic_weights(0, hz, m), m) for m, hz in zip(names, hzs)}   # one seed: the same CPC tensors in every model
         grp = engine.TrunkGroup(blobs, hzs, ctxs, max_streams=S, max_batch=args.max_batch or None, groups=args.groups,
-                                split_f16=args.split_f16)
-        port_samples = {m: grp.hop_of[m] for m in names} if any(r > 1 for r in grp.R.values()) else None
+                                split_f16=args.split_f16, **rate_kw)
+        port_samples = {m: grp.hop_of[m] * args.input_rate // 16000 for m in names} if any(r > 1 for r in grp.R.values()) else None
         srv = ingest.NativeServer.for_group(grp, port_in=0, ports_out=[0] * len(names), max_wait_s=args.max_wait_ms * 1e-3, min_batch=args.min_batch,
                                             rx_threads=args.rx_threads, tx_threads=args.tx_threads, target_util=args.target_util, cores=cores,
                                             core_set=(args.pin_mode == "set"))
@@ -333,7 +338,7 @@ def main():
             devs = [int(d) for d in args.devices.split(",") if d != ""] or [0] * N
             assert len(devs) == N, "--devices needs one id per shard"
             engs = [engine.Engine(blob, args.hz, args.ctx_sec, max_streams=(S + N - 1) // N, max_batch=args.max_batch or None, groups=args.groups,
-                                  device_id=devs[k], mode=args.mode, split_f16=args.split_f16) for k in range(N)]
+                                  device_id=devs[k], mode=args.mode, split_f16=args.split_f16, **rate_kw) for k in range(N)]
             shards = [ingest.NativeServer(e, port_in=-1, port_out=-1, max_wait_s=args.max_wait_ms * 1e-3, min_batch=args.min_batch,
                                           rx_threads=args.rx_threads, tx_threads=args.tx_threads, target_util=args.target_util,
                                           cores=(None if args.no_pin else dist_util.front_end_placement(devs[k], 1 + args.rx_threads + args.tx_threads,
@@ -361,7 +366,7 @@ def main():
             kind = f"ONE front door (vapx_frontdoor_*) + {N} passive native front-ends + {N} engines on devices {devs}"
         else:
             eng = engine.Engine(W.pack_blob(cpc, vap_sd, args.mode), args.hz, args.ctx_sec, max_streams=S, max_batch=args.max_batch or None, groups=args.groups,
-                                mode=args.mode, split_f16=args.split_f16)
+                                mode=args.mode, split_f16=args.split_f16, **rate_kw)
             srv = ingest.NativeServer(eng, port_in=0, port_out=0, max_wait_s=args.max_wait_ms * 1e-3, min_batch=args.min_batch,
                                       rx_threads=args.rx_threads, tx_threads=args.tx_threads, target_util=args.target_util, cores=cores,
                                       core_set=(args.pin_mode == "set"))
@@ -380,6 +385,8 @@ def main():
                                                         ["--port-out", str(srv.port_out)])
         if ports and port_samples:                      # a model slower than the leader answers every R-th frame with one packet of R hops
             c += ["--port-samples", ",".join(str(port_samples[m]) for m in ports)]
+        if args.input_rate != 16000:
+            c += ["--input-rate", str(args.input_rate)]
         c += ["--streams", str(per_proc[r]), "--hz", str(args.hz),
              "--seconds", str(args.seconds), "--warm", str(args.warm), "--packet-ms", str(args.packet_ms), "--threads", str(args.client_threads)]
         if inband:

@@ -105,6 +105,13 @@ struct vapx_engine {
   size_t ffn_trace_wgs = 0, attn_trace_wgs = 0;
   std::string ffn_trace_path, attn_trace_path;
 #endif
+  // input at 8 / 32 / 48 kHz (vapx_set_input_rate; resample.hip): resample_kernel turns the tick's hop_in samples into rs_out [max_batch][2][hop],
+  // which takes the place of the caller's audio in front of conv0
+  int in_hz = 0;                          // 0: the input is 16 kHz, nothing below exists
+  ResampleGeom rs = {};
+  int hop_in = 0, rs_rec = 0;             // input samples per channel and tick; floats of a stream's history [2][H], padded to a multiple of 4
+  float *rs_hist = nullptr, *rs_out = nullptr;   // [max_streams][rs_rec], [max_batch][2][hop]
+  int* rs_started = nullptr;              // [max_streams * 2] the (stream, channel) has consumed a tick since its reset
   float* out_pinned = nullptr;
   float* audio_pinned = nullptr;          // staging for pageable host audio (callers holding vapx_host_alloc memory skip it)
   hipEvent_t audio_evt = nullptr;         // the H2D copy out of audio_pinned has completed
@@ -609,11 +616,16 @@ __global__ void fill_int_kernel(int* p, int v, int n) {
 // clearing: rows beyond frames_seen are never read).  One workgroup per slot.
 struct ResetList { int n; int ids[16]; int* fs[4]; };   // fs[0] = this engine's frames_seen, fs[1..] = trunk followers'
 // ids[k] < 0 encodes "carry only" for stream -ids[k] - 1 (what a reconnect does in the reference, vap_main.py:368-369)
-__global__ void reset_streams_kernel(ResetList r, float* h_state, float* c_state, float* carry) {
+// an engine with an input rate: the resampler history goes with the carry (a new connection is a new signal)
+__global__ void reset_streams_kernel(ResetList r, float* h_state, float* c_state, float* carry, float* rs_hist, int* rs_started, int rs_rec) {
   const int raw = r.ids[blockIdx.x];
   const bool carry_only = raw < 0;
   const int sid = carry_only ? -raw - 1 : raw;
   for (int i = threadIdx.x; i < 2 * VAPX_PAD; i += blockDim.x) carry[(long)sid * 2 * VAPX_PAD + i] = 0.f;
+  if (rs_hist) {
+    for (int i = threadIdx.x; i < rs_rec; i += blockDim.x) rs_hist[(long)sid * rs_rec + i] = 0.f;
+    if (threadIdx.x < 2) rs_started[sid * 2 + threadIdx.x] = 0;
+  }
   if (carry_only) return;
   for (int i = threadIdx.x; i < 512; i += blockDim.x) { h_state[(long)sid * 512 + i] = 0.f; c_state[(long)sid * 512 + i] = 0.f; }
   if (threadIdx.x < 4 && r.fs[threadIdx.x]) r.fs[threadIdx.x][sid] = 0;
@@ -724,7 +736,7 @@ int flush_resets(vapx_engine* h, hipStream_t st) {
   for (size_t i = 0; i < h->pending_resets.size(); i += 16) {
     r.n = (int)std::min<size_t>(16, h->pending_resets.size() - i);
     for (int k = 0; k < r.n; ++k) r.ids[k] = h->pending_resets[i + k];
-    hipLaunchKernelGGL(reset_streams_kernel, dim3(r.n), dim3(256), 0, st, r, h->h_state, h->c_state, h->carry);
+    hipLaunchKernelGGL(reset_streams_kernel, dim3(r.n), dim3(256), 0, st, r, h->h_state, h->c_state, h->carry, h->rs_hist, h->rs_started, h->rs_rec);
     for (size_t f = 3; f < h->followers.size(); ++f)
       for (int k = 0; k < r.n; ++k)
         if (r.ids[k] >= 0) hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, st, h->followers[f]->frames_seen + r.ids[k], 0, 1);
@@ -890,6 +902,7 @@ void vapx_destroy(vapx_handle h) {
   for (float* p : fp) dfree(p);
   int* ip[] = {h->frames_seen, h->ids_dev, h->sc.bn, h->sc.bhead, h->sc.rot};
   for (int* p : ip) dfree(p);
+  dfree(h->rs_hist); dfree(h->rs_out); dfree(h->rs_started);
   dfree(h->gw_dev);
   dfree(h->acc); dfree(h->mixA); dfree(h->out_c); dfree(h->mix_dev);
   if (h->mix_pinned) (void)hipHostFree(h->mix_pinned);
@@ -1120,7 +1133,11 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
                   "needs host ids (or none), the host decides which streams have a frame due", h->R);
   } else {
     if (!audio) return fail(h, VAPX_E_INVAL, "null audio");
-    if (spc != h->hop && spc != h->L) return fail(h, VAPX_E_INVAL, "samples_per_ch must be %d (hop) or %d (full frame)", h->hop, h->L);
+    if (h->in_hz) {
+      if (spc != h->hop_in)
+        return fail(h, VAPX_E_INVAL, "samples_per_ch must be %d (the hop at the engine's input rate of %d Hz); a full frame with the caller's carry "
+                    "is defined at 16 kHz only", h->hop_in, h->in_hz);
+    } else if (spc != h->hop && spc != h->L) return fail(h, VAPX_E_INVAL, "samples_per_ch must be %d (hop) or %d (full frame)", h->hop, h->L);
   }
   if (!stream_ids && n > h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "n exceeds max_streams");
   hipStream_t st = (hipStream_t)hip_stream;
@@ -1140,7 +1157,7 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
   // free-running groups are only safe when nothing of this step is staged through engine-owned buffers on `st`
   // (host audio / host ids would be overwritten under a still-running group of the previous tick)
   const bool all_device = (flags & VAPX_OUT_DEVICE) && (lead || (flags & VAPX_AUDIO_DEVICE)) && (!stream_ids || (flags & VAPX_IDS_DEVICE));
-  const bool defer_join = G > 1 && (flags & VAPX_DEFER_JOIN) && all_device && !slower;
+  const bool defer_join = G > 1 && (flags & VAPX_DEFER_JOIN) && all_device && !slower && !h->in_hz;   // rs_out is one buffer: the next tick's resampler must not overtake a running group
   int rc = VAPX_OK;
   // a different batch split re-slices the shared scratch, and a reset touches state a running group may still use:
   // in both cases the previous tick's groups are joined first
@@ -1203,6 +1220,15 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     HIPCHK(h, hipMemcpyAsync(h->audio_dev, src, bytes, hipMemcpyHostToDevice, st));
     if (src == h->audio_pinned) HIPCHK(h, hipEventRecord(h->audio_evt, st));
     ad = h->audio_dev;
+  }
+  if (h->in_hz) {   // input rate -> 16 kHz, one launch for the whole batch before the overlap groups fork; conv0 and its carry see plain hops
+    ResampleArgs ra;
+    ra.in = ad; ra.ids = ids; ra.hist = h->rs_hist; ra.started = h->rs_started; ra.out = h->rs_out;
+    ra.orig = h->rs.orig; ra.nnew = h->rs.nnew; ra.K = h->rs.K; ra.d = h->rs.d; ra.H = h->rs.H; ra.rec = h->rs_rec;
+    ra.hop_in = h->hop_in; ra.hop = h->hop;
+    HIPCHK(h, launch_resample(ra, n, st));
+    ad = h->rs_out;
+    spc = h->hop;
   }
   float* od = (flags & VAPX_OUT_DEVICE) ? out : h->out_dev;
   float* orows = slower ? h->out_c : od;   // a slower follower's kernels write compact rows; one scatter places them in `od`
@@ -1384,6 +1410,7 @@ int vapx_attach_trunk(vapx_handle f, vapx_handle lead) {
   if (f == lead || lead->trunk || f->trunk || !f->followers.empty())
     return fail(f, VAPX_E_INVAL, "attach a stand-alone engine to a leader that is not itself a follower");
   if (f->tick != 0 || lead->tick != 0) return fail(f, VAPX_E_INVAL, "attach before the first step of either engine");
+  if (f->in_hz) return fail(f, VAPX_E_INVAL, "this engine has an input rate of its own (%d Hz): a follower takes no audio, set the rate on the leader", f->in_hz);
   if (f->cfg.device_id != lead->cfg.device_id || f->cfg.max_streams != lead->cfg.max_streams || f->cfg.max_batch != lead->cfg.max_batch)
     return fail(f, VAPX_E_INVAL, "device, max_streams and max_batch must match the leader's");
   // window and rate may differ: the follower's frame is R consecutive leader ticks (a CPC frame is a function of real samples only)
@@ -1505,6 +1532,10 @@ int vapx_set_state(vapx_handle h, int32_t sid, const float* ring, int32_t n_fram
   if (h->trunk && (lstm || carry)) return fail(h, VAPX_E_INVAL, "LSTM / carry state lives in the trunk leader");
   { int rc = quiesce(h); if (rc) return rc; }
   const int T = h->T;
+  if (h->in_hz) {   // the call has no place for the resampler history: the stream's input starts as a new signal
+    HIPCHK(h, hipMemset(h->rs_hist + (size_t)sid * h->rs_rec, 0, (size_t)h->rs_rec * sizeof(float)));
+    HIPCHK(h, hipMemset(h->rs_started + (size_t)sid * 2, 0, 2 * sizeof(int)));
+  }
   if (ring) {
     // chronological rows land in slots 0..n-1 and frames_seen = n, so the next append goes to slot n % T
     for (int c = 0; c < 2; ++c)
@@ -1543,7 +1574,7 @@ constexpr size_t kStateStageFloats = (size_t)8 << 20;   // 32 MiB: host records 
 bool sio_follower(const vapx_engine* h) { return h->trunk != nullptr || h->orphaned; }
 
 size_t state_floats(const vapx_engine* h, int flags) {
-  return VAPX_STATE_HEADER_FLOATS + (sio_follower(h) ? 0 : (size_t)(1024 + 2 * VAPX_PAD)) + (size_t)2 * h->T * 256 +
+  return VAPX_STATE_HEADER_FLOATS + (sio_follower(h) ? 0 : (size_t)(1024 + 2 * VAPX_PAD)) + (size_t)h->rs_rec + (size_t)2 * h->T * 256 +
          ((flags & VAPX_STATE_CACHE) ? (size_t)2 * h->T * 768 : 0);
 }
 
@@ -1626,7 +1657,8 @@ StateIoArgs sio_args(vapx_engine* h, int flags, float* rec, const int* ids, int 
   a.frames_seen = h->frames_seen; a.T = h->T; a.n = n;
   a.with_state = sio_follower(h) ? 0 : 1; a.with_cache = (flags & VAPX_STATE_CACHE) ? 1 : 0;
   a.hdr[0] = VAPX_STATE_MAGIC; a.hdr[1] = h->T; a.hdr[2] = h->cfg.frame_hz;
-  a.hdr[3] = (a.with_state ? VAPX_STATE_HAS_LSTM : 0) |
+  a.rs_hist = h->rs_hist; a.rs_started = h->rs_started; a.rs_rec = h->rs_rec; a.hdr[6] = h->in_hz;
+  a.hdr[3] = (a.with_state ? VAPX_STATE_HAS_LSTM : 0) | (h->in_hz ? VAPX_STATE_HAS_RESAMPLE : 0) |
              (a.with_cache ? VAPX_STATE_HAS_CACHE | ((h->cfg.flags & VAPX_FLAG_SPLIT_F16) ? VAPX_STATE_CACHE_SPLIT : 0) : 0);
   a.hdr[5] = h->cfg.mode;
   return a;
@@ -1691,6 +1723,10 @@ int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, con
         return fail(h, VAPX_E_INVAL, "record %d: content bits 0x%x: %s", k, hd[3],
                     sio_follower(h) ? "a leader / stand-alone record (LSTM + carry) offered to a trunk follower"
                                     : "a trunk follower's record (no LSTM + carry) offered to a leader / stand-alone engine");
+      if (((hd[3] & VAPX_STATE_HAS_RESAMPLE) != 0) != (h->in_hz != 0) || hd[6] != h->in_hz)
+        return fail(h, VAPX_E_INVAL, "record %d: input_hz %d (content bits 0x%x) differs from this engine's %d: the record %s a resampler history, "
+                    "this engine %s", k, hd[6] ? hd[6] : 16000, hd[3], h->in_hz ? h->in_hz : 16000,
+                    (hd[3] & VAPX_STATE_HAS_RESAMPLE) ? "carries" : "carries no", h->in_hz ? "keeps one" : "keeps none");
       if ((hd[3] & VAPX_STATE_HAS_CACHE) != (want_bits & VAPX_STATE_HAS_CACHE))
         return fail(h, VAPX_E_INVAL, "record %d: content bits 0x%x: the record %s a Q|K|V cache, the call's flags say it %s", k, hd[3],
                     (hd[3] & VAPX_STATE_HAS_CACHE) ? "carries" : "carries no", with_cache ? "does" : "does not");
@@ -1751,6 +1787,7 @@ int vapx_encode_audio(vapx_handle h, int32_t n, const int32_t* stream_ids, const
   if (h->trunk || h->orphaned) return fail(h, VAPX_E_INVAL, "a trunk follower has no encoder; call the leader");
   if (n < 1 || n > h->cfg.max_batch) return fail(h, VAPX_E_RANGE, "n=%d outside [1,%d]", n, h->cfg.max_batch);
   if (!frames || !e) return fail(h, VAPX_E_INVAL, "null frames/e");
+  if (h->in_hz) return fail(h, VAPX_E_INVAL, "vapx_encode_audio takes complete 16 kHz frames that carry their own carry; this engine's input rate is %d Hz", h->in_hz);
   hipStream_t st = (hipStream_t)hip_stream;
   (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -1933,6 +1970,56 @@ int vapx_aux_head(vapx_handle h, int32_t which, int64_t rows, const float* x, fl
                      h->W("aux.b") + row0, y, (long)rows, nout);
   HIPCHK(h, hipGetLastError());
   return VAPX_OK;
+}
+
+int vapx_set_input_rate(vapx_handle h, int32_t input_hz) {
+  if (!h) return VAPX_E_INVAL;
+  ResampleGeom g = {};
+  if (input_hz != 16000 && !resample_geometry(input_hz, &g))
+    return fail(h, VAPX_E_INVAL, "input rate %d Hz: supported are 8000, 16000, 32000 and 48000", input_hz);
+  if (h->trunk || h->orphaned) return fail(h, VAPX_E_INVAL, "a trunk follower takes no audio: set the input rate on the leader");
+  if (h->tick != 0 || h->in_hz) return fail(h, VAPX_E_INVAL, "set the input rate once, on a freshly created engine, before its first step");
+  if (input_hz == 16000) return VAPX_OK;
+  (void)hipGetLastError();
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  HIPCHK(h, hipDeviceSynchronize());
+  const size_t S = h->cfg.max_streams, B = h->cfg.max_batch;
+  const int hop_in = input_hz / h->cfg.frame_hz, rec = (2 * g.H + 3) & ~3;
+  float *hist = nullptr, *rout = nullptr, *adev = nullptr, *apin = nullptr;
+  int* started = nullptr;
+  hipError_t e = dalloc(&hist, S * (size_t)rec);
+  if (e == hipSuccess) e = dalloc(&started, S * 2);
+  if (e == hipSuccess) e = dalloc(&rout, B * 2 * (size_t)h->hop);
+  if (e == hipSuccess && hop_in > h->L) {   // staging for host audio at the input rate
+    e = dalloc(&adev, B * 2 * (size_t)hop_in);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&apin, B * 2 * (size_t)hop_in * sizeof(float), hipHostMallocDefault);
+  }
+  if (e != hipSuccess) {   // the engine stays as it was
+    (void)hipGetLastError();
+    dfree(hist); dfree(started); dfree(rout); dfree(adev);
+    if (apin) (void)hipHostFree(apin);
+    return fail(h, e == hipErrorOutOfMemory ? VAPX_E_NOMEM : VAPX_E_HIP, "resampler state for %d Hz: %s", input_hz, hipGetErrorString(e));
+  }
+  if (adev) {
+    dfree(h->audio_dev); h->audio_dev = adev;
+    (void)hipHostFree(h->audio_pinned); h->audio_pinned = apin;
+  }
+  h->rs_hist = hist; h->rs_started = started; h->rs_out = rout;
+  h->rs = g; h->hop_in = hop_in; h->rs_rec = rec; h->in_hz = input_hz;
+  if (!h->poison.empty()) h->poison.push_back({rout, B * 2 * (size_t)h->hop * sizeof(float)});
+  return VAPX_OK;
+}
+
+int32_t vapx_get_input_rate(vapx_handle h) { return !h ? VAPX_E_INVAL : (h->in_hz ? h->in_hz : 16000); }
+
+int vapx_resample(int32_t input_hz, int64_t rows, int64_t n_in, const float* x, float* y, void* hip_stream) {
+  if (!x || !y || rows < 1 || n_in < 1 || n_in > ((int64_t)1 << 40)) return VAPX_E_INVAL;
+  (void)hipGetLastError();
+  if (input_hz == 16000)
+    return hipMemcpyAsync(y, x, (size_t)rows * (size_t)n_in * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)hip_stream) == hipSuccess ? VAPX_OK : VAPX_E_HIP;
+  ResampleGeom g = {};
+  if (!resample_geometry(input_hz, &g)) return VAPX_E_INVAL;
+  return launch_resample_whole(g, (long)rows, (long)n_in, x, y, (hipStream_t)hip_stream) == hipSuccess ? VAPX_OK : VAPX_E_HIP;
 }
 
 int vapx_softmax256(int64_t rows, const float* x, float* y, void* hip_stream) {

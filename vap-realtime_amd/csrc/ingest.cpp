@@ -48,6 +48,8 @@
 // engine calls (tests/native); vapx_ingest_open_group says so if they are missing
 #pragma weak vapx_step_group
 #pragma weak vapx_group_wire_floats
+// the engine's input rate (vapx_set_input_rate): weak for the same reason; a program without it serves 16 kHz
+#pragma weak vapx_get_input_rate
 
 namespace {
 
@@ -205,7 +207,8 @@ struct vapx_ingest {
   vapx_ingest_reset_fn reset = nullptr;
   void* user = nullptr;
   vapx_handle engine = nullptr;
-  int S = 0, max_batch = 0, hop = 0, hz = 0;
+  int S = 0, max_batch = 0, hop = 0, hz = 0;   // hop: sample PAIRS per frame on the wire = in_hz / hz (the engine resamples: vapx_set_input_rate)
+  int in_hz = 16000;
   int M = 1;                               // models = output ports (> 1: a trunk group, `step` fills wire blocks)
   OutPort ports[MAX_MODELS];
   size_t row_floats = VAPX_OUT_STRIDE;     // floats per stream in a job's block, all models
@@ -1034,7 +1037,7 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in) {
   g->R = cfg->rx_threads > 0 ? std::min(cfg->rx_threads, 16) : 2;
   g->X = cfg->tx_threads > 0 ? std::min(cfg->tx_threads, 16) : 2;
   g->broadcast = cfg->broadcast < 0 ? (g->S == 1) : (cfg->broadcast != 0);
-  g->hop = 16000 / g->hz;
+  g->hop = g->in_hz / g->hz;
   g->slots.reset(new Slot[g->S]);
   const size_t per = (size_t)g->S * NBUF * 2 * g->hop;
   const size_t ba = (size_t)g->max_batch * 2 * g->hop;
@@ -1111,12 +1114,18 @@ int engine_group_step(void* user, int32_t n, const int32_t* ids, const float* au
   return vapx_step_group(g->engine, n, ids, audio, g->hop, wire_out, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
 }
 
+// sample rate of the audio the engine takes: 16000 unless vapx_set_input_rate said otherwise
+int engine_input_hz(vapx_handle engine) {
+  const int32_t r = vapx_get_input_rate ? vapx_get_input_rate(engine) : 16000;
+  return r > 0 ? r : 16000;
+}
+
 thread_local std::string g_open_error;   // vapx_ingest_last_open_error
 int open_refused(const char* why) { g_open_error = why; return VAPX_E_INVAL; }
 
 // a trunk group's ports: model m's framing, the geometry of its rows in the tick's wire block (vapx_step_group) and its requested port
 int setup_group(vapx_ingest* g, int n_streams, const int32_t* frame_hzs, const int32_t* ctx_frames, const int32_t* modes, int n_models,
-                const vapx_ingest_config& cfg, const int32_t* follower_ports_out) {
+                const vapx_ingest_config& cfg, const int32_t* follower_ports_out, int in_hz = 16000) {
   if (n_models < 1 || n_models > MAX_MODELS) return open_refused("a group serves one to three models");
   for (int m = 0; m < n_models; ++m) {
     const int hz = frame_hzs[m];
@@ -1138,7 +1147,7 @@ int setup_group(vapx_ingest* g, int n_streams, const int32_t* frame_hzs, const i
     g->ports[m].off = acc;
     g->ports[m].R = frame_hzs[0] / frame_hzs[m];
     if (g->ports[m].R > 1) {   // input framing, ticks and batching stay the leader's; this model's packets echo R leader hops
-      const size_t hop = (size_t)(16000 / frame_hzs[0]);
+      const size_t hop = (size_t)(in_hz / frame_hzs[0]);   // the leader's hop as received
       g->ports[m].hist.assign((size_t)n_streams * (g->ports[m].R - 1) * 2 * hop, 0.0);
       g->ports[m].hist_n.assign(n_streams, 0);
       g->ports[m].hist_gen.assign(n_streams, 0u);
@@ -1181,11 +1190,12 @@ int vapx_ingest_open(vapx_handle engine, const vapx_ingest_config* cfg, vapx_ing
   g->engine = engine;
   g->step = engine_step; g->reset = engine_reset; g->user = g;
   g->S = ec.max_streams; g->max_batch = ec.max_batch; g->hz = ec.frame_hz; g->ports[0].mode = ec.mode;
+  g->in_hz = engine_input_hz(engine);
   if (!(probe.flags & VAPX_INGEST_KEEP_STATE)) {
      // warm the engine up before the first client connects: the first vapx_step of a process loads the code objects and sizes
      // the runtime's pools (hundreds of ms) — paid here on silence, then every touched stream is reset (VAPX_INGEST_KEEP_STATE: the
      // streams hold imported state and the caller has warmed the engine up before importing)
-    const int nw = ec.max_batch, hop = 16000 / ec.frame_hz;
+    const int nw = ec.max_batch, hop = g->in_hz / ec.frame_hz;
     float* a = (float*)vapx_host_alloc((size_t)nw * 2 * hop * sizeof(float));
     float* o = (float*)vapx_host_alloc((size_t)nw * VAPX_OUT_STRIDE * sizeof(float));
     if (a && o) {
@@ -1271,7 +1281,8 @@ int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int
     modes[i + 1] = fc.mode; hzs[i + 1] = fc.frame_hz; ctxs[i + 1] = fc.ctx_frames;
   }
   vapx_ingest* g = new vapx_ingest();
-  rc = setup_group(g, ec.max_streams, hzs, ctxs, modes, n_followers + 1, probe, follower_ports_out);
+  g->in_hz = engine_input_hz(leader);
+  rc = setup_group(g, ec.max_streams, hzs, ctxs, modes, n_followers + 1, probe, follower_ports_out, g->in_hz);
   if (rc == VAPX_OK && g->row_floats != vapx_group_wire_floats(leader)) {
     rc = open_refused("`followers` are not the leader's attached followers (vapx_attach_trunk) in attach order");
   }
@@ -1280,7 +1291,7 @@ int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int
   g->step = engine_group_step; g->reset = engine_reset; g->user = g;
   g->S = ec.max_streams; g->max_batch = ec.max_batch; g->hz = ec.frame_hz;
   if (!(probe.flags & VAPX_INGEST_KEEP_STATE)) {  // warm-up on silence as in vapx_ingest_open, the whole group per tick; every touched stream is reset (the leader cascades)
-    const int nw = ec.max_batch, hop = 16000 / ec.frame_hz;
+    const int nw = ec.max_batch, hop = g->in_hz / ec.frame_hz;
     float* a = (float*)vapx_host_alloc((size_t)nw * 2 * hop * sizeof(float));
     float* o = (float*)vapx_host_alloc((size_t)nw * g->row_floats * sizeof(float));
     if (a && o) {

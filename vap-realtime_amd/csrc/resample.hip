@@ -1,0 +1,111 @@
+// Input at 8 / 32 / 48 kHz -> the model's 16 kHz on the device (vapx_set_input_rate, vapx_resample; include/vapx.h "Input rate").
+// The filter is torchaudio.functional.resample's default (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99), restated in
+// vap-realtime_amd/resample.py, which also writes the fp32 tap tables of resample_taps.h.  With orig = in_hz / g, new = 16000 / g:
+//   Y[new*i + p] = sum_k h[p][k] * x[orig*i + k - width],  k = 0 .. K-1,  x = 0 outside the signal
+// A stream has no future samples: the engine's 16 kHz stream is Y delayed by d = ceil(width / orig) = 7 blocks (0.875 ms at 8 kHz,
+// 0.4375 ms at 32 and 48 kHz), z[m] = Y[m - new*d] and zero for m < new*d; a tick needs the last H = orig*d + width input samples
+// of the stream's earlier ticks.
+// Both kernels stage their input window in LDS with coalesced 4-byte loads (lane i at base + 4 i), keep the taps in LDS (copied from
+// constant memory) and produce every output with resample_dot: one fmaf chain over k = 0 .. K-1.  The streaming kernel and the
+// whole-signal kernel therefore agree bit for bit.  A tick of 4096 streams moves about 40 MB: nothing here is tuned past that.
+#include <hip/hip_runtime.h>
+
+#include "resample_taps.h"
+#include "vap_kernels.h"
+
+namespace {
+
+constexpr int kTapSlots = 48;   // floats reserved for h[new][K]: 2 x 15, 1 x 28, 1 x 41
+
+__constant__ float c_taps_8k[] = {VAPX_RESAMPLE_TAPS_8000};
+__constant__ float c_taps_32k[] = {VAPX_RESAMPLE_TAPS_32000};
+__constant__ float c_taps_48k[] = {VAPX_RESAMPLE_TAPS_48000};
+static_assert(sizeof(c_taps_8k) == 2 * 15 * 4 && sizeof(c_taps_32k) == 28 * 4 && sizeof(c_taps_48k) == 41 * 4, "tap tables");
+
+__device__ __forceinline__ const float* taps_of(int orig) { return orig == 1 ? c_taps_8k : orig == 2 ? c_taps_32k : c_taps_48k; }
+
+// one output: h = the phase's K taps, w = the K input samples under them.  The order of the chain is the definition.
+__device__ __forceinline__ float resample_dot(const float* __restrict__ h, const float* __restrict__ w, int K) {
+  float acc = 0.f;
+  for (int k = 0; k < K; ++k) acc = fmaf(h[k], w[k], acc);
+  return acc;
+}
+
+// One workgroup per (batch slot, channel): LDS = taps | history [H] ++ this tick's hop_in samples.
+__global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {
+  extern __shared__ float lds[];
+  float* th = lds;
+  float* buf = lds + kTapSlots;
+  const int tid = threadIdx.x, row = blockIdx.x, b = row >> 1, c = row & 1;
+  const int sid = a.ids ? a.ids[b] : b;
+  const float* tp = taps_of(a.orig);
+  for (int i = tid; i < a.nnew * a.K; i += 256) th[i] = tp[i];
+  float* hs = a.hist + (long)sid * a.rec + c * a.H;
+  const float* in = a.in + (long)row * a.hop_in;
+  for (int i = tid; i < a.H; i += 256) buf[i] = hs[i];
+  for (int i = tid; i < a.hop_in; i += 256) buf[a.H + i] = in[i];
+  const bool fresh = a.started[sid * 2 + c] == 0;   // no tick since the stream's reset: Y has no samples before its block 0
+  __syncthreads();
+  for (int i = tid; i < a.H; i += 256) hs[i] = buf[a.hop_in + i];   // hop_in >= 160 > H: the new history is all of this tick
+  if (tid == 0) a.started[sid * 2 + c] = 1;
+  float* o = a.out + (long)row * a.hop;
+  for (int m = tid; m < a.hop; m += 256) {
+    const int j = m / a.nnew, p = m - j * a.nnew;
+    const float v = resample_dot(th + p * a.K, buf + a.orig * j, a.K);   // last index read: hop_in + 2 width - 1 < H + hop_in
+    o[m] = (fresh && j < a.d) ? 0.f : v;
+  }
+}
+
+// Whole signals: a workgroup makes 256 output blocks (256 * new outputs) of one row from a window of orig * 255 + K inputs.
+constexpr int kWholeBlocks = 256;
+constexpr int kWholeWindow = 3 * (kWholeBlocks - 1) + 41;   // the largest: 48 kHz
+__global__ __launch_bounds__(256) void resample_whole_kernel(const float* __restrict__ x, float* __restrict__ y, long n_in, long n_out,
+                                                             int orig, int nnew, int width, int K, long row0) {
+  __shared__ float th[kTapSlots];
+  __shared__ float win[kWholeWindow];
+  const int tid = threadIdx.x;
+  const long r = row0 + blockIdx.y, i0 = (long)blockIdx.x * kWholeBlocks;
+  const float* tp = taps_of(orig);
+  for (int i = tid; i < nnew * K; i += 256) th[i] = tp[i];
+  const float* xr = x + r * n_in;
+  const long s0 = orig * i0 - width;
+  const int wlen = orig * (kWholeBlocks - 1) + K;
+  for (int i = tid; i < wlen; i += 256) {
+    const long s = s0 + i;
+    win[i] = (s >= 0 && s < n_in) ? xr[s] : 0.f;
+  }
+  __syncthreads();
+  for (int q = tid; q < kWholeBlocks * nnew; q += 256) {
+    const int j = q / nnew, p = q - j * nnew;
+    const long m = nnew * i0 + q;
+    if (m < n_out) y[r * n_out + m] = resample_dot(th + p * K, win + orig * j, K);
+  }
+}
+
+}  // namespace
+
+bool resample_geometry(int in_hz, ResampleGeom* g) {
+  switch (in_hz) {
+    case 8000: *g = {1, 2, 7, 15, 7, 14}; return true;
+    case 32000: *g = {2, 1, 13, 28, 7, 27}; return true;
+    case 48000: *g = {3, 1, 19, 41, 7, 40}; return true;
+  }
+  return false;
+}
+
+hipError_t launch_resample(const ResampleArgs& a, int n, hipStream_t st) {
+  const size_t lds = (size_t)(kTapSlots + a.H + a.hop_in) * sizeof(float);
+  hipLaunchKernelGGL(resample_kernel, dim3((unsigned)n * 2), dim3(256), lds, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_resample_whole(const ResampleGeom& g, long rows, long n_in, const float* x, float* y, hipStream_t st) {
+  const long n_out = (g.nnew * n_in + g.orig - 1) / g.orig;
+  const long per = (long)kWholeBlocks * g.nnew;
+  const unsigned gx = (unsigned)((n_out + per - 1) / per);
+  for (long r0 = 0; r0 < rows; r0 += 32768) {   // gridDim.y is a 16-bit quantity
+    const unsigned gy = (unsigned)(rows - r0 < 32768 ? rows - r0 : 32768);
+    hipLaunchKernelGGL(resample_whole_kernel, dim3(gx, gy), dim3(256), 0, st, x, y, n_in, n_out, g.orig, g.nnew, g.width, g.K, r0);
+  }
+  return hipGetLastError();
+}

@@ -2,7 +2,7 @@
 // Pure data movement: no LDS, no atomics, every access a plain 16-byte vector load / store.  One wave moves one 256-float ring row
 // (64 lanes x 16 bytes, coalesced on both sides) and, when the cache travels, the row's three 256-float Q | K | V segments with it: four
 // independent 16-byte loads in flight per lane before the first store.  A workgroup is four such waves; the grid is
-// (items / 4, streams) with 2T row items + 8 small ones (4 LSTM rows, 3 carry chunks, the header) per stream, so the C3 shape
+// (items / 4, streams) with 2T row items + 9 small ones (4 LSTM rows, 3 carry chunks, the header, the resampler history of an engine with an input rate) per stream, so the C3 shape
 // (4096 streams, T = 250) is half a million workgroups of 16 KiB each: the chip is oversubscribed many times over and the only limit is HBM.
 #include <hip/hip_runtime.h>
 
@@ -14,7 +14,8 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kStateFloats = 2 * 2 * 256 + 2 * VAPX_PAD;   // lstm [2][2][256] + carry [2][320]
 constexpr int kHeaderFloats = 8;
-constexpr int kSmallItems = 8;                             // 4 LSTM rows, 3 carry chunks (640 floats = 2.5 rows), 1 header
+constexpr int kSmallItems = 9;                             // 4 LSTM rows, 3 carry chunks (640 floats = 2.5 rows), 1 header, 1 resampler history
+constexpr int kHeaderItem = 7, kResampleItem = 8;
 constexpr int kMaxGridY = 32768;
 
 // export: ring slot ((fs - n + t) mod T) -> chronological row t, zero rows beyond n = min(fs, T)
@@ -27,7 +28,7 @@ __global__ __launch_bounds__(256) void state_export_kernel(StateIoArgs a) {
   const int fs = a.frames_seen[sid];
   const int nn = fs < 0 ? 0 : (fs < T ? fs : T);
   float* r = a.rec + (long)k * a.rec_floats;
-  const long o_ring = kHeaderFloats + (a.with_state ? kStateFloats : 0);
+  const long o_ring = kHeaderFloats + (a.with_state ? kStateFloats : 0) + a.rs_rec;
   if (item < 2 * T) {
     const int c = item >= T ? 1 : 0, t = item - c * T;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -49,12 +50,20 @@ __global__ __launch_bounds__(256) void state_export_kernel(StateIoArgs a) {
     return;
   }
   const int j = item - 2 * T;
-  if (j == kSmallItems - 1) {   // header
+  if (j == kHeaderItem) {
     if (lane == 0) *(i32x4*)(r) = i32x4{a.hdr[0], a.hdr[1], a.hdr[2], a.hdr[3]};
-    if (lane == 1) *(i32x4*)(r + 4) = i32x4{nn, a.hdr[5], 0, 0};
+    if (lane == 1) {
+      const int st = a.rs_started ? (a.rs_started[sid * 2] != 0) | ((a.rs_started[sid * 2 + 1] != 0) << 1) : 0;
+      *(i32x4*)(r + 4) = i32x4{nn, a.hdr[5], a.hdr[6], st};
+    }
     return;
   }
   if (!a.with_state) return;
+  if (j == kResampleItem) {     // history [2][H] + padding, after the carry
+    if (a.rs_hist && lane * 4 < a.rs_rec)
+      *(f32x4*)(r + kHeaderFloats + kStateFloats + lane * 4) = *(const f32x4*)(a.rs_hist + (long)sid * a.rs_rec + lane * 4);
+    return;
+  }
   if (j < 4) {                  // record lstm [ch][(h, c)][256]  <-  h_state / c_state [S*2][256]
     const float* src = ((j & 1) ? a.c_state : a.h_state) + ((long)sid * 2 + (j >> 1)) * 256;
     *(f32x4*)(r + kHeaderFloats + j * 256 + lane * 4) = *(const f32x4*)(src + lane * 4);
@@ -75,7 +84,7 @@ __global__ __launch_bounds__(256) void state_import_kernel(StateIoArgs a) {
   const float* r = a.rec + (long)k * a.rec_floats;
   int nn = ((const int*)r)[4];
   nn = nn < 0 ? 0 : (nn < T ? nn : T);
-  const long o_ring = kHeaderFloats + (a.with_state ? kStateFloats : 0);
+  const long o_ring = kHeaderFloats + (a.with_state ? kStateFloats : 0) + a.rs_rec;
   if (item < 2 * T) {
     const int c = item >= T ? 1 : 0, t = item - c * T;
     if (t >= nn) return;
@@ -91,11 +100,17 @@ __global__ __launch_bounds__(256) void state_import_kernel(StateIoArgs a) {
     return;
   }
   const int j = item - 2 * T;
-  if (j == kSmallItems - 1) {
+  if (j == kHeaderItem) {
     if (lane == 0) a.frames_seen[sid] = nn;
+    if (lane < 2 && a.rs_started) a.rs_started[sid * 2 + lane] = (((const int*)r)[7] >> lane) & 1;
     return;
   }
   if (!a.with_state) return;
+  if (j == kResampleItem) {
+    if (a.rs_hist && lane * 4 < a.rs_rec)
+      *(f32x4*)(a.rs_hist + (long)sid * a.rs_rec + lane * 4) = *(const f32x4*)(r + kHeaderFloats + kStateFloats + lane * 4);
+    return;
+  }
   if (j < 4) {
     float* dst = ((j & 1) ? a.c_state : a.h_state) + ((long)sid * 2 + (j >> 1)) * 256;
     *(f32x4*)(dst + lane * 4) = *(const f32x4*)(r + kHeaderFloats + j * 256 + lane * 4);

@@ -161,7 +161,23 @@ struct StateIoArgs {    // state_io.hip: bulk stream-state export / import (vapx
   int* frames_seen;
   int T, n, with_state, with_cache;
   int hdr[8];           // export: the header words as they are written, [4] (n_frames) filled in per stream
+  float* rs_hist;       // engines with an input rate: [S][rs_rec] resampler history, travels after the carry (null: none, rs_rec = 0)
+  int* rs_started;      // [S*2], travels as bits 0-1 of header word [7]
+  int rs_rec;           // floats per stream, a multiple of 4, at most 256
 };
+
+struct ResampleGeom { int orig, nnew, width, K, d, H; };   // resample.hip: in_hz / g, 16000 / g, filter half width, taps per phase, delay blocks, history
+struct ResampleArgs {   // resample.hip: one tick of the streaming resampler (vapx_set_input_rate)
+  const float* in;      // [n][2][hop_in] this tick's samples at the input rate
+  const int* ids;       // [n] stream ids (device) or null = identity
+  float* hist;          // [S][rec]: per stream [2][H] input samples of its earlier ticks, then padding
+  int* started;         // [S*2] 0 until the (stream, channel) has consumed a tick since its reset
+  float* out;           // [n][2][hop] the 16 kHz samples conv0 takes
+  int orig, nnew, K, d, H, rec, hop_in, hop;
+};
+bool resample_geometry(int in_hz, ResampleGeom* g);   // false: not 8000 / 32000 / 48000
+hipError_t launch_resample(const ResampleArgs& a, int n, hipStream_t st);
+hipError_t launch_resample_whole(const ResampleGeom& g, long rows, long n_in, const float* x, float* y, hipStream_t st);
 
 hipError_t launch_state_export(const StateIoArgs& a, hipStream_t st);
 hipError_t launch_state_import(const StateIoArgs& a, hipStream_t st);

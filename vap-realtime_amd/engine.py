@@ -27,6 +27,7 @@ AUDIO_DEVICE, OUT_DEVICE, IDS_DEVICE = 1, 2, 4
 STATE_CACHE = 16
 STATE_MAGIC = 0x31535056
 STATE_HAS_LSTM, STATE_HAS_CACHE, STATE_CACHE_SPLIT = 1, 2, 4
+STATE_HAS_RESAMPLE = 8   # the record carries a resampler history (an engine with an input rate), header word [6] = input_hz
 STATE_HEADER_FLOATS = 8
 STATE_LSTM_FLOATS, STATE_CARRY_FLOATS = 2 * 2 * 256, 2 * 320
 MODE = {"vap": 0, "bc": 1, "nod": 2}
@@ -40,7 +41,8 @@ EXPORTS = ("vapx_abi_version", "vapx_blob_floats", "vapx_create", "vapx_destroy"
            "vapx_aggregate", "vapx_aux_head", "vapx_frontdoor_open", "vapx_frontdoor_open_links", "vapx_ingest_attach_link", "vapx_frontdoor_ports", "vapx_frontdoor_counts", "vapx_frontdoor_close",
            "vapx_wire_floats", "vapx_group_wire_floats", "vapx_step_group", "vapx_group_bad", "vapx_ingest_open_group",
            "vapx_ingest_open_group_fn", "vapx_ingest_open_group_fn2", "vapx_ingest_group_ports", "vapx_ingest_last_open_error",
-           "vapx_state_floats", "vapx_export_streams", "vapx_import_streams")
+           "vapx_state_floats", "vapx_export_streams", "vapx_import_streams",
+           "vapx_set_input_rate", "vapx_get_input_rate", "vapx_resample")
 PROF_CLASSES = {0: "gemm_store", 1: "gemm_gelu", 2: "gemm_resid", 3: "gemm_resid_ln", 4: "gemm_cn_relu",
                 5: "conv_tail", 6: "ffn_block", 7: "last_row", 8: "conv0", 9: "lstm", 10: "gather_ln", 11: "attention", 12: "head",
                 13: "gemm_bias_ln_gelu", 14: "ffn_proj", 15: "trunk_collect"}
@@ -100,6 +102,12 @@ def load_library(path: Optional[str] = None):
     lib.vapx_export_streams.argtypes = [vp, i32, i32p, f32p, i32, vp]
     lib.vapx_import_streams.restype = i32
     lib.vapx_import_streams.argtypes = [vp, i32, i32p, f32p, i32, vp]
+    lib.vapx_set_input_rate.restype = i32
+    lib.vapx_set_input_rate.argtypes = [vp, i32]
+    lib.vapx_get_input_rate.restype = i32
+    lib.vapx_get_input_rate.argtypes = [vp]
+    lib.vapx_resample.restype = i32
+    lib.vapx_resample.argtypes = [i32, C.c_int64, C.c_int64, f32p, f32p, vp]
     lib.vapx_encode_audio.restype = i32
     lib.vapx_encode_audio.argtypes = [vp, i32, i32p, f32p, f32p, vp]
     lib.vapx_transformer.restype = i32
@@ -231,12 +239,14 @@ class Engine:
                  max_streams: int = 1, max_batch: Optional[int] = None, mode: str = "vap", device_id: int = 0,
                  groups: int = 0, full_last_layer: bool = False, unfused_conv: bool = False,
                  materialize_x0: bool = False, unfused_last_row: bool = False, split_f16: bool = False,
-                 unfused_proj: bool = False, split_qkv_in_ffn: bool = False):
+                 unfused_proj: bool = False, split_qkv_in_ffn: bool = False, input_hz: int = 16000):
         self.lib = load_library()
         self.frame_hz = frame_hz
         self.T = int(context_len_sec * frame_hz)           # vap_main.py:221
         self.hop = 16000 // frame_hz
         self.L = self.hop + 320                             # vap_main.py:230
+        self.input_hz = int(input_hz)                       # sample rate of the audio ``step`` takes (vapx.h, vapx_set_input_rate)
+        self.hop_in = self.input_hz // frame_hz             # samples per channel and tick at that rate (== hop at 16 kHz)
         self.max_streams = max_streams
         self.max_batch = max_batch or max_streams
         self.mode = mode
@@ -252,6 +262,12 @@ class Engine:
         if rc != 0:
             raise VapxError(f"vapx_create failed ({rc}): {self.lib.vapx_last_error(None).decode()}")
         self._h = h
+        if self.input_hz != 16000:
+            rc = self.lib.vapx_set_input_rate(h, self.input_hz)
+            if rc != 0:
+                msg = self.lib.vapx_last_error(h).decode()
+                self.close()
+                raise VapxError(f"vapx_set_input_rate failed ({rc}): {msg}")
 
     # -- lifecycle -------------------------------------------------------------------------------
     def close(self):
@@ -274,7 +290,7 @@ class Engine:
     def step(self, audio: np.ndarray, stream_ids: Optional[Sequence[int]] = None, out: Optional[np.ndarray] = None,
              on_numeric: str = "raise") -> np.ndarray:
         """Host path.  audio: float [n,2,hop] (new samples; engine keeps the carry) or [n,2,hop+320]
-        (complete frames as ``process_vap`` receives them).  Returns float32 [n, OUT_STRIDE] (``out`` if given, e.g. a
+        (complete frames as ``process_vap`` receives them); with ``input_hz`` other than 16000: [n,2,hop_in] and nothing else.  Returns float32 [n, OUT_STRIDE] (``out`` if given, e.g. a
         ``pinned_empty`` block).  A stream with non-finite results (VAPX_E_NUMERIC) raises by default; with
         ``on_numeric="status"`` the block is returned — every other row is valid, the bad rows have column OUT_STATUS = 1
         and ``bad_slots()`` lists them."""
@@ -529,7 +545,8 @@ class TrunkGroup:
     The reference runs one process per model, each re-encoding the same audio with the same ``cpc_model``
     weights (vap_main.py:199-201, vap_bc_main.py, vap_nod_main.py).  Here ``blobs`` is ``{mode: blob}``.  ``frame_hz`` and
     ``context_len_sec`` are scalars (every model, as before) or per model: ``{mode: value}`` or a sequence in ``blobs`` order — the
-    reference's own deployment is vap 20 Hz / 2.5 s, bc 20 Hz / 5 s, nod 10 Hz / 10 s.  The fastest model leads (runs the encoder;
+    reference's own deployment is vap 20 Hz / 2.5 s, bc 20 Hz / 5 s, nod 10 Hz / 10 s.  ``input_hz`` (8000 / 16000 / 32000 / 48000) is the
+    sample rate of the audio and is applied to the leader, which then takes ``hop_in`` samples per tick.  The fastest model leads (runs the encoder;
     ties: the first entry), the others follow; ``hz / hop_of / L_of / T_of / R`` hold each mode's geometry, ``R[mode]`` being the
     leader ticks per frame of that model.  Input framing (``hop``, ``L``) is the leader's.
 
@@ -537,18 +554,20 @@ class TrunkGroup:
     n rows in the batch order, rows without a frame are zero with column OUT_STATUS = STATUS_NO_FRAME (``due`` masks them)."""
 
     def __init__(self, blobs: dict, frame_hz=20, context_len_sec=2.5, max_streams: int = 1,
-                 max_batch: Optional[int] = None, device_id: int = 0, **engine_kw):
+                 max_batch: Optional[int] = None, device_id: int = 0, input_hz: int = 16000, **engine_kw):
         self.modes = list(blobs)
         plan = trunk_plan(self.modes, frame_hz, context_len_sec)
         self.hz, self.ctx, self.hop_of, self.L_of, self.T_of, self.R = (plan[k] for k in ("hz", "ctx", "hop", "L", "T", "R"))
         self.order = plan["order"]                             # model order of vapx_step_group's wire block: leader, then followers
         self.engines = {}
         for m in self.order:                                   # engine_kw: groups / split_f16 / ... — the same for every weight set
-            self.engines[m] = Engine(blobs[m], self.hz[m], self.ctx[m], max_streams, max_batch, m, device_id, **engine_kw)
+            kw = dict(engine_kw, input_hz=input_hz) if m == self.order[0] else engine_kw      # the leader owns the audio
+            self.engines[m] = Engine(blobs[m], self.hz[m], self.ctx[m], max_streams, max_batch, m, device_id, **kw)
         self.leader = self.engines[self.order[0]]
         for m in self.order[1:]:
             self.engines[m].attach_trunk(self.leader)
         self.hop, self.L, self.T = self.leader.hop, self.leader.L, self.leader.T
+        self.input_hz, self.hop_in = self.leader.input_hz, self.leader.hop_in
 
     def step(self, audio: np.ndarray, stream_ids: Optional[Sequence[int]] = None) -> dict:
         res = {self.order[0]: self.leader.step(audio, stream_ids)}
@@ -615,31 +634,40 @@ def split_outputs(out: np.ndarray) -> dict:
     }
 
 
-def state_record_floats(ctx_frames: int, cache: bool = False, follower: bool = False) -> int:
-    """Length of a state record (the layout in vapx.h): header, LSTM + carry unless ``follower``, ring, optional Q|K|V cache."""
+def state_record_floats(ctx_frames: int, cache: bool = False, follower: bool = False, input_hz: int = 16000) -> int:
+    """Length of a state record (the layout in vapx.h): header, LSTM + carry unless ``follower``, the resampler history of a leader /
+    stand-alone engine with an input rate, ring, optional Q|K|V cache."""
+    from .resample import history_floats
     T = int(ctx_frames)
-    return (STATE_HEADER_FLOATS + (0 if follower else STATE_LSTM_FLOATS + STATE_CARRY_FLOATS) + 2 * T * 256
+    return (STATE_HEADER_FLOATS + (0 if follower else STATE_LSTM_FLOATS + STATE_CARRY_FLOATS + history_floats(input_hz)) + 2 * T * 256
             + (2 * T * 768 if cache else 0))
 
 
-def split_state(records: np.ndarray, T: int, follower: bool = False) -> dict:
+def split_state(records: np.ndarray, T: int, follower: bool = False, input_hz: int = 16000) -> dict:
     """Name the fields of state records [n, floats] (views, as ``split_outputs`` does for output rows): the header words
     ``magic`` / ``ctx_frames`` / ``frame_hz`` / ``bits`` / ``n_frames`` / ``mode``, ``lstm`` [n,2,2,256] and ``carry`` [n,2,320] (None
-    for a follower's records), ``ring`` [n,2,T,256] oldest -> newest (zero beyond ``n_frames``) and ``cache`` [n,2,T,768] or None."""
+    for a follower's records), ``ring`` [n,2,T,256] oldest -> newest (zero beyond ``n_frames``) and ``cache`` [n,2,T,768] or None.  Records
+    of an engine with ``input_hz`` other than 16000 also give ``input_hz`` (header word [6]), ``resample_started`` (word [7]) and
+    ``resample_hist`` [n,2,H]; for the others the three are 0 / 0 / None."""
+    from .resample import geometry, history_floats
     records = np.asarray(records)
     n, fl = records.shape
-    cache = fl == state_record_floats(T, True, follower)
-    if fl != state_record_floats(T, cache, follower):
+    cache = fl == state_record_floats(T, True, follower, input_hz)
+    if fl != state_record_floats(T, cache, follower, input_hz):
         raise VapxError(f"record length {fl} fits no layout of a {'follower' if follower else 'leader / stand-alone'} engine with T={T}")
     hdr = records[:, :STATE_HEADER_FLOATS].view(np.int32)
     d = {"magic": hdr[:, 0], "ctx_frames": hdr[:, 1], "frame_hz": hdr[:, 2], "bits": hdr[:, 3], "n_frames": hdr[:, 4], "mode": hdr[:, 5],
-         "lstm": None, "carry": None, "cache": None}
+         "lstm": None, "carry": None, "cache": None, "input_hz": hdr[:, 6], "resample_started": hdr[:, 7], "resample_hist": None}
     at = STATE_HEADER_FLOATS
     if not follower:
         d["lstm"] = records[:, at:at + STATE_LSTM_FLOATS].reshape(n, 2, 2, 256)
         at += STATE_LSTM_FLOATS
         d["carry"] = records[:, at:at + STATE_CARRY_FLOATS].reshape(n, 2, 320)
         at += STATE_CARRY_FLOATS
+        if history_floats(input_hz):
+            H = geometry(input_hz)["H"]
+            d["resample_hist"] = records[:, at:at + 2 * H].reshape(n, 2, H)
+            at += history_floats(input_hz)
     d["ring"] = records[:, at:at + 2 * T * 256].reshape(n, 2, T, 256)
     at += 2 * T * 256
     if cache:

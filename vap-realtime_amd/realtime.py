@@ -188,18 +188,20 @@ class ManyStreamVAP:
     """S independent streams on one GPU.  ``process(new_samples[, stream_ids])`` = one tick."""
 
     def __init__(self, cpc_sd, vap_sd, frame_rate: int = 20, context_len_sec: float = 2.5, n_streams: int = 256,
-                 max_batch: Optional[int] = None, mode: str = "vap", device_id: int = 0, **engine_options):
-        """``engine_options`` go to ``engine.Engine`` (e.g. ``split_f16=True``, ``groups=2``)."""
+                 max_batch: Optional[int] = None, mode: str = "vap", device_id: int = 0, input_hz: int = 16000, **engine_options):
+        """``engine_options`` go to ``engine.Engine`` (e.g. ``split_f16=True``, ``groups=2``).  ``input_hz`` (8000 / 16000 / 32000 /
+        48000): the sample rate of the audio ``process`` takes; the engine resamples to 16 kHz on the device."""
         self.engine = _engine.Engine(_weights.pack_blob(cpc_sd, vap_sd, mode), frame_rate, context_len_sec,
                                      max_streams=n_streams, max_batch=max_batch, mode=mode, device_id=device_id,
-                                     **engine_options)
+                                     input_hz=input_hz, **engine_options)
         self.n_streams = n_streams
-        self.hop = 16000 // frame_rate
+        self.hop = 16000 // frame_rate                      # the model's hop, at 16 kHz
+        self.hop_in = self.engine.hop_in                    # samples per channel ``process`` takes per tick
         self.mode = mode
 
     def process(self, new_samples: np.ndarray, stream_ids: Optional[Sequence[int]] = None,
                 on_numeric: str = "raise") -> Dict[str, np.ndarray]:
-        """new_samples float [n,2,hop] (or [n,2,hop+320] complete frames) -> dict of [n,...] arrays.  A stream with non-finite
+        """new_samples float [n,2,hop] (or [n,2,hop+320] complete frames; with ``input_hz``: [n,2,hop_in] only) -> dict of [n,...] arrays.  A stream with non-finite
         results raises ``VapxError`` (the engine's fail-loudly rule: an offline run must not write 'nan' rows for the rest of a
         file); a caller that handles the per-stream ``status`` column itself — the TCP front-end resets that dialogue and keeps
         serving the others — passes ``on_numeric="status"``."""

@@ -71,7 +71,7 @@ def _warm_up(target):
     lead = target.leader if hasattr(target, "leader") else target
     if not hasattr(lead, "reset_stream"):
         return
-    silence = np.zeros((lead.max_batch, 2, lead.hop), np.float32)
+    silence = np.zeros((lead.max_batch, 2, getattr(lead, "hop_in", lead.hop)), np.float32)      # hop_in: the hop at --input_rate
     if hasattr(target, "step_wire"):
         target.step_wire(silence)
     else:
@@ -109,6 +109,11 @@ def save_state(path, target, tag: str = "") -> bool:
         return False
     print(f"[vapx] {tag}state of {len(hdr['ids'])} dialogue slot(s) saved to {path}", flush=True)
     return True
+
+
+def rate_kw(args) -> dict:
+    """``--input_rate`` as an ``Engine`` / ``TrunkGroup`` keyword; nothing at 16000, so such engines are built exactly as before."""
+    return {"input_hz": args.input_rate} if getattr(args, "input_rate", 16000) != 16000 else {}
 
 
 def group_modes(mode):
@@ -192,7 +197,8 @@ def build_group(args, names):
     grp = srv = None
     try:
         grp = engine.TrunkGroup(blobs, gp["hz"], gp["ctx"], max_streams=args.streams,
-                                max_batch=min(args.streams, args.max_batch), device_id=0, groups=2, split_f16=(args.precision == "split"))
+                                max_batch=min(args.streams, args.max_batch), device_id=0, groups=2, split_f16=(args.precision == "split"),
+                                **rate_kw(args))
         warm = load_state(state_path(args.load_state, 0, 1), grp)
         cores = None
         if args.pin:
@@ -218,7 +224,7 @@ def run_group(args, names, stop) -> int:
     outs = ", ".join(f"{m} :{srv.ports_out[m]}" for m in names)
     geo = ", ".join(f"{m} {grp.hz[m]} Hz / {grp.ctx[m]:g} s" for m in names)
     print(f"[vapx] 1 GPU(s) x {args.streams} dialogue slots, modes {'+'.join(names)} on one CPC trunk ({grp.order[0]} leads), {args.precision} "
-          f"arithmetic, {geo} — input :{srv.port_in}, output {outs}", flush=True)
+          f"arithmetic, {geo}, audio at {args.input_rate} Hz — input :{srv.port_in}, output {outs}", flush=True)
     last = time.time()
     while not stop["now"]:
         time.sleep(0.2)
@@ -272,7 +278,7 @@ def build(args):
             eng = engine.Engine(blob, args.vap_process_rate, args.context_len_sec, max_streams=args.streams,
                                 max_batch=min(args.streams, args.max_batch), mode=mode, device_id=dev,
                                 groups=2,   # two intra-tick overlap groups: ragged ticks of a few hundred streams get 20 % shorter
-                                split_f16=(args.precision == "split"))
+                                split_f16=(args.precision == "split"), **rate_kw(args))
             engines.append(eng)
             warm = load_state(state_path(args.load_state, r, n), eng, f"GPU {r}: ")
             passive = n > 1
@@ -305,7 +311,7 @@ def run_worker(args) -> int:
         blob, mode = load_blob(args)
         dev = 0 if args.share_gpu else r
         eng = engine.Engine(blob, args.vap_process_rate, args.context_len_sec, max_streams=args.streams, max_batch=min(args.streams, args.max_batch),
-                            mode=mode, device_id=dev, groups=2, split_f16=(args.precision == "split"))
+                            mode=mode, device_id=dev, groups=2, split_f16=(args.precision == "split"), **rate_kw(args))
         warm = load_state(state_path(args.load_state, r, max(1, args.gpus), worker=True), eng, f"GPU {r}: ")
         cores = None
         if args.pin:
@@ -370,7 +376,7 @@ def run_door(args, argv) -> int:
             w.terminate()
         return 1
     print(f"[vapx] {n} GPU(s) x {args.streams} dialogue slots in {n} worker processes, mode {mode or ('vap' if args.synthetic_weights is not None else 'from the state dict')}, {args.precision} arithmetic, "
-          f"{args.vap_process_rate} Hz / {args.context_len_sec} s — input :{door.port_in}, output :{door.port_out} (front-door process: dialogue k -> GPU k mod N)", flush=True)
+          f"{args.vap_process_rate} Hz / {args.context_len_sec} s, audio at {args.input_rate} Hz — input :{door.port_in}, output :{door.port_out} (front-door process: dialogue k -> GPU k mod N)", flush=True)
     rc = 0
     while not stop["now"]:
         time.sleep(0.2)
@@ -417,6 +423,10 @@ def main(argv=None) -> int:
     ap.add_argument("--mode", type=str, default=None,
                     help="head set: vap, bc or nod (default: inferred from the state dict), or a+b[+c] of distinct ones: several models on one shared "
                          "CPC trunk, the first leads (then --vap_model takes one path per model, comma-separated)")
+    ap.add_argument("--input_rate", type=int, choices=[8000, 16000, 32000, 48000], default=16000,
+                    help="sample rate of the clients' audio: every packet still carries 10 ms (input_rate / 100 sample pairs); other rates than "
+                         "16000 are resampled on the GPU with torchaudio's default filter, which delays the audio by 0.44 - 0.88 ms; the rate "
+                         "travels in --save_state / --load_state files")
     ap.add_argument("--streams", type=int, default=1, help="dialogue slots per GPU (the reference serves exactly one)")
     ap.add_argument("--max_batch", type=int, default=1024)
     ap.add_argument("--gpus", type=int, default=1)
@@ -484,7 +494,7 @@ def main(argv=None) -> int:
         print(f"[vapx] start-up failed: {e}", file=sys.stderr, flush=True)
         return 1
     pin, pout = (door.port_in, door.port_out) if door else (shards[0].port_in, shards[0].port_out)
-    print(f"[vapx] {len(engines)} GPU(s) x {args.streams} dialogue slots, mode {mode}, {args.precision} arithmetic, {args.vap_process_rate} Hz / {args.context_len_sec} s — "
+    print(f"[vapx] {len(engines)} GPU(s) x {args.streams} dialogue slots, mode {mode}, {args.precision} arithmetic, {args.vap_process_rate} Hz / {args.context_len_sec} s, audio at {args.input_rate} Hz — "
           f"input :{pin}, output :{pout}" + (" (front door: dialogue k -> GPU k mod N)" if door else ""), flush=True)
     last = time.time()
     while not stop["now"]:

@@ -37,6 +37,9 @@ class ManyStreamServer:
     def __init__(self, vap, port_in: int = 50007, port_out: int = 50008, host: str = "127.0.0.1", gain: float = 1.0,
                  max_wait_s: float = 0.004, broadcast: Optional[bool] = None, reset_on_connect: bool = True):
         self.vap = vap
+        if getattr(vap, "hop_in", vap.hop) != vap.hop:      # this twin frames 16 kHz packets only; the native front-end follows the engine's rate
+            raise ValueError(f"the model takes {vap.hop_in} samples per frame, not the {vap.hop} of 16 kHz audio: this Python server frames 16 kHz "
+                             f"only — serve an engine with an input rate through the native front-end (ingest.NativeServer, serve.py)")
         # which contract the model's process() has is decided ONCE, from its signature (a blanket `except TypeError` around the call would
         # also swallow a TypeError raised INSIDE a model that does take on_numeric, and step its state a second time: advisor r04)
         try:

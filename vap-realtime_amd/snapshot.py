@@ -6,7 +6,8 @@ A file is the state records of ``Engine.export_streams`` (include/vapx.h "Bulk s
     8 bytes   b"VAPXSNP1"
     4 bytes   length of the JSON header, little-endian u32
     JSON      {"version", "frame_hz", "ctx_frames", "modes" (attach order, the first leads), "split_f16" (the precision path the
-               records' Q|K|V cache was made on), "cache", "ids" (stream slots, one record each), "record_floats" (per mode)}
+               records' Q|K|V cache was made on), "cache", "ids" (stream slots, one record each), "record_floats" (per mode),
+               and "input_hz" ONLY when the engine takes audio at another rate than 16000 (a file without the key is a 16 kHz file)}
     padding   zero bytes up to a multiple of 16
     records   per mode in ``modes`` order: float32 [len(ids)][record_floats[mode]], little-endian
 
@@ -25,7 +26,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .engine import (STATE_CACHE_SPLIT, STATE_HAS_CACHE, STATE_HAS_LSTM, STATE_HEADER_FLOATS, STATE_MAGIC, VapxError,
+from .engine import (STATE_CACHE_SPLIT, STATE_HAS_CACHE, STATE_HAS_LSTM, STATE_HAS_RESAMPLE, STATE_HEADER_FLOATS, STATE_MAGIC, VapxError,
                      state_record_floats)
 
 FILE_MAGIC = b"VAPXSNP1"
@@ -41,15 +42,21 @@ def describe(target) -> dict:
         modes = list(target.modes)
     else:
         lead, modes = target, [target.mode]
-    return {"frame_hz": int(lead.frame_hz), "ctx_frames": int(lead.T), "modes": modes, "split_f16": bool(getattr(lead, "split_f16", False)),
+    desc = {"frame_hz": int(lead.frame_hz), "ctx_frames": int(lead.T), "modes": modes, "split_f16": bool(getattr(lead, "split_f16", False)),
             "max_streams": int(lead.max_streams)}
+    if int(getattr(lead, "input_hz", 16000)) != 16000:       # the leader owns the audio; 16 kHz descriptions stay as they were
+        desc["input_hz"] = int(lead.input_hz)
+    return desc
 
 
 def make_header(desc: dict, ids: Sequence[int], cache: bool) -> dict:
-    T = desc["ctx_frames"]
-    return {"version": VERSION, "frame_hz": desc["frame_hz"], "ctx_frames": T, "modes": list(desc["modes"]),
-            "split_f16": bool(desc["split_f16"]), "cache": bool(cache), "ids": [int(i) for i in ids],
-            "record_floats": [state_record_floats(T, cache, follower=k > 0) for k in range(len(desc["modes"]))]}
+    T, in_hz = desc["ctx_frames"], int(desc.get("input_hz", 16000))
+    hdr = {"version": VERSION, "frame_hz": desc["frame_hz"], "ctx_frames": T, "modes": list(desc["modes"]),
+           "split_f16": bool(desc["split_f16"]), "cache": bool(cache), "ids": [int(i) for i in ids],
+           "record_floats": [state_record_floats(T, cache, follower=k > 0, input_hz=in_hz) for k in range(len(desc["modes"]))]}
+    if in_hz != 16000:
+        hdr["input_hz"] = in_hz
+    return hdr
 
 
 def _data_offset(json_len: int) -> int:
@@ -125,6 +132,9 @@ def validate(hdr: dict, desc: dict, ids: Optional[Sequence[int]] = None) -> list
     for k in ("frame_hz", "ctx_frames"):
         if int(hdr[k]) != int(desc[k]):
             raise VapxError(f"snapshot {k} = {hdr[k]}, the engine has {k} = {desc[k]}")
+    if int(hdr.get("input_hz", 16000)) != int(desc.get("input_hz", 16000)):
+        raise VapxError(f"snapshot input_hz = {hdr.get('input_hz', 16000)}, the engine has input_hz = {desc.get('input_hz', 16000)}: the "
+                        f"records of an engine with an input rate carry its resampler history")
     if list(hdr["modes"]) != list(desc["modes"]):
         raise VapxError(f"snapshot modes = {hdr['modes']}, the engine serves modes = {desc['modes']} (same models, same attach order)")
     if hdr["cache"] and bool(hdr["split_f16"]) != bool(desc["split_f16"]):
@@ -132,7 +142,7 @@ def validate(hdr: dict, desc: dict, ids: Optional[Sequence[int]] = None) -> list
                         f"cached values differ between the precision paths (save with cache=False to move between them)")
     T = int(desc["ctx_frames"])
     for k, fl in enumerate(hdr["record_floats"]):
-        want = state_record_floats(T, bool(hdr["cache"]), follower=k > 0)
+        want = state_record_floats(T, bool(hdr["cache"]), follower=k > 0, input_hz=int(desc.get("input_hz", 16000)))
         if int(fl) != want:
             raise VapxError(f"snapshot record_floats[{k}] = {fl}, a {'follower' if k else 'leader'} record of this engine has {want}")
     use = [int(i) for i in (hdr["ids"] if ids is None else ids)]
@@ -147,11 +157,14 @@ def check_records(records: np.ndarray, desc: dict, cache: bool, follower: bool, 
     """The per-record header checks of vapx_import_streams, on the host and without an engine — so that a group load can refuse a bad
     follower block before its leader was touched."""
     hdr = np.ascontiguousarray(records[:, :STATE_HEADER_FLOATS]).view(np.int32)
-    bits = (0 if follower else STATE_HAS_LSTM) | (STATE_HAS_CACHE if cache else 0) | (STATE_CACHE_SPLIT if cache and desc["split_f16"] else 0)
+    in_hz = int(desc.get("input_hz", 16000))
+    in_hz = 0 if follower or in_hz == 16000 else in_hz       # header word [6]: 0 at 16 kHz and in a follower's records
+    bits = ((0 if follower else STATE_HAS_LSTM) | (STATE_HAS_CACHE if cache else 0) | (STATE_CACHE_SPLIT if cache and desc["split_f16"] else 0)
+            | (STATE_HAS_RESAMPLE if in_hz else 0))
     T = int(desc["ctx_frames"])
     for k, h in enumerate(hdr):
         for name, got, want in (("magic", int(h[0]), STATE_MAGIC), ("ctx_frames", int(h[1]), T), ("frame_hz", int(h[2]), int(desc["frame_hz"])),
-                                ("content bits", int(h[3]), bits)):
+                                ("input_hz", int(h[6]), in_hz), ("content bits", int(h[3]), bits)):
             if got != want:
                 raise VapxError(f"{what} {k}: {name} {got:#x} does not match {want:#x}" if name in ("magic", "content bits")
                                 else f"{what} {k}: {name} {got} differs from the engine's {want}")
