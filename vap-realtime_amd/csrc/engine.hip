@@ -15,10 +15,13 @@
 #include <vector>
 
 #include "../../include/vapx.h"
+#include "engine_buffers.h"
 #include "fused_blocks.h"
 #include "gemm_f32.h"
 #include "vap_kernels.h"
 #include "vapx_layout.h"
+
+static_assert(kCarrySamples == VAPX_PAD, "engine_buffers.h and common.h disagree on the carry");
 
 namespace {
 
@@ -35,30 +38,39 @@ struct Layer {
   float hid_scale = 1.0f;   // split-precision path: static power-of-two scale of the GELU hidden row (1 unless the weights allow |gelu(h)| >= 2^15)
 };
 
-}  // namespace
+// everything outside the transformer layers, resolved once in vapx_create like layer[]: every member is required (vapx_create refuses a
+// layout without it), except the copies a conv does not have (conv0: w16, wf; conv1: wf), which stay null and are never read
+struct ConvW { const float *w, *w16, *wf, *b, *g, *beta; };   // conv i with its ChannelNorm; w16: split-precision GEMM copy, wf: conv_tail_kernel's
+struct Weights {
+  ConvW conv[5];
+  const float *lstm_wih, *lstm_wih16, *lstm_whh, *lstm_b;
+  const float *down_w, *down_wf, *down_b, *down_g, *down_beta;
+  const float *l0_wqkv16, *l3_last16;
+  const float *comb_wa, *comb_wb, *comb_waT, *comb_wbT, *comb_g, *comb_b;
+  const float *head_w, *head_wT, *head_b, *vad_w, *vad_b, *aux_w, *aux_b;
+};
 
-struct Scratch {
-  int *bn = nullptr, *bhead = nullptr, *rot = nullptr;
-  float *h0 = nullptr, *h1 = nullptr, *h2 = nullptr, *h3 = nullptr, *z = nullptr, *gx = nullptr, *lstm_out = nullptr, *e = nullptr;
-  float* xl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // layer inputs/outputs: x0, o, stereo0..2
-  float *xn = nullptr, *xmid = nullptr, *att = nullptr, *qkv = nullptr, *qx = nullptr, *kvx = nullptr, *ffn = nullptr;
-  float* last[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  float *en = nullptr, *qkv_new = nullptr;   // [B*2][256], [B*2][768]: LN0(e) and layer-0 Q|K|V of the new row
-  float* lffn = nullptr;                     // [B*2][768] FFN hidden of the last-row path  // [B*2][256] each: x, xn, q, att, xmid, out (last-row path)
-  Scratch slice(size_t b0, const int* P, int ncpc, int T) const {
-    Scratch s = *this;
-    const size_t bc = b0 * 2, rows = bc * T;
-    s.bn += b0; s.bhead += b0; s.rot += b0;
-    s.h0 += bc * (P[0] + 4) * 256; s.h1 += bc * (P[1] + 2) * 256; s.h2 += bc * (P[2] + 2) * 256; s.h3 += bc * (P[3] + 2) * 256;
-    s.z += bc * ncpc * 256; s.gx += bc * ncpc * 1024; s.lstm_out += bc * ncpc * 256; s.e += bc * 256;
-    for (int i = 0; i < 5; ++i) s.xl[i] += rows * 256;
-    s.xn += rows * 256; s.xmid += rows * 256; s.att += rows * 256; s.qkv += rows * 768; s.qx += rows * 256;
-    s.kvx += rows * 512; s.ffn += rows * 768;
-    for (int i = 0; i < 6; ++i) s.last[i] += bc * 256;
-    s.en += bc * 256; s.qkv_new += bc * 768; s.lffn += bc * 768;
-    return s;
+// host -> pinned -> device behind an event: the pinned block is reused by the next upload only after the copy out of it has completed
+template <typename T>
+struct Staged {
+  T *dev = nullptr, *pin = nullptr;
+  hipEvent_t evt = nullptr;   // the latest copy out of `pin` has completed
+  hipError_t create_pinned(size_t n) {
+    hipError_t e = hipHostMalloc((void**)&pin, n * sizeof(T), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&evt, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(evt, nullptr);
+    return e;
+  }
+  hipError_t upload(const T* src, size_t n, hipStream_t st) {
+    hipError_t e = hipEventSynchronize(evt);
+    if (e != hipSuccess) return e;
+    memcpy(pin, src, n * sizeof(T));
+    if ((e = hipMemcpyAsync(dev, pin, n * sizeof(T), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+    return hipEventRecord(evt, st);
   }
 };
+
+}  // namespace
 
 // per-stream state bases; for identity stream ids of a sub-batch starting at slot b0 the bases are
 // simply advanced by b0 streams
@@ -67,35 +79,34 @@ struct StateView {
   int* frames_seen;
 };
 
-struct vapx_engine {
+struct vapx_engine : Geometry {
   vapx_config cfg;
-  int hop, L, P[5], ncpc, T, K;
   std::string err;
 
   float* w = nullptr;  // weight blob
-  size_t w_floats = 0;
   const vapx_layout::Entry* lay = nullptr;
   size_t lay_n = 0;
   Layer layer[4];
+  Weights wt = {};
 
   // per-stream state
   float *ring = nullptr, *ring_qkv = nullptr, *h_state = nullptr, *c_state = nullptr, *carry = nullptr;
   int* frames_seen = nullptr;
 
   // scratch (max_batch); every buffer is linear in the batch index, so a sub-batch starting at
-  // stream slot b0 is just the same struct with offset pointers (Scratch::slice)
-  float *audio_dev = nullptr, *out_dev = nullptr;
-  int* ids_dev = nullptr;
+  // stream slot b0 is just the same struct with offset pointers (Scratch::slice, engine_buffers.h)
   Scratch sc;
+  Staged<float> audio;   // host audio: device block of the step; pageable memory is staged through the pinned one (vapx_host_alloc memory skips it)
+  Staged<int> ids;       // host stream ids of a step
   // intra-tick overlap: the batch is split into groups that run on their own HIP streams
   static constexpr int kMaxGroups = 8;
   hipStream_t gstream[kMaxGroups] = {};
   hipEvent_t gdone[kMaxGroups] = {};
   hipEvent_t gstart = nullptr;
   int n_groups = 1;
-  // debug knob (env VAPX_POISON_SCRATCH): every scratch buffer is refilled with NaN bit patterns before each step and the rings start as
-  // NaNs, so a kernel that consumes anything it (or an earlier kernel of the same tick) did not write shows up as a non-finite output
-  std::vector<std::pair<void*, size_t>> poison;
+  // debug knob (env VAPX_POISON_SCRATCH): every scratch buffer the table marks is refilled with NaN bit patterns before each step and the
+  // rings start as NaNs, so a kernel that consumes anything it (or an earlier kernel of the same tick) did not write shows up as a non-finite output
+  bool poison = false;
   // debug knob (env VAPX_FORCE_ATTENTION_XL, read once per engine in vapx_create): every long window of the fp32 path runs
   // attention_xl_kernel, so tests can hold it against attention_long2_kernel on windows both kernels take
   bool force_xl = false;
@@ -113,10 +124,6 @@ struct vapx_engine {
   float *rs_hist = nullptr, *rs_out = nullptr;   // [max_streams][rs_rec], [max_batch][2][hop]
   int* rs_started = nullptr;              // [max_streams * 2] the (stream, channel) has consumed a tick since its reset
   float* out_pinned = nullptr;
-  float* audio_pinned = nullptr;          // staging for pageable host audio (callers holding vapx_host_alloc memory skip it)
-  hipEvent_t audio_evt = nullptr;         // the H2D copy out of audio_pinned has completed
-  int* ids_pinned = nullptr;
-  hipEvent_t ids_evt = nullptr;
   int last_B = 0, last_G = 1;
   bool last_tail_fused = false;           // some overlap group of the latest encoder pass ran conv_tail_kernel: h2 / h3 were not written
   bool deferred_pending = false;          // the latest step left its overlap groups un-joined (VAPX_DEFER_JOIN)
@@ -138,16 +145,16 @@ struct vapx_engine {
   bool last_ids_known = false;            // ... unless they were device ids
   std::vector<int32_t> phase;             // R > 1: leader ticks since the stream's last follower frame, per stream
   float *acc = nullptr, *mixA = nullptr, *out_c = nullptr;   // R > 1: TrunkCollectArgs acc / A, compact output rows [max_batch][784]
-  int *mix_dev = nullptr, *mix_pinned = nullptr;             // R > 1: [3][max_batch] stream id | leader slot | pos of this tick's entries
-  hipEvent_t mix_evt = nullptr;           // the copy out of mix_pinned has completed
+  Staged<int> mix;                        // R > 1: [3][max_batch] stream id | leader slot | pos of this tick's entries
+  std::vector<int> mix_host;              // ... as the host sorts them
   // vapx_step_group (leader only): the tick's wire rows, model-major, on the device and in page-locked host memory
   float *gw_dev = nullptr, *gw_pinned = nullptr;
   size_t gw_cap = 0;                      // floats either block holds
   std::vector<std::pair<int32_t, int32_t>> group_bad;   // (batch slot, model index) pairs of the latest host-output vapx_step_group
   // vapx_export_streams / vapx_import_streams: ids of up to max_streams streams; bounded staging blocks for host records (allocated
   // on the first host-buffer call; the pinned one only for pageable memory)
-  int *sio_ids_dev = nullptr, *sio_ids_pinned = nullptr;
-  hipEvent_t sio_ids_evt = nullptr, sio_evt = nullptr;   // the copy out of sio_ids_pinned / the copy out of (into) sio_pin has completed
+  Staged<int> sio_ids;
+  hipEvent_t sio_evt = nullptr;           // the copy out of sio_pin has completed
   float *sio_dev = nullptr, *sio_pin = nullptr;
   size_t sio_dev_cap = 0, sio_pin_cap = 0;               // floats
 
@@ -157,12 +164,6 @@ struct vapx_engine {
   struct ProfRec { hipEvent_t a, b; int cls; };
   std::vector<ProfRec> prof_recs;
   std::vector<hipEvent_t> prof_pool;
-
-  const float* W(const char* name) const {
-    for (size_t i = 0; i < lay_n; ++i)
-      if (!strcmp(lay[i].name, name)) return w + lay[i].off;
-    return nullptr;
-  }
 };
 
 namespace {
@@ -244,18 +245,35 @@ bool is_pinned_host(const void* p) {
   return at.type == hipMemoryTypeHost;
 }
 
-int rate_ok(int hz) { return hz == 5 || hz == 10 || hz == 20 || hz == 50; }
-
-void geometry(int hz, int* hop, int* L, int P[5], int* ncpc) {
-  *hop = 16000 / hz;
-  *L = *hop + VAPX_PAD;
-  P[0] = *L / 5;
-  P[1] = P[0] / 4;
-  P[2] = P[1] / 2;
-  P[3] = P[2] / 2;
-  P[4] = P[3] / 2;
-  *ncpc = P[4] - 2;
+// device -> host: straight into the caller's block when it is page-locked (the copy is then still in flight on return), else through
+// `pinned`, synchronised and copied on
+hipError_t download(void* dst, const void* src_dev, size_t bytes, void* pinned, hipStream_t st) {
+  if (is_pinned_host(dst)) return hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, st);
+  hipError_t e = hipMemcpyAsync(pinned, src_dev, bytes, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) memcpy(dst, pinned, bytes);
+  return e;
 }
+
+template <typename T>
+void release(Staged<T>& s) {
+  dfree(s.dev);
+  if (s.pin) (void)hipHostFree(s.pin);
+  if (s.evt) (void)hipEventDestroy(s.evt);
+  s = Staged<T>();
+}
+
+// free (and null) the buffers of the scratch table: all of them, or the encoder's (what a trunk follower never uses)
+void release_scratch(Scratch& sc, bool encoder_only) {
+  for (const ScratchRow& r : kScratchTable) {
+    if (encoder_only && !r.encoder) continue;
+    const ScratchSlot p = r.slot(sc);
+    if (p.f) { dfree(*p.f); *p.f = nullptr; }
+    else { dfree(*p.i); *p.i = nullptr; }
+  }
+}
+
+int rate_ok(int hz) { return hz == 5 || hz == 10 || hz == 20 || hz == 50; }
 
 // kernel classes for profiling: 0..4 = GEMM by epilogue (EPI_STORE .. EPI_CN_RELU), then the rest; EPI_BIAS_LN_GELU (= 5 as an epilogue id)
 // is booked as class 13 — 5 is the fused conv tail (round 3 booked both under 5: a follower's downsample GEMM was priced as conv_tail)
@@ -312,64 +330,59 @@ GemmArgs gemm_args(const float* A, RowMap am, const float* W, int M, int N, int 
 int run_encoder(vapx_engine* h, const Scratch& sc, const StateView& sv, int B, const int* ids_dev, const float* audio,
                 int spc, bool use_state_meta, hipStream_t st) {
   const int* P = h->P;
+  const Weights& w = h->wt;
   Conv0Args c0;
   c0.audio = audio; c0.ids = ids_dev; c0.carry = use_state_meta ? sv.carry : nullptr;
-  c0.h0 = sc.h0; c0.w = h->W("conv0.w"); c0.bias = h->W("conv0.b"); c0.gamma = h->W("cn0.g"); c0.beta = h->W("cn0.b");
+  c0.h0 = sc.h0; c0.w = w.conv[0].w; c0.bias = w.conv[0].b; c0.gamma = w.conv[0].g; c0.beta = w.conv[0].beta;
   c0.frames_seen = use_state_meta ? sv.frames_seen : nullptr; c0.bn = sc.bn; c0.bhead = sc.bhead;
   c0.L = h->L; c0.spc = spc; c0.T = h->T;
   { ProfScope ps(h, CLS_CONV0, st); HIPCHK(h, launch_conv0(c0, B, st)); }
 
-  struct ConvSpec { const float* in; int Pin, guard_in, k, s; float* out; int Pout, guard_out; const char* idx; };
-  const ConvSpec cs[3] = {
-      {sc.h0, P[0], 2, 8, 4, sc.h1, P[1], 1, "1"},
-      {sc.h1, P[1], 1, 4, 2, sc.h2, P[2], 1, "2"},
-      {sc.h2, P[2], 1, 4, 2, sc.h3, P[3], 1, "3"},
+  struct ConvSpec { const float* in; int Pin, guard_in, k, s; float* out; int Pout, guard_out; };
+  const ConvSpec cs[3] = {   // conv1 .. conv3
+      {sc.h0, P[0], 2, 8, 4, sc.h1, P[1], 1},
+      {sc.h1, P[1], 1, 4, 2, sc.h2, P[2], 1},
+      {sc.h2, P[2], 1, 4, 2, sc.h3, P[3], 1},
   };
   // one stream per workgroup pays 27 % row padding: worth it only while the three GEMMs cannot fill the chip
   // (on the split-precision path the three GEMMs are 2x cheaper and beat the fp32 fused tail even at 256 streams)
   const bool fused_tail = conv_tail_supported(P[1], h->ncpc) && !(h->cfg.flags & VAPX_FLAG_UNFUSED_CONV) &&
                           !(h->cfg.flags & VAPX_FLAG_SPLIT_F16) && B <= 512;
   if (fused_tail) h->last_tail_fused = true;   // B is this group's batch: vapx_peek must not re-derive the decision from last_B
-  char nm[32];
   for (int i = 0; i < (fused_tail ? 1 : 3); ++i) {
     const ConvSpec& c = cs[i];
+    const ConvW& cw = w.conv[i + 1];
     RowMap am{(long)(c.Pin + 2 * c.guard_in) * 256, (long)c.s * 256, c.Pout};
     RowMap cm{(long)(c.Pout + 2 * c.guard_out) * 256, 256, c.Pout};
-    snprintf(nm, sizeof nm, "conv%s.w", c.idx);
-    GemmArgs g = gemm_args(c.in, am, h->W(nm), B * 2 * c.Pout, 256, c.k * 256, c.out + c.guard_out * 256, cm);
-    snprintf(nm, sizeof nm, "conv%s.w16", c.idx); g.W16 = h->W(nm);
-    snprintf(nm, sizeof nm, "conv%s.b", c.idx); g.bias = h->W(nm);
-    snprintf(nm, sizeof nm, "cn%s.g", c.idx); g.gamma = h->W(nm);
-    snprintf(nm, sizeof nm, "cn%s.b", c.idx); g.beta = h->W(nm);
+    GemmArgs g = gemm_args(c.in, am, cw.w, B * 2 * c.Pout, 256, c.k * 256, c.out + c.guard_out * 256, cm);
+    g.W16 = cw.w16; g.bias = cw.b; g.gamma = cw.g; g.beta = cw.beta;
     HIPCHK(h, gemm(h, g, EPI_CN_RELU, st));
   }
   if (fused_tail) {
     // conv2 -> conv3 -> conv4 for one stream per workgroup, intermediates in LDS
     ConvTailArgs ct;
-    ct.h1 = sc.h1; ct.w2f = h->W("conv2.wf"); ct.w3f = h->W("conv3.wf"); ct.w4f = h->W("conv4.wf");
-    ct.b2 = h->W("conv2.b"); ct.g2 = h->W("cn2.g"); ct.be2 = h->W("cn2.b");
-    ct.b3 = h->W("conv3.b"); ct.g3 = h->W("cn3.g"); ct.be3 = h->W("cn3.b");
-    ct.b4 = h->W("conv4.b"); ct.g4 = h->W("cn4.g"); ct.be4 = h->W("cn4.b");
+    ct.h1 = sc.h1; ct.w2f = w.conv[2].wf; ct.w3f = w.conv[3].wf; ct.w4f = w.conv[4].wf;
+    ct.b2 = w.conv[2].b; ct.g2 = w.conv[2].g; ct.be2 = w.conv[2].beta;
+    ct.b3 = w.conv[3].b; ct.g3 = w.conv[3].g; ct.be3 = w.conv[3].beta;
+    ct.b4 = w.conv[4].b; ct.g4 = w.conv[4].g; ct.be4 = w.conv[4].beta;
     ct.z = sc.z; ct.P1 = P[1]; ct.ncpc = h->ncpc;
     { ProfScope ps(h, CLS_CONVTAIL, st); HIPCHK(h, launch_conv_tail(ct, B, st)); }
   } else {  // conv4: only positions 1..P4-2 survive z[:, 1:-1] (encoder.py:76)
     RowMap am{(long)(P[3] + 2) * 256, 2 * 256, h->ncpc};
-    GemmArgs g = gemm_args(sc.h3 + 2 * 256, am, h->W("conv4.w"), B * 2 * h->ncpc, 256, 4 * 256, sc.z, contiguous_rows(256));
-    g.W16 = h->W("conv4.w16");
-    g.bias = h->W("conv4.b"); g.gamma = h->W("cn4.g"); g.beta = h->W("cn4.b");
+    GemmArgs g = gemm_args(sc.h3 + 2 * 256, am, w.conv[4].w, B * 2 * h->ncpc, 256, 4 * 256, sc.z, contiguous_rows(256));
+    g.W16 = w.conv[4].w16; g.bias = w.conv[4].b; g.gamma = w.conv[4].g; g.beta = w.conv[4].beta;
     HIPCHK(h, gemm(h, g, EPI_CN_RELU, st));
   }
   {  // LSTM input projection for all n_cpc steps at once: gx = z.W_ih^T + (b_ih + b_hh)
-    GemmArgs g = gemm_args(sc.z, contiguous_rows(256), h->W("lstm.wih"), B * 2 * h->ncpc, 1024, 256, sc.gx, contiguous_rows(1024));
-    g.W16 = h->W("lstm.wih16");
-    g.bias = h->W("lstm.b");
+    GemmArgs g = gemm_args(sc.z, contiguous_rows(256), w.lstm_wih, B * 2 * h->ncpc, 1024, 256, sc.gx, contiguous_rows(1024));
+    g.W16 = w.lstm_wih16; g.bias = w.lstm_b;
     HIPCHK(h, gemm(h, g, EPI_STORE, st));
   }
   LstmArgs la;
   la.gx = sc.gx; la.ids = ids_dev; la.h_state = sv.h_state; la.c_state = sv.c_state;
-  la.wfrag = h->W("lstm.whh"); la.out = sc.lstm_out; la.M = B * 2; la.ncpc = h->ncpc;
+  la.wfrag = w.lstm_whh; la.out = sc.lstm_out; la.M = B * 2; la.ncpc = h->ncpc;
   // downsample (single-output Conv1d == dense [ncpc*256 -> 256]) + LN + GELU fused into the LSTM kernel
-  la.down_wf = h->W("down.wf"); la.down_b = h->W("down.b"); la.down_g = h->W("down.g"); la.down_beta = h->W("down.beta");
+  la.down_wf = w.down_wf; la.down_b = w.down_b; la.down_g = w.down_g; la.down_beta = w.down_beta;
   la.e = sc.e;
   la.ln0_g = h->layer[0].ln_self_g; la.ln0_b = h->layer[0].ln_self_b; la.en = use_state_meta ? sc.en : nullptr;
   { ProfScope ps(h, CLS_LSTM, st); HIPCHK(h, launch_lstm(la, st)); }
@@ -380,6 +393,184 @@ struct RingView { const float* ring; const float* ring_qkv; const int* ids; };  
 // vapx_transformer_maps: destinations of the attention weights (device, any may be null), each [B][2][layers][4][rows][rows]
 struct MapOut { float *attn, *self_attn, *cross_attn; int rows; };
 
+// one run_layers call, as its parts see it
+struct LayerRun {
+  vapx_engine* h; const Scratch& sc; int B; hipStream_t st; const RingView* rv; const MapOut* maps;
+  int T, M;      // window rows; B * 2 * T
+  bool split;    // VAPX_FLAG_SPLIT_F16: fp32-accurate products on the f16 matrix cores
+};
+// what a layer's attention part leaves to its FFN block: null att = xmid is complete (the short-window block and the GEMM chain project and
+// normalise themselves); else the block first computes xmid = resid + att . w^T (long window: the projection is fused into the FFN block)
+struct AttnOut { const float *att = nullptr, *w = nullptr, *resid = nullptr; bool resid_from_ring = false; };
+
+// maps: one attention_map_kernel launch next to an attention launch, on that launch's own Q and K rows (after their producers, before the
+// layer's FFN block overwrites sc.qkv / sc.kvx with the next layer's); no ProfScope: a diagnostic path outside the class table
+hipError_t emit_map(const LayerRun& r, int l, bool cross) {
+  const MapOut* maps = r.maps;
+  const Scratch& sc = r.sc;
+  float* dst = !maps ? nullptr : cross ? maps->cross_attn : l == 0 ? maps->attn : maps->self_attn;
+  if (!dst || (cross && l == 0)) return hipSuccess;
+  const long rr = (long)maps->rows * maps->rows;
+  const int n_layers = l == 0 ? 1 : 3, li = l == 0 ? 0 : l - 1;
+  AttnMapArgs ma{cross ? sc.qx : sc.qkv, cross ? sc.kvx : sc.qkv + 256, sc.bn, r.T, cross ? 256 : 768, cross ? 512 : 768, cross ? 1 : 0,
+                 dst + li * 4 * rr, n_layers * 4 * rr, rr, maps->rows};
+  return launch_attention_map(ma, r.B, r.st);
+}
+
+// the stand-alone attention kernel of a long window: split-precision up to 256 rows, else fp32 (attention_xl_kernel when forced or needed)
+hipError_t launch_attn(vapx_engine* h, const AttnArgs& a, int B, hipStream_t st) {
+  ProfScope ps(h, CLS_ATTN, st);
+  return (h->cfg.flags & VAPX_FLAG_SPLIT_F16) && h->T <= 256 ? launch_attention_f16x3(a, B, st) : launch_attention(a, B, st, h->force_xl);
+}
+
+// T <= 64, fused: attention + output projection + residual + LayerNorm (+ cross-attention queries)
+int attn_short(const LayerRun& r, int l, AttnOut*) {
+  vapx_engine* h = r.h; const Scratch& sc = r.sc; const int B = r.B, T = r.T; hipStream_t st = r.st; const RingView* rv = r.rv;
+  const Layer& Lw = h->layer[l];
+  const float* xin = sc.xl[l];
+  AttnBlockArgs ab;
+  memset(&ab, 0, sizeof ab);
+  ab.q = sc.qkv; ab.k = sc.qkv + 256; ab.v = sc.qkv + 512; ab.ldq = 768; ab.ldkv = 768; ab.swap_kv = 0;
+  const bool asplit = r.split;
+  ab.split = asplit ? 1 : 0;
+  ab.bn = sc.bn; ab.T = T; ab.wprojf = asplit ? Lw.wprojh : Lw.wprojf; ab.resid = xin; ab.xmid = sc.xmid;
+  if (l == 0 && rv && rv->ring) {   // Q|K|V and the residual straight from the per-stream rings
+    ab.q = rv->ring_qkv; ab.k = rv->ring_qkv + 256; ab.v = rv->ring_qkv + 512; ab.resid = rv->ring;
+    ab.ring_rot = sc.rot; ab.ids = rv->ids;
+  }
+  if (l == 0) { ab.ln_g = Lw.ln_ffn_g; ab.ln_b = Lw.ln_ffn_b; }
+  else { ab.ln_g = Lw.ln_src_g; ab.ln_b = Lw.ln_src_b; ab.wqxf = asplit ? Lw.wqxh : Lw.wqxf; ab.qx = sc.qx; }
+#ifdef VAPX_TRACE
+  if (h->attn_trace && l == 1 && (size_t)B * 2 <= 16384) { ab.trace = h->attn_trace; h->attn_trace_wgs = (size_t)B * 2; }
+#endif
+  { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, launch_attn_block(ab, B, st)); }
+#ifdef VAPX_TRACE
+  ab.trace = nullptr;
+#endif
+  if (r.maps) { HIPCHK(h, emit_map(r, l, false)); HIPCHK(h, emit_map(r, l, true)); }   // sc.qx: written by the launch above
+  if (l > 0) {
+    ab.q = sc.qx; ab.k = sc.kvx; ab.v = sc.kvx + 256; ab.ldq = 256; ab.ldkv = 512; ab.swap_kv = 1;
+    ab.wprojf = asplit ? Lw.wprojxh : Lw.wprojxf; ab.resid = sc.xmid; ab.ln_g = Lw.ln_ffn_g; ab.ln_b = Lw.ln_ffn_b;
+    ab.wqxf = nullptr; ab.qx = nullptr; ab.ring_rot = nullptr; ab.ids = nullptr;
+    { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, launch_attn_block(ab, B, st)); }
+  }
+  return VAPX_OK;
+}
+
+// long window: plain attention kernels; every projection rides in a fused flat-row block (no [rows x 256] GEMM launches).
+// xn_ready: sc.xn holds LN_self(layer l)(x) of every row, sc.qkv does NOT hold this layer's Q|K|V
+int attn_long_fused(const LayerRun& r, int l, bool xn_ready, AttnOut* out) {
+  vapx_engine* h = r.h; const Scratch& sc = r.sc; const int B = r.B, T = r.T; hipStream_t st = r.st; const RingView* rv = r.rv;
+  const bool split = r.split;
+  const Layer& Lw = h->layer[l];
+  const float* xin = sc.xl[l];
+  AttnArgs aa{sc.qkv, sc.qkv + 256, sc.qkv + 512, sc.att, sc.bn, T, 768, 768, 0};
+  const bool ring0 = l == 0 && rv && rv->ring;
+  if (ring0) {   // Q|K|V straight from the per-stream rings (no chronological gather)
+    aa.q = rv->ring_qkv; aa.k = rv->ring_qkv + 256; aa.v = rv->ring_qkv + 512;
+    aa.ring_rot = sc.rot; aa.ids = rv->ids;
+  }
+  const bool proj_here = xn_ready && l > 0 && Lw.wqkvp;
+#ifdef VAPX_TRACE
+  if (h->attn_trace && l == 1) { aa.trace = h->attn_trace; h->attn_trace_wgs = std::min<size_t>(16384, (size_t)B * 8); }
+#endif
+  if (proj_here) {
+    AttnProjArgs ap{sc.xn, Lw.wqkvp, sc.att, sc.bn, T, 0};
+    ProfScope ps(h, CLS_ATTN, st);
+    HIPCHK(h, launch_attention_proj_f16x3(ap, B, st));
+  } else {
+    HIPCHK(h, launch_attn(h, aa, B, st));
+  }
+  if (r.maps) HIPCHK(h, emit_map(r, l, false));
+  out->att = sc.att; out->w = split ? Lw.wproj8 : Lw.wprojf; out->resid = ring0 ? rv->ring : xin;
+  out->resid_from_ring = ring0;
+  if (l > 0) {
+    // self half: xmid = xin + att.Wproj^T ; qx = LN_src(xmid).Wq_x^T
+    FfnArgs fp;
+    memset(&fp, 0, sizeof fp);
+    fp.mode = 2; fp.M = r.M; fp.att = sc.att; fp.wprojf = split ? Lw.wproj8 : Lw.wprojf; fp.resid = xin; fp.xmid_out = sc.xmid;
+    fp.ln_g = Lw.ln_src_g; fp.ln_b = Lw.ln_src_b; fp.wqkvf = split ? Lw.wqx8 : Lw.wqxf; fp.n_qkv_chunks = 1; fp.qkv = sc.qx;
+    { ProfScope ps(h, CLS_FFN_PROJ, st); HIPCHK(h, split ? launch_ffn_block_f16x3(fp, st) : launch_ffn_block(fp, st)); }
+    AttnArgs ax{sc.qx, sc.kvx, sc.kvx + 256, sc.att, sc.bn, T, 256, 512, 1};
+    HIPCHK(h, launch_attn(h, ax, B, st));
+    if (r.maps) HIPCHK(h, emit_map(r, l, true));
+    out->w = split ? Lw.wprojx8 : Lw.wprojxf; out->resid = sc.xmid;
+  }
+  return VAPX_OK;
+}
+
+// long window, VAPX_FLAG_UNFUSED_PROJ: attention kernels with stand-alone projection GEMMs
+int attn_gemm_chain(const LayerRun& r, int l, AttnOut*) {
+  vapx_engine* h = r.h; const Scratch& sc = r.sc; const int B = r.B, T = r.T, M = r.M; hipStream_t st = r.st;
+  const RowMap r256 = contiguous_rows(256);
+  const Layer& Lw = h->layer[l];
+  const float* xin = sc.xl[l];
+  // self attention
+  AttnArgs aa{sc.qkv, sc.qkv + 256, sc.qkv + 512, sc.att, sc.bn, T, 768, 768, 0};
+  HIPCHK(h, launch_attn(h, aa, B, st));
+  if (r.maps) HIPCHK(h, emit_map(r, l, false));
+  GemmArgs g = gemm_args(sc.att, r256, Lw.wproj, M, 256, 256, sc.xmid, r256);
+  g.resid = xin; g.C2 = sc.xn;
+  if (l == 0) { g.gamma = Lw.ln_ffn_g; g.beta = Lw.ln_ffn_b; }
+  else { g.gamma = Lw.ln_src_g; g.beta = Lw.ln_src_b; }
+  HIPCHK(h, gemm(h, g, EPI_RESID_LN, st, /*bounded_A=*/false));   // raw attention rows
+  if (l > 0) {
+    // cross attention: Q from LN_src(x), K/V from the OTHER channel's raw layer input
+    g = gemm_args(sc.xn, r256, Lw.wq_x, M, 256, 256, sc.qx, r256);
+    HIPCHK(h, gemm(h, g, EPI_STORE, st));
+    AttnArgs ax{sc.qx, sc.kvx, sc.kvx + 256, sc.att, sc.bn, T, 256, 512, 1};
+    HIPCHK(h, launch_attn(h, ax, B, st));
+    if (r.maps) HIPCHK(h, emit_map(r, l, true));
+    g = gemm_args(sc.att, r256, Lw.wproj_x, M, 256, 256, sc.xmid, r256);
+    g.resid = sc.xmid; g.C2 = sc.xn; g.gamma = Lw.ln_ffn_g; g.beta = Lw.ln_ffn_b;
+    HIPCHK(h, gemm(h, g, EPI_RESID_LN, st, /*bounded_A=*/false));
+  }
+  return VAPX_OK;
+}
+
+// ---- layer 3 on the newest row of every (stream, channel) only; K/V (all rows) came from the
+//      previous layer's FFN block: sc.qkv = [K | V] [M][512], sc.kvx = cross [K | V] [M][512] ----
+int run_last_row(vapx_engine* h, const Scratch& sc, int B, hipStream_t st) {
+  const int T = h->T;
+  const RowMap r256 = contiguous_rows(256), r768 = contiguous_rows(768);
+  const Layer& Lw = h->layer[3];
+  const int Ml = B * 2;
+  if (!(h->cfg.flags & VAPX_FLAG_UNFUSED_LAST_ROW)) {
+    LastBlockArgs lb;
+    lb.x = sc.xl[3]; lb.xn = sc.xn; lb.bn = sc.bn; lb.wf = h->wt.l3_last16;
+    lb.ln_src_g = Lw.ln_src_g; lb.ln_src_b = Lw.ln_src_b;
+    lb.ln_ffn_g = Lw.ln_ffn_g; lb.ln_ffn_b = Lw.ln_ffn_b; lb.out = sc.last[5]; lb.B = B; lb.T = T;
+    ProfScope ps(h, CLS_LASTROW, st);
+    HIPCHK(h, launch_last_block(lb, st));
+    return VAPX_OK;
+  }
+  float *lx = sc.last[0], *lxn = sc.last[1], *lq = sc.last[2], *latt = sc.last[3], *lxmid = sc.last[4], *lout = sc.last[5];
+  ProfScope ps(h, CLS_LASTROW, st);
+  LastRowArgs lr{sc.xl[3], sc.bn, lx, lxn, Lw.ln_self_g, Lw.ln_self_b, B, T};
+  HIPCHK(h, launch_gather_last_ln(lr, st));
+  GemmArgs g = gemm_args(lxn, r256, Lw.wqkv, Ml, 256, 256, lq, r256);            // Q rows of Wqkv
+  HIPCHK(h, launch_gemm_f32(g, EPI_STORE, 0, st));
+  AttnArgs aa{lq, sc.qkv, sc.qkv + 256, latt, sc.bn, T, 256, 512, 0};
+  HIPCHK(h, launch_attention_last(aa, B, st));
+  g = gemm_args(latt, r256, Lw.wproj, Ml, 256, 256, lxmid, r256);
+  g.resid = lx; g.C2 = lxn; g.gamma = Lw.ln_src_g; g.beta = Lw.ln_src_b;
+  HIPCHK(h, launch_gemm_f32(g, EPI_RESID_LN, 0, st));
+  g = gemm_args(lxn, r256, Lw.wq_x, Ml, 256, 256, lq, r256);
+  HIPCHK(h, launch_gemm_f32(g, EPI_STORE, 0, st));
+  AttnArgs ax{lq, sc.kvx, sc.kvx + 256, latt, sc.bn, T, 256, 512, 1};
+  HIPCHK(h, launch_attention_last(ax, B, st));
+  g = gemm_args(latt, r256, Lw.wproj_x, Ml, 256, 256, lxmid, r256);
+  g.resid = lxmid; g.C2 = lxn; g.gamma = Lw.ln_ffn_g; g.beta = Lw.ln_ffn_b;
+  HIPCHK(h, launch_gemm_f32(g, EPI_RESID_LN, 0, st));
+  // FFN on 2B rows: two plain GEMMs spread over more workgroups than one fused 32-row block would
+  g = gemm_args(lxn, r256, Lw.w0, Ml, 768, 256, sc.lffn, r768);
+  HIPCHK(h, launch_gemm_f32(g, EPI_GELU, 0, st));
+  g = gemm_args(sc.lffn, r768, Lw.w3, Ml, 256, 768, lout, r256);
+  g.resid = lxmid;
+  HIPCHK(h, launch_gemm_f32(g, EPI_RESID, 0, st));
+  return VAPX_OK;
+}
+
 // ---- 1 self + 3 self/cross layers on x0 = xl[l_begin] (LN_self already in xn) ---------------------
 // Per layer: [QKV (+cross KV) projections] -> self-attention -> proj+residual+LN -> (cross: q GEMM,
 // cross-attention, proj+residual+LN) -> fused FFN block, which also emits the NEXT layer's
@@ -388,18 +579,9 @@ int run_layers(vapx_engine* h, const Scratch& sc, int B, hipStream_t st, int l_b
                bool prune_last = false, bool qkv0_ready = false, const RingView* rv = nullptr, const MapOut* maps = nullptr) {
   const int T = h->T;
   if (maps && (rv || prune_last)) return fail(h, VAPX_E_INVAL, "attention maps need chronological buffers and every row of every layer");
-  // maps: one attention_map_kernel launch next to an attention launch, on that launch's own Q and K rows (after their producers, before the
-  // layer's FFN block overwrites sc.qkv / sc.kvx with the next layer's); no ProfScope: a diagnostic path outside the class table
-  auto emit_map = [&](int l, bool cross) -> hipError_t {
-    float* dst = !maps ? nullptr : cross ? maps->cross_attn : l == 0 ? maps->attn : maps->self_attn;
-    if (!dst || (cross && l == 0)) return hipSuccess;
-    const long rr = (long)maps->rows * maps->rows;
-    const int n_layers = l == 0 ? 1 : 3, li = l == 0 ? 0 : l - 1;
-    AttnMapArgs ma{cross ? sc.qx : sc.qkv, cross ? sc.kvx : sc.qkv + 256, sc.bn, T, cross ? 256 : 768, cross ? 512 : 768, cross ? 1 : 0,
-                   dst + li * 4 * rr, n_layers * 4 * rr, rr, maps->rows};
-    return launch_attention_map(ma, B, st);
-  };
   const int M = B * 2 * T;
+  const bool split = (h->cfg.flags & VAPX_FLAG_SPLIT_F16) != 0;
+  const LayerRun r{h, sc, B, st, rv, maps, T, M, split};
   const RowMap r256 = contiguous_rows(256), r768 = contiguous_rows(768), r512 = contiguous_rows(512);
   if (prune_last && (l_end != 4 || l_begin > 2)) prune_last = false;
   const int l_full_end = prune_last ? 3 : l_end;
@@ -407,116 +589,29 @@ int run_layers(vapx_engine* h, const Scratch& sc, int B, hipStream_t st, int l_b
   // its own Q|K|V (attention_proj_f16x3_kernel); that block then skips the three contractions and never writes sc.qkv
   // (windows of 257 .. 512 frames: attention_xl_kernel — fp32, Q|K|V from the flat-row blocks — on both paths)
   // (a call that wants the self-attention maps needs Q and K in HBM: it takes the VAPX_FLAG_SPLIT_QKV_IN_FFN routing for that call)
-  const bool qkv_in_attn = (h->cfg.flags & VAPX_FLAG_SPLIT_F16) && !(h->cfg.flags & (VAPX_FLAG_SPLIT_QKV_IN_FFN | VAPX_FLAG_UNFUSED_PROJ)) && T > 64 && T <= 256 &&
+  const bool qkv_in_attn = split && !(h->cfg.flags & (VAPX_FLAG_SPLIT_QKV_IN_FFN | VAPX_FLAG_UNFUSED_PROJ)) && T > 64 && T <= 256 &&
                            !(maps && maps->self_attn);
   bool xn_ready = false;                   // sc.xn holds LN_self(layer l)(x) of every row, sc.qkv does NOT hold this layer's Q|K|V
   for (int l = l_begin; l < l_full_end; ++l) {
     const Layer& Lw = h->layer[l];
-    const float* xin = sc.xl[l];
-    float* xout = sc.xl[l + 1];
-    GemmArgs g;
-    const bool split = (h->cfg.flags & VAPX_FLAG_SPLIT_F16) != 0;   // fp32-accurate products on the f16 matrix cores
-    const float *pre_att = nullptr, *pre_w = nullptr, *pre_resid = nullptr;   // long window: projection fused into the FFN block
-    bool pre_ring = false;
     if (l == l_begin && !(l == 0 && qkv0_ready)) {
-      g = gemm_args(sc.xn, r256, Lw.wqkv, M, 768, 256, sc.qkv, r768);
+      GemmArgs g = gemm_args(sc.xn, r256, Lw.wqkv, M, 768, 256, sc.qkv, r768);
       HIPCHK(h, gemm(h, g, EPI_STORE, st));
       if (l > 0) {
-        g = gemm_args(xin, r256, Lw.wkv_x, M, 512, 256, sc.kvx, r512);
+        g = gemm_args(sc.xl[l], r256, Lw.wkv_x, M, 512, 256, sc.kvx, r512);
         HIPCHK(h, gemm(h, g, EPI_STORE, st, /*bounded_A=*/false));   // raw residual rows
       }
     }
-    if (T <= 64) {
-      // fused: attention + output projection + residual + LayerNorm (+ cross-attention queries)
-      AttnBlockArgs ab;
-      memset(&ab, 0, sizeof ab);
-      ab.q = sc.qkv; ab.k = sc.qkv + 256; ab.v = sc.qkv + 512; ab.ldq = 768; ab.ldkv = 768; ab.swap_kv = 0;
-      const bool asplit = (h->cfg.flags & VAPX_FLAG_SPLIT_F16) != 0;
-      ab.split = asplit ? 1 : 0;
-      ab.bn = sc.bn; ab.T = T; ab.wprojf = asplit ? Lw.wprojh : Lw.wprojf; ab.resid = xin; ab.xmid = sc.xmid;
-      if (l == 0 && rv && rv->ring) {   // Q|K|V and the residual straight from the per-stream rings
-        ab.q = rv->ring_qkv; ab.k = rv->ring_qkv + 256; ab.v = rv->ring_qkv + 512; ab.resid = rv->ring;
-        ab.ring_rot = sc.rot; ab.ids = rv->ids;
-      }
-      if (l == 0) { ab.ln_g = Lw.ln_ffn_g; ab.ln_b = Lw.ln_ffn_b; }
-      else { ab.ln_g = Lw.ln_src_g; ab.ln_b = Lw.ln_src_b; ab.wqxf = asplit ? Lw.wqxh : Lw.wqxf; ab.qx = sc.qx; }
-#ifdef VAPX_TRACE
-      if (h->attn_trace && l == 1 && (size_t)B * 2 <= 16384) { ab.trace = h->attn_trace; h->attn_trace_wgs = (size_t)B * 2; }
-#endif
-      { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, launch_attn_block(ab, B, st)); }
-#ifdef VAPX_TRACE
-      ab.trace = nullptr;
-#endif
-      if (maps) { HIPCHK(h, emit_map(l, false)); HIPCHK(h, emit_map(l, true)); }   // sc.qx: written by the launch above
-      if (l > 0) {
-        ab.q = sc.qx; ab.k = sc.kvx; ab.v = sc.kvx + 256; ab.ldq = 256; ab.ldkv = 512; ab.swap_kv = 1;
-        ab.wprojf = asplit ? Lw.wprojxh : Lw.wprojxf; ab.resid = sc.xmid; ab.ln_g = Lw.ln_ffn_g; ab.ln_b = Lw.ln_ffn_b;
-        ab.wqxf = nullptr; ab.qx = nullptr; ab.ring_rot = nullptr; ab.ids = nullptr;
-        { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, launch_attn_block(ab, B, st)); }
-      }
-    } else if (!(h->cfg.flags & VAPX_FLAG_UNFUSED_PROJ)) {
-      // long window: plain attention kernels; every projection rides in a fused flat-row block (no [rows x 256] GEMM launches)
-      AttnArgs aa{sc.qkv, sc.qkv + 256, sc.qkv + 512, sc.att, sc.bn, T, 768, 768, 0};
-      const bool ring0 = l == 0 && rv && rv->ring;
-      if (ring0) {   // Q|K|V straight from the per-stream rings (no chronological gather)
-        aa.q = rv->ring_qkv; aa.k = rv->ring_qkv + 256; aa.v = rv->ring_qkv + 512;
-        aa.ring_rot = sc.rot; aa.ids = rv->ids;
-      }
-      const bool proj_here = xn_ready && l > 0 && Lw.wqkvp;
-#ifdef VAPX_TRACE
-      if (h->attn_trace && l == 1) { aa.trace = h->attn_trace; h->attn_trace_wgs = std::min<size_t>(16384, (size_t)B * 8); }
-#endif
-      if (proj_here) {
-        AttnProjArgs ap{sc.xn, Lw.wqkvp, sc.att, sc.bn, T, 0};
-        ProfScope ps(h, CLS_ATTN, st);
-        HIPCHK(h, launch_attention_proj_f16x3(ap, B, st));
-      } else {
-        ProfScope ps(h, CLS_ATTN, st);
-        HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(aa, B, st) : launch_attention(aa, B, st, h->force_xl));
-      }
-      if (maps) HIPCHK(h, emit_map(l, false));
-      pre_att = sc.att; pre_w = split ? Lw.wproj8 : Lw.wprojf; pre_resid = ring0 ? rv->ring : xin;
-      pre_ring = ring0;
-      if (l > 0) {
-        // self half: xmid = xin + att.Wproj^T ; qx = LN_src(xmid).Wq_x^T
-        FfnArgs fp;
-        memset(&fp, 0, sizeof fp);
-        fp.mode = 2; fp.M = M; fp.att = sc.att; fp.wprojf = split ? Lw.wproj8 : Lw.wprojf; fp.resid = xin; fp.xmid_out = sc.xmid;
-        fp.ln_g = Lw.ln_src_g; fp.ln_b = Lw.ln_src_b; fp.wqkvf = split ? Lw.wqx8 : Lw.wqxf; fp.n_qkv_chunks = 1; fp.qkv = sc.qx;
-        { ProfScope ps(h, CLS_FFN_PROJ, st); HIPCHK(h, split ? launch_ffn_block_f16x3(fp, st) : launch_ffn_block(fp, st)); }
-        AttnArgs ax{sc.qx, sc.kvx, sc.kvx + 256, sc.att, sc.bn, T, 256, 512, 1};
-        { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(ax, B, st) : launch_attention(ax, B, st, h->force_xl)); }
-        if (maps) HIPCHK(h, emit_map(l, true));
-        pre_w = split ? Lw.wprojx8 : Lw.wprojxf; pre_resid = sc.xmid;
-      }
-    } else {
-    // self attention
-      AttnArgs aa{sc.qkv, sc.qkv + 256, sc.qkv + 512, sc.att, sc.bn, T, 768, 768, 0};
-      { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(aa, B, st) : launch_attention(aa, B, st, h->force_xl)); }
-      if (maps) HIPCHK(h, emit_map(l, false));
-      g = gemm_args(sc.att, r256, Lw.wproj, M, 256, 256, sc.xmid, r256);
-      g.resid = xin; g.C2 = sc.xn;
-      if (l == 0) { g.gamma = Lw.ln_ffn_g; g.beta = Lw.ln_ffn_b; }
-      else { g.gamma = Lw.ln_src_g; g.beta = Lw.ln_src_b; }
-      HIPCHK(h, gemm(h, g, EPI_RESID_LN, st, /*bounded_A=*/false));   // raw attention rows
-      if (l > 0) {
-        // cross attention: Q from LN_src(x), K/V from the OTHER channel's raw layer input
-        g = gemm_args(sc.xn, r256, Lw.wq_x, M, 256, 256, sc.qx, r256);
-        HIPCHK(h, gemm(h, g, EPI_STORE, st));
-        AttnArgs ax{sc.qx, sc.kvx, sc.kvx + 256, sc.att, sc.bn, T, 256, 512, 1};
-        { ProfScope ps(h, CLS_ATTN, st); HIPCHK(h, split && T <= 256 ? launch_attention_f16x3(ax, B, st) : launch_attention(ax, B, st, h->force_xl)); }
-        if (maps) HIPCHK(h, emit_map(l, true));
-        g = gemm_args(sc.att, r256, Lw.wproj_x, M, 256, 256, sc.xmid, r256);
-        g.resid = sc.xmid; g.C2 = sc.xn; g.gamma = Lw.ln_ffn_g; g.beta = Lw.ln_ffn_b;
-        HIPCHK(h, gemm(h, g, EPI_RESID_LN, st, /*bounded_A=*/false));
-      }
-    }
+    AttnOut pre;
+    const int rc = T <= 64 ? attn_short(r, l, &pre)
+                 : !(h->cfg.flags & VAPX_FLAG_UNFUSED_PROJ) ? attn_long_fused(r, l, xn_ready, &pre) : attn_gemm_chain(r, l, &pre);
+    if (rc) return rc;
     // feed-forward (+ next layer's projections)
     FfnArgs fa;
     memset(&fa, 0, sizeof fa);
-    fa.xmid = sc.xmid; fa.lnf_g = Lw.ln_ffn_g; fa.lnf_b = Lw.ln_ffn_b; fa.xout = xout; fa.M = M;
-    if (pre_att) { fa.mode = 1; fa.att = pre_att; fa.wprojf = pre_w; fa.resid = pre_resid; fa.xmid_out = sc.xmid; }
-    if (pre_ring) { fa.resid_rot = sc.rot; fa.resid_ids = rv->ids; fa.resid_T = T; }
+    fa.xmid = sc.xmid; fa.lnf_g = Lw.ln_ffn_g; fa.lnf_b = Lw.ln_ffn_b; fa.xout = sc.xl[l + 1]; fa.M = M;
+    if (pre.att) { fa.mode = 1; fa.att = pre.att; fa.wprojf = pre.w; fa.resid = pre.resid; fa.xmid_out = sc.xmid; }
+    if (pre.resid_from_ring) { fa.resid_rot = sc.rot; fa.resid_ids = rv->ids; fa.resid_T = T; }
     fa.w0f = split ? Lw.w0h : Lw.w0f; fa.w3f = split ? Lw.w3h : Lw.w3f; fa.hid_scale = Lw.hid_scale;
     xn_ready = false;
     if (l + 1 < l_end) {
@@ -524,7 +619,7 @@ int run_layers(vapx_engine* h, const Scratch& sc, int B, hipStream_t st, int l_b
       const float* nqkv = split ? Ln.wqkvh : Ln.wqkvf;
       fa.ln_g = Ln.ln_self_g; fa.ln_b = Ln.ln_self_b; fa.wqkvf = nqkv; fa.qkv = sc.qkv; fa.n_qkv_chunks = 3;
       fa.wkvxf = split ? Ln.wkvxh : Ln.wkvxf; fa.kvx = sc.kvx;
-      if (qkv_in_attn && pre_att && Ln.wqkvp && !(prune_last && l + 1 == 3)) {   // the next layer's self-attention projects Q|K|V itself
+      if (qkv_in_attn && pre.att && Ln.wqkvp && !(prune_last && l + 1 == 3)) {   // the next layer's self-attention projects Q|K|V itself
         fa.wqkvf = nullptr; fa.n_qkv_chunks = 0; fa.xn_out = sc.xn;
         xn_ready = true;
       }
@@ -544,50 +639,9 @@ int run_layers(vapx_engine* h, const Scratch& sc, int B, hipStream_t st, int l_b
       if ((size_t)(M + 31) / 32 > 16384) fa.trace = nullptr;
     }
 #endif
-    if (split) { ProfScope ps(h, CLS_FFN, st); HIPCHK(h, launch_ffn_block_f16x3(fa, st)); }
-    else
-    { ProfScope ps(h, CLS_FFN, st); HIPCHK(h, launch_ffn_block(fa, st)); }
+    { ProfScope ps(h, CLS_FFN, st); HIPCHK(h, split ? launch_ffn_block_f16x3(fa, st) : launch_ffn_block(fa, st)); }
   }
-  if (prune_last) {
-    // ---- layer 3 on the newest row of every (stream, channel) only; K/V (all rows) came from the
-    //      previous layer's FFN block: sc.qkv = [K | V] [M][512], sc.kvx = cross [K | V] [M][512] ----
-    const Layer& Lw = h->layer[3];
-    const int Ml = B * 2;
-    if (!(h->cfg.flags & VAPX_FLAG_UNFUSED_LAST_ROW)) {
-      LastBlockArgs lb;
-      lb.x = sc.xl[3]; lb.xn = sc.xn; lb.bn = sc.bn; lb.wf = h->W("L3.last16");
-      lb.ln_src_g = Lw.ln_src_g; lb.ln_src_b = Lw.ln_src_b;
-      lb.ln_ffn_g = Lw.ln_ffn_g; lb.ln_ffn_b = Lw.ln_ffn_b; lb.out = sc.last[5]; lb.B = B; lb.T = T;
-      ProfScope ps(h, CLS_LASTROW, st);
-      HIPCHK(h, launch_last_block(lb, st));
-      return VAPX_OK;
-    }
-    float *lx = sc.last[0], *lxn = sc.last[1], *lq = sc.last[2], *latt = sc.last[3], *lxmid = sc.last[4], *lout = sc.last[5];
-    ProfScope ps(h, CLS_LASTROW, st);
-    LastRowArgs lr{sc.xl[3], sc.bn, lx, lxn, Lw.ln_self_g, Lw.ln_self_b, B, T};
-    HIPCHK(h, launch_gather_last_ln(lr, st));
-    GemmArgs g = gemm_args(lxn, r256, Lw.wqkv, Ml, 256, 256, lq, r256);            // Q rows of Wqkv
-    HIPCHK(h, launch_gemm_f32(g, EPI_STORE, 0, st));
-    AttnArgs aa{lq, sc.qkv, sc.qkv + 256, latt, sc.bn, T, 256, 512, 0};
-    HIPCHK(h, launch_attention_last(aa, B, st));
-    g = gemm_args(latt, r256, Lw.wproj, Ml, 256, 256, lxmid, r256);
-    g.resid = lx; g.C2 = lxn; g.gamma = Lw.ln_src_g; g.beta = Lw.ln_src_b;
-    HIPCHK(h, launch_gemm_f32(g, EPI_RESID_LN, 0, st));
-    g = gemm_args(lxn, r256, Lw.wq_x, Ml, 256, 256, lq, r256);
-    HIPCHK(h, launch_gemm_f32(g, EPI_STORE, 0, st));
-    AttnArgs ax{lq, sc.kvx, sc.kvx + 256, latt, sc.bn, T, 256, 512, 1};
-    HIPCHK(h, launch_attention_last(ax, B, st));
-    g = gemm_args(latt, r256, Lw.wproj_x, Ml, 256, 256, lxmid, r256);
-    g.resid = lxmid; g.C2 = lxn; g.gamma = Lw.ln_ffn_g; g.beta = Lw.ln_ffn_b;
-    HIPCHK(h, launch_gemm_f32(g, EPI_RESID_LN, 0, st));
-    // FFN on 2B rows: two plain GEMMs spread over more workgroups than one fused 32-row block would
-    g = gemm_args(lxn, r256, Lw.w0, Ml, 768, 256, sc.lffn, r768);
-    HIPCHK(h, launch_gemm_f32(g, EPI_GELU, 0, st));
-    g = gemm_args(sc.lffn, r768, Lw.w3, Ml, 256, 768, lout, r256);
-    g.resid = lxmid;
-    HIPCHK(h, launch_gemm_f32(g, EPI_RESID, 0, st));
-  }
-  return VAPX_OK;
+  return prune_last ? run_last_row(h, sc, B, st) : VAPX_OK;
 }
 
 // nod variant: p_bc = sigmoid(bc_head(comb)) for EVERY row of the window (vap_nod_main.py:276 indexes the
@@ -715,14 +769,10 @@ int upload_ids(vapx_engine* h, int n, const int32_t* ids, int flags, hipStream_t
   if (!ids) { *out = nullptr; return VAPX_OK; }
   if (flags & VAPX_IDS_DEVICE) { *out = ids; return VAPX_OK; }
   { int rc = check_ids(h, n, ids); if (rc) return rc; }
-  HIPCHK(h, hipEventSynchronize(h->ids_evt));  // previous async copy out of the pinned buffer is done
-  memcpy(h->ids_pinned, ids, n * sizeof(int));
-  HIPCHK(h, hipMemcpyAsync(h->ids_dev, h->ids_pinned, n * sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipEventRecord(h->ids_evt, st));
-  *out = h->ids_dev;
+  HIPCHK(h, h->ids.upload(ids, n, st));
+  *out = h->ids.dev;
   return VAPX_OK;
 }
-
 
 // apply the vapx_reset_stream requests collected since the last step, ordered on `st` (no host or device sync)
 int flush_resets(vapx_engine* h, hipStream_t st) {
@@ -779,9 +829,9 @@ int run_combinator_all_rows(vapx_engine* h, const Scratch& sc, int n, hipStream_
   const int T = h->T, M = n * T;
   for (int c = 0; c < 2; ++c) {
     RowMap am{(long)2 * T * 256, 256, T};
-    GemmArgs g = gemm_args(sc.xl[4] + (long)c * T * 256, am, h->W(c ? "comb.wb" : "comb.wa"), M, 256, 256,
+    GemmArgs g = gemm_args(sc.xl[4] + (long)c * T * 256, am, c ? h->wt.comb_wb : h->wt.comb_wa, M, 256, 256,
                            c ? sc.qx : sc.att, contiguous_rows(256));
-    g.gamma = h->W("comb.g"); g.beta = h->W("comb.b");
+    g.gamma = h->wt.comb_g; g.beta = h->wt.comb_b;
     HIPCHK(h, gemm(h, g, EPI_BIAS_LN_GELU, st, /*bounded_A=*/false));   // raw last-layer rows
   }
   const long tot = (long)M * 256;
@@ -807,16 +857,16 @@ int step_group(vapx_engine* h, const Scratch& sc_own, int nb, int b0, const int*
   } else {
     if (h->own_window) HIPCHK(h, launch_window_meta(ids, sv.frames_seen, h->T, sc.bn, sc.bhead, nb, st));
     // this weight set's own downsample on the shared LSTM outputs: e = gelu(LN(Conv1d_K(lstm_out))), en = LN0(e)
-    GemmArgs g = gemm_args(lead->lstm_out, contiguous_rows(h->ncpc * 256), h->W("down.w"), nb * 2, 256, h->ncpc * 256, sc.e,
+    GemmArgs g = gemm_args(lead->lstm_out, contiguous_rows(h->ncpc * 256), h->wt.down_w, nb * 2, 256, h->ncpc * 256, sc.e,
                            contiguous_rows(256));
-    g.bias = h->W("down.b"); g.gamma = h->W("down.g"); g.beta = h->W("down.beta");
+    g.bias = h->wt.down_b; g.gamma = h->wt.down_g; g.beta = h->wt.down_beta;
     HIPCHK(h, gemm(h, g, EPI_BIAS_LN_GELU, st));
     HIPCHK(h, launch_ln_rows(sc.e, sc.en, h->layer[0].ln_self_g, h->layer[0].ln_self_b, nb * 2, st));
   }
   {  // layer-0 Q|K|V of the NEW row only: they are per-row functions of the embedding, so the other
      // rows' values are cached next to the ring (exact; saves the [rows x 768] GEMM every tick)
     GemmArgs g = gemm_args(sc.en, contiguous_rows(256), h->layer[0].wqkv, nb * 2, 768, 256, sc.qkv_new, contiguous_rows(768));
-    g.W16 = h->W("L0.wqkv16");
+    g.W16 = h->wt.l0_wqkv16;
     HIPCHK(h, gemm(h, g, EPI_STORE, st));
   }
   GatherArgs ga;
@@ -839,17 +889,18 @@ int step_group(vapx_engine* h, const Scratch& sc_own, int nb, int b0, const int*
   if (rc) return rc;
   HeadArgs ha;
   ha.x = prune ? sc.last[5] : sc.xl[4]; ha.x_last_only = prune ? 1 : 0; ha.o = sc.xl[1]; ha.e = sc.e; ha.bn = sc.bn; ha.ids = ids; ha.frames_seen = sv.frames_seen;
-  ha.waT = h->W("comb.waT"); ha.wbT = h->W("comb.wbT"); ha.cg = h->W("comb.g"); ha.cb = h->W("comb.b");
-  ha.hwT = h->W("head.wT"); ha.hb = h->W("head.b"); ha.vw = h->W("vad.w"); ha.vb = h->W("vad.b");
-  ha.aw = h->W("aux.w"); ha.ab = h->W("aux.b"); ha.out = out; ha.B = nb; ha.T = h->T; ha.mode = h->cfg.mode;
+  const Weights& w = h->wt;
+  ha.waT = w.comb_waT; ha.wbT = w.comb_wbT; ha.cg = w.comb_g; ha.cb = w.comb_b;
+  ha.hwT = w.head_wT; ha.hb = w.head_b; ha.vw = w.vad_w; ha.vb = w.vad_b;
+  ha.aw = w.aux_w; ha.ab = w.aux_b; ha.out = out; ha.B = nb; ha.T = h->T; ha.mode = h->cfg.mode;
   ha.out_stride = VAPX_OUT_STRIDE;
   { ProfScope ps(h, CLS_HEAD, st); HIPCHK(h, launch_head(ha, st)); }
   if (h->cfg.mode == VAPX_MODE_NOD) {
     rc = run_combinator_all_rows(h, sc, nb, st);
     if (rc) return rc;
     const long rows = (long)nb * h->T;
-    hipLaunchKernelGGL(pbc_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, sc.xmid, h->W("aux.w") + 4 * 256,
-                       h->W("aux.b") + 4, sc.bn, out, nb, h->T, VAPX_OUT_STRIDE);
+    hipLaunchKernelGGL(pbc_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, sc.xmid, w.aux_w + 4 * 256,
+                       w.aux_b + 4, sc.bn, out, nb, h->T, VAPX_OUT_STRIDE);
     HIPCHK(h, hipGetLastError());
   }
   return VAPX_OK;
@@ -863,10 +914,8 @@ int32_t vapx_abi_version(void) { return VAPX_ABI_VERSION; }
 
 size_t vapx_blob_floats(int32_t frame_hz) {
   if (!rate_ok(frame_hz)) return 0;
-  int hop, L, P[5], ncpc;
-  geometry(frame_hz, &hop, &L, P, &ncpc);
   size_t n = 0;
-  const vapx_layout::Entry* lay = vapx_layout::layout_for_K(ncpc, &n);
+  const vapx_layout::Entry* lay = vapx_layout::layout_for_K(geometry(frame_hz).ncpc, &n);
   if (!lay) return 0;
   return lay[n - 1].off;  // "__total__"
 }
@@ -895,30 +944,17 @@ void vapx_destroy(vapx_handle h) {
   dump_trace(h->ffn_trace, h->ffn_trace_wgs, h->ffn_trace_path);
   dump_trace(h->attn_trace, h->attn_trace_wgs, h->attn_trace_path);
 #endif
-  float* fp[] = {h->w, h->ring, h->ring_qkv, h->h_state, h->c_state, h->carry, h->audio_dev, h->out_dev, h->sc.h0, h->sc.h1, h->sc.h2, h->sc.h3,
-                 h->sc.z, h->sc.lstm_out, h->sc.e, h->sc.xl[0], h->sc.xl[1], h->sc.xl[2], h->sc.xl[3], h->sc.xl[4], h->sc.xn, h->sc.xmid, h->sc.att,
-                 h->sc.qkv, h->sc.qx, h->sc.kvx, h->sc.ffn, h->sc.gx, h->sc.last[0], h->sc.last[1], h->sc.last[2],
-                 h->sc.last[3], h->sc.last[4], h->sc.last[5], h->sc.en, h->sc.qkv_new, h->sc.lffn};
-  for (float* p : fp) dfree(p);
-  int* ip[] = {h->frames_seen, h->ids_dev, h->sc.bn, h->sc.bhead, h->sc.rot};
-  for (int* p : ip) dfree(p);
+  for (void* p : {(void*)h->w, (void*)h->ring, (void*)h->ring_qkv, (void*)h->h_state, (void*)h->c_state, (void*)h->carry, (void*)h->frames_seen}) dfree(p);
+  release_scratch(h->sc, /*encoder_only=*/false);
+  release(h->audio); release(h->ids); release(h->mix); release(h->sio_ids);
   dfree(h->rs_hist); dfree(h->rs_out); dfree(h->rs_started);
   dfree(h->gw_dev);
-  dfree(h->acc); dfree(h->mixA); dfree(h->out_c); dfree(h->mix_dev);
-  if (h->mix_pinned) (void)hipHostFree(h->mix_pinned);
-  if (h->mix_evt) (void)hipEventDestroy(h->mix_evt);
+  dfree(h->acc); dfree(h->mixA); dfree(h->out_c);
   dfree(h->sio_dev);
-  dfree(h->sio_ids_dev);
   if (h->sio_pin) (void)hipHostFree(h->sio_pin);
-  if (h->sio_ids_pinned) (void)hipHostFree(h->sio_ids_pinned);
-  if (h->sio_ids_evt) (void)hipEventDestroy(h->sio_ids_evt);
   if (h->sio_evt) (void)hipEventDestroy(h->sio_evt);
   if (h->gw_pinned) (void)hipHostFree(h->gw_pinned);
   if (h->out_pinned) (void)hipHostFree(h->out_pinned);
-  if (h->ids_pinned) (void)hipHostFree(h->ids_pinned);
-  if (h->audio_pinned) (void)hipHostFree(h->audio_pinned);
-  if (h->ids_evt) (void)hipEventDestroy(h->ids_evt);
-  if (h->audio_evt) (void)hipEventDestroy(h->audio_evt);
   if (h->gstart) (void)hipEventDestroy(h->gstart);
   for (int g = 0; g < vapx_engine::kMaxGroups; ++g) {
     if (h->gdone[g]) (void)hipEventDestroy(h->gdone[g]);
@@ -950,9 +986,7 @@ int vapx_create(const vapx_config* cfg, const float* blob, size_t n_floats, vapx
 
   vapx_engine* h = new vapx_engine();
   h->cfg = *cfg;
-  geometry(cfg->frame_hz, &h->hop, &h->L, h->P, &h->ncpc);
-  h->T = cfg->ctx_frames;
-  h->K = h->ncpc;
+  static_cast<Geometry&>(*h) = geometry(cfg->frame_hz, cfg->ctx_frames);
   h->lay = vapx_layout::layout_for_K(h->ncpc, &h->lay_n);
   const size_t need = vapx_blob_floats(cfg->frame_hz);
   if (n_floats != need) {
@@ -973,20 +1007,46 @@ int vapx_create(const vapx_config* cfg, const float* blob, size_t n_floats, vapx
   CR(hipSetDevice(cfg->device_id));
   CR(dalloc(&h->w, need, false));
   CR(hipMemcpy(h->w, blob, need * sizeof(float), hipMemcpyHostToDevice));
-  h->w_floats = need;
-  char nm[64];
+  // every weight pointer is resolved here, once; `missing` names the first required entry the layout does not have
+  std::string missing;
+  auto find = [&](const std::string& name, bool required) -> const float* {
+    for (size_t i = 0; i < h->lay_n; ++i)
+      if (name == h->lay[i].name) return h->w + h->lay[i].off;
+    if (required && missing.empty()) missing = name;
+    return nullptr;
+  };
+  auto req = [&](const std::string& name) { return find(name, true); };
+  Weights& wt = h->wt;
+  for (int i = 0; i < 5; ++i) {
+    const std::string c = "conv" + std::to_string(i), n = "cn" + std::to_string(i);
+    wt.conv[i] = {req(c + ".w"), i >= 1 ? req(c + ".w16") : nullptr, i >= 2 ? req(c + ".wf") : nullptr, req(c + ".b"), req(n + ".g"), req(n + ".b")};
+  }
+  wt.lstm_wih = req("lstm.wih"); wt.lstm_wih16 = req("lstm.wih16"); wt.lstm_whh = req("lstm.whh"); wt.lstm_b = req("lstm.b");
+  wt.down_w = req("down.w"); wt.down_wf = req("down.wf"); wt.down_b = req("down.b"); wt.down_g = req("down.g"); wt.down_beta = req("down.beta");
+  wt.l0_wqkv16 = req("L0.wqkv16"); wt.l3_last16 = req("L3.last16");
+  wt.comb_wa = req("comb.wa"); wt.comb_wb = req("comb.wb"); wt.comb_waT = req("comb.waT"); wt.comb_wbT = req("comb.wbT");
+  wt.comb_g = req("comb.g"); wt.comb_b = req("comb.b");
+  wt.head_w = req("head.w"); wt.head_wT = req("head.wT"); wt.head_b = req("head.b"); wt.vad_w = req("vad.w"); wt.vad_b = req("vad.b");
+  wt.aux_w = req("aux.w"); wt.aux_b = req("aux.b");
   for (int l = 0; l < 4; ++l) {
     Layer& Lw = h->layer[l];
-    auto get = [&](const char* suffix) { snprintf(nm, sizeof nm, "L%d.%s", l, suffix); return h->W(nm); };
+    // layer 0 has no cross-attention: its entries stay null there, as does wqkvp wherever the layout lacks it (tested where it is used)
+    auto get = [&](const char* suffix) { return find("L" + std::to_string(l) + "." + suffix, true); };
+    auto cross = [&](const char* suffix) { return find("L" + std::to_string(l) + "." + suffix, l > 0); };
     Lw.ln_self_g = get("ln_self.g"); Lw.ln_self_b = get("ln_self.b"); Lw.wqkv = get("wqkv"); Lw.wproj = get("wproj");
-    Lw.ln_src_g = get("ln_src.g"); Lw.ln_src_b = get("ln_src.b"); Lw.wq_x = get("wq_x"); Lw.wkv_x = get("wkv_x");
-    Lw.wproj_x = get("wproj_x"); Lw.ln_ffn_g = get("ln_ffn.g"); Lw.ln_ffn_b = get("ln_ffn.b"); Lw.w0 = get("w0"); Lw.w3 = get("w3");
-    Lw.w0f = get("w0f"); Lw.w3f = get("w3f"); Lw.wqkvf = get("wqkvf"); Lw.wkvxf = get("wkvxf");
-    Lw.wprojf = get("wprojf"); Lw.wqxf = get("wqxf"); Lw.wprojxf = get("wprojxf");
-    Lw.w0h = get("w0h"); Lw.w3h = get("w3h"); Lw.wqkvh = get("wqkvh"); Lw.wkvxh = get("wkvxh");
-    Lw.wprojh = get("wprojh"); Lw.wqxh = get("wqxh"); Lw.wprojxh = get("wprojxh");
-    Lw.wproj8 = get("wproj8"); Lw.wqx8 = get("wqx8"); Lw.wprojx8 = get("wprojx8");
-    Lw.wqkvp = get("wqkvp");
+    Lw.ln_src_g = cross("ln_src.g"); Lw.ln_src_b = cross("ln_src.b"); Lw.wq_x = cross("wq_x"); Lw.wkv_x = cross("wkv_x");
+    Lw.wproj_x = cross("wproj_x"); Lw.ln_ffn_g = get("ln_ffn.g"); Lw.ln_ffn_b = get("ln_ffn.b"); Lw.w0 = get("w0"); Lw.w3 = get("w3");
+    Lw.w0f = get("w0f"); Lw.w3f = get("w3f"); Lw.wqkvf = get("wqkvf"); Lw.wkvxf = cross("wkvxf");
+    Lw.wprojf = get("wprojf"); Lw.wqxf = cross("wqxf"); Lw.wprojxf = cross("wprojxf");
+    Lw.w0h = get("w0h"); Lw.w3h = get("w3h"); Lw.wqkvh = get("wqkvh"); Lw.wkvxh = cross("wkvxh");
+    Lw.wprojh = get("wprojh"); Lw.wqxh = cross("wqxh"); Lw.wprojxh = cross("wprojxh");
+    Lw.wproj8 = get("wproj8"); Lw.wqx8 = cross("wqx8"); Lw.wprojx8 = cross("wprojx8");
+    Lw.wqkvp = find("L" + std::to_string(l) + ".wqkvp", false);
+  }
+  if (!missing.empty()) {
+    int rc = fail(nullptr, VAPX_E_INVAL, "the weights layout for %d Hz has no entry \"%s\"", cfg->frame_hz, missing.c_str());
+    vapx_destroy(h);
+    return rc;
   }
   if (cfg->flags & VAPX_FLAG_SPLIT_F16) {
     // Static guarantees of the split-precision path, from the weights alone (host copy of the blob):
@@ -1032,57 +1092,30 @@ int vapx_create(const vapx_config* cfg, const float* blob, size_t n_floats, vapx
     }
   }
   const size_t S = cfg->max_streams, B = cfg->max_batch, T = h->T;
-  const int* P = h->P;
   CR(dalloc(&h->ring, S * 2 * T * 256));
   CR(dalloc(&h->ring_qkv, S * 2 * T * 768));   // layer-0 Q|K|V cache, one entry per ring row
   CR(dalloc(&h->h_state, S * 2 * 256));
   CR(dalloc(&h->c_state, S * 2 * 256));
   CR(dalloc(&h->carry, S * 2 * VAPX_PAD));
   CR(dalloc(&h->frames_seen, S));
-  CR(dalloc(&h->audio_dev, B * 2 * h->L));
-  CR(dalloc(&h->out_dev, B * VAPX_OUT_STRIDE));
-  CR(dalloc(&h->ids_dev, B));
-  CR(dalloc(&h->sc.bn, B));
-  CR(dalloc(&h->sc.bhead, B));
-  CR(dalloc(&h->sc.rot, B));
-  CR(dalloc(&h->sc.h0, B * 2 * (P[0] + 4) * 256));  // guard rows stay zero forever
-  CR(dalloc(&h->sc.h1, B * 2 * (P[1] + 2) * 256));
-  CR(dalloc(&h->sc.h2, B * 2 * (P[2] + 2) * 256));
-  CR(dalloc(&h->sc.h3, B * 2 * (P[3] + 2) * 256));
-  CR(dalloc(&h->sc.z, B * 2 * h->ncpc * 256));
-  CR(dalloc(&h->sc.lstm_out, B * 2 * h->ncpc * 256));
-  CR(dalloc(&h->sc.gx, B * 2 * h->ncpc * 1024));
-  CR(dalloc(&h->sc.e, B * 2 * 256));
-  const size_t rows = B * 2 * T;
-  for (int i = 0; i < 5; ++i) CR(dalloc(&h->sc.xl[i], rows * 256));
-  CR(dalloc(&h->sc.xn, rows * 256));
-  CR(dalloc(&h->sc.xmid, rows * 256));
-  CR(dalloc(&h->sc.att, rows * 256));
-  CR(dalloc(&h->sc.qkv, rows * 768));
-  CR(dalloc(&h->sc.qx, rows * 256));
-  CR(dalloc(&h->sc.kvx, rows * 512));
-  h->sc.ffn = nullptr;  // FFN hidden activations never leave the fused FFN block
-  for (int i = 0; i < 6; ++i) CR(dalloc(&h->sc.last[i], B * 2 * 256));
-  CR(dalloc(&h->sc.en, B * 2 * 256));
-  CR(dalloc(&h->sc.qkv_new, B * 2 * 768));
-  CR(dalloc(&h->sc.lffn, B * 2 * 768));
+  CR(dalloc(&h->audio.dev, B * 2 * h->L));
+  CR(dalloc(&h->ids.dev, B));
+  for (const ScratchRow& r : kScratchTable) {   // zero-filled: the guard rows of h0 .. h3 stay zero forever
+    const ScratchSlot p = r.slot(h->sc);
+    if (p.f) CR(dalloc(p.f, B * r.per_slot(*h)));
+    else CR(dalloc(p.i, B * r.per_slot(*h)));
+  }
   CR(hipHostMalloc((void**)&h->out_pinned, B * VAPX_OUT_STRIDE * sizeof(float), hipHostMallocDefault));
-  CR(hipHostMalloc((void**)&h->ids_pinned, B * sizeof(int), hipHostMallocDefault));
-  CR(hipHostMalloc((void**)&h->audio_pinned, B * 2 * h->L * sizeof(float), hipHostMallocDefault));
-  CR(dalloc(&h->sio_ids_dev, S));
-  CR(hipHostMalloc((void**)&h->sio_ids_pinned, S * sizeof(int), hipHostMallocDefault));
+  CR(h->ids.create_pinned(B));
+  CR(h->audio.create_pinned(B * 2 * h->L));
+  CR(dalloc(&h->sio_ids.dev, S));
+  CR(h->sio_ids.create_pinned(S));
   h->id_stamp.assign(S, 0u);
   h->force_xl = getenv("VAPX_FORCE_ATTENTION_XL") != nullptr;
   if (getenv("VAPX_POISON_SCRATCH")) {
     CR(hipMemset(h->ring, 0xFF, S * 2 * T * 256 * sizeof(float)));          // rows beyond frames_seen are never read: prove it
     CR(hipMemset(h->ring_qkv, 0xFF, S * 2 * T * 768 * sizeof(float)));
-    auto add = [&](float* q, size_t n) { h->poison.push_back({q, n * sizeof(float)}); };
-    add(h->sc.z, B * 2 * h->ncpc * 256); add(h->sc.lstm_out, B * 2 * h->ncpc * 256); add(h->sc.gx, B * 2 * h->ncpc * 1024); add(h->sc.e, B * 2 * 256);
-    for (int i = 0; i < 5; ++i) add(h->sc.xl[i], rows * 256);
-    add(h->sc.xn, rows * 256); add(h->sc.xmid, rows * 256); add(h->sc.att, rows * 256); add(h->sc.qkv, rows * 768); add(h->sc.qx, rows * 256);
-    add(h->sc.kvx, rows * 512);
-    for (int i = 0; i < 6; ++i) add(h->sc.last[i], B * 2 * 256);
-    add(h->sc.en, B * 2 * 256); add(h->sc.qkv_new, B * 2 * 768); add(h->sc.lffn, B * 2 * 768); add(h->out_dev, B * VAPX_OUT_STRIDE);
+    h->poison = true;
   }
 #ifdef VAPX_TRACE
   if (const char* ev = getenv("VAPX_FFN_TRACE")) {
@@ -1102,12 +1135,6 @@ int vapx_create(const vapx_config* cfg, const float* blob, size_t n_floats, vapx
     CR(hipEventCreateWithFlags(&h->gdone[g], hipEventDisableTiming));
   }
   CR(hipEventCreateWithFlags(&h->gstart, hipEventDisableTiming));
-  CR(hipEventCreateWithFlags(&h->ids_evt, hipEventDisableTiming));
-  CR(hipEventRecord(h->ids_evt, nullptr));
-  CR(hipEventCreateWithFlags(&h->audio_evt, hipEventDisableTiming));
-  CR(hipEventRecord(h->audio_evt, nullptr));
-  CR(hipEventCreateWithFlags(&h->sio_ids_evt, hipEventDisableTiming));
-  CR(hipEventRecord(h->sio_ids_evt, nullptr));
   CR(hipEventCreateWithFlags(&h->sio_evt, hipEventDisableTiming));
   CR(hipEventRecord(h->sio_evt, nullptr));
   CR(hipDeviceSynchronize());
@@ -1165,10 +1192,13 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     rc = join_deferred(h, st);
     if (rc) return rc;
   }
-  if (!h->poison.empty()) {
+  if (h->poison) {
     rc = join_deferred(h, st);
     if (rc) return rc;
-    for (auto& pb : h->poison) HIPCHK(h, hipMemsetAsync(pb.first, 0xFF, pb.second, st));
+    for (const ScratchRow& r : kScratchTable)
+      if (r.poison && !(r.encoder && lead))   // a follower has released its encoder scratch
+        HIPCHK(h, hipMemsetAsync(scratch_ptr(r, h->sc), 0xFF, (size_t)h->cfg.max_batch * r.per_slot(*h) * sizeof(float), st));
+    if (h->rs_out) HIPCHK(h, hipMemsetAsync(h->rs_out, 0xFF, (size_t)h->cfg.max_batch * 2 * h->hop * sizeof(float), st));
   }
   if (!lead) { rc = flush_resets(h, st); if (rc) return rc; }
   const int* ids = nullptr;
@@ -1188,8 +1218,7 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     if (lead->deferred_pending)   // the collect reads every overlap group's LSTM rows (the leader's own flag stays: only `st` waits)
       for (int g = 0; g < lead->last_G; ++g) HIPCHK(h, hipStreamWaitEvent(st, lead->gdone[g], 0));
     const int32_t* lid = lead->last_ids_host.data();
-    HIPCHK(h, hipEventSynchronize(h->mix_evt));
-    int *e_sid = h->mix_pinned, *e_slot = h->mix_pinned + n, *e_pos = h->mix_pinned + 2 * n;
+    int *e_sid = h->mix_host.data(), *e_slot = e_sid + n, *e_pos = e_sid + 2 * n;
     int kd = 0, kn = n_run;
     for (int i = 0; i < n; ++i) {
       const int sid = lid[i], ph = h->phase[sid];
@@ -1198,28 +1227,22 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
       e_sid[k] = sid; e_slot[k] = i; e_pos[k] = ph;
       h->phase[sid] = due ? 0 : ph + 1;
     }
-    HIPCHK(h, hipMemcpyAsync(h->mix_dev, h->mix_pinned, (size_t)3 * n * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipEventRecord(h->mix_evt, st));
+    HIPCHK(h, h->mix.upload(e_sid, (size_t)3 * n, st));
     TrunkCollectArgs ca;
-    ca.lstm_out = lead->sc.lstm_out; ca.acc = h->acc; ca.A = h->mixA; ca.sid = h->mix_dev; ca.slot = h->mix_dev + n; ca.pos = h->mix_dev + 2 * n;
+    ca.lstm_out = lead->sc.lstm_out; ca.acc = h->acc; ca.A = h->mixA; ca.sid = h->mix.dev; ca.slot = h->mix.dev + n; ca.pos = h->mix.dev + 2 * n;
     ca.frames_seen = h->frames_seen; ca.bn = h->sc.bn; ca.bhead = h->sc.bhead;
     ca.n = n; ca.n_due = n_run; ca.ncpc_l = lead->ncpc; ca.R = h->R; ca.T = h->T;
     { ProfScope ps(h, CLS_TRUNK_COLLECT, st); HIPCHK(h, launch_trunk_collect(ca, st)); }
-    ids = h->mix_dev;   // the due streams' ids, in compact order
+    ids = h->mix.dev;   // the due streams' ids, in compact order
   }
   const float* ad = audio;
   if (!lead && !(flags & VAPX_AUDIO_DEVICE)) {
     const size_t bytes = (size_t)n * 2 * spc * sizeof(float);
-    const float* src = audio;
-    if (!is_pinned_host(audio)) {   // pageable memory: stage through the engine's pinned buffer (an async copy from
-                                    // pageable memory is a hidden synchronous staging copy inside the runtime)
-      HIPCHK(h, hipEventSynchronize(h->audio_evt));
-      memcpy(h->audio_pinned, audio, bytes);
-      src = h->audio_pinned;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->audio_dev, src, bytes, hipMemcpyHostToDevice, st));
-    if (src == h->audio_pinned) HIPCHK(h, hipEventRecord(h->audio_evt, st));
-    ad = h->audio_dev;
+    // pageable memory: stage through the engine's pinned buffer (an async copy from pageable memory is a hidden synchronous staging
+    // copy inside the runtime); vapx_host_alloc memory: copy straight from the caller
+    if (is_pinned_host(audio)) HIPCHK(h, hipMemcpyAsync(h->audio.dev, audio, bytes, hipMemcpyHostToDevice, st));
+    else HIPCHK(h, h->audio.upload(audio, (size_t)n * 2 * spc, st));
+    ad = h->audio.dev;
   }
   if (h->in_hz) {   // input rate -> 16 kHz, one launch for the whole batch before the overlap groups fork; conv0 and its carry see plain hops
     ResampleArgs ra;
@@ -1230,7 +1253,7 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     ad = h->rs_out;
     spc = h->hop;
   }
-  float* od = (flags & VAPX_OUT_DEVICE) ? out : h->out_dev;
+  float* od = (flags & VAPX_OUT_DEVICE) ? out : h->sc.out_dev;
   float* orows = slower ? h->out_c : od;   // a slower follower's kernels write compact rows; one scatter places them in `od`
   if (G > 1) {
     HIPCHK(h, hipEventRecord(h->gstart, st));
@@ -1241,11 +1264,11 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     int b0 = (int)((long)n_run * g / G), b1 = (int)((long)n_run * (g + 1) / G);
     const int nb = b1 - b0;
     hipStream_t gs = G > 1 ? h->gstream[g] : st;
-    const Scratch sc = h->sc.slice(b0, h->P, h->ncpc, h->T);
+    const Scratch sc = h->sc.slice(b0, *h);
     const int* gids = ids ? ids + b0 : nullptr;
     Scratch lsc;
     if (slower) lsc.lstm_out = h->mixA + (size_t)b0 * 2 * h->ncpc * 256;   // the collected operand: this engine's own n_cpc rows per frame
-    else if (lead) lsc = lead->sc.slice(b0, lead->P, lead->ncpc, lead->T);
+    else if (lead) lsc = lead->sc.slice(b0, *lead);
     rc = step_group(h, sc, nb, b0, gids, lead ? nullptr : ad + (size_t)b0 * 2 * spc, spc, orows + (size_t)b0 * VAPX_OUT_STRIDE, gs,
                     lead ? &lsc : nullptr);
     if (rc) return rc;
@@ -1254,7 +1277,7 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
   if (G > 1 && !defer_join)
     for (int g = 0; g < G; ++g) HIPCHK(h, hipStreamWaitEvent(st, h->gdone[g], 0));
   if (slower) {
-    OutScatterArgs oa{h->out_c, od, h->mix_dev + n, n, n_run, VAPX_OUT_STRIDE};
+    OutScatterArgs oa{h->out_c, od, h->mix.dev + n, n, n_run, VAPX_OUT_STRIDE};
     ProfScope ps(h, CLS_TRUNK_COLLECT, st);
     HIPCHK(h, launch_out_scatter(oa, st));
   }
@@ -1265,14 +1288,8 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
   if (lead) h->followed_tick = lead->tick; else ++h->tick;
   if (!(flags & VAPX_OUT_DEVICE)) {
     const size_t bytes = (size_t)n * VAPX_OUT_STRIDE * sizeof(float);
-    if (is_pinned_host(out)) {   // vapx_host_alloc memory: the D2H lands in the caller's buffer directly
-      HIPCHK(h, hipMemcpyAsync(out, h->out_dev, bytes, hipMemcpyDeviceToHost, st));
-      HIPCHK(h, hipStreamSynchronize(st));
-    } else {
-      HIPCHK(h, hipMemcpyAsync(h->out_pinned, h->out_dev, bytes, hipMemcpyDeviceToHost, st));
-      HIPCHK(h, hipStreamSynchronize(st));
-      memcpy(out, h->out_pinned, bytes);
-    }
+    HIPCHK(h, download(out, h->sc.out_dev, bytes, h->out_pinned, st));   // vapx_host_alloc memory: lands in the caller's buffer directly
+    HIPCHK(h, hipStreamSynchronize(st));
     // Fail loudly rather than hand NaNs to a dialogue system — but per stream: the out block is complete, the healthy rows
     // are valid, the offending batch slots carry VAPX_OUT_STATUS = 1 and are listed by vapx_bad_slots().
     h->bad_slots.clear();
@@ -1327,11 +1344,11 @@ int vapx_step_group(vapx_handle h, int32_t n, const int32_t* stream_ids, const f
   }
   // every model device-resident, on the one stream: exactly the vapx_step(.., VAPX_OUT_DEVICE, ..) path (VAPX_DEFER_JOIN is dropped:
   // the pack kernel below consumes every overlap group's rows)
-  int rc = vapx_step(h, n, stream_ids, audio, spc, h->out_dev, (flags & (VAPX_AUDIO_DEVICE | VAPX_IDS_DEVICE)) | VAPX_OUT_DEVICE, hip_stream);
+  int rc = vapx_step(h, n, stream_ids, audio, spc, h->sc.out_dev, (flags & (VAPX_AUDIO_DEVICE | VAPX_IDS_DEVICE)) | VAPX_OUT_DEVICE, hip_stream);
   if (rc) return rc;
   for (size_t i = 0; i < h->followers.size(); ++i) {
     vapx_engine* f = h->followers[i];
-    rc = vapx_step(f, n, nullptr, nullptr, 0, f->out_dev, VAPX_OUT_DEVICE, hip_stream);
+    rc = vapx_step(f, n, nullptr, nullptr, 0, f->sc.out_dev, VAPX_OUT_DEVICE, hip_stream);
     if (rc) return fail(h, rc, "follower %zu: %s", i, f->err.c_str());
   }
   float* wd = to_host ? h->gw_dev : wire_out;
@@ -1350,7 +1367,7 @@ int vapx_step_group(vapx_handle h, int32_t n, const int32_t* stream_ids, const f
     memset(&a, 0, sizeof a);
     a.dst = wd; a.n = n; a.src_stride = VAPX_OUT_STRIDE; a.n_models = std::min(4, M - m0);
     for (int k = 0; k < a.n_models; ++k) {
-      a.src[k] = (m0 + k) ? h->followers[m0 + k - 1]->out_dev : h->out_dev;
+      a.src[k] = (m0 + k) ? h->followers[m0 + k - 1]->sc.out_dev : h->sc.out_dev;
       a.dst_off[k] = (long)off[m0 + k];
       a.wf4[k] = wf[m0 + k] / 4;
     }
@@ -1359,10 +1376,8 @@ int vapx_step_group(vapx_handle h, int32_t n, const int32_t* stream_ids, const f
   h->group_bad.clear();
   if (!to_host) return VAPX_OK;
   const size_t bytes = (size_t)n * per * sizeof(float);
-  const bool direct = is_pinned_host(wire_out);   // vapx_host_alloc memory: the one D2H copy of the tick lands in the caller's block
-  HIPCHK(h, hipMemcpyAsync(direct ? wire_out : h->gw_pinned, h->gw_dev, bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, download(wire_out, h->gw_dev, bytes, h->gw_pinned, st));   // vapx_host_alloc memory: the one D2H copy of the tick lands in the caller's block
   HIPCHK(h, hipStreamSynchronize(st));
-  if (!direct) memcpy(wire_out, h->gw_pinned, bytes);
   // per stream and per model, as vapx_step: the block is complete, the offending rows carry VAPX_OUT_STATUS = 1
   for (int m = 0; m < M; ++m) {
     vapx_engine* e = m ? h->followers[m - 1] : h;
@@ -1425,8 +1440,8 @@ int vapx_attach_trunk(vapx_handle f, vapx_handle lead) {
   HIPCHK(f, hipSetDevice(f->cfg.device_id));
   HIPCHK(f, hipDeviceSynchronize());
   {  // the CPC CNN + LSTM weights must be the same tensors (they come from the common cpc_model file, vap_main.py:199-201)
-    const float* a0 = f->W("conv0.w"); const float* a1 = f->W("down.w");
-    const float* b0 = lead->W("conv0.w");
+    const float* a0 = f->wt.conv[0].w; const float* a1 = f->wt.down_w;
+    const float* b0 = lead->wt.conv[0].w;
     const size_t nfl = (size_t)(a1 - a0);
     std::vector<float> ha(nfl), hb(nfl);
     HIPCHK(f, hipMemcpy(ha.data(), a0, nfl * sizeof(float), hipMemcpyDeviceToHost));
@@ -1439,27 +1454,18 @@ int vapx_attach_trunk(vapx_handle f, vapx_handle lead) {
     hipError_t e = dalloc(&f->acc, S * 2 * (size_t)(R - 1) * lead->ncpc * 256);
     if (e == hipSuccess) e = dalloc(&f->mixA, B * 2 * (size_t)f->ncpc * 256);
     if (e == hipSuccess) e = dalloc(&f->out_c, B * VAPX_OUT_STRIDE);
-    if (e == hipSuccess) e = dalloc(&f->mix_dev, 3 * B);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&f->mix_pinned, 3 * B * sizeof(int), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->mix_evt, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(f->mix_evt, nullptr);
+    if (e == hipSuccess) e = dalloc(&f->mix.dev, 3 * B);
+    if (e == hipSuccess) e = f->mix.create_pinned(3 * B);
     if (e != hipSuccess) {   // nothing of the engine is released yet: it stays a stand-alone engine
       (void)hipGetLastError();
       return fail(f, e == hipErrorOutOfMemory ? VAPX_E_NOMEM : VAPX_E_HIP, "state of a 1/%d-rate follower: %s", R, hipGetErrorString(e));
     }
     f->phase.assign(S, 0);
+    f->mix_host.assign(3 * B, 0);
   }
   // a follower never runs the encoder: release its encoder scratch and LSTM / carry state
-  float** drop[] = {&f->sc.h0, &f->sc.h1, &f->sc.h2, &f->sc.h3, &f->sc.z, &f->sc.gx, &f->sc.lstm_out, &f->audio_dev,
-                    &f->h_state, &f->c_state, &f->carry};
-  for (float** p : drop) {
-    if (*p) {
-      f->poison.erase(std::remove_if(f->poison.begin(), f->poison.end(), [&](const std::pair<void*, size_t>& pb) { return pb.first == (void*)*p; }),
-                      f->poison.end());
-      dfree(*p);
-    }
-    *p = nullptr;
-  }
+  release_scratch(f->sc, /*encoder_only=*/true);
+  for (float** p : {&f->audio.dev, &f->h_state, &f->c_state, &f->carry}) { dfree(*p); *p = nullptr; }
   f->R = R;
   f->own_window = R == 1 && f->T != lead->T;
   f->trunk = lead;
@@ -1612,11 +1618,8 @@ int sio_check(vapx_engine* h, const char* what, int n, const int32_t* ids, const
 // device copy of host ids (up to max_streams of them: the step's id buffers hold max_batch)
 int sio_ids(vapx_engine* h, int n, const int32_t* ids, int flags, hipStream_t st, const int** out) {
   if (!ids || (flags & VAPX_IDS_DEVICE)) { *out = ids; return VAPX_OK; }
-  HIPCHK(h, hipEventSynchronize(h->sio_ids_evt));   // the previous copy out of the pinned buffer is done
-  memcpy(h->sio_ids_pinned, ids, (size_t)n * sizeof(int));
-  HIPCHK(h, hipMemcpyAsync(h->sio_ids_dev, h->sio_ids_pinned, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipEventRecord(h->sio_ids_evt, st));
-  *out = h->sio_ids_dev;
+  HIPCHK(h, h->sio_ids.upload(ids, n, st));
+  *out = h->sio_ids.dev;
   return VAPX_OK;
 }
 
@@ -1691,14 +1694,7 @@ int vapx_export_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, flo
     HIPCHK(h, launch_state_export(a, st));
     const size_t bytes = (size_t)nb * rec * sizeof(float);
     float* to = dst + (size_t)k0 * rec;
-    if (direct) {
-      HIPCHK(h, hipMemcpyAsync(to, h->sio_dev, bytes, hipMemcpyDeviceToHost, st));
-    } else {   // pageable: block by block through the pinned buffer
-      HIPCHK(h, hipMemcpyAsync(h->sio_pin, h->sio_dev, bytes, hipMemcpyDeviceToHost, st));
-      HIPCHK(h, hipEventRecord(h->sio_evt, st));
-      HIPCHK(h, hipEventSynchronize(h->sio_evt));
-      memcpy(to, h->sio_pin, bytes);
-    }
+    HIPCHK(h, download(to, h->sio_dev, bytes, h->sio_pin, st));   // pageable: block by block through the pinned buffer
   }
   HIPCHK(h, hipStreamSynchronize(st));
   return VAPX_OK;
@@ -1859,54 +1855,32 @@ int vapx_transformer_maps(vapx_handle h, int32_t n, int32_t rows, const float* x
 int64_t vapx_peek(vapx_handle h, const char* name, float* dst, size_t max_floats) {
   if (!h || !name || !dst) return VAPX_E_INVAL;
   { int rc = quiesce(h); if (rc) return rc; }
-  const size_t B = h->last_B, T = h->T;
-  const int* P = h->P;
-  const float* src = nullptr;
-  size_t n = 0;
   if (!strcmp(name, "guard_violations")) {   // debug: see VAPX_GUARD_ZONES
     dst[0] = guard_enabled() ? (float)guard_violations() : -1.f;
     return 1;
   }
-  if (!strcmp(name, "h0")) { src = h->sc.h0; n = B * 2 * (P[0] + 4) * 256; }
-  else if (!strcmp(name, "h1")) { src = h->sc.h1; n = B * 2 * (P[1] + 2) * 256; }
-  else if (!strcmp(name, "h2") || !strcmp(name, "h3")) {
+  // what exists after the latest step depends on the path it took: refuse what was not written
+  const bool full_last = (h->cfg.flags & VAPX_FLAG_FULL_LAST_LAYER) || h->cfg.mode == VAPX_MODE_NOD;
+  if ((!strcmp(name, "h2") || !strcmp(name, "h3")) && h->last_tail_fused)
     // what run_encoder ran for the latest step, not a guess from last_B: the 512-stream limit holds per overlap group, so a batch of
     // 1000 in two groups runs the fused tail twice and leaves h2 / h3 stale
-    if (h->last_tail_fused)
-      return fail(h, VAPX_E_INVAL, "\"%s\" stays in LDS in the fused conv tail; create the engine with VAPX_FLAG_UNFUSED_CONV to peek it", name);
-    if (name[1] == '2') { src = h->sc.h2; n = B * 2 * (P[2] + 2) * 256; }
-    else { src = h->sc.h3; n = B * 2 * (P[3] + 2) * 256; }
-  }
-  else if (!strcmp(name, "z")) { src = h->sc.z; n = B * 2 * h->ncpc * 256; }
-  else if (!strcmp(name, "lstm_out")) { src = h->sc.lstm_out; n = B * 2 * h->ncpc * 256; }
-  else if (!strcmp(name, "e")) { src = h->sc.e; n = B * 2 * 256; }
-  else if (!strcmp(name, "x0")) {
-    if (!(h->cfg.flags & VAPX_FLAG_MATERIALIZE_X0) && (h->T <= 64 || !(h->cfg.flags & VAPX_FLAG_UNFUSED_PROJ)))
-      return fail(h, VAPX_E_INVAL, "\"x0\" is read straight from the ring; create the engine with VAPX_FLAG_MATERIALIZE_X0 to peek it");
-    src = h->sc.xl[0]; n = B * 2 * T * 256;
-  }
-  else if (!strcmp(name, "o")) { src = h->sc.xl[1]; n = B * 2 * T * 256; }
-  else if (!strcmp(name, "stereo0")) { src = h->sc.xl[2]; n = B * 2 * T * 256; }
-  else if (!strcmp(name, "stereo1")) { src = h->sc.xl[3]; n = B * 2 * T * 256; }
-  else if (!strcmp(name, "stereo2")) {
-    if (!(h->cfg.flags & VAPX_FLAG_FULL_LAST_LAYER) && h->cfg.mode != VAPX_MODE_NOD)
-      return fail(h, VAPX_E_INVAL, "\"stereo2\" is only materialised with VAPX_FLAG_FULL_LAST_LAYER (default: last layer runs on the newest row only)");
-    src = h->sc.xl[4]; n = B * 2 * T * 256;
-  }
-  else if (!strcmp(name, "last")) {   // the last layer's newest row of every (stream, channel): fused block and the ten-launch path alike
-    if ((h->cfg.flags & VAPX_FLAG_FULL_LAST_LAYER) || h->cfg.mode == VAPX_MODE_NOD)
-      return fail(h, VAPX_E_INVAL, "\"last\" exists only where the last layer runs on the newest row alone; this engine (VAPX_FLAG_FULL_LAST_LAYER "
-                  "or nod mode) computes every row: peek \"stereo2\" and take row n - 1");
-    src = h->sc.last[5]; n = B * 2 * 256;   // overlap groups slice it by batch row, so one copy spans them
-  }
-  else if (!strcmp(name, "comb")) {   // the all-rows combinator of the nod variant, [n][T][256]
-    if (h->cfg.mode != VAPX_MODE_NOD)
-      return fail(h, VAPX_E_INVAL, "\"comb\" is only materialised in nod mode (vap / bc: the combinator of the newest row stays inside head_kernel)");
-    if (h->last_G > 1)   // a group's block starts at its first row of the [B*2*T]-row scratch, twice the stride of the [nb*T] rows it holds
-      return fail(h, VAPX_E_INVAL, "\"comb\" is not contiguous when the latest step ran in %d overlap groups; step with groups = 1 to peek it", h->last_G);
-    src = h->sc.xmid; n = B * T * 256;
-  }
-  else return fail(h, VAPX_E_INVAL, "unknown buffer '%s'", name);
+    return fail(h, VAPX_E_INVAL, "\"%s\" stays in LDS in the fused conv tail; create the engine with VAPX_FLAG_UNFUSED_CONV to peek it", name);
+  if (!strcmp(name, "x0") && !(h->cfg.flags & VAPX_FLAG_MATERIALIZE_X0) && (h->T <= 64 || !(h->cfg.flags & VAPX_FLAG_UNFUSED_PROJ)))
+    return fail(h, VAPX_E_INVAL, "\"x0\" is read straight from the ring; create the engine with VAPX_FLAG_MATERIALIZE_X0 to peek it");
+  if (!strcmp(name, "stereo2") && !full_last)
+    return fail(h, VAPX_E_INVAL, "\"stereo2\" is only materialised with VAPX_FLAG_FULL_LAST_LAYER (default: last layer runs on the newest row only)");
+  if (!strcmp(name, "last") && full_last)   // the last layer's newest row of every (stream, channel): fused block and the ten-launch path alike
+    return fail(h, VAPX_E_INVAL, "\"last\" exists only where the last layer runs on the newest row alone; this engine (VAPX_FLAG_FULL_LAST_LAYER "
+                "or nod mode) computes every row: peek \"stereo2\" and take row n - 1");
+  const bool comb = !strcmp(name, "comb");   // the all-rows combinator of the nod variant, [n][T][256] of xmid
+  if (comb && h->cfg.mode != VAPX_MODE_NOD)
+    return fail(h, VAPX_E_INVAL, "\"comb\" is only materialised in nod mode (vap / bc: the combinator of the newest row stays inside head_kernel)");
+  if (comb && h->last_G > 1)   // a group's block starts at its first row of the [B*2*T]-row scratch, twice the stride of the [nb*T] rows it holds
+    return fail(h, VAPX_E_INVAL, "\"comb\" is not contiguous when the latest step ran in %d overlap groups; step with groups = 1 to peek it", h->last_G);
+  const ScratchRow* row = scratch_row_by_peek(name);
+  if (!row) return fail(h, VAPX_E_INVAL, "unknown buffer '%s'", name);
+  const float* src = (const float*)scratch_ptr(*row, h->sc);   // overlap groups slice every buffer by batch row, so one copy spans them
+  size_t n = (size_t)h->last_B * (comb ? (size_t)h->T * 256 : row->per_slot(*h));
   if (!src)   // vapx_attach_trunk freed the follower's encoder scratch
     return fail(h, VAPX_E_INVAL, "\"%s\" is released: this engine is a trunk follower, peek its leader", name);
   if (n > max_floats) n = max_floats;
@@ -1941,8 +1915,8 @@ int vapx_vap_head(vapx_handle h, int64_t rows, const float* x, float* logits, vo
   if (h->cfg.mode != VAPX_MODE_VAP) return fail(h, VAPX_E_INVAL, "this weight set has no vap_head (bc / nod variant)");
   (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  GemmArgs g = gemm_args(x, contiguous_rows(256), h->W("head.w"), (int)rows, 256, 256, logits, contiguous_rows(256));
-  g.bias = h->W("head.b");
+  GemmArgs g = gemm_args(x, contiguous_rows(256), h->wt.head_w, (int)rows, 256, 256, logits, contiguous_rows(256));
+  g.bias = h->wt.head_b;
   HIPCHK(h, launch_gemm_f32(g, EPI_STORE, 0, (hipStream_t)hip_stream));
   return VAPX_OK;
 }
@@ -1951,7 +1925,7 @@ int vapx_va_classifier(vapx_handle h, int64_t rows, const float* x, float* y, vo
   if (!h || !x || !y || rows < 1) return VAPX_E_INVAL;
   (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, x, h->W("vad.w"), h->W("vad.b"), y, (long)rows);
+  hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, x, h->wt.vad_w, h->wt.vad_b, y, (long)rows);
   HIPCHK(h, hipGetLastError());
   return VAPX_OK;
 }
@@ -1966,8 +1940,8 @@ int vapx_aux_head(vapx_handle h, int32_t which, int64_t rows, const float* x, fl
   else return fail(h, VAPX_E_INVAL, "this weight set has no such head (bc_head: bc / nod variants, nod_head: nod variant)");
   (void)hipGetLastError();
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  hipLaunchKernelGGL(rowheads_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, x, h->W("aux.w") + row0 * 256,
-                     h->W("aux.b") + row0, y, (long)rows, nout);
+  hipLaunchKernelGGL(rowheads_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, x, h->wt.aux_w + row0 * 256,
+                     h->wt.aux_b + row0, y, (long)rows, nout);
   HIPCHK(h, hipGetLastError());
   return VAPX_OK;
 }
@@ -2001,12 +1975,11 @@ int vapx_set_input_rate(vapx_handle h, int32_t input_hz) {
     return fail(h, e == hipErrorOutOfMemory ? VAPX_E_NOMEM : VAPX_E_HIP, "resampler state for %d Hz: %s", input_hz, hipGetErrorString(e));
   }
   if (adev) {
-    dfree(h->audio_dev); h->audio_dev = adev;
-    (void)hipHostFree(h->audio_pinned); h->audio_pinned = apin;
+    dfree(h->audio.dev); h->audio.dev = adev;
+    (void)hipHostFree(h->audio.pin); h->audio.pin = apin;
   }
   h->rs_hist = hist; h->rs_started = started; h->rs_out = rout;
   h->rs = g; h->hop_in = hop_in; h->rs_rec = rec; h->in_hz = input_hz;
-  if (!h->poison.empty()) h->poison.push_back({rout, B * 2 * (size_t)h->hop * sizeof(float)});
   return VAPX_OK;
 }
 

@@ -1,0 +1,121 @@
+// The engine's geometry and its batch-linear scratch buffers, described once.  Plain C++17, no HIP: tests/native/engine_buffers_check.cpp
+// compiles this header alone and holds the table against the sizes written out by hand.
+//
+// Every buffer of Scratch is linear in the batch index: a sub-batch that starts at stream slot b0 is the same struct with every pointer
+// advanced by b0 x (elements per slot).  kScratchTable has one row per buffer; vapx_create (allocation), Scratch::slice (offsets), the
+// VAPX_POISON_SCRATCH refill, vapx_peek (name -> pointer, size), vapx_attach_trunk (what a follower releases) and vapx_destroy all walk it,
+// so a buffer is added, resized or renamed in exactly one place.
+#pragma once
+#include <cstddef>
+#include <cstring>
+
+#include "../../include/vapx.h"
+
+constexpr int kCarrySamples = 320;   // VAPX_PAD of common.h (engine.hip asserts it): samples of the previous frame in front of a hop
+
+struct Geometry {
+  int hop, L, P[5], ncpc, T;   // samples per frame, frame + carry, positions after conv0..4, CPC steps per frame, window rows
+};
+
+// the CPC encoder's strides (5, 4, 2, 2, 2) on one frame of `hz` frames per second; T is the caller's (ctx_frames)
+inline Geometry geometry(int hz, int T = 0) {
+  Geometry g;
+  g.hop = 16000 / hz;
+  g.L = g.hop + kCarrySamples;
+  g.P[0] = g.L / 5;
+  g.P[1] = g.P[0] / 4;
+  g.P[2] = g.P[1] / 2;
+  g.P[3] = g.P[2] / 2;
+  g.P[4] = g.P[3] / 2;
+  g.ncpc = g.P[4] - 2;
+  g.T = T;
+  return g;
+}
+
+struct Scratch {
+  float* out_dev = nullptr;   // [B][VAPX_OUT_STRIDE] the step's output rows before they leave (or the caller's device block instead)
+  int *bn = nullptr, *bhead = nullptr, *rot = nullptr;
+  float *h0 = nullptr, *h1 = nullptr, *h2 = nullptr, *h3 = nullptr, *z = nullptr, *gx = nullptr, *lstm_out = nullptr, *e = nullptr;
+  float* xl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // layer inputs/outputs: x0, o, stereo0..2
+  float *xn = nullptr, *xmid = nullptr, *att = nullptr, *qkv = nullptr, *qx = nullptr, *kvx = nullptr;
+  float* last[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [B*2][256] each: x, xn, q, att, xmid, out (last-row path)
+  float *en = nullptr, *qkv_new = nullptr;   // [B*2][256], [B*2][768]: LN0(e) and layer-0 Q|K|V of the new row
+  float* lffn = nullptr;                     // [B*2][768] FFN hidden of the last-row path
+  inline Scratch slice(size_t b0, const Geometry& g) const;
+};
+
+struct ScratchSlot { float** f; int** i; };   // a Scratch member: exactly one of the two is set
+
+struct ScratchRow {
+  const char* member;                       // the Scratch member, as written in the code
+  ScratchSlot (*slot)(Scratch&);
+  size_t (*per_slot)(const Geometry&);      // floats / ints per batch slot
+  bool poison;                              // VAPX_POISON_SCRATCH refills it before every step (never: h0..h3, whose guard rows must stay
+                                            // zero, and bn / bhead / rot, which conv0 or the window kernels write before anyone reads)
+  bool encoder;                             // encoder scratch: a trunk follower releases it (vapx_attach_trunk)
+  const char* peek;                         // vapx_peek name, or null
+};
+
+#define VAPX_F(m) #m, [](Scratch& s) { return ScratchSlot{&s.m, nullptr}; }
+#define VAPX_I(m) #m, [](Scratch& s) { return ScratchSlot{nullptr, &s.m}; }
+#define VAPX_N(expr) [](const Geometry& g) { (void)g; return (size_t)(expr); }
+inline constexpr ScratchRow kScratchTable[] = {
+    //  member            per batch slot                      poison encoder peek
+    {VAPX_F(out_dev),  VAPX_N(VAPX_OUT_STRIDE),               true,  false, nullptr},
+    {VAPX_I(bn),       VAPX_N(1),                             false, false, nullptr},
+    {VAPX_I(bhead),    VAPX_N(1),                             false, false, nullptr},
+    {VAPX_I(rot),      VAPX_N(1),                             false, false, nullptr},
+    {VAPX_F(h0),       VAPX_N(2 * (g.P[0] + 4) * 256),        false, true,  "h0"},   // conv outputs with their zero guard rows
+    {VAPX_F(h1),       VAPX_N(2 * (g.P[1] + 2) * 256),        false, true,  "h1"},
+    {VAPX_F(h2),       VAPX_N(2 * (g.P[2] + 2) * 256),        false, true,  "h2"},
+    {VAPX_F(h3),       VAPX_N(2 * (g.P[3] + 2) * 256),        false, true,  "h3"},
+    {VAPX_F(z),        VAPX_N(2 * g.ncpc * 256),              true,  true,  "z"},
+    {VAPX_F(lstm_out), VAPX_N(2 * g.ncpc * 256),              true,  true,  "lstm_out"},
+    {VAPX_F(gx),       VAPX_N(2 * g.ncpc * 1024),             true,  true,  nullptr},
+    {VAPX_F(e),        VAPX_N(2 * 256),                       true,  false, "e"},
+    {VAPX_F(xl[0]),    VAPX_N((size_t)2 * g.T * 256),         true,  false, "x0"},
+    {VAPX_F(xl[1]),    VAPX_N((size_t)2 * g.T * 256),         true,  false, "o"},
+    {VAPX_F(xl[2]),    VAPX_N((size_t)2 * g.T * 256),         true,  false, "stereo0"},
+    {VAPX_F(xl[3]),    VAPX_N((size_t)2 * g.T * 256),         true,  false, "stereo1"},
+    {VAPX_F(xl[4]),    VAPX_N((size_t)2 * g.T * 256),         true,  false, "stereo2"},
+    {VAPX_F(xn),       VAPX_N((size_t)2 * g.T * 256),         true,  false, nullptr},
+    {VAPX_F(xmid),     VAPX_N((size_t)2 * g.T * 256),         true,  false, "comb"},   // nod mode: [B][T][256] of it (vapx_peek)
+    {VAPX_F(att),      VAPX_N((size_t)2 * g.T * 256),         true,  false, nullptr},
+    {VAPX_F(qkv),      VAPX_N((size_t)2 * g.T * 768),         true,  false, nullptr},
+    {VAPX_F(qx),       VAPX_N((size_t)2 * g.T * 256),         true,  false, nullptr},
+    {VAPX_F(kvx),      VAPX_N((size_t)2 * g.T * 512),         true,  false, nullptr},
+    {VAPX_F(last[0]),  VAPX_N(2 * 256),                       true,  false, nullptr},
+    {VAPX_F(last[1]),  VAPX_N(2 * 256),                       true,  false, nullptr},
+    {VAPX_F(last[2]),  VAPX_N(2 * 256),                       true,  false, nullptr},
+    {VAPX_F(last[3]),  VAPX_N(2 * 256),                       true,  false, nullptr},
+    {VAPX_F(last[4]),  VAPX_N(2 * 256),                       true,  false, nullptr},
+    {VAPX_F(last[5]),  VAPX_N(2 * 256),                       true,  false, "last"},
+    {VAPX_F(en),       VAPX_N(2 * 256),                       true,  false, nullptr},
+    {VAPX_F(qkv_new),  VAPX_N(2 * 768),                       true,  false, nullptr},
+    {VAPX_F(lffn),     VAPX_N(2 * 768),                       true,  false, nullptr},
+};
+#undef VAPX_F
+#undef VAPX_I
+#undef VAPX_N
+
+inline Scratch Scratch::slice(size_t b0, const Geometry& g) const {
+  Scratch s = *this;
+  for (const ScratchRow& r : kScratchTable) {
+    const ScratchSlot p = r.slot(s);
+    const size_t off = b0 * r.per_slot(g);
+    if (p.f) { if (*p.f) *p.f += off; }   // a released buffer stays null
+    else if (*p.i) *p.i += off;
+  }
+  return s;
+}
+
+inline void* scratch_ptr(const ScratchRow& r, Scratch& s) {
+  const ScratchSlot p = r.slot(s);
+  return p.f ? (void*)*p.f : (void*)*p.i;
+}
+
+inline const ScratchRow* scratch_row_by_peek(const char* name) {
+  for (const ScratchRow& r : kScratchTable)
+    if (r.peek && !strcmp(r.peek, name)) return &r;
+  return nullptr;
+}
