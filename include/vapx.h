@@ -180,6 +180,38 @@ int vapx_set_input_rate(vapx_handle h, int32_t input_hz);
 int32_t vapx_get_input_rate(vapx_handle h);
 int vapx_resample(int32_t input_hz, int64_t rows, int64_t n_in, const float* x, float* y, void* hip_stream);
 
+/* Input format: audio in the sample format a telephone gateway or a WebRTC stack already has, decoded to the model's fp32 on the device
+ * (csrc/pcm.hip).  vap-realtime_amd/pcm.py is the definition and writes the G.711 tables of csrc/pcm_tables.h:
+ *   VAPX_PCM_F32    4 bytes / sample   the float itself (the default: an engine that never makes the call)
+ *   VAPX_PCM_S16    2, little-endian   (float)v * 2^-15
+ *   VAPX_PCM_MULAW  1                  (float)U[c] * 2^-15      U, A: the ITU-T G.711 expansions to 16-bit linear
+ *   VAPX_PCM_ALAW   1                  (float)A[c] * 2^-15      (U[0x00] = -32124, U[0x7F] = U[0xFF] = 0; A[0xD5] = 8, A[0xAA] = 32256)
+ * Every value is exact in fp32 and both mu-law zero codes give +0.0f: nothing rounds, so an engine stepped in a raw format equals, bit
+ * for bit, an engine fed the decoded floats.
+ *
+ * vapx_set_input_format: the rules of vapx_set_input_rate — allowed once, on a freshly created engine with no step yet; refused on a
+ * trunk follower and for an unknown id (VAPX_E_INVAL).  VAPX_PCM_F32 is accepted and changes nothing.  Independent of
+ * vapx_set_input_rate: the two may be called in either order.  From then on
+ *   - `audio` of vapx_step / vapx_step_group points to [n][2][samples_per_ch] SAMPLES OF THAT FORMAT: the parameter keeps its type
+ *     `const float*` and is reinterpreted.  samples_per_ch keeps its meaning and its checks (hop or hop + 320 at 16 kHz, hop_in with an
+ *     input rate); every legal value is a multiple of 16, so rows stay dword-aligned.  The block's base address must be 4-byte aligned
+ *     (VAPX_E_INVAL otherwise).  VAPX_AUDIO_HOST (page-locked or pageable, staged as before but in bytes) and VAPX_AUDIO_DEVICE both work;
+ *   - one launch per step decodes the whole batch into an engine buffer [max_batch][2][max(hop_in, hop + 320)], before the resampler
+ *     and before the overlap groups fork; the resampler or conv0 then reads fp32 as before;
+ *   - vapx_encode_audio always takes fp32 frames and is unaffected; state records, snapshots and vapx_reset_* are untouched (the decoder
+ *     has no state: a record moves freely between engines of different input formats);
+ *   - VAPX_DEFER_JOIN is not honoured (the decoded hops of a tick live in one buffer).
+ * vapx_get_input_format: the id (VAPX_PCM_F32 unless another was set); on a follower VAPX_PCM_F32.
+ * vapx_pcm_decode: n samples of `format` (S16 / MULAW / ALAW) at src -> n floats at dst, device pointers, src 4-byte and dst 16-byte
+ * aligned; stateless and without a handle, like vapx_resample; the same kernel as the engine's step. */
+#define VAPX_PCM_F32 0
+#define VAPX_PCM_S16 1
+#define VAPX_PCM_MULAW 2
+#define VAPX_PCM_ALAW 3
+int vapx_set_input_format(vapx_handle h, int32_t format);
+int32_t vapx_get_input_format(vapx_handle h);
+int vapx_pcm_decode(int32_t format, int64_t n, const void* src, float* dst, void* hip_stream);
+
 /* Batch slots (row indices of `out`) of the latest host-output vapx_step whose results were not finite; returns their number
  * (writes at most max_slots of them; slots may be NULL to just count). */
 int32_t vapx_bad_slots(vapx_handle h, int32_t* slots, int32_t max_slots);
@@ -467,6 +499,12 @@ typedef struct vapx_ingest_config {
      front-end thread happens to run on and its tail latency follows the neighbours'. */
   int32_t cpu_first;
   int32_t cpu_count;
+  /* wire format of the input port (optional; a caller that passes a shorter struct gets 0): 0 = the reference's framing, 160 x {f64 ch1, f64 ch2}
+     per 10 ms, cast to f32 on the host; VAPX_PCM_S16 / _MULAW / _ALAW = 10 ms packets of in_hz / 100 interleaved (ch1, ch2) sample pairs in that
+     format (640 bytes s16 or 320 bytes G.711 at 16 kHz, 160 bytes G.711 at 8 kHz), de-interleaved into the staging as they are and decoded by
+     the engine (vapx_set_input_format).  The result packet is unchanged: its x1 / x2 blocks carry the decoded samples as f64.  With an engine the
+     format is the engine's and this field must be 0 or equal to it; the _fn variants take it from here.  gain != 1 with a raw format is refused. */
+  int32_t input_format;
 } vapx_ingest_config;
 #define VAPX_INGEST_CORE_SET 2      /* with cpu_count > 0: every front-end thread may run on ANY core of the range (one affinity set) instead of
                                        one core each: keeps other processes' work off the range without nailing a thread to a core that the
@@ -496,7 +534,8 @@ typedef struct vapx_ingest_stats {
 int vapx_ingest_open(vapx_handle engine, const vapx_ingest_config* cfg, vapx_ingest_handle* out);
 /* The same front-end over a caller-supplied step function instead of an engine (host-logic tests without a GPU):
  * step(user, n, stream_ids, audio[n][2][hop], out[n][VAPX_OUT_STRIDE]) returns 0 or a negative VAPX_E_* code;
- * reset(user, stream_id) may be NULL. */
+ * reset(user, stream_id) may be NULL.  With cfg->input_format S16 / MULAW / ALAW `audio` points to the raw samples [n][2][hop] of that
+ * format (the type stays const float*), exactly as an engine with that input format takes them. */
 typedef int (*vapx_ingest_step_fn)(void* user, int32_t n, const int32_t* stream_ids, const float* audio, float* out);
 typedef void (*vapx_ingest_reset_fn)(void* user, int32_t stream_id);
 int vapx_ingest_open_fn(vapx_ingest_step_fn step, vapx_ingest_reset_fn reset, void* user, int32_t n_streams, int32_t max_batch,

@@ -23,6 +23,8 @@
 //                     is checked, and the latency percentiles are also reported per port (last byte of the packet's LAST frame sent -> packet read).
 //   --input-rate R    sample rate of the dialogues' audio (8000, 16000, 32000, 48000; default 16000): a 10 ms packet carries R / 100 sample
 //                     pairs and a frame R / hz; the server's engines resample on the GPU (serve --input_rate R) and echo the samples as received
+//   --input-format F  sample format of the dialogues' audio on the input port: f64 (default, the reference's framing), s16, mulaw or alaw: a 10 ms packet
+//                     then carries R / 100 pairs of 2 / 1 / 1 bytes per sample (serve --input_format F decodes on the GPU); not with --inband
 //   --hist-out F      latency histogram (50 us bins up to 400 ms) as JSON, for merging the processes' percentiles
 // Build: make -C vap-realtime_amd/csrc loadgen   (plain C++17, no dependencies)
 #include <arpa/inet.h>
@@ -103,6 +105,7 @@ int main(int argc, char** argv) {
   std::vector<int> ports_out{50008};
   std::vector<int> port_samples;
   int port_in = 50007, S = 256, hz = 20, packet_ms = 10, threads = 4, input_rate = 16000;
+  std::string input_format = "f64";
   double seconds = 10.0, late_ms = 10.0, warm = 3.0;
   int inband = 0, procs = 1, rank = 0, total_streams = 0;
   const char* sync_dir = nullptr;
@@ -122,7 +125,8 @@ int main(int argc, char** argv) {
     }
     else if (k == "--streams") S = atoi(v);
     else if (k == "--hz") hz = atoi(v);
-    else if (k == "--input-rate") input_rate = atoi(v);
+    else if (k == "--input-rate" || k == "--input_rate") input_rate = atoi(v);
+    else if (k == "--input-format" || k == "--input_format") input_format = v;
     else if (k == "--seconds") seconds = atof(v);
     else if (k == "--warm") warm = atof(v);
     else if (k == "--packet-ms") packet_ms = atoi(v);
@@ -153,6 +157,9 @@ int main(int argc, char** argv) {
     }
   };
   if (input_rate != 8000 && input_rate != 16000 && input_rate != 32000 && input_rate != 48000) { fprintf(stderr, "--input-rate: 8000, 16000, 32000 or 48000\n"); return 2; }
+  if (input_format != "f64" && input_format != "s16" && input_format != "mulaw" && input_format != "alaw") { fprintf(stderr, "--input-format: f64, s16, mulaw or alaw\n"); return 2; }
+  if (input_format != "f64" && inband) { fprintf(stderr, "--inband needs --input-format f64: the stamps ride in f64 samples\n"); return 2; }
+  const size_t pair_bytes = input_format == "f64" ? 16 : input_format == "s16" ? 4 : 2;   // one sample of both channels on the wire
   const int hop = input_rate / hz;                   // sample pairs per frame on the wire
   std::vector<int> ratio(P, 1);                      // frames per packet of each port
   if (!port_samples.empty()) {
@@ -176,6 +183,31 @@ int main(int argc, char** argv) {
     const double t = i / (double)input_rate;
     audio[2 * i] = 0.2 * sin(2 * M_PI * 140.0 * t) * (0.6 + 0.4 * sin(2 * M_PI * 4.0 * t)) + 1e-3 * ((rand() % 2001) / 1000.0 - 1.0);
     audio[2 * i + 1] = 0.15 * sin(2 * M_PI * 210.0 * t + 1.0) * (i / hop % 2 ? 1.0 : 0.05) + 1e-3 * ((rand() % 2001) / 1000.0 - 1.0);
+  }
+  // the same audio as the input port takes it: f64 pairs (the reference's framing), or s16 / G.711 pairs (serve --input_format)
+  std::vector<uint8_t> wire((size_t)NF * hop * pair_bytes);
+  if (input_format == "f64") memcpy(wire.data(), audio.data(), wire.size());
+  else {
+    int table[256];                                  // the G.711 expansion to 16-bit linear (ITU-T closed forms)
+    for (int c = 0; c < 256; ++c) {
+      if (input_format == "mulaw") {
+        const int u = ~c & 0xFF, e = (u >> 4) & 7, m = u & 15, t = (((m << 3) + 0x84) << e) - 0x84;
+        table[c] = (u & 0x80) ? -t : t;
+      } else {
+        const int a = c ^ 0x55, e = (a >> 4) & 7, m = a & 15, t = e == 0 ? (m << 4) + 8 : ((m << 4) + 0x108) << (e - 1);
+        table[c] = (a & 0x80) ? t : -t;
+      }
+    }
+    for (size_t i = 0; i < audio.size(); ++i) {
+      const long v = std::max(-32768L, std::min(32767L, lround(audio[i] * 32768.0)));
+      if (input_format == "s16") { const int16_t q = (int16_t)v; memcpy(&wire[2 * i], &q, 2); continue; }
+      int best = 0;                                  // nearest table value, ties to the smaller magnitude
+      for (int c = 1; c < 256; ++c) {
+        const long d = labs(table[c] - v), db = labs(table[best] - v);
+        if (d < db || (d == db && abs(table[c]) < abs(table[best]))) best = c;
+      }
+      wire[i] = (uint8_t)best;
+    }
   }
   {   // two sockets per stream: raise the soft descriptor limit if it is short
     rlimit rl;
@@ -257,8 +289,8 @@ int main(int argc, char** argv) {
         clock_nanosleep(CLOCK_MONOTONIC, TIMER_ABSTIME, &ts, nullptr);
         n = now_s();
       }
-      const uint8_t* p = (const uint8_t*)(audio.data() + ((size_t)(e.frame % NF) * hop + (size_t)e.pk * pk_samples) * 2);
-      size_t left = (size_t)pk_samples * 16;
+      const uint8_t* p = wire.data() + ((size_t)(e.frame % NF) * hop + (size_t)e.pk * pk_samples) * pair_bytes;
+      size_t left = (size_t)pk_samples * pair_bytes;
       if (e.pk + 1 == packets_per_frame) {   // time stamp BEFORE the frame's last packet leaves: the answer may overtake us
         const double ts = now_s();
         if (inband) {                          // the stamp and the dialogue id travel in the first sample pair of this packet

@@ -138,9 +138,13 @@ def main():
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--warm", type=float, default=4.0)
     ap.add_argument("--packet-ms", type=int, default=10)
-    ap.add_argument("--input-rate", type=int, default=16000, choices=[8000, 16000, 32000, 48000],
+    ap.add_argument("--input-rate", "--input_rate", dest="input_rate", type=int, default=16000, choices=[8000, 16000, 32000, 48000],
                     help="sample rate of the dialogues' audio: a 10 ms packet carries input_rate / 100 sample pairs and the engines resample on "
                          "the GPU (serve --input_rate); real engines behind the native front-end only")
+    ap.add_argument("--input-format", "--input_format", dest="input_format", default="f64", choices=["f64", "s16", "mulaw", "alaw"],
+                    help="sample format of the dialogues' audio on the input port: f64 is the reference's framing; s16 / mulaw / alaw packets carry "
+                         "input_rate / 100 sample pairs of 2 / 1 / 1 bytes per sample and the engines decode on the GPU (serve --input_format); the "
+                         "native front-end only, and not with --inband (the stamps ride in f64 samples)")
     ap.add_argument("--max-wait-ms", type=float, default=2.0)
     ap.add_argument("--min-batch", type=int, default=0)
     ap.add_argument("--max-batch", type=int, default=0)
@@ -184,7 +188,13 @@ def main():
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "vap-realtime_amd", "csrc"), "../../tools/loadgen"])
     S = args.streams
     rate_kw = {"input_hz": args.input_rate} if args.input_rate != 16000 else {}
-    assert not rate_kw or not (args.fake or args.standin or args.python), "--input-rate needs real engines behind the native front-end"
+    # several load-generator processes find their frames by stamps that ride in f64 samples (--inband, which loadgen --procs > 1 requires): a raw
+    # format has no room for them, so it is driven by ONE generator process (--client-threads sizes it)
+    assert args.input_format == "f64" or not (args.standin or args.python or args.inband or args.loadgen_procs > 1), \
+        "--input_format needs the native front-end (real engines or --fake) and no --inband, hence one load-generator process"
+    if args.input_format != "f64":
+        rate_kw["input_format"] = args.input_format
+    assert args.input_rate == 16000 or not (args.fake or args.standin or args.python), "--input-rate needs real engines behind the native front-end"
     from vap_realtime_amd import dist_util, engine, ingest
     srv = None
     # placement: the front-end's tick / receive / sender threads on consecutive cores of the GPU's NUMA node, the load generator on the
@@ -300,10 +310,11 @@ def main():
                 "native front-end over the native stand-in step function")
     elif args.fake:
         def step(ids, audio, out):
-            out[:, 0:2] = np.abs(audio).mean(axis=2)
+            out[:, 0:2] = np.abs(audio.astype(np.float32)).mean(axis=2)
             return 0
         srv = ingest.NativeServer.over_function(step, S, args.hz, max_batch=args.max_batch or S, max_wait_s=args.max_wait_ms * 1e-3,
-                                                min_batch=args.min_batch, rx_threads=args.rx_threads, tx_threads=args.tx_threads)
+                                                min_batch=args.min_batch, rx_threads=args.rx_threads, tx_threads=args.tx_threads,
+                                                input_format=args.input_format)
         cores = client_cores = None                       # (over_function has no placement argument)
         kind = "native front-end over a trivial step function"
     elif "+" in args.mode:
@@ -387,6 +398,8 @@ def main():
             c += ["--port-samples", ",".join(str(port_samples[m]) for m in ports)]
         if args.input_rate != 16000:
             c += ["--input-rate", str(args.input_rate)]
+        if args.input_format != "f64":
+            c += ["--input-format", args.input_format]
         c += ["--streams", str(per_proc[r]), "--hz", str(args.hz),
              "--seconds", str(args.seconds), "--warm", str(args.warm), "--packet-ms", str(args.packet_ms), "--threads", str(args.client_threads)]
         if inband:
@@ -452,6 +465,8 @@ def main():
     res["cpu_cores_used"] = {"server_process": round(((cpu1[1].user + cpu1[1].system) - (cpu0[1].user + cpu0[1].system)) / wall, 2),
                              "load_generators": round(((cpu1[1].children_user + cpu1[1].children_system) - (cpu0[1].children_user + cpu0[1].children_system)) / wall, 2),
                              "wall_s": round(wall, 2)}
+    res["server_process_cpu_s"] = round((cpu1[1].user + cpu1[1].system) - (cpu0[1].user + cpu0[1].system), 2)   # front-end threads + the tick's host side
+    res["input_format"], res["input_rate"] = args.input_format, args.input_rate
     res["server"] = kind
     res["placement"] = {"front_end_cores": list(cores) if cores else None, "client_cores": ([client_cores[0], client_cores[-1], len(client_cores)] if client_cores else None)}
     if hasattr(srv, "stats"):

@@ -123,6 +123,11 @@ struct vapx_engine : Geometry {
   int hop_in = 0, rs_rec = 0;             // input samples per channel and tick; floats of a stream's history [2][H], padded to a multiple of 4
   float *rs_hist = nullptr, *rs_out = nullptr;   // [max_streams][rs_rec], [max_batch][2][hop]
   int* rs_started = nullptr;              // [max_streams * 2] the (stream, channel) has consumed a tick since its reset
+  // input as 16-bit PCM or G.711 (vapx_set_input_format; pcm.hip): one launch decodes the tick's raw samples into pcm_out, which takes the
+  // place of the caller's audio in front of the resampler or conv0
+  int in_fmt = VAPX_PCM_F32;              // VAPX_PCM_F32: the input is fp32, pcm_out does not exist
+  float* pcm_out = nullptr;               // [max_batch][2][max(hop_in, L)]
+  size_t pcm_floats() const { return (size_t)cfg.max_batch * 2 * (size_t)std::max(hop_in, L); }
   float* out_pinned = nullptr;
   int last_B = 0, last_G = 1;
   bool last_tail_fused = false;           // some overlap group of the latest encoder pass ran conv_tail_kernel: h2 / h3 were not written
@@ -948,6 +953,7 @@ void vapx_destroy(vapx_handle h) {
   release_scratch(h->sc, /*encoder_only=*/false);
   release(h->audio); release(h->ids); release(h->mix); release(h->sio_ids);
   dfree(h->rs_hist); dfree(h->rs_out); dfree(h->rs_started);
+  dfree(h->pcm_out);
   dfree(h->gw_dev);
   dfree(h->acc); dfree(h->mixA); dfree(h->out_c);
   dfree(h->sio_dev);
@@ -1167,6 +1173,11 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     } else if (spc != h->hop && spc != h->L) return fail(h, VAPX_E_INVAL, "samples_per_ch must be %d (hop) or %d (full frame)", h->hop, h->L);
   }
   if (!stream_ids && n > h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "n exceeds max_streams");
+  const size_t bps = h->in_fmt ? (size_t)pcm_bytes_per_sample(h->in_fmt) : sizeof(float);   // bytes per sample of `audio`
+  if (!lead && h->in_fmt) {   // lane i of the decoder reads the dword at base + 4 i
+    if ((uintptr_t)audio & 3) return fail(h, VAPX_E_INVAL, "audio in a raw input format must be 4-byte aligned");
+    if (((size_t)spc * bps) & 3) return fail(h, VAPX_E_INVAL, "samples_per_ch = %d: a row of %zu-byte samples is not a whole number of dwords", spc, bps);
+  }
   hipStream_t st = (hipStream_t)hip_stream;
   (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -1184,7 +1195,7 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
   // free-running groups are only safe when nothing of this step is staged through engine-owned buffers on `st`
   // (host audio / host ids would be overwritten under a still-running group of the previous tick)
   const bool all_device = (flags & VAPX_OUT_DEVICE) && (lead || (flags & VAPX_AUDIO_DEVICE)) && (!stream_ids || (flags & VAPX_IDS_DEVICE));
-  const bool defer_join = G > 1 && (flags & VAPX_DEFER_JOIN) && all_device && !slower && !h->in_hz;   // rs_out is one buffer: the next tick's resampler must not overtake a running group
+  const bool defer_join = G > 1 && (flags & VAPX_DEFER_JOIN) && all_device && !slower && !h->in_hz && !h->in_fmt;   // rs_out / pcm_out is one buffer: the next tick's resampler / decoder must not overtake a running group
   int rc = VAPX_OK;
   // a different batch split re-slices the shared scratch, and a reset touches state a running group may still use:
   // in both cases the previous tick's groups are joined first
@@ -1199,6 +1210,7 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
       if (r.poison && !(r.encoder && lead))   // a follower has released its encoder scratch
         HIPCHK(h, hipMemsetAsync(scratch_ptr(r, h->sc), 0xFF, (size_t)h->cfg.max_batch * r.per_slot(*h) * sizeof(float), st));
     if (h->rs_out) HIPCHK(h, hipMemsetAsync(h->rs_out, 0xFF, (size_t)h->cfg.max_batch * 2 * h->hop * sizeof(float), st));
+    if (h->pcm_out) HIPCHK(h, hipMemsetAsync(h->pcm_out, 0xFF, h->pcm_floats() * sizeof(float), st));
   }
   if (!lead) { rc = flush_resets(h, st); if (rc) return rc; }
   const int* ids = nullptr;
@@ -1237,12 +1249,16 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
   }
   const float* ad = audio;
   if (!lead && !(flags & VAPX_AUDIO_DEVICE)) {
-    const size_t bytes = (size_t)n * 2 * spc * sizeof(float);
+    const size_t bytes = (size_t)n * 2 * spc * bps;   // a raw format: a whole number of dwords (checked above), never more than the fp32 block
     // pageable memory: stage through the engine's pinned buffer (an async copy from pageable memory is a hidden synchronous staging
     // copy inside the runtime); vapx_host_alloc memory: copy straight from the caller
     if (is_pinned_host(audio)) HIPCHK(h, hipMemcpyAsync(h->audio.dev, audio, bytes, hipMemcpyHostToDevice, st));
-    else HIPCHK(h, h->audio.upload(audio, (size_t)n * 2 * spc, st));
+    else HIPCHK(h, h->audio.upload(audio, bytes / sizeof(float), st));
     ad = h->audio.dev;
+  }
+  if (!lead && h->in_fmt) {   // raw samples -> fp32, one launch for the whole batch; the resampler or conv0 reads fp32 as ever
+    HIPCHK(h, launch_pcm_decode(h->in_fmt, (long)n * 2 * spc, ad, h->pcm_out, st));
+    ad = h->pcm_out;
   }
   if (h->in_hz) {   // input rate -> 16 kHz, one launch for the whole batch before the overlap groups fork; conv0 and its carry see plain hops
     ResampleArgs ra;
@@ -1426,6 +1442,7 @@ int vapx_attach_trunk(vapx_handle f, vapx_handle lead) {
     return fail(f, VAPX_E_INVAL, "attach a stand-alone engine to a leader that is not itself a follower");
   if (f->tick != 0 || lead->tick != 0) return fail(f, VAPX_E_INVAL, "attach before the first step of either engine");
   if (f->in_hz) return fail(f, VAPX_E_INVAL, "this engine has an input rate of its own (%d Hz): a follower takes no audio, set the rate on the leader", f->in_hz);
+  if (f->in_fmt) return fail(f, VAPX_E_INVAL, "this engine has an input format of its own (%d): a follower takes no audio, set the format on the leader", f->in_fmt);
   if (f->cfg.device_id != lead->cfg.device_id || f->cfg.max_streams != lead->cfg.max_streams || f->cfg.max_batch != lead->cfg.max_batch)
     return fail(f, VAPX_E_INVAL, "device, max_streams and max_batch must match the leader's");
   // window and rate may differ: the follower's frame is R consecutive leader ticks (a CPC frame is a function of real samples only)
@@ -1946,6 +1963,19 @@ int vapx_aux_head(vapx_handle h, int32_t which, int64_t rows, const float* x, fl
   return VAPX_OK;
 }
 
+// (re)allocate the decoder's output for an engine whose format is `format` and whose input hop is `hop_in` (0: 16 kHz); on failure the engine stays as it was
+static int alloc_pcm_out(vapx_engine* h, int format, int hop_in) {
+  float* p = nullptr;
+  const hipError_t e = dalloc(&p, (size_t)h->cfg.max_batch * 2 * (size_t)std::max(hop_in, h->L));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(h, e == hipErrorOutOfMemory ? VAPX_E_NOMEM : VAPX_E_HIP, "decoded-input buffer for input format %d: %s", format, hipGetErrorString(e));
+  }
+  dfree(h->pcm_out);
+  h->pcm_out = p;
+  return VAPX_OK;
+}
+
 int vapx_set_input_rate(vapx_handle h, int32_t input_hz) {
   if (!h) return VAPX_E_INVAL;
   ResampleGeom g = {};
@@ -1974,6 +2004,10 @@ int vapx_set_input_rate(vapx_handle h, int32_t input_hz) {
     if (apin) (void)hipHostFree(apin);
     return fail(h, e == hipErrorOutOfMemory ? VAPX_E_NOMEM : VAPX_E_HIP, "resampler state for %d Hz: %s", input_hz, hipGetErrorString(e));
   }
+  if (h->in_fmt && hop_in > h->L) {   // the format came first: its buffer has to hold hop_in samples now
+    const int rc = alloc_pcm_out(h, h->in_fmt, hop_in);
+    if (rc) { dfree(hist); dfree(started); dfree(rout); dfree(adev); if (apin) (void)hipHostFree(apin); return rc; }
+  }
   if (adev) {
     dfree(h->audio.dev); h->audio.dev = adev;
     (void)hipHostFree(h->audio.pin); h->audio.pin = apin;
@@ -1984,6 +2018,32 @@ int vapx_set_input_rate(vapx_handle h, int32_t input_hz) {
 }
 
 int32_t vapx_get_input_rate(vapx_handle h) { return !h ? VAPX_E_INVAL : (h->in_hz ? h->in_hz : 16000); }
+
+int vapx_set_input_format(vapx_handle h, int32_t format) {
+  if (!h) return VAPX_E_INVAL;
+  if (format < VAPX_PCM_F32 || format > VAPX_PCM_ALAW)
+    return fail(h, VAPX_E_INVAL, "input format %d: known are 0 (f32), 1 (s16), 2 (mulaw) and 3 (alaw)", format);
+  if (h->trunk || h->orphaned) return fail(h, VAPX_E_INVAL, "a trunk follower takes no audio: set the input format on the leader");
+  if (h->tick != 0 || h->in_fmt) return fail(h, VAPX_E_INVAL, "set the input format once, on a freshly created engine, before its first step");
+  if (format == VAPX_PCM_F32) return VAPX_OK;
+  (void)hipGetLastError();
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  HIPCHK(h, hipDeviceSynchronize());
+  const int rc = alloc_pcm_out(h, format, h->hop_in);
+  if (rc == VAPX_OK) h->in_fmt = format;
+  return rc;
+}
+
+int32_t vapx_get_input_format(vapx_handle h) { return !h ? VAPX_E_INVAL : h->in_fmt; }
+
+int vapx_pcm_decode(int32_t format, int64_t n, const void* src, float* dst, void* hip_stream) {
+  if (!src || !dst || n < 1 || n > ((int64_t)1 << 40) || format < VAPX_PCM_S16 || format > VAPX_PCM_ALAW) return VAPX_E_INVAL;
+  // dword loads; the stores are 16 bytes for G.711 and 8 for s16, which would do with an 8-byte aligned dst: one documented rule (vapx.h) for
+  // all three formats instead, which every device allocation meets
+  if (((uintptr_t)src & 3) || ((uintptr_t)dst & 15)) return VAPX_E_INVAL;
+  (void)hipGetLastError();
+  return launch_pcm_decode(format, (long)n, src, dst, (hipStream_t)hip_stream) == hipSuccess ? VAPX_OK : VAPX_E_HIP;
+}
 
 int vapx_resample(int32_t input_hz, int64_t rows, int64_t n_in, const float* x, float* y, void* hip_stream) {
   if (!x || !y || rows < 1 || n_in < 1 || n_in > ((int64_t)1 << 40)) return VAPX_E_INVAL;

@@ -8,6 +8,10 @@
 //   tick thread             batches the ready frames (ragged), vapx_step (host in / host out), hands rows to the senders
 //   tx threads              encode header / tail, sendmsg() with the echo arrays as iovecs (no copy), free the frame buffer
 //
+// A raw input format (vapx_ingest_config.input_format: s16, mulaw, alaw; vapx.h "Input format"): the receive threads only de-interleave
+// the samples into the staging as they are (no cast, no f32 staging, no f64 echo copy), the tick hands the raw block to the step, whose
+// engine decodes on the device, and a sender expands the frame's echo from the raw staging by pcm_tables.h when it encodes the packet.
+//
 // Every stream owns NBUF frame buffers (filling / waiting / in flight / being sent + slack), so reception never waits for the GPU
 // unless a sender outruns the engine by four whole frames; then the connection is paused (TCP back-pressure), never dropped.
 #include <arpa/inet.h>
@@ -43,6 +47,7 @@
 #include <vector>
 
 #include "../../include/vapx.h"
+#include "pcm_tables.h"
 
 // the engine's group entry points: weak here, so the front-end still links into a program that stubs only the single-model
 // engine calls (tests/native); vapx_ingest_open_group says so if they are missing
@@ -50,12 +55,17 @@
 #pragma weak vapx_group_wire_floats
 // the engine's input rate (vapx_set_input_rate): weak for the same reason; a program without it serves 16 kHz
 #pragma weak vapx_get_input_rate
+// the engine's input format (vapx_set_input_format): weak for the same reason; a program without it takes fp32
+#pragma weak vapx_get_input_format
 
 namespace {
 
 constexpr int NBUF = 5;   // frame buffers per stream: filling + waiting + in flight + two of slack for a client that bursts after a stall
 constexpr int MAX_MODELS = 3;                 // output ports of one front-end: a trunk group serves up to vap + bc + nod
 constexpr int PAIR_BYTES = 16;                 // one sample of both channels: f64 ch1, f64 ch2 (util.py:52-62)
+// raw input formats (vapx.h "Input format"): the 16-bit linear value of a sample; its value is that times 2^-15, exact in f32 and f64
+constexpr int16_t kMulaw[256] = {VAPX_PCM_MULAW_TABLE};
+constexpr int16_t kAlaw[256] = {VAPX_PCM_ALAW_TABLE};
 enum BufState : int { B_FREE = 0, B_FILLING = 1, B_READY = 2, B_INFLIGHT = 3 };
 
 // Timed condition wait.  Under ThreadSanitizer the wait goes through system_clock (pthread_cond_timedwait): gcc-11's libtsan does
@@ -209,6 +219,11 @@ struct vapx_ingest {
   vapx_handle engine = nullptr;
   int S = 0, max_batch = 0, hop = 0, hz = 0;   // hop: sample PAIRS per frame on the wire = in_hz / hz (the engine resamples: vapx_set_input_rate)
   int in_hz = 16000;
+  // wire format of the input port: VAPX_PCM_F32 = the reference's f64 pairs, cast to f32 on the host (the engine's format is f32); S16 / MULAW /
+  // ALAW = raw samples, staged as they are and handed to the step as they are (the engine decodes: vapx_set_input_format)
+  int fmt = VAPX_PCM_F32;
+  int bps = 4;                             // bytes per sample of the staging blocks
+  int pair_bytes = PAIR_BYTES;             // one sample of both channels on the wire
   int M = 1;                               // models = output ports (> 1: a trunk group, `step` fills wire blocks)
   OutPort ports[MAX_MODELS];
   size_t row_floats = VAPX_OUT_STRIDE;     // floats per stream in a job's block, all models
@@ -217,9 +232,9 @@ struct vapx_ingest {
   int R = 2, X = 2;
 
   std::unique_ptr<Slot[]> slots;
-  float* stage = nullptr;                  // pinned [S][NBUF][2][hop] f32
-  std::vector<double> echo;                // [S][NBUF][2][hop] f64
-  float* batch_audio = nullptr;            // pinned [max_batch][2][hop]
+  float* stage = nullptr;                  // pinned [S][NBUF][2][hop] f32, or raw samples of bps bytes
+  std::vector<double> echo;                // [S][NBUF][2][hop] f64; a raw format keeps none: the echo is expanded from `stage` when a packet is encoded
+  float* batch_audio = nullptr;            // pinned [max_batch][2][hop], f32 or raw
   std::vector<int32_t> batch_ids;
   Job jobs[2];
 
@@ -269,6 +284,7 @@ struct vapx_ingest {
 
   float* f32buf(int slot, int buf) { return stage + ((size_t)slot * NBUF + buf) * 2 * hop; }
   double* f64buf(int slot, int buf) { return echo.data() + ((size_t)slot * NBUF + buf) * 2 * hop; }
+  uint8_t* rawbuf(int slot, int buf) { return (uint8_t*)stage + ((size_t)slot * NBUF + buf) * 2 * hop * bps; }
 };
 
 namespace {
@@ -412,8 +428,80 @@ void drop_input(vapx_ingest* g, int r, int slot) {
   g->in_conns.fetch_sub(1);
 }
 
+// the slot's write buffer holds a whole frame: hand it to the tick thread
+void frame_complete(vapx_ingest* g, int slot, Slot& s) {
+  const int b = s.wbuf;
+  const double t = mono_now();
+  s.t_ready[b] = t;
+  if (s.dbg_ready.fetch_add(1, std::memory_order_relaxed) == 0) s.dbg_t_first_ready = t;
+  s.state[b].store(B_READY, std::memory_order_release);
+  s.wbuf = -1; s.fill = 0;
+  {
+    std::lock_guard<std::mutex> lk(g->ready_mu);
+    g->ready.push_back({slot, b, s.gen.load(std::memory_order_relaxed), t});
+  }
+  g->ready_cv.notify_one();
+}
+
+// a raw input format: interleaved (ch1, ch2) samples of bps bytes are de-interleaved into the slot's staging as they are: no cast, no
+// f32 staging, no f64 echo copy.  Same contract as feed()
+size_t feed_raw(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
+  Slot& s = g->slots[slot];
+  const size_t hop = (size_t)g->hop, bps = (size_t)g->bps, pb = (size_t)g->pair_bytes;
+  size_t used = 0;
+  while (used < n) {
+    if (s.wbuf < 0) {
+      s.wbuf = pick_free(s);
+      if (s.wbuf < 0) return used;
+      s.fill = 0;
+    }
+    uint8_t* d = g->rawbuf(slot, s.wbuf);
+    if (s.npartial) {                       // finish a sample pair split across two reads
+      const size_t take = std::min<size_t>(pb - s.npartial, n - used);
+      memcpy(s.partial + s.npartial, p + used, take);
+      s.npartial += (int)take; used += take;
+      if ((size_t)s.npartial < pb) break;
+      s.npartial = 0;
+      memcpy(d + (size_t)s.fill * bps, s.partial, bps);
+      memcpy(d + (hop + s.fill) * bps, s.partial + bps, bps);
+      ++s.fill;
+    } else {
+      const size_t pairs = std::min<size_t>((n - used) / pb, hop - (size_t)s.fill);
+      if (pairs == 0) {                     // less than a pair left: keep it for the next read
+        const size_t rest = n - used;
+        memcpy(s.partial, p + used, rest); s.npartial = (int)rest; used = n;
+        break;
+      }
+      const uint8_t* q = p + used;
+      if (bps == 2) {
+        uint8_t *d1 = d + (size_t)s.fill * 2, *d2 = d + (hop + s.fill) * 2;
+        for (size_t i = 0; i < pairs; ++i) { memcpy(d1 + 2 * i, q + 4 * i, 2); memcpy(d2 + 2 * i, q + 4 * i + 2, 2); }
+      } else {
+        uint8_t *d1 = d + s.fill, *d2 = d + hop + s.fill;
+        for (size_t i = 0; i < pairs; ++i) { d1[i] = q[2 * i]; d2[i] = q[2 * i + 1]; }
+      }
+      s.fill += (int)pairs;
+      used += pairs * pb;
+    }
+    if ((size_t)s.fill == hop) frame_complete(g, slot, s);
+  }
+  return used;
+}
+
+// a frame of a raw format as the result packet echoes it: the decoded samples as float64, [2][hop]
+void expand_raw(const vapx_ingest* g, const uint8_t* raw, double* e) {
+  const size_t n = (size_t)2 * g->hop;
+  if (g->fmt == VAPX_PCM_S16) {
+    for (size_t i = 0; i < n; ++i) { int16_t v; memcpy(&v, raw + 2 * i, 2); e[i] = (double)v * 0x1p-15; }
+  } else {
+    const int16_t* t = g->fmt == VAPX_PCM_MULAW ? kMulaw : kAlaw;
+    for (size_t i = 0; i < n; ++i) e[i] = (double)t[raw[i]] * 0x1p-15;
+  }
+}
+
 // decode `n` bytes of the stream into the slot's frame buffers; returns bytes consumed (< n: no free buffer)
 size_t feed(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
+  if (g->fmt) return feed_raw(g, slot, p, n);
   Slot& s = g->slots[slot];
   const int hop = g->hop;
   const double gain = g->cfg.gain;
@@ -467,19 +555,7 @@ size_t feed(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
       s.fill += (int)pairs;
       used += pairs * PAIR_BYTES;
     }
-    if (s.fill == hop) {                    // frame complete -> tick thread
-      const int b = s.wbuf;
-      const double t = mono_now();
-      s.t_ready[b] = t;
-      if (s.dbg_ready.fetch_add(1, std::memory_order_relaxed) == 0) s.dbg_t_first_ready = t;
-      s.state[b].store(B_READY, std::memory_order_release);
-      s.wbuf = -1; s.fill = 0;
-      {
-        std::lock_guard<std::mutex> lk(g->ready_mu);
-        g->ready.push_back({slot, b, s.gen.load(std::memory_order_relaxed), t});
-      }
-      g->ready_cv.notify_one();
-    }
+    if (s.fill == hop) frame_complete(g, slot, s);   // -> tick thread
   }
   return used;
 }
@@ -490,7 +566,7 @@ size_t feed(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
 // runs there (round 5: on a box with load average 60 from other tenants every front-end thread was losing ~10 ms slices).  Re-armed only
 // when the value changes: a sender that delivers whole frames never causes a setsockopt.
 void arm_lowat(vapx_ingest* g, Slot& s) {
-  long need = (long)(g->hop - (s.wbuf >= 0 ? s.fill : 0)) * (long)PAIR_BYTES - s.npartial;
+  long need = (long)(g->hop - (s.wbuf >= 0 ? s.fill : 0)) * (long)g->pair_bytes - s.npartial;
   if (need < 1) need = 1;
   if (need > 65536) need = 65536;           // (5 Hz frames are 51 KB; stay well inside the receive buffer)
   if ((int)need == s.lowat || s.fd_in < 0 || g->no_lowat) return;
@@ -775,6 +851,7 @@ bool send_packet(int fd, iovec* iov, int niov, size_t total) {
 void tx_main(vapx_ingest* g, int x) {
   std::vector<uint8_t> tail(64 + 8 * 256);
   const int hop = g->hop;
+  std::vector<double> expanded(g->fmt ? (size_t)2 * hop : 0);   // a raw format: the row's echo, decoded from the staging by the table
   constexpr int MAX_R = 10;                  // 50 Hz -> 5 Hz
   int64_t next = 0;                          // the job this thread sends next: every sender walks over EVERY job, in publication order
   while (true) {
@@ -799,11 +876,12 @@ void tx_main(vapx_ingest* g, int x) {
       } else {
         // u32 len | f64 t | u32 n | x1 | u32 n | x2 | tail   (util.py:122-143; length prefix vap_main.py:446-448); a trunk group sends one
         // packet per model, each to its own port's listeners, tail in that model's framing (bc util.py:193-211, nod :213-237)
+        double* e = g->fmt ? expanded.data() : g->f64buf(rd.slot, rd.buf);
+        if (g->fmt) expand_raw(g, g->rawbuf(rd.slot, rd.buf), e);
         for (int m = 0; m < g->M; ++m) {
           OutPort& o = g->ports[m];
           const float* row = job.out + (size_t)job.n * o.off + (size_t)k * o.wf;
           uint8_t head[16], mid[4];
-          double* e = g->f64buf(rd.slot, rd.buf);
           // a model at 1/R of the leader's rate answers every R-th leader hop of a dialogue with ONE packet echoing all R hops, what
           // its reference program sends (n = R * hop samples per channel); the hops in between (VAPX_STATUS_NO_FRAME) only add to its
           // echo history: no packet, no reset
@@ -948,11 +1026,11 @@ void tick_main(vapx_ingest* g) {
     if (!pending.empty()) first_ready = pending.front().t;
     const int n = (int)job.rows.size();
     if (n == 0) continue;
-    const size_t fb = (size_t)2 * g->hop * sizeof(float);
+    const size_t fb = (size_t)2 * g->hop * g->bps;   // a frame of the staging, f32 or raw
     for (int k = 0; k < n; ++k) {
       in_batch[job.rows[k].slot] = 0;
       g->batch_ids[k] = job.rows[k].slot;
-      memcpy(g->batch_audio + (size_t)k * 2 * g->hop, g->f32buf(job.rows[k].slot, job.rows[k].buf), fb);
+      memcpy((uint8_t*)g->batch_audio + (size_t)k * fb, g->rawbuf(job.rows[k].slot, job.rows[k].buf), fb);
     }
     const double t0 = mono_now();
     const int rc = g->step(g->user, n, g->batch_ids.data(), g->batch_audio, job.out);
@@ -1021,26 +1099,48 @@ void pin_to(std::thread& t, const vapx_ingest_config& c, int k) {
 // the caller's config, whatever its vintage: the struct only ever grows at the end and says how long it is
 bool read_config(const vapx_ingest_config* cfg, vapx_ingest_config* out) {
   constexpr int32_t kFirst = (int32_t)offsetof(vapx_ingest_config, cpu_first);   // ABI 2 as first shipped: up to `reserved` (now `flags`)
-  if (!cfg || (cfg->struct_size != kFirst && cfg->struct_size != (int32_t)sizeof(vapx_ingest_config))) return false;
+  constexpr int32_t kPlaced = (int32_t)offsetof(vapx_ingest_config, input_format);   // ... with the thread placement, before the input format
+  if (!cfg || (cfg->struct_size != kFirst && cfg->struct_size != kPlaced && cfg->struct_size != (int32_t)sizeof(vapx_ingest_config))) return false;
   memset(out, 0, sizeof *out);
   memcpy(out, cfg, (size_t)cfg->struct_size);
   out->struct_size = (int32_t)sizeof(vapx_ingest_config);
   return true;
 }
 
-int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in) {
+thread_local std::string g_open_error;   // vapx_ingest_last_open_error
+int open_refused(const char* why) { g_open_error = why; return VAPX_E_INVAL; }
+
+// what the config's input format may be: engine_fmt is the engine's (vapx_get_input_format), or -1 for a front-end over a step function,
+// which takes the config's.  VAPX_OK or the refusal, with its message
+int check_format(const vapx_ingest_config* cfg, int engine_fmt) {
+  if (cfg->input_format < VAPX_PCM_F32 || cfg->input_format > VAPX_PCM_ALAW)
+    return open_refused("input_format: known are 0 (f64 pairs, the reference's framing), 1 (s16), 2 (mulaw) and 3 (alaw)");
+  if (engine_fmt >= 0 && cfg->input_format != 0 && cfg->input_format != engine_fmt)
+    return open_refused("vapx_ingest_config.input_format differs from the engine's input format (vapx_set_input_format): leave it 0 or make them equal");
+  const int fmt = engine_fmt >= 0 ? engine_fmt : cfg->input_format;
+  if (fmt && cfg->gain != 1.0 && cfg->gain != 0.0)
+    return open_refused("gain with a raw input format: the gain is a float64 multiply in front of the f32 cast, and raw samples are never cast on the host");
+  return VAPX_OK;
+}
+
+int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt = -1) {
   if (!read_config(cfg_in, &g->cfg)) return VAPX_E_INVAL;
   const vapx_ingest_config* cfg = &g->cfg;
   g->debug = getenv("VAPX_INGEST_DEBUG") != nullptr;
   g->no_lowat = getenv("VAPX_INGEST_NO_LOWAT") != nullptr;
   if (g->cfg.gain == 0.0) g->cfg.gain = 1.0;
+  { const int rc = check_format(cfg, engine_fmt); if (rc) return rc; }
+  g->fmt = engine_fmt >= 0 ? engine_fmt : cfg->input_format;
+  g->bps = g->fmt == VAPX_PCM_F32 ? 4 : g->fmt == VAPX_PCM_S16 ? 2 : 1;
+  g->pair_bytes = g->fmt ? 2 * g->bps : PAIR_BYTES;
   g->R = cfg->rx_threads > 0 ? std::min(cfg->rx_threads, 16) : 2;
   g->X = cfg->tx_threads > 0 ? std::min(cfg->tx_threads, 16) : 2;
   g->broadcast = cfg->broadcast < 0 ? (g->S == 1) : (cfg->broadcast != 0);
   g->hop = g->in_hz / g->hz;
   g->slots.reset(new Slot[g->S]);
-  const size_t per = (size_t)g->S * NBUF * 2 * g->hop;
-  const size_t ba = (size_t)g->max_batch * 2 * g->hop;
+  const size_t per_samples = (size_t)g->S * NBUF * 2 * g->hop;
+  const size_t per = (per_samples * g->bps + 3) / 4;                       // the staging blocks in floats: f32 samples, or raw ones of bps bytes
+  const size_t ba = ((size_t)g->max_batch * 2 * g->hop * g->bps + 3) / 4;
   const size_t ob = (size_t)g->max_batch * g->row_floats;
   // page-locked staging so vapx_step DMAs straight out of / into it; without a HIP device (host-logic tests over a step
   // function) plain memory does
@@ -1048,7 +1148,7 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in) {
   g->pinned_blocks = g->stage != nullptr;
   auto grab = [&](size_t n) { return (float*)(g->pinned_blocks ? vapx_host_alloc(n * sizeof(float)) : calloc(n, sizeof(float))); };
   if (!g->stage) g->stage = grab(per);
-  g->echo.assign(per, 0.0);
+  if (!g->fmt) g->echo.assign(per_samples, 0.0);
   g->batch_audio = grab(ba);
   g->batch_ids.assign(g->max_batch, 0);
   for (auto& j : g->jobs) {
@@ -1114,14 +1214,20 @@ int engine_group_step(void* user, int32_t n, const int32_t* ids, const float* au
   return vapx_step_group(g->engine, n, ids, audio, g->hop, wire_out, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
 }
 
+// sample format of the audio the engine takes: fp32 unless vapx_set_input_format said otherwise
+int engine_input_format(vapx_handle engine) {
+  const int32_t f = vapx_get_input_format ? vapx_get_input_format(engine) : VAPX_PCM_F32;
+  return f > 0 ? f : VAPX_PCM_F32;
+}
+
+// silence in a raw format, for the warm-up: the code of the smallest magnitude (0.0 for s16 and mulaw, 8 * 2^-15 for alaw)
+int silence_byte(int fmt) { return fmt == VAPX_PCM_MULAW ? 0xFF : fmt == VAPX_PCM_ALAW ? 0xD5 : 0; }
+
 // sample rate of the audio the engine takes: 16000 unless vapx_set_input_rate said otherwise
 int engine_input_hz(vapx_handle engine) {
   const int32_t r = vapx_get_input_rate ? vapx_get_input_rate(engine) : 16000;
   return r > 0 ? r : 16000;
 }
-
-thread_local std::string g_open_error;   // vapx_ingest_last_open_error
-int open_refused(const char* why) { g_open_error = why; return VAPX_E_INVAL; }
 
 // a trunk group's ports: model m's framing, the geometry of its rows in the tick's wire block (vapx_step_group) and its requested port
 int setup_group(vapx_ingest* g, int n_streams, const int32_t* frame_hzs, const int32_t* ctx_frames, const int32_t* modes, int n_models,
@@ -1166,6 +1272,7 @@ extern "C" {
 
 int vapx_ingest_open_fn(vapx_ingest_step_fn step, vapx_ingest_reset_fn reset, void* user, int32_t n_streams, int32_t max_batch,
                         int32_t frame_hz, int32_t mode, const vapx_ingest_config* cfg, vapx_ingest_handle* out) {
+  g_open_error.clear();
   vapx_ingest_config probe;
   if (!step || !out || !read_config(cfg, &probe)) return VAPX_E_INVAL;
   if (n_streams < 1 || max_batch < 1 || max_batch > n_streams) return VAPX_E_INVAL;
@@ -1181,6 +1288,7 @@ int vapx_ingest_open_fn(vapx_ingest_step_fn step, vapx_ingest_reset_fn reset, vo
 }
 
 int vapx_ingest_open(vapx_handle engine, const vapx_ingest_config* cfg, vapx_ingest_handle* out) {
+  g_open_error.clear();
   vapx_ingest_config probe;
   if (!engine || !out || !read_config(cfg, &probe)) return VAPX_E_INVAL;
   vapx_config ec;
@@ -1191,6 +1299,9 @@ int vapx_ingest_open(vapx_handle engine, const vapx_ingest_config* cfg, vapx_ing
   g->step = engine_step; g->reset = engine_reset; g->user = g;
   g->S = ec.max_streams; g->max_batch = ec.max_batch; g->hz = ec.frame_hz; g->ports[0].mode = ec.mode;
   g->in_hz = engine_input_hz(engine);
+  const int efmt = engine_input_format(engine);
+  rc = check_format(&probe, efmt);   // before the warm-up: a refused open leaves the engine untouched
+  if (rc != VAPX_OK) { delete g; return rc; }
   if (!(probe.flags & VAPX_INGEST_KEEP_STATE)) {
      // warm the engine up before the first client connects: the first vapx_step of a process loads the code objects and sizes
      // the runtime's pools (hundreds of ms) — paid here on silence, then every touched stream is reset (VAPX_INGEST_KEEP_STATE: the
@@ -1199,14 +1310,14 @@ int vapx_ingest_open(vapx_handle engine, const vapx_ingest_config* cfg, vapx_ing
     float* a = (float*)vapx_host_alloc((size_t)nw * 2 * hop * sizeof(float));
     float* o = (float*)vapx_host_alloc((size_t)nw * VAPX_OUT_STRIDE * sizeof(float));
     if (a && o) {
-      memset(a, 0, (size_t)nw * 2 * hop * sizeof(float));
+      memset(a, silence_byte(efmt), (size_t)nw * 2 * hop * sizeof(float));   // (a raw format reads the front of the block)
       for (int k = 0; k < 3; ++k) (void)vapx_step(engine, nw, nullptr, a, hop, o, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
       for (int i = 0; i < nw; ++i) (void)vapx_reset_stream(engine, i);
     }
     vapx_host_free(a);
     vapx_host_free(o);
   }
-  rc = open_common(g, cfg);
+  rc = open_common(g, cfg, efmt);
   if (rc != VAPX_OK) { vapx_ingest_close(g); return rc; }
   *out = g;
   return VAPX_OK;
@@ -1258,7 +1369,7 @@ int vapx_ingest_open_group_fn2(vapx_ingest_group_step_fn step, vapx_ingest_reset
   g->step = step; g->reset = reset; g->user = user;
   g->S = n_streams; g->max_batch = max_batch; g->hz = frame_hz;
   rc = open_common(g, cfg);
-  if (rc != VAPX_OK) { vapx_ingest_close(g); return open_refused("could not allocate the staging blocks or bind the ports"); }
+  if (rc != VAPX_OK) { vapx_ingest_close(g); return g_open_error.empty() ? open_refused("could not allocate the staging blocks or bind the ports") : rc; }
   *out = g;
   return VAPX_OK;
 }
@@ -1282,7 +1393,9 @@ int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int
   }
   vapx_ingest* g = new vapx_ingest();
   g->in_hz = engine_input_hz(leader);
-  rc = setup_group(g, ec.max_streams, hzs, ctxs, modes, n_followers + 1, probe, follower_ports_out, g->in_hz);
+  const int efmt = engine_input_format(leader);
+  rc = check_format(&probe, efmt);
+  if (rc == VAPX_OK) rc = setup_group(g, ec.max_streams, hzs, ctxs, modes, n_followers + 1, probe, follower_ports_out, g->in_hz);
   if (rc == VAPX_OK && g->row_floats != vapx_group_wire_floats(leader)) {
     rc = open_refused("`followers` are not the leader's attached followers (vapx_attach_trunk) in attach order");
   }
@@ -1295,7 +1408,7 @@ int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int
     float* a = (float*)vapx_host_alloc((size_t)nw * 2 * hop * sizeof(float));
     float* o = (float*)vapx_host_alloc((size_t)nw * g->row_floats * sizeof(float));
     if (a && o) {
-      memset(a, 0, (size_t)nw * 2 * hop * sizeof(float));
+      memset(a, silence_byte(efmt), (size_t)nw * 2 * hop * sizeof(float));   // (a raw format reads the front of the block)
       int nwarm = 3;   // every model's chain at least once: a slower follower's runs on every R-th tick
       for (int m = 0; m <= n_followers; ++m) nwarm = std::max(nwarm, g->ports[m].R);
       for (int k = 0; k < nwarm; ++k) (void)vapx_step_group(leader, nw, nullptr, a, hop, o, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
@@ -1304,8 +1417,8 @@ int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int
     vapx_host_free(a);
     vapx_host_free(o);
   }
-  rc = open_common(g, cfg);
-  if (rc != VAPX_OK) { vapx_ingest_close(g); return open_refused("could not allocate the staging blocks or bind the ports"); }
+  rc = open_common(g, cfg, efmt);
+  if (rc != VAPX_OK) { vapx_ingest_close(g); return g_open_error.empty() ? open_refused("could not allocate the staging blocks or bind the ports") : rc; }
   *out = g;
   return VAPX_OK;
 }

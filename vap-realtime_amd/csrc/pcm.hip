@@ -1,0 +1,111 @@
+// Input in the sample format it already has: 16-bit linear PCM and G.711 mu-law / A-law -> the fp32 the model computes in, on the device
+// (vapx_set_input_format, vapx_pcm_decode; include/vapx.h "Input format").  The definition is vap-realtime_amd/pcm.py, which also writes
+// the two 256-entry tables of pcm_tables.h:  s16: float(v) * 2^-15;  mulaw / alaw: float(table[c]) * 2^-15.  Every value is exact in
+// fp32 and integer zero converts to +0.0f, so a stream stepped in a raw format equals, bit for bit, one fed the decoded floats.
+//
+// G.711 is expanded by the CLOSED FORM in integer ALU (a handful of shifts and adds per code), not by a table in LDS: no LDS, no barrier,
+// no constant-memory traffic.  The static_asserts below hold the closed forms to pcm_tables.h for all 256 codes at compile time; the host
+// side (the front-end's echo, csrc/ingest.cpp) reads the tables.
+//
+// One kernel for the engine's step and for vapx_pcm_decode: the block is flat, [rows][spc] samples are n = rows * spc samples in a row.
+// Lane i reads the aligned dword at base + 4 i (two s16 samples or four codes) and writes its outputs with one 8-byte or one 16-byte
+// store.  A tick of 4096 streams moves at most about 40 MB; the kernel is bound by that traffic and nothing is tuned past the access
+// pattern.  A sample count that does not fill the last dword (vapx_pcm_decode only: every row of a step is a multiple of 16 samples) is
+// finished by that dword's lane with single loads and stores, so nothing is read or written past n samples.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/vapx.h"
+#include "pcm_tables.h"
+#include "vap_kernels.h"
+
+namespace {
+
+__host__ __device__ constexpr int mulaw_linear(unsigned c) {
+  c = ~c & 0xFFu;
+  const int e = (int)(c >> 4) & 7, m = (int)(c & 15u);
+  const int t = (((m << 3) + 0x84) << e) - 0x84;
+  return (c & 0x80u) ? -t : t;
+}
+
+__host__ __device__ constexpr int alaw_linear(unsigned c) {
+  c = (c ^ 0x55u) & 0xFFu;
+  const int e = (int)(c >> 4) & 7, m = (int)(c & 15u);
+  const int t = e == 0 ? (m << 4) + 8 : ((m << 4) + 0x108) << (e - 1);
+  return (c & 0x80u) ? t : -t;
+}
+
+constexpr short kMulawTable[256] = {VAPX_PCM_MULAW_TABLE};
+constexpr short kAlawTable[256] = {VAPX_PCM_ALAW_TABLE};
+constexpr bool closed_forms_match_tables() {
+  for (unsigned c = 0; c < 256; ++c)
+    if (mulaw_linear(c) != kMulawTable[c] || alaw_linear(c) != kAlawTable[c]) return false;
+  return true;
+}
+static_assert(closed_forms_match_tables(), "pcm.hip's closed forms and pcm_tables.h (vap-realtime_amd/pcm.py) disagree");
+
+// one sample: 16-bit linear -> fp32.  Exact; (float)0 is +0.0f
+__device__ __forceinline__ float pcm_value(int v) { return (float)v * 0x1p-15f; }
+
+template <int FMT>
+__device__ __forceinline__ float pcm_code(unsigned c) {
+  return pcm_value(FMT == VAPX_PCM_MULAW ? mulaw_linear(c) : alaw_linear(c));
+}
+
+// n samples at src (dword-aligned) -> n floats at dst (8-byte aligned for s16, 16-byte aligned for G.711)
+template <int FMT>
+__global__ __launch_bounds__(256) void pcm_decode_kernel(const uint32_t* __restrict__ src, float* __restrict__ dst, long n) {
+  constexpr int PER = FMT == VAPX_PCM_S16 ? 2 : 4;   // samples in a dword
+  const long full = n / PER;                         // whole dwords
+  const long stride = (long)gridDim.x * 256;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < full; i += stride) {
+    const uint32_t w = src[i];
+    if (FMT == VAPX_PCM_S16) {
+      float2 o;
+      o.x = pcm_value((int)(short)(w & 0xFFFFu));
+      o.y = pcm_value((int)(short)(w >> 16));
+      *reinterpret_cast<float2*>(dst + 2 * i) = o;
+    } else {
+      float4 o;
+      o.x = pcm_code<FMT>(w & 0xFFu);
+      o.y = pcm_code<FMT>((w >> 8) & 0xFFu);
+      o.z = pcm_code<FMT>((w >> 16) & 0xFFu);
+      o.w = pcm_code<FMT>(w >> 24);
+      *reinterpret_cast<float4*>(dst + 4 * i) = o;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {         // the samples of a last, partial dword
+    for (long s = full * PER; s < n; ++s) {
+      if (FMT == VAPX_PCM_S16) dst[s] = pcm_value((int)reinterpret_cast<const short*>(src)[s]);
+      else dst[s] = pcm_code<FMT>(reinterpret_cast<const uint8_t*>(src)[s]);
+    }
+  }
+}
+
+}  // namespace
+
+int pcm_bytes_per_sample(int format) {
+  switch (format) {
+    case VAPX_PCM_F32: return 4;
+    case VAPX_PCM_S16: return 2;
+    case VAPX_PCM_MULAW: case VAPX_PCM_ALAW: return 1;
+  }
+  return 0;
+}
+
+hipError_t launch_pcm_decode(int format, long n, const void* src, float* dst, hipStream_t st) {
+  const int per = format == VAPX_PCM_S16 ? 2 : 4;
+  const long dwords = (n + per - 1) / per;
+  long blocks = (dwords + 255) / 256;
+  if (blocks > 16384) blocks = 16384;                // the loop strides over the rest
+  const dim3 grid((unsigned)blocks), wg(256);
+  const uint32_t* s = (const uint32_t*)src;
+  switch (format) {
+    case VAPX_PCM_S16: hipLaunchKernelGGL(pcm_decode_kernel<VAPX_PCM_S16>, grid, wg, 0, st, s, dst, n); break;
+    case VAPX_PCM_MULAW: hipLaunchKernelGGL(pcm_decode_kernel<VAPX_PCM_MULAW>, grid, wg, 0, st, s, dst, n); break;
+    case VAPX_PCM_ALAW: hipLaunchKernelGGL(pcm_decode_kernel<VAPX_PCM_ALAW>, grid, wg, 0, st, s, dst, n); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}

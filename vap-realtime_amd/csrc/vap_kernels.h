@@ -179,6 +179,10 @@ bool resample_geometry(int in_hz, ResampleGeom* g);   // false: not 8000 / 32000
 hipError_t launch_resample(const ResampleArgs& a, int n, hipStream_t st);
 hipError_t launch_resample_whole(const ResampleGeom& g, long rows, long n_in, const float* x, float* y, hipStream_t st);
 
+// pcm.hip: n raw samples (VAPX_PCM_S16 / _MULAW / _ALAW; src dword-aligned) -> n floats (dst 16-byte aligned), the engine's step and vapx_pcm_decode alike
+int pcm_bytes_per_sample(int format);   // 0: unknown format id
+hipError_t launch_pcm_decode(int format, long n, const void* src, float* dst, hipStream_t st);
+
 hipError_t launch_state_export(const StateIoArgs& a, hipStream_t st);
 hipError_t launch_state_import(const StateIoArgs& a, hipStream_t st);
 // cache rebuild of an import without cache: xn[(k*2+c)*T + t] = LayerNorm(ring row (slot ids[k], c, t)); after the GEMM, rows t < window fill

@@ -42,7 +42,8 @@ EXPORTS = ("vapx_abi_version", "vapx_blob_floats", "vapx_create", "vapx_destroy"
            "vapx_wire_floats", "vapx_group_wire_floats", "vapx_step_group", "vapx_group_bad", "vapx_ingest_open_group",
            "vapx_ingest_open_group_fn", "vapx_ingest_open_group_fn2", "vapx_ingest_group_ports", "vapx_ingest_last_open_error",
            "vapx_state_floats", "vapx_export_streams", "vapx_import_streams",
-           "vapx_set_input_rate", "vapx_get_input_rate", "vapx_resample")
+           "vapx_set_input_rate", "vapx_get_input_rate", "vapx_resample",
+           "vapx_set_input_format", "vapx_get_input_format", "vapx_pcm_decode")
 PROF_CLASSES = {0: "gemm_store", 1: "gemm_gelu", 2: "gemm_resid", 3: "gemm_resid_ln", 4: "gemm_cn_relu",
                 5: "conv_tail", 6: "ffn_block", 7: "last_row", 8: "conv0", 9: "lstm", 10: "gather_ln", 11: "attention", 12: "head",
                 13: "gemm_bias_ln_gelu", 14: "ffn_proj", 15: "trunk_collect"}
@@ -108,6 +109,12 @@ def load_library(path: Optional[str] = None):
     lib.vapx_get_input_rate.argtypes = [vp]
     lib.vapx_resample.restype = i32
     lib.vapx_resample.argtypes = [i32, C.c_int64, C.c_int64, f32p, f32p, vp]
+    lib.vapx_set_input_format.restype = i32
+    lib.vapx_set_input_format.argtypes = [vp, i32]
+    lib.vapx_get_input_format.restype = i32
+    lib.vapx_get_input_format.argtypes = [vp]
+    lib.vapx_pcm_decode.restype = i32
+    lib.vapx_pcm_decode.argtypes = [i32, C.c_int64, vp, f32p, vp]
     lib.vapx_encode_audio.restype = i32
     lib.vapx_encode_audio.argtypes = [vp, i32, i32p, f32p, f32p, vp]
     lib.vapx_transformer.restype = i32
@@ -239,8 +246,11 @@ class Engine:
                  max_streams: int = 1, max_batch: Optional[int] = None, mode: str = "vap", device_id: int = 0,
                  groups: int = 0, full_last_layer: bool = False, unfused_conv: bool = False,
                  materialize_x0: bool = False, unfused_last_row: bool = False, split_f16: bool = False,
-                 unfused_proj: bool = False, split_qkv_in_ffn: bool = False, input_hz: int = 16000):
+                 unfused_proj: bool = False, split_qkv_in_ffn: bool = False, input_hz: int = 16000,
+                 input_format: str = "f32"):
+        from . import pcm
         self.lib = load_library()
+        self.input_format = pcm.format_name(input_format)   # sample format of the audio ``step`` takes (vapx.h, vapx_set_input_format)
         self.frame_hz = frame_hz
         self.T = int(context_len_sec * frame_hz)           # vap_main.py:221
         self.hop = 16000 // frame_hz
@@ -268,6 +278,12 @@ class Engine:
                 msg = self.lib.vapx_last_error(h).decode()
                 self.close()
                 raise VapxError(f"vapx_set_input_rate failed ({rc}): {msg}")
+        if self.input_format != "f32":
+            rc = self.lib.vapx_set_input_format(h, pcm.FORMATS[self.input_format])
+            if rc != 0:
+                msg = self.lib.vapx_last_error(h).decode()
+                self.close()
+                raise VapxError(f"vapx_set_input_format failed ({rc}): {msg}")
 
     # -- lifecycle -------------------------------------------------------------------------------
     def close(self):
@@ -287,14 +303,54 @@ class Engine:
         return rc
 
     # -- the step --------------------------------------------------------------------------------
+    def _host_audio(self, audio):
+        """The audio block of a host-path step as a contiguous array of the engine's input format: float32 for "f32" (anything numeric is
+        cast, as ever); for a raw format the samples themselves, int16 ("s16") or uint8 ("mulaw" / "alaw") arrays or CPU tensors."""
+        if hasattr(audio, "detach") and hasattr(audio, "numpy"):      # a torch tensor
+            audio = audio.detach().cpu().numpy()
+        if self.input_format == "f32":
+            return np.ascontiguousarray(audio, dtype=np.float32)
+        from . import pcm
+        want = pcm.DTYPES[self.input_format]
+        audio = np.asarray(audio)
+        if audio.dtype != want:
+            raise TypeError(f"an engine with input_format={self.input_format!r} takes {want.name} samples, not {audio.dtype.name}")
+        return np.ascontiguousarray(audio)
+
+    def pcm_decode(self, fmt, samples):
+        """``vapx_pcm_decode``: a CUDA tensor of raw samples (int16 for "s16", uint8 for "mulaw" / "alaw"; numpy arrays are uploaded) ->
+        a float32 CUDA tensor of the same shape, decoded by the kernel the engine's step uses."""
+        import torch
+        from . import pcm
+        name = pcm.format_name(fmt)
+        if name == "f32":
+            raise ValueError("pcm_decode takes s16, mulaw or alaw samples")
+        want = pcm.DTYPES[name]
+        if not isinstance(samples, torch.Tensor):
+            samples = np.asarray(samples)
+            if samples.dtype != want:
+                raise TypeError(f"{name} samples are {want.name}, not {samples.dtype.name}")
+            samples = torch.from_numpy(np.ascontiguousarray(samples))
+        if samples.dtype != (torch.int16 if name == "s16" else torch.uint8):
+            raise TypeError(f"{name} samples are {want.name}, not {samples.dtype}")
+        src = samples.to(f"cuda:{self.device_id}").contiguous()
+        dst = torch.empty(src.shape, dtype=torch.float32, device=src.device)
+        if src.numel():
+            rc = self.lib.vapx_pcm_decode(pcm.FORMATS[name], src.numel(), src.data_ptr(), dst.data_ptr(),
+                                          torch.cuda.current_stream(src.device).cuda_stream or None)
+            if rc != 0:
+                raise VapxError(f"vapx_pcm_decode failed ({rc})")
+        return dst
+
     def step(self, audio: np.ndarray, stream_ids: Optional[Sequence[int]] = None, out: Optional[np.ndarray] = None,
              on_numeric: str = "raise") -> np.ndarray:
         """Host path.  audio: float [n,2,hop] (new samples; engine keeps the carry) or [n,2,hop+320]
-        (complete frames as ``process_vap`` receives them); with ``input_hz`` other than 16000: [n,2,hop_in] and nothing else.  Returns float32 [n, OUT_STRIDE] (``out`` if given, e.g. a
+        (complete frames as ``process_vap`` receives them); with ``input_hz`` other than 16000: [n,2,hop_in] and nothing else; with an
+        ``input_format`` other than "f32": the same shapes as int16 ("s16") or uint8 ("mulaw" / "alaw") samples, any other dtype is refused.  Returns float32 [n, OUT_STRIDE] (``out`` if given, e.g. a
         ``pinned_empty`` block).  A stream with non-finite results (VAPX_E_NUMERIC) raises by default; with
         ``on_numeric="status"`` the block is returned — every other row is valid, the bad rows have column OUT_STATUS = 1
         and ``bad_slots()`` lists them."""
-        audio = np.ascontiguousarray(audio, dtype=np.float32)
+        audio = self._host_audio(audio)
         n, two, spc = audio.shape
         assert two == 2
         ids = None if stream_ids is None else np.ascontiguousarray(stream_ids, dtype=np.int32)
@@ -355,7 +411,7 @@ class Engine:
         """Host path of ``vapx_step_group``: steps this leader and every follower and returns the tick's wire block, flat float32
         [n * group_wire_floats()], model-major (``TrunkGroup.step_wire`` slices it).  ``out``: e.g. a ``pinned_empty`` block.
         ``on_numeric`` as in ``step``; ``group_bad()`` lists the (slot, model) pairs."""
-        audio = np.ascontiguousarray(audio, dtype=np.float32)
+        audio = self._host_audio(audio)
         n, two, spc = audio.shape
         assert two == 2
         ids = None if stream_ids is None else np.ascontiguousarray(stream_ids, dtype=np.int32)
@@ -546,7 +602,8 @@ class TrunkGroup:
     weights (vap_main.py:199-201, vap_bc_main.py, vap_nod_main.py).  Here ``blobs`` is ``{mode: blob}``.  ``frame_hz`` and
     ``context_len_sec`` are scalars (every model, as before) or per model: ``{mode: value}`` or a sequence in ``blobs`` order — the
     reference's own deployment is vap 20 Hz / 2.5 s, bc 20 Hz / 5 s, nod 10 Hz / 10 s.  ``input_hz`` (8000 / 16000 / 32000 / 48000) is the
-    sample rate of the audio and is applied to the leader, which then takes ``hop_in`` samples per tick.  The fastest model leads (runs the encoder;
+    sample rate of the audio and ``input_format`` ("f32" / "s16" / "mulaw" / "alaw") its sample format; both are applied to the leader, which then
+    takes ``hop_in`` samples of that format per tick.  The fastest model leads (runs the encoder;
     ties: the first entry), the others follow; ``hz / hop_of / L_of / T_of / R`` hold each mode's geometry, ``R[mode]`` being the
     leader ticks per frame of that model.  Input framing (``hop``, ``L``) is the leader's.
 
@@ -554,20 +611,20 @@ class TrunkGroup:
     n rows in the batch order, rows without a frame are zero with column OUT_STATUS = STATUS_NO_FRAME (``due`` masks them)."""
 
     def __init__(self, blobs: dict, frame_hz=20, context_len_sec=2.5, max_streams: int = 1,
-                 max_batch: Optional[int] = None, device_id: int = 0, input_hz: int = 16000, **engine_kw):
+                 max_batch: Optional[int] = None, device_id: int = 0, input_hz: int = 16000, input_format: str = "f32", **engine_kw):
         self.modes = list(blobs)
         plan = trunk_plan(self.modes, frame_hz, context_len_sec)
         self.hz, self.ctx, self.hop_of, self.L_of, self.T_of, self.R = (plan[k] for k in ("hz", "ctx", "hop", "L", "T", "R"))
         self.order = plan["order"]                             # model order of vapx_step_group's wire block: leader, then followers
         self.engines = {}
         for m in self.order:                                   # engine_kw: groups / split_f16 / ... — the same for every weight set
-            kw = dict(engine_kw, input_hz=input_hz) if m == self.order[0] else engine_kw      # the leader owns the audio
+            kw = dict(engine_kw, input_hz=input_hz, input_format=input_format) if m == self.order[0] else engine_kw      # the leader owns the audio
             self.engines[m] = Engine(blobs[m], self.hz[m], self.ctx[m], max_streams, max_batch, m, device_id, **kw)
         self.leader = self.engines[self.order[0]]
         for m in self.order[1:]:
             self.engines[m].attach_trunk(self.leader)
         self.hop, self.L, self.T = self.leader.hop, self.leader.L, self.leader.T
-        self.input_hz, self.hop_in = self.leader.input_hz, self.leader.hop_in
+        self.input_hz, self.hop_in, self.input_format = self.leader.input_hz, self.leader.hop_in, self.leader.input_format
 
     def step(self, audio: np.ndarray, stream_ids: Optional[Sequence[int]] = None) -> dict:
         res = {self.order[0]: self.leader.step(audio, stream_ids)}

@@ -25,7 +25,29 @@ class _IngestConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("port_in", C.c_int32), ("port_out", C.c_int32), ("rx_threads", C.c_int32),
                 ("tx_threads", C.c_int32), ("max_wait_us", C.c_int32), ("min_batch", C.c_int32), ("reset_on_connect", C.c_int32),
                 ("broadcast", C.c_int32), ("bind_any", C.c_int32), ("gain", C.c_double), ("target_util_pct", C.c_int32),
-                ("flags", C.c_int32), ("cpu_first", C.c_int32), ("cpu_count", C.c_int32)]
+                ("flags", C.c_int32), ("cpu_first", C.c_int32), ("cpu_count", C.c_int32), ("input_format", C.c_int32)]
+
+
+WIRE_FORMATS = {"f64": 0, "s16": 1, "mulaw": 2, "alaw": 3}      # wire format of the input port; f64 = the reference's framing (engine format f32)
+
+
+def wire_format_id(fmt) -> int:
+    """Name or id of an input-port wire format -> the id of vapx_ingest_config.input_format; None -> 0 (the engine's own)."""
+    if fmt is None:
+        return 0
+    if isinstance(fmt, str):
+        if fmt not in WIRE_FORMATS:
+            raise ValueError(f"unknown input format {fmt!r}: one of {', '.join(WIRE_FORMATS)}")
+        return WIRE_FORMATS[fmt]
+    return int(fmt)
+
+
+def _raw_view(audio_ptr, n: int, hop: int, fmt_id: int) -> np.ndarray:
+    """The audio block a step function receives, [n, 2, hop]: float32, or the raw samples of the wire format (int16 / uint8)."""
+    dt = {0: np.float32, 1: np.int16, 2: np.uint8, 3: np.uint8}[fmt_id]
+    nbytes = n * 2 * hop * np.dtype(dt).itemsize
+    buf = (C.c_char * nbytes).from_address(C.addressof(audio_ptr.contents))
+    return np.frombuffer(buf, dtype=dt).reshape(n, 2, hop)
 
 
 class _IngestStats(C.Structure):
@@ -43,45 +65,57 @@ class NativeServer:
     def __init__(self, eng: "_engine.Engine", port_in: int = 50007, port_out: int = 50008, gain: float = 1.0, max_wait_s: float = 0.002,
                  min_batch: int = 0, reset_on_connect: bool = True, broadcast: Optional[bool] = None, rx_threads: int = 0,
                  tx_threads: int = 0, bind_any: bool = False, target_util: float = 0.9, cores: Optional[tuple] = None,
-                 keep_nofile: bool = False, core_set: bool = False, keep_state: bool = False):
-        """``cores`` = (first, count): pin the front-end's tick / receive / sender threads to that core range (the GPU's NUMA node; keep
+                 keep_nofile: bool = False, core_set: bool = False, keep_state: bool = False, input_format: Optional[str] = None):
+        """``input_format``: wire format of the input port, "f64" (the reference's framing) / "s16" / "mulaw" / "alaw"; it is the engine's
+        (``Engine(input_format=...)``, "f32" there is "f64" here) and may be left out; one that disagrees with the engine's is refused.
+        ``cores`` = (first, count): pin the front-end's tick / receive / sender threads to that core range (the GPU's NUMA node; keep
         load generators and other tenants off it), one core each — or, with ``core_set``, all of them to the range as one affinity set.  ``keep_nofile``: never raise the process's RLIMIT_NOFILE (include/vapx.h).
         ``keep_state``: the engine holds imported stream state — skip the warm-up steps and resets of the open (VAPX_INGEST_KEEP_STATE);
         pass ``reset_on_connect=False`` with it."""
         self.lib = _engine.load_library()
         self._keep = [eng]
+        self._check_format(getattr(eng, "input_format", "f32"), input_format)
         cfg = self._cfg(port_in, port_out, gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, bind_any, target_util,
-                        cores, keep_nofile, core_set, keep_state)
+                        cores, keep_nofile, core_set, keep_state, input_format)
         h = C.c_void_p()
         rc = self.lib.vapx_ingest_open(eng._h, C.byref(cfg), C.byref(h))
         if rc != 0:
-            raise _engine.VapxError(f"vapx_ingest_open failed ({rc})")
+            raise _engine.VapxError(f"vapx_ingest_open failed ({rc}): {self.lib.vapx_ingest_last_open_error().decode()}")
         self._h = h
         self._ports()
 
     @staticmethod
+    def _check_format(engine_format: str, input_format):
+        """"f64" asked of an engine with a raw format cannot be told to the library (0 there means "the engine's"): refuse it here."""
+        if input_format is not None and wire_format_id(input_format) != wire_format_id("f64" if engine_format == "f32" else engine_format):
+            raise _engine.VapxError(f"input_format {input_format!r} differs from the engine's input format {engine_format!r}")
+
+    @staticmethod
     def _cfg(port_in, port_out, gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, bind_any, target_util=0.9,
-             cores=None, keep_nofile=False, core_set=False, keep_state=False):
+             cores=None, keep_nofile=False, core_set=False, keep_state=False, input_format=None):
         first, count = (int(cores[0]), int(cores[1])) if cores else (0, 0)
         return _IngestConfig(C.sizeof(_IngestConfig), port_in, port_out, rx_threads, tx_threads, int(max_wait_s * 1e6), min_batch,
                              1 if reset_on_connect else 0, -1 if broadcast is None else int(bool(broadcast)), int(bool(bind_any)), gain,
-                             int(round(target_util * 100)), (1 if keep_nofile else 0) | (2 if core_set else 0) | (4 if keep_state else 0), first, count)
+                             int(round(target_util * 100)), (1 if keep_nofile else 0) | (2 if core_set else 0) | (4 if keep_state else 0), first, count,
+                             wire_format_id(input_format))
 
     @classmethod
     def over_function(cls, step: Callable, n_streams: int, frame_hz: int = 20, mode: str = "vap", max_batch: Optional[int] = None,
                       reset: Optional[Callable] = None, port_in: int = 0, port_out: int = 0, gain: float = 1.0, max_wait_s: float = 0.002,
                       min_batch: int = 0, reset_on_connect: bool = True, broadcast: Optional[bool] = None, rx_threads: int = 0,
-                      tx_threads: int = 0, target_util: float = 1.0):
+                      tx_threads: int = 0, target_util: float = 1.0, input_format: Optional[str] = None):
         """``step(ids int32[n], audio float32[n,2,hop], out float32[n,OUT_STRIDE]) -> int`` fills ``out`` in place;
-        ``reset(stream_id)`` gets negative ids (``-(id+1)``) for carry-only resets."""
+        ``reset(stream_id)`` gets negative ids (``-(id+1)``) for carry-only resets.  With ``input_format`` "s16" / "mulaw" / "alaw" the
+        input port takes packets of that format and ``audio`` is the de-interleaved raw block, int16 or uint8 [n,2,hop]."""
         self = cls.__new__(cls)
         self.lib = _engine.load_library()
         hop = 16000 // frame_hz
+        fmt_id = wire_format_id(input_format)
 
         def _step(_user, n, ids, audio, out):
             try:
                 i = np.ctypeslib.as_array(ids, shape=(n,))
-                a = np.ctypeslib.as_array(audio, shape=(n, 2, hop))
+                a = _raw_view(audio, n, hop, fmt_id)
                 o = np.ctypeslib.as_array(out, shape=(n, _engine.OUT_STRIDE))
                 o[:, _engine.OUT_STATUS] = 0.0
                 return int(step(i, a, o) or 0)
@@ -95,12 +129,13 @@ class NativeServer:
                 reset(int(sid))
 
         self._keep = [_STEP_FN(_step), _RESET_FN(_reset)]
-        cfg = cls._cfg(port_in, port_out, gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, False, target_util)
+        cfg = cls._cfg(port_in, port_out, gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, False, target_util,
+                       input_format=fmt_id)
         h = C.c_void_p()
         rc = self.lib.vapx_ingest_open_fn(C.cast(self._keep[0], C.c_void_p), C.cast(self._keep[1], C.c_void_p), None, n_streams,
                                           max_batch or n_streams, frame_hz, MODE[mode], C.byref(cfg), C.byref(h))
         if rc != 0:
-            raise _engine.VapxError(f"vapx_ingest_open_fn failed ({rc})")
+            raise _engine.VapxError(f"vapx_ingest_open_fn failed ({rc}): {self.lib.vapx_ingest_last_open_error().decode()}")
         self._h = h
         self._ports()
         return self
@@ -109,7 +144,7 @@ class NativeServer:
     def for_group(cls, trunk_group: "_engine.TrunkGroup", port_in: int = 50007, ports_out=None, gain: float = 1.0, max_wait_s: float = 0.002,
                   min_batch: int = 0, reset_on_connect: bool = True, broadcast: Optional[bool] = None, rx_threads: int = 0,
                   tx_threads: int = 0, bind_any: bool = False, target_util: float = 0.9, cores: Optional[tuple] = None,
-                  keep_nofile: bool = False, core_set: bool = False, keep_state: bool = False):
+                  keep_nofile: bool = False, core_set: bool = False, keep_state: bool = False, input_format: Optional[str] = None):
         """One front-end for a whole ``engine.TrunkGroup`` (``vapx_ingest_open_group``): one input port, the audio encoded once, one
         output port per model in ``trunk_group.modes`` order (``ports_out``: one per model, default 50008, 50009, ...; 0 = ephemeral),
         each with its model's reference framing.  ``.ports_out`` is the bound ``{mode: port}``.  In a mixed group (models with rates
@@ -124,8 +159,9 @@ class NativeServer:
         modes = list(trunk_group.order)                        # the engine's model order: the leader (fastest model) first
         ports = [by_mode[m] for m in modes]
         self._keep = [trunk_group]
+        cls._check_format(getattr(trunk_group, "input_format", "f32"), input_format)               # the leader's (``TrunkGroup(input_format=...)``)
         cfg = cls._cfg(port_in, ports[0], gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, bind_any, target_util,
-                       cores, keep_nofile, core_set, keep_state)
+                       cores, keep_nofile, core_set, keep_state, input_format)
         fol = (C.c_void_p * max(len(modes) - 1, 1))(*[trunk_group.engines[m]._h.value for m in modes[1:]])
         fports = (C.c_int32 * max(len(modes) - 1, 1))(*ports[1:])
         h = C.c_void_p()
@@ -140,7 +176,8 @@ class NativeServer:
     def over_group_function(cls, step: Callable, modes, n_streams: int, frame_hz=20, ctx_frames=50,
                             max_batch: Optional[int] = None, reset: Optional[Callable] = None, port_in: int = 0, ports_out=None,
                             gain: float = 1.0, max_wait_s: float = 0.002, min_batch: int = 0, reset_on_connect: bool = True,
-                            broadcast: Optional[bool] = None, rx_threads: int = 0, tx_threads: int = 0, target_util: float = 1.0):
+                            broadcast: Optional[bool] = None, rx_threads: int = 0, tx_threads: int = 0, target_util: float = 1.0,
+                            input_format: Optional[str] = None):
         """The group front-end over a Python step function (``vapx_ingest_open_group_fn``; host-logic tests without a GPU):
         ``step(ids int32[n], audio float32[n,2,hop], wire {mode: float32[n, wire_floats]}) -> int`` fills the views of that tick's wire
         block in place (status columns start at 0); ``reset`` as in ``over_function``.  ``frame_hz`` / ``ctx_frames`` may be sequences,
@@ -156,6 +193,7 @@ class NativeServer:
             raise ValueError(f"{len(modes)} models need {len(modes)} rates and windows")
         frame_hz = hzs[0]
         hop = 16000 // frame_hz
+        fmt_id = wire_format_id(input_format)                  # a raw format: ``audio`` is the raw block, as in ``over_function``
         wf = [int(self.lib.vapx_wire_floats(MODE[m], c)) for m, c in zip(modes, ctxs)]
         ports = list(ports_out) if ports_out is not None else [0] * len(modes)
         if len(ports) != len(modes):
@@ -164,7 +202,7 @@ class NativeServer:
         def _step(_user, n, ids, audio, out):
             try:
                 i = np.ctypeslib.as_array(ids, shape=(n,))
-                a = np.ctypeslib.as_array(audio, shape=(n, 2, hop))
+                a = _raw_view(audio, n, hop, fmt_id)
                 block = np.ctypeslib.as_array(out, shape=(n * sum(wf),))
                 wire, at = {}, 0
                 for m, w in zip(modes, wf):
@@ -182,7 +220,8 @@ class NativeServer:
                 reset(int(sid))
 
         self._keep = [_STEP_FN(_step), _RESET_FN(_reset)]
-        cfg = cls._cfg(port_in, ports[0], gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, False, target_util)
+        cfg = cls._cfg(port_in, ports[0], gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, False, target_util,
+                       input_format=fmt_id)
         marr = (C.c_int32 * len(modes))(*[MODE[m] for m in modes])
         fports = (C.c_int32 * max(len(modes) - 1, 1))(*ports[1:])
         h = C.c_void_p()
@@ -210,19 +249,21 @@ class NativeServer:
     @classmethod
     def over_native_function(cls, step_ptr: int, user_ptr: int, n_streams: int, frame_hz: int = 20, mode: str = "vap", max_batch: Optional[int] = None,
                              keep=(), port_in: int = 0, port_out: int = 0, gain: float = 1.0, max_wait_s: float = 0.002, min_batch: int = 0,
-                             rx_threads: int = 0, tx_threads: int = 0, target_util: float = 0.9, cores: Optional[tuple] = None):
+                             rx_threads: int = 0, tx_threads: int = 0, target_util: float = 0.9, cores: Optional[tuple] = None,
+                             input_format: Optional[str] = None):
         """The same front-end over a C step function (address of a ``vapx_ingest_step_fn``, ``user_ptr`` handed to it): no Python on the tick
         thread.  ``tools/server_load.py --standin`` puts a stand-in for the GPU engine here (tools/standin_step.cpp) to load-test the host side of
         N x 4096 dialogues; ``port_in = port_out = -1`` makes it a passive shard of a ``FrontDoor``.  ``keep``: objects that must outlive it."""
         self = cls.__new__(cls)
         self.lib = _engine.load_library()
         self._keep = list(keep)
-        cfg = cls._cfg(port_in, port_out, gain, max_wait_s, min_batch, True, None, rx_threads, tx_threads, False, target_util, cores)
+        cfg = cls._cfg(port_in, port_out, gain, max_wait_s, min_batch, True, None, rx_threads, tx_threads, False, target_util, cores,
+                       input_format=input_format)
         h = C.c_void_p()
         rc = self.lib.vapx_ingest_open_fn(C.c_void_p(step_ptr), None, C.c_void_p(user_ptr), n_streams, max_batch or n_streams, frame_hz, MODE[mode],
                                           C.byref(cfg), C.byref(h))
         if rc != 0:
-            raise _engine.VapxError(f"vapx_ingest_open_fn failed ({rc})")
+            raise _engine.VapxError(f"vapx_ingest_open_fn failed ({rc}): {self.lib.vapx_ingest_last_open_error().decode()}")
         self._h = h
         self._ports()
         return self

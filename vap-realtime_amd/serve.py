@@ -71,7 +71,9 @@ def _warm_up(target):
     lead = target.leader if hasattr(target, "leader") else target
     if not hasattr(lead, "reset_stream"):
         return
-    silence = np.zeros((lead.max_batch, 2, getattr(lead, "hop_in", lead.hop)), np.float32)      # hop_in: the hop at --input_rate
+    from . import pcm
+    fmt = getattr(lead, "input_format", "f32")                                                   # --input_format: silence in that format
+    silence = np.full((lead.max_batch, 2, getattr(lead, "hop_in", lead.hop)), pcm.SILENCE[fmt], pcm.DTYPES[fmt])      # hop_in: the hop at --input_rate
     if hasattr(target, "step_wire"):
         target.step_wire(silence)
     else:
@@ -112,8 +114,12 @@ def save_state(path, target, tag: str = "") -> bool:
 
 
 def rate_kw(args) -> dict:
-    """``--input_rate`` as an ``Engine`` / ``TrunkGroup`` keyword; nothing at 16000, so such engines are built exactly as before."""
-    return {"input_hz": args.input_rate} if getattr(args, "input_rate", 16000) != 16000 else {}
+    """``--input_rate`` and ``--input_format`` as ``Engine`` / ``TrunkGroup`` keywords; nothing at 16000 / f64, so such engines are built
+    exactly as before.  The front-end reads both from the engine."""
+    kw = {"input_hz": args.input_rate} if getattr(args, "input_rate", 16000) != 16000 else {}
+    if getattr(args, "input_format", "f64") != "f64":
+        kw["input_format"] = args.input_format
+    return kw
 
 
 def group_modes(mode):
@@ -224,7 +230,7 @@ def run_group(args, names, stop) -> int:
     outs = ", ".join(f"{m} :{srv.ports_out[m]}" for m in names)
     geo = ", ".join(f"{m} {grp.hz[m]} Hz / {grp.ctx[m]:g} s" for m in names)
     print(f"[vapx] 1 GPU(s) x {args.streams} dialogue slots, modes {'+'.join(names)} on one CPC trunk ({grp.order[0]} leads), {args.precision} "
-          f"arithmetic, {geo}, audio at {args.input_rate} Hz — input :{srv.port_in}, output {outs}", flush=True)
+          f"arithmetic, {geo}, audio at {args.input_rate} Hz ({args.input_format}) — input :{srv.port_in}, output {outs}", flush=True)
     last = time.time()
     while not stop["now"]:
         time.sleep(0.2)
@@ -376,7 +382,7 @@ def run_door(args, argv) -> int:
             w.terminate()
         return 1
     print(f"[vapx] {n} GPU(s) x {args.streams} dialogue slots in {n} worker processes, mode {mode or ('vap' if args.synthetic_weights is not None else 'from the state dict')}, {args.precision} arithmetic, "
-          f"{args.vap_process_rate} Hz / {args.context_len_sec} s, audio at {args.input_rate} Hz — input :{door.port_in}, output :{door.port_out} (front-door process: dialogue k -> GPU k mod N)", flush=True)
+          f"{args.vap_process_rate} Hz / {args.context_len_sec} s, audio at {args.input_rate} Hz ({args.input_format}) — input :{door.port_in}, output :{door.port_out} (front-door process: dialogue k -> GPU k mod N)", flush=True)
     rc = 0
     while not stop["now"]:
         time.sleep(0.2)
@@ -427,6 +433,10 @@ def main(argv=None) -> int:
                     help="sample rate of the clients' audio: every packet still carries 10 ms (input_rate / 100 sample pairs); other rates than "
                          "16000 are resampled on the GPU with torchaudio's default filter, which delays the audio by 0.44 - 0.88 ms; the rate "
                          "travels in --save_state / --load_state files")
+    ap.add_argument("--input_format", choices=["f64", "s16", "mulaw", "alaw"], default="f64",
+                    help="sample format of the clients' audio on the input port: f64 (default) is the reference's framing, 160 x {f64, f64} per "
+                         "10 ms; s16 (16-bit little-endian PCM) and mulaw / alaw (G.711) packets carry input_rate / 100 interleaved (ch1, ch2) pairs "
+                         "of 2 or 1 bytes per sample and are decoded on the GPU; result packets are unchanged.  Not with --audio_gain")
     ap.add_argument("--streams", type=int, default=1, help="dialogue slots per GPU (the reference serves exactly one)")
     ap.add_argument("--max_batch", type=int, default=1024)
     ap.add_argument("--gpus", type=int, default=1)
@@ -494,7 +504,7 @@ def main(argv=None) -> int:
         print(f"[vapx] start-up failed: {e}", file=sys.stderr, flush=True)
         return 1
     pin, pout = (door.port_in, door.port_out) if door else (shards[0].port_in, shards[0].port_out)
-    print(f"[vapx] {len(engines)} GPU(s) x {args.streams} dialogue slots, mode {mode}, {args.precision} arithmetic, {args.vap_process_rate} Hz / {args.context_len_sec} s, audio at {args.input_rate} Hz — "
+    print(f"[vapx] {len(engines)} GPU(s) x {args.streams} dialogue slots, mode {mode}, {args.precision} arithmetic, {args.vap_process_rate} Hz / {args.context_len_sec} s, audio at {args.input_rate} Hz ({args.input_format}) — "
           f"input :{pin}, output :{pout}" + (" (front door: dialogue k -> GPU k mod N)" if door else ""), flush=True)
     last = time.time()
     while not stop["now"]:

@@ -35,8 +35,12 @@ from . import wire
 
 class ManyStreamServer:
     def __init__(self, vap, port_in: int = 50007, port_out: int = 50008, host: str = "127.0.0.1", gain: float = 1.0,
-                 max_wait_s: float = 0.004, broadcast: Optional[bool] = None, reset_on_connect: bool = True):
+                 max_wait_s: float = 0.004, broadcast: Optional[bool] = None, reset_on_connect: bool = True, input_format: str = "f64"):
         self.vap = vap
+        model_format = getattr(getattr(vap, "engine", vap), "input_format", "f32")
+        if input_format != "f64" or model_format != "f32":  # this twin decodes the reference's f64 packets only
+            raise ValueError(f"input format {input_format if input_format != 'f64' else model_format!r}: this Python server frames the reference's f64 "
+                             f"packets only — serve s16 / mulaw / alaw input through the native front-end (ingest.NativeServer, serve.py)")
         if getattr(vap, "hop_in", vap.hop) != vap.hop:      # this twin frames 16 kHz packets only; the native front-end follows the engine's rate
             raise ValueError(f"the model takes {vap.hop_in} samples per frame, not the {vap.hop} of 16 kHz audio: this Python server frames 16 kHz "
                              f"only — serve an engine with an input rate through the native front-end (ingest.NativeServer, serve.py)")

@@ -19,16 +19,50 @@ SAMPLES_PER_PACKET = 160
 INPUT_PACKET_BYTES = 8 * 2 * SAMPLES_PER_PACKET       # 2560
 
 
-def decode_input(data: bytes) -> Tuple[np.ndarray, np.ndarray]:
-    """bytes (multiple of 16) -> (x1, x2) float64 arrays; == util.conv_bytearray_2_2floatarray."""
+INPUT_FORMATS = ("f64", "s16", "mulaw", "alaw")       # wire formats of the input port (vapx.h, vapx_ingest_config.input_format)
+PAIR_BYTES = {"f64": 16, "s16": 4, "mulaw": 2, "alaw": 2}
+
+
+def input_packet_bytes(fmt: str = "f64", input_hz: int = 16000) -> int:
+    """Bytes of one 10 ms input packet: ``input_hz / 100`` interleaved (ch1, ch2) pairs — 2560 for the reference's f64 framing, 640 (s16)
+    or 320 (G.711) at 16 kHz, 160 for 8 kHz G.711."""
+    if fmt not in PAIR_BYTES:
+        raise ValueError(f"unknown input format {fmt!r}: one of {', '.join(INPUT_FORMATS)}")
+    return PAIR_BYTES[fmt] * (input_hz // 100)
+
+
+def decode_input(data: bytes, fmt: str = "f64") -> Tuple[np.ndarray, np.ndarray]:
+    """bytes (multiple of 16) -> (x1, x2) float64 arrays; == util.conv_bytearray_2_2floatarray.  ``fmt`` "s16" / "mulaw" / "alaw": packets of
+    interleaved raw pairs -> the decoded samples (``pcm.decode``), float64 as the result packet echoes them."""
+    if fmt != "f64":
+        from . import pcm
+        if len(data) % input_packet_bytes(fmt, 100):
+            raise ValueError(f"{fmt} input length must be a multiple of {PAIR_BYTES[fmt]} bytes")
+        a = pcm.decode(fmt, np.frombuffer(data, dtype=pcm.DTYPES[fmt]).reshape(-1, 2), np.float64)
+        return a[:, 0].copy(), a[:, 1].copy()
     if len(data) % 16:
         raise ValueError("input packet length must be a multiple of 16 bytes")
     a = np.frombuffer(data, dtype="<f8").reshape(-1, 2)
     return a[:, 0].copy(), a[:, 1].copy()
 
 
-def encode_input(x1: Sequence[float], x2: Sequence[float]) -> bytes:
-    """== util.conv_2floatarray_2_bytearray."""
+def encode_input(x1: Sequence[float], x2: Sequence[float], fmt: str = "f64") -> bytes:
+    """== util.conv_2floatarray_2_bytearray.  ``fmt`` "s16" / "mulaw" / "alaw": what a client of such an input port sends — the floats
+    encoded with ``pcm.encode`` (s16: round(x * 2**15); G.711: nearest table value, ties to the smaller magnitude), interleaved;
+    arrays that already hold raw samples (int16 for s16, uint8 for G.711) are sent as they are.  Integers of any other type are refused
+    by name: they are neither floats in [-1, 1) nor samples of this format."""
+    if fmt != "f64":
+        from . import pcm
+        input_packet_bytes(fmt)
+        raw = []
+        for x in (x1, x2):
+            x = np.asarray(x)
+            if x.dtype != pcm.DTYPES[fmt] and x.dtype.kind in "iub":
+                raise TypeError(f"{fmt} input: raw samples are {pcm.DTYPES[fmt].name} and floats are encoded, {x.dtype.name} is neither")
+            raw.append(x if x.dtype == pcm.DTYPES[fmt] else pcm.encode(fmt, x))
+        if raw[0].shape != raw[1].shape:
+            raise ValueError("Two arrays must have the same length")
+        return np.stack(raw, axis=1).astype(pcm.DTYPES[fmt]).tobytes()
     x1 = np.asarray(x1, dtype="<f8")
     x2 = np.asarray(x2, dtype="<f8")
     if x1.shape != x2.shape:
