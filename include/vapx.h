@@ -212,6 +212,50 @@ int vapx_set_input_format(vapx_handle h, int32_t format);
 int32_t vapx_get_input_format(vapx_handle h);
 int vapx_pcm_decode(int32_t format, int64_t n, const void* src, float* dst, void* hip_stream);
 
+/* Input classes: streams of DIFFERENT sample formats and rates in one engine (csrc/input_classes.hip).  vapx_set_input_rate and
+ * vapx_set_input_format hold for every stream of an engine; a service that faces telephone gateways (8 kHz mu-law), WebRTC peers (48 kHz
+ * s16) and clients with the reference's f64 framing at once would need one engine - weights, state, scratch, ports - per combination.  An
+ * input class is a pair (sample format, sample rate); an engine gets a table of classes once, every stream belongs to one class, and ONE
+ * kernel launch per step decodes and resamples the whole ragged batch.  An engine that never gets a table behaves bit for bit as before,
+ * on the kernels and code paths it had.
+ *
+ * vapx_set_input_classes: the rules of vapx_set_input_rate - allowed once, on a freshly created engine with no step yet; refused
+ * (VAPX_E_INVAL, with a message) on a trunk follower, together with vapx_set_input_rate / vapx_set_input_format in either order, for n
+ * outside 1 .. VAPX_MAX_INPUT_CLASSES, for an unknown rate or format and for two equal entries.  The engine allocates the per-stream
+ * history for the largest H among the classes, the `started` flags, the 16 kHz hops [max_batch][2][hop] and staging for the largest slot.
+ * Every stream starts in class 0.  vapx_get_input_classes: the table (at most max entries) and its length; 0 = no table.
+ *
+ * vapx_set_stream_class: queued like vapx_reset_carry and applied by the next step before it touches any state: the stream's 320-sample
+ * carry, its resampler history and its `started` flags are zeroed (a new class is a new signal); the LSTM and the context ring stay, as on
+ * the reference's reconnect.  VAPX_E_RANGE for a bad stream id or class; VAPX_E_INVAL on an engine without a table.
+ * vapx_get_stream_class: the stream's class (negative error code on a bad id or an engine without a table).
+ * vapx_input_slot_bytes: bytes of one batch slot of class cls: 2 * hop_in(cls) * bytes_per_sample(cls), hop_in(c) = input_hz(c) / frame_hz;
+ * 0 for a bad class or an engine without a table.
+ *
+ * LAYOUT of a step on an engine with a table (vapx_step and vapx_step_group): `audio` points to a PACKED block.  Slot k (batch order) holds
+ * [2][hop_in(c_k)] samples of format(c_k) at byte offset sum_{j<k} vapx_input_slot_bytes(c_j), c_k = the class of stream_ids[k].  Every slot
+ * size is a multiple of 16 bytes (every legal hop_in is a multiple of 16 samples); the base address must be 16-byte aligned
+ * (VAPX_E_INVAL).  samples_per_ch must be 0: the classes define the sizes, and a full frame with the caller's carry is refused as with an
+ * input rate.  The engine computes the offsets from the ids, so they must be on the host: VAPX_IDS_DEVICE is VAPX_E_INVAL (the rule a
+ * slower trunk follower already has).  VAPX_AUDIO_HOST (page-locked or pageable, staged in bytes) and VAPX_AUDIO_DEVICE both work;
+ * VAPX_DEFER_JOIN is not honoured (the hops of a tick live in one buffer).  Followers of such a leader work unchanged: the leader owns the
+ * audio.  A class (f, r) stream equals, bit for bit, the stream of an engine with vapx_set_input_format(f) and vapx_set_input_rate(r): the
+ * kernels share one definition of each expansion and of the resampler's chain (csrc/input_decode.h).
+ *
+ * Other calls: vapx_encode_audio is refused, as with an input rate.  vapx_get_state / vapx_set_state behave as with an input rate (the
+ * history restarts).  DELIBERATE GAPS: vapx_export_streams / vapx_import_streams are REFUSED (VAPX_E_INVAL) - a state record has one history
+ * size per engine, records with per-stream history sizes are a follow-up (the precedent of the mixed-rate follower); the group and door front-ends
+ * (vapx_ingest_open_group*, passive shards behind vapx_frontdoor_*) refuse a table - vapx_ingest_open and vapx_ingest_open_fn serve one, with an
+ * input port per class (vapx_ingest_config.input_classes); offline.py keeps
+ * its one engine per rate (its 16 kHz pairs use full frames with a real carry, which a class engine refuses by design). */
+#define VAPX_MAX_INPUT_CLASSES 16      /* 4 formats x 4 rates: every combination fits */
+typedef struct vapx_input_class { int32_t input_hz; int32_t format; } vapx_input_class;   /* 8000|16000|32000|48000, VAPX_PCM_* */
+int vapx_set_input_classes(vapx_handle h, int32_t n, const vapx_input_class* classes);
+int32_t vapx_get_input_classes(vapx_handle h, vapx_input_class* out, int32_t max);
+int vapx_set_stream_class(vapx_handle h, int32_t stream_id, int32_t cls);
+int32_t vapx_get_stream_class(vapx_handle h, int32_t stream_id);
+int64_t vapx_input_slot_bytes(vapx_handle h, int32_t cls);
+
 /* Batch slots (row indices of `out`) of the latest host-output vapx_step whose results were not finite; returns their number
  * (writes at most max_slots of them; slots may be NULL to just count). */
 int32_t vapx_bad_slots(vapx_handle h, int32_t* slots, int32_t max_slots);
@@ -505,6 +549,19 @@ typedef struct vapx_ingest_config {
      the engine (vapx_set_input_format).  The result packet is unchanged: its x1 / x2 blocks carry the decoded samples as f64.  With an engine the
      format is the engine's and this field must be 0 or equal to it; the _fn variants take it from here.  gain != 1 with a raw format is refused. */
   int32_t input_format;
+  /* input classes (optional; a caller that passes a shorter struct - up to and including input_format - gets 0 = no classes): one INPUT PORT PER
+     CLASS in front of an engine with a class table (vapx_set_input_classes).  A connection accepted on class c's port takes the lowest free
+     slot; the front-end calls vapx_set_stream_class(slot, c) and then receives that class's 10 ms packets: f64 pairs cast on the host for
+     VAPX_PCM_F32 (the reference's framing), raw interleaved pairs de-interleaved as they are for s16 and G.711 (the sizes documented at
+     input_format).  The tick packs the ready streams' slots into page-locked staging in batch order: the packed block of "Input classes".
+     Result packets, output ports and the pairing of output connections to streams are unchanged; the echo carries the stream's decoded hop_in
+     samples as f64, as a uniform front-end of that class sends them.  With an engine the table is the engine's: the config's must be empty
+     (n_input_classes = 0) or equal to it; the _fn variant takes it from here.  class_ports_in[c] is the input port of class c (0 = ephemeral,
+     see vapx_ingest_class_ports); port_in is ignored when a table is present.  Refused: input_format != 0 or gain != 1 with a raw class; a
+     passive shard (port_in = -1), vapx_ingest_open_group* and therefore the front door: multi-port groups and doors are not part of this. */
+  int32_t n_input_classes;
+  vapx_input_class input_classes[VAPX_MAX_INPUT_CLASSES];
+  int32_t class_ports_in[VAPX_MAX_INPUT_CLASSES];
 } vapx_ingest_config;
 #define VAPX_INGEST_CORE_SET 2      /* with cpu_count > 0: every front-end thread may run on ANY core of the range (one affinity set) instead of
                                        one core each: keeps other processes' work off the range without nailing a thread to a core that the
@@ -541,6 +598,13 @@ typedef void (*vapx_ingest_reset_fn)(void* user, int32_t stream_id);
 int vapx_ingest_open_fn(vapx_ingest_step_fn step, vapx_ingest_reset_fn reset, void* user, int32_t n_streams, int32_t max_batch,
                         int32_t frame_hz, int32_t mode, const vapx_ingest_config* cfg, vapx_ingest_handle* out);
 int vapx_ingest_ports(vapx_ingest_handle g, int32_t* port_in, int32_t* port_out);   /* (0, 0) for a passive shard */
+/* A front-end with input classes.  vapx_ingest_class_ports: the bound input port of every class (at most max), returns the number of classes
+ * (0 without a table); vapx_ingest_ports then reports class 0's as port_in.  vapx_ingest_stream_class: for the step function of the _fn
+ * variant, which receives the packed block exactly as an engine would - slot k of the batch holds [2][hop_in(c_k)] samples of format(c_k), c_k =
+ * vapx_ingest_stream_class(g, stream_ids[k]), at the byte offset the earlier slots add up to; valid inside the step function (the tick
+ * thread owns the answer); VAPX_E_INVAL without a table, VAPX_E_RANGE for a bad id. */
+int32_t vapx_ingest_class_ports(vapx_ingest_handle g, int32_t* ports, int32_t max);
+int32_t vapx_ingest_stream_class(vapx_ingest_handle g, int32_t stream_id);
 /* One front-end for a trunk group (vapx_attach_trunk): the reference's deployment of vap_main.py, vap_bc_main.py and vap_nod_main.py
  * side by side on one cpc_model file, with ONE input port and the audio encoded once.
  *   - input: cfg->port_in; every accepted connection is a dialogue exactly as with vapx_ingest_open (lowest free slot, carry re-zeroed,

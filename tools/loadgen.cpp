@@ -25,6 +25,10 @@
 //                     pairs and a frame R / hz; the server's engines resample on the GPU (serve --input_rate R) and echo the samples as received
 //   --input-format F  sample format of the dialogues' audio on the input port: f64 (default, the reference's framing), s16, mulaw or alaw: a 10 ms packet
 //                     then carries R / 100 pairs of 2 / 1 / 1 bytes per sample (serve --input_format F decodes on the GPU); not with --inband
+//   --input-class F@R:PORT   repeatable: a server with input classes (serve --input_class F@R:PORT) has one INPUT port per kind of client.  The
+//                     dialogues are dealt over the classes by --class-mix a,b,... (shares, default even), class by class: dialogues 0 .. n0-1 dial
+//                     class 0's port, the next n1 class 1's, ... so that the k-th dialogue still takes slot k; each sends 10 ms packets of its
+//                     class (R / 100 pairs of F).  --port-in, --input-rate and --input-format are then unused; not with --inband
 //   --hist-out F      latency histogram (50 us bins up to 400 ms) as JSON, for merging the processes' percentiles
 // Build: make -C vap-realtime_amd/csrc loadgen   (plain C++17, no dependencies)
 #include <arpa/inet.h>
@@ -88,8 +92,19 @@ static int dial(const char* host, int port) {
   exit(2);
 }
 
+// the audio of one kind of client as its input port takes it (--input-rate / --input-format, or one --input-class)
+struct InClass {
+  std::string format = "f64";
+  int rate = 16000, port = 50007;
+  size_t pair_bytes = 16;           // one sample of both channels on the wire
+  int hop = 0, pk_samples = 0;      // sample pairs per frame / per packet
+  int streams = 0;                  // dialogues of this class
+  std::vector<uint8_t> wire;        // NF frames
+};
+
 struct Stream {
   int fd_in = -1;
+  int cls = 0;
   std::vector<int> fd_out;          // one listener per output port (--ports-out)
   std::vector<std::vector<uint8_t>> rbufs;
   std::vector<long> got;            // result packets read per port; frame k is answered when every port has delivered the packets due up to it
@@ -110,6 +125,8 @@ int main(int argc, char** argv) {
   int inband = 0, procs = 1, rank = 0, total_streams = 0;
   const char* sync_dir = nullptr;
   const char* hist_out = nullptr;
+  std::vector<InClass> classes;     // --input-class; empty: the one class of --port-in / --input-rate / --input-format
+  std::vector<double> class_mix;
   for (int i = 1; i + 1 < argc; i += 2) {
     std::string k = argv[i];
     const char* v = argv[i + 1];
@@ -139,6 +156,16 @@ int main(int argc, char** argv) {
     else if (k == "--sync-dir") sync_dir = v;
     else if (k == "--src-ips") g_src_ips = atoi(v);
     else if (k == "--hist-out") hist_out = v;
+    else if (k == "--input-class" || k == "--input_class") {
+      InClass c;
+      const char *at = strchr(v, '@'), *colon = strchr(v, ':');
+      if (!at || !colon || colon < at) { fprintf(stderr, "--input-class: FORMAT@RATE:PORT, e.g. mulaw@8000:50017\n"); return 2; }
+      c.format.assign(v, at - v); c.rate = atoi(at + 1); c.port = atoi(colon + 1);
+      classes.push_back(c);
+    }
+    else if (k == "--class-mix" || k == "--class_mix") {
+      for (const char* q = v; *q;) { class_mix.push_back(atof(q)); q = strchr(q, ','); if (!q) break; ++q; }
+    }
     else { fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
   }
   if (total_streams <= 0) total_streams = S * procs;
@@ -159,8 +186,24 @@ int main(int argc, char** argv) {
   if (input_rate != 8000 && input_rate != 16000 && input_rate != 32000 && input_rate != 48000) { fprintf(stderr, "--input-rate: 8000, 16000, 32000 or 48000\n"); return 2; }
   if (input_format != "f64" && input_format != "s16" && input_format != "mulaw" && input_format != "alaw") { fprintf(stderr, "--input-format: f64, s16, mulaw or alaw\n"); return 2; }
   if (input_format != "f64" && inband) { fprintf(stderr, "--inband needs --input-format f64: the stamps ride in f64 samples\n"); return 2; }
-  const size_t pair_bytes = input_format == "f64" ? 16 : input_format == "s16" ? 4 : 2;   // one sample of both channels on the wire
-  const int hop = input_rate / hz;                   // sample pairs per frame on the wire
+  const bool by_class = !classes.empty();
+  if (by_class && (inband || P > 1)) { fprintf(stderr, "--input-class does not combine with --inband or several output ports\n"); return 2; }
+  if (!class_mix.empty() && class_mix.size() != classes.size()) { fprintf(stderr, "--class-mix needs one share per --input-class\n"); return 2; }
+  if (!by_class) { InClass c; c.format = input_format; c.rate = input_rate; c.port = port_in; classes.push_back(c); }
+  {   // deal the dialogues over the classes by their shares; the last class takes what rounding leaves
+    double total = 0;
+    for (size_t c = 0; c < classes.size(); ++c) total += class_mix.empty() ? 1.0 : class_mix[c];
+    int dealt = 0;
+    for (size_t c = 0; c < classes.size(); ++c) {
+      InClass& q = classes[c];
+      if (q.rate != 8000 && q.rate != 16000 && q.rate != 32000 && q.rate != 48000) { fprintf(stderr, "--input-class: rates are 8000, 16000, 32000 or 48000\n"); return 2; }
+      if (q.format != "f64" && q.format != "s16" && q.format != "mulaw" && q.format != "alaw") { fprintf(stderr, "--input-class: formats are f64, s16, mulaw or alaw\n"); return 2; }
+      q.streams = c + 1 == classes.size() ? S - dealt : (int)lround(S * (class_mix.empty() ? 1.0 : class_mix[c]) / total);
+      if (q.streams < 0 || total <= 0) { fprintf(stderr, "--class-mix: shares must be positive\n"); return 2; }
+      dealt += q.streams;
+    }
+  }
+  const int hop = classes[0].rate / hz;              // sample pairs per frame on the wire (several output ports / --inband: the one class)
   std::vector<int> ratio(P, 1);                      // frames per packet of each port
   if (!port_samples.empty()) {
     if ((int)port_samples.size() != P) { fprintf(stderr, "--port-samples needs one value per output port\n"); return 2; }
@@ -178,6 +221,12 @@ int main(int argc, char** argv) {
   const int pk_samples = hop / packets_per_frame;
   // 8 frames of synthetic two-speaker audio per phase class (harmonic stack + noise), f64 interleaved like the wire
   const int NF = 8;
+  for (InClass& cl : classes) {
+  const std::string& input_format = cl.format;
+  const int input_rate = cl.rate, hop = input_rate / hz;
+  const size_t pair_bytes = input_format == "f64" ? 16 : input_format == "s16" ? 4 : 2;
+  cl.pair_bytes = pair_bytes; cl.hop = hop; cl.pk_samples = hop / packets_per_frame;
+  std::vector<uint8_t>& wire = cl.wire;
   std::vector<double> audio((size_t)NF * hop * 2);
   for (int i = 0; i < NF * hop; ++i) {
     const double t = i / (double)input_rate;
@@ -185,7 +234,7 @@ int main(int argc, char** argv) {
     audio[2 * i + 1] = 0.15 * sin(2 * M_PI * 210.0 * t + 1.0) * (i / hop % 2 ? 1.0 : 0.05) + 1e-3 * ((rand() % 2001) / 1000.0 - 1.0);
   }
   // the same audio as the input port takes it: f64 pairs (the reference's framing), or s16 / G.711 pairs (serve --input_format)
-  std::vector<uint8_t> wire((size_t)NF * hop * pair_bytes);
+  wire.assign((size_t)NF * hop * pair_bytes, 0);
   if (input_format == "f64") memcpy(wire.data(), audio.data(), wire.size());
   else {
     int table[256];                                  // the G.711 expansion to 16-bit linear (ITU-T closed forms)
@@ -209,6 +258,7 @@ int main(int argc, char** argv) {
       wire[i] = (uint8_t)best;
     }
   }
+  }   // every class's wire audio
   {   // two sockets per stream: raise the soft descriptor limit if it is short
     rlimit rl;
     const rlim_t need = (rlim_t)(1 + P) * S + 256;
@@ -220,7 +270,13 @@ int main(int argc, char** argv) {
   }
   std::vector<Stream> st(S);
   const double td0 = now_s();
-  for (int i = 0; i < S; ++i) st[i].fd_in = dial(host, port_in);
+  {   // class by class: within a port the server adopts in dial order, so dialogue k takes slot k and the k-th output connection hears it
+    int i = 0;
+    for (size_t c = 0; c < classes.size(); ++c) {
+      for (int k = 0; k < classes[c].streams; ++k, ++i) { st[i].cls = (int)c; st[i].fd_in = dial(host, classes[c].port); }
+      if (c + 1 < classes.size()) usleep((useconds_t)(300000 + 100 * classes[c].streams));
+    }
+  }
   const double td1 = now_s();
   usleep((useconds_t)(300000 + 100 * S));            // let the server adopt every connection before the next step
   meet("inputs");
@@ -272,7 +328,7 @@ int main(int argc, char** argv) {
     auto later = [](const Ev& a, const Ev& b) { return a.t > b.t; };
     std::priority_queue<Ev, std::vector<Ev>, decltype(later)> q(later);
     for (int i : mine) q.push({t_start + period * ((long)i * procs + rank) / total_streams + period / packets_per_frame, i, 0, 0});
-    std::vector<double> pkt((size_t)pk_samples * 2);
+    std::vector<double> pkt((size_t)pk_samples * 2);   // (--inband: the one class)
     while (!stop.load() && !q.empty()) {
       Ev e = q.top();
       q.pop();
@@ -289,8 +345,9 @@ int main(int argc, char** argv) {
         clock_nanosleep(CLOCK_MONOTONIC, TIMER_ABSTIME, &ts, nullptr);
         n = now_s();
       }
-      const uint8_t* p = wire.data() + ((size_t)(e.frame % NF) * hop + (size_t)e.pk * pk_samples) * pair_bytes;
-      size_t left = (size_t)pk_samples * pair_bytes;
+      const InClass& cl = classes[st[e.s].cls];
+      const uint8_t* p = cl.wire.data() + ((size_t)(e.frame % NF) * cl.hop + (size_t)e.pk * cl.pk_samples) * cl.pair_bytes;
+      size_t left = (size_t)cl.pk_samples * cl.pair_bytes;
       if (e.pk + 1 == packets_per_frame) {   // time stamp BEFORE the frame's last packet leaves: the answer may overtake us
         const double ts = now_s();
         if (inband) {                          // the stamp and the dialogue id travel in the first sample pair of this packet
@@ -460,6 +517,13 @@ int main(int argc, char** argv) {
   }
   printf("\"inband\": %d, \"procs\": %d, \"rank\": %d, \"route_changes\": %ld, \"inband_unreadable\": %ld, ", inband, procs, rank, route_changes.load(), inband_bad.load());
   printf("\"output_ports\": %d, ", P);
+  if (by_class) {
+    printf("\"input_classes\": [");
+    for (size_t c = 0; c < classes.size(); ++c)
+      printf("%s{\"class\": \"%s@%d\", \"port\": %d, \"streams\": %d, \"packet_bytes\": %zu}", c ? ", " : "", classes[c].format.c_str(), classes[c].rate,
+             classes[c].port, classes[c].streams, (size_t)classes[c].pk_samples * classes[c].pair_bytes);
+    printf("], ");
+  }
   if (mixed) {
     printf("\"port_size_mismatches\": %ld, \"per_port\": [", size_mismatch.load());
     for (int p = 0; p < P; ++p) {

@@ -145,6 +145,11 @@ def main():
                     help="sample format of the dialogues' audio on the input port: f64 is the reference's framing; s16 / mulaw / alaw packets carry "
                          "input_rate / 100 sample pairs of 2 / 1 / 1 bytes per sample and the engines decode on the GPU (serve --input_format); the "
                          "native front-end only, and not with --inband (the stamps ride in f64 samples)")
+    ap.add_argument("--input-class", "--input_class", dest="input_class", action="append", default=None, metavar="FORMAT@RATE",
+                    help="repeatable: ONE engine with input classes behind one input port per class (serve --input_class); the dialogues are spread "
+                         "over the class ports by --class_mix.  Real engines (or --fake) behind the native front-end, one load-generator process")
+    ap.add_argument("--class-mix", "--class_mix", dest="class_mix", default="", help="with --input_class: the share of the dialogues on each class, "
+                                                                                      "comma-separated (0.5,0.25,0.25; default: even)")
     ap.add_argument("--max-wait-ms", type=float, default=2.0)
     ap.add_argument("--min-batch", type=int, default=0)
     ap.add_argument("--max-batch", type=int, default=0)
@@ -196,6 +201,13 @@ def main():
         rate_kw["input_format"] = args.input_format
     assert args.input_rate == 16000 or not (args.fake or args.standin or args.python), "--input-rate needs real engines behind the native front-end"
     from vap_realtime_amd import dist_util, engine, ingest
+    classes = None
+    if args.input_class:
+        assert args.input_rate == 16000 and args.input_format == "f64", "--input_class names every class's rate and format itself"
+        assert not (args.standin or args.python or args.inband or args.loadgen_procs > 1 or args.shards > 1 or "+" in args.mode), \
+            "--input_class: one engine (or --fake) behind the native front-end, one load-generator process, no --inband"
+        classes = [ingest.parse_input_class(t)[0] for t in args.input_class]
+        rate_kw = {"input_classes": classes}
     srv = None
     # placement: the front-end's tick / receive / sender threads on consecutive cores of the GPU's NUMA node, the load generator on the
     # other cores (another node's first) — 4096 client sockets' softirq work otherwise lands on whatever core a front-end thread runs on
@@ -310,11 +322,14 @@ def main():
                 "native front-end over the native stand-in step function")
     elif args.fake:
         def step(ids, audio, out):
+            if classes:                                   # the packed block of an engine with input classes: a uint8 array, slots of their classes' sizes
+                out[:, 0:2] = float(audio[:16].mean())
+                return 0
             out[:, 0:2] = np.abs(audio.astype(np.float32)).mean(axis=2)
             return 0
         srv = ingest.NativeServer.over_function(step, S, args.hz, max_batch=args.max_batch or S, max_wait_s=args.max_wait_ms * 1e-3,
                                                 min_batch=args.min_batch, rx_threads=args.rx_threads, tx_threads=args.tx_threads,
-                                                input_format=args.input_format)
+                                                **({"input_classes": classes} if classes else {"input_format": args.input_format}))
         cores = client_cores = None                       # (over_function has no placement argument)
         kind = "native front-end over a trivial step function"
     elif "+" in args.mode:
@@ -392,7 +407,8 @@ def main():
 
     def cmd_for(r):
         ports = getattr(srv, "ports_out", None)         # a group front-end: one output port per model
-        c = [loadgen, "--port-in", str(srv.port_in)] + (["--ports-out", ",".join(str(p) for p in ports.values())] if ports else
+        c = [loadgen] + (sum((["--input-class", f"{t.split(':')[0]}:{port}"] for t, port in zip(args.input_class, srv.class_ports)), []) +
+                         (["--class-mix", args.class_mix] if args.class_mix else []) if classes else ["--port-in", str(srv.port_in)]) + (["--ports-out", ",".join(str(p) for p in ports.values())] if ports else
                                                         ["--port-out", str(srv.port_out)])
         if ports and port_samples:                      # a model slower than the leader answers every R-th frame with one packet of R hops
             c += ["--port-samples", ",".join(str(port_samples[m]) for m in ports)]
@@ -467,6 +483,9 @@ def main():
                              "wall_s": round(wall, 2)}
     res["server_process_cpu_s"] = round((cpu1[1].user + cpu1[1].system) - (cpu0[1].user + cpu0[1].system), 2)   # front-end threads + the tick's host side
     res["input_format"], res["input_rate"] = args.input_format, args.input_rate
+    if classes:
+        res["input_format"] = res["input_rate"] = None
+        res["class_mix"] = args.class_mix or "even"
     res["server"] = kind
     res["placement"] = {"front_end_cores": list(cores) if cores else None, "client_cores": ([client_cores[0], client_cores[-1], len(client_cores)] if client_cores else None)}
     if hasattr(srv, "stats"):

@@ -18,6 +18,7 @@
 #include "engine_buffers.h"
 #include "fused_blocks.h"
 #include "gemm_f32.h"
+#include "input_classes.h"
 #include "vap_kernels.h"
 #include "vapx_layout.h"
 
@@ -128,6 +129,16 @@ struct vapx_engine : Geometry {
   int in_fmt = VAPX_PCM_F32;              // VAPX_PCM_F32: the input is fp32, pcm_out does not exist
   float* pcm_out = nullptr;               // [max_batch][2][max(hop_in, L)]
   size_t pcm_floats() const { return (size_t)cfg.max_batch * 2 * (size_t)std::max(hop_in, L); }
+  // input classes (vapx_set_input_classes; input_classes.hip): every stream has a (format, rate) of its own; ONE launch turns the tick's packed
+  // block into rs_out.  rs_hist (a record for the largest H of the table), rs_started and rs_out above serve it; in_hz and in_fmt stay unset
+  int n_cls = 0;                          // 0: no table, nothing below exists
+  InputClassGeom cls[VAPX_MAX_INPUT_CLASSES] = {};
+  vapx_input_class cls_pub[VAPX_MAX_INPUT_CLASSES] = {};   // the table as the caller gave it
+  size_t cls_lds = 0;                     // floats of dynamic LDS: the largest window of the table
+  std::vector<int32_t> stream_cls;        // [max_streams] a stream's class; the host builds the slot descriptors from it
+  Staged<int> cls_slots;                  // [max_batch] InputSlot {byte_off, cls} of a step
+  std::vector<InputSlot> cls_slots_host;
+  size_t cls_slot_bytes(int c) const { return (size_t)2 * cls[c].hop_in * (size_t)pcm_bytes_per_sample(cls[c].fmt); }
   float* out_pinned = nullptr;
   int last_B = 0, last_G = 1;
   bool last_tail_fused = false;           // some overlap group of the latest encoder pass ran conv_tail_kernel: h2 / h3 were not written
@@ -951,7 +962,7 @@ void vapx_destroy(vapx_handle h) {
 #endif
   for (void* p : {(void*)h->w, (void*)h->ring, (void*)h->ring_qkv, (void*)h->h_state, (void*)h->c_state, (void*)h->carry, (void*)h->frames_seen}) dfree(p);
   release_scratch(h->sc, /*encoder_only=*/false);
-  release(h->audio); release(h->ids); release(h->mix); release(h->sio_ids);
+  release(h->audio); release(h->ids); release(h->mix); release(h->sio_ids); release(h->cls_slots);
   dfree(h->rs_hist); dfree(h->rs_out); dfree(h->rs_started);
   dfree(h->pcm_out);
   dfree(h->gw_dev);
@@ -1166,7 +1177,15 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
                   "needs host ids (or none), the host decides which streams have a frame due", h->R);
   } else {
     if (!audio) return fail(h, VAPX_E_INVAL, "null audio");
-    if (h->in_hz) {
+    if (h->n_cls) {
+      if (spc != 0)
+        return fail(h, VAPX_E_INVAL, "samples_per_ch must be 0 on an engine with input classes: every slot's size is its stream's class's "
+                    "(vapx_input_slot_bytes); a full frame with the caller's carry is defined at 16 kHz fp32 only");
+      if (stream_ids && (flags & VAPX_IDS_DEVICE))
+        return fail(h, VAPX_E_INVAL, "an engine with input classes needs host stream ids (VAPX_IDS_DEVICE is refused): the host computes every "
+                    "slot's offset in the packed block from its stream's class");
+      if ((uintptr_t)audio & 15) return fail(h, VAPX_E_INVAL, "the packed audio block of an engine with input classes must be 16-byte aligned");
+    } else if (h->in_hz) {
       if (spc != h->hop_in)
         return fail(h, VAPX_E_INVAL, "samples_per_ch must be %d (the hop at the engine's input rate of %d Hz); a full frame with the caller's carry "
                     "is defined at 16 kHz only", h->hop_in, h->in_hz);
@@ -1195,7 +1214,7 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
   // free-running groups are only safe when nothing of this step is staged through engine-owned buffers on `st`
   // (host audio / host ids would be overwritten under a still-running group of the previous tick)
   const bool all_device = (flags & VAPX_OUT_DEVICE) && (lead || (flags & VAPX_AUDIO_DEVICE)) && (!stream_ids || (flags & VAPX_IDS_DEVICE));
-  const bool defer_join = G > 1 && (flags & VAPX_DEFER_JOIN) && all_device && !slower && !h->in_hz && !h->in_fmt;   // rs_out / pcm_out is one buffer: the next tick's resampler / decoder must not overtake a running group
+  const bool defer_join = G > 1 && (flags & VAPX_DEFER_JOIN) && all_device && !slower && !h->in_hz && !h->in_fmt && !h->n_cls;   // rs_out / pcm_out is one buffer: the next tick's resampler / decoder must not overtake a running group
   int rc = VAPX_OK;
   // a different batch split re-slices the shared scratch, and a reset touches state a running group may still use:
   // in both cases the previous tick's groups are joined first
@@ -1248,7 +1267,27 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     ids = h->mix.dev;   // the due streams' ids, in compact order
   }
   const float* ad = audio;
-  if (!lead && !(flags & VAPX_AUDIO_DEVICE)) {
+  if (h->n_cls) {   // a packed block of per-class slots -> 16 kHz fp32 hops, one launch for the whole ragged batch before the overlap groups fork
+    size_t bytes = 0;
+    for (int i = 0; i < n; ++i) {
+      const int c = h->stream_cls[stream_ids ? stream_ids[i] : i];
+      h->cls_slots_host[i] = {(uint32_t)bytes, c};
+      bytes += h->cls_slot_bytes(c);   // below 2^32: vapx_set_input_classes refused a table whose largest slot x max_batch is not
+    }
+    HIPCHK(h, h->cls_slots.upload((const int*)h->cls_slots_host.data(), (size_t)2 * n, st));
+    if (!(flags & VAPX_AUDIO_DEVICE)) {   // as below, in bytes: every slot is a multiple of 16
+      if (is_pinned_host(audio)) HIPCHK(h, hipMemcpyAsync(h->audio.dev, audio, bytes, hipMemcpyHostToDevice, st));
+      else HIPCHK(h, h->audio.upload(audio, bytes / sizeof(float), st));
+      ad = h->audio.dev;
+    }
+    InputClassesArgs ia;
+    ia.in = (const unsigned char*)ad; ia.slots = (const InputSlot*)h->cls_slots.dev; ia.ids = ids; ia.hist = h->rs_hist; ia.started = h->rs_started;
+    ia.out = h->rs_out; ia.rec = h->rs_rec; ia.hop = h->hop;
+    memcpy(ia.cls, h->cls, sizeof ia.cls);
+    HIPCHK(h, launch_input_classes(ia, n, h->cls_lds, st));
+    ad = h->rs_out;
+    spc = h->hop;
+  } else if (!lead && !(flags & VAPX_AUDIO_DEVICE)) {
     const size_t bytes = (size_t)n * 2 * spc * bps;   // a raw format: a whole number of dwords (checked above), never more than the fp32 block
     // pageable memory: stage through the engine's pinned buffer (an async copy from pageable memory is a hidden synchronous staging
     // copy inside the runtime); vapx_host_alloc memory: copy straight from the caller
@@ -1442,6 +1481,7 @@ int vapx_attach_trunk(vapx_handle f, vapx_handle lead) {
     return fail(f, VAPX_E_INVAL, "attach a stand-alone engine to a leader that is not itself a follower");
   if (f->tick != 0 || lead->tick != 0) return fail(f, VAPX_E_INVAL, "attach before the first step of either engine");
   if (f->in_hz) return fail(f, VAPX_E_INVAL, "this engine has an input rate of its own (%d Hz): a follower takes no audio, set the rate on the leader", f->in_hz);
+  if (f->n_cls) return fail(f, VAPX_E_INVAL, "this engine has input classes of its own: a follower takes no audio, set the table on the leader");
   if (f->in_fmt) return fail(f, VAPX_E_INVAL, "this engine has an input format of its own (%d): a follower takes no audio, set the format on the leader", f->in_fmt);
   if (f->cfg.device_id != lead->cfg.device_id || f->cfg.max_streams != lead->cfg.max_streams || f->cfg.max_batch != lead->cfg.max_batch)
     return fail(f, VAPX_E_INVAL, "device, max_streams and max_batch must match the leader's");
@@ -1555,7 +1595,7 @@ int vapx_set_state(vapx_handle h, int32_t sid, const float* ring, int32_t n_fram
   if (h->trunk && (lstm || carry)) return fail(h, VAPX_E_INVAL, "LSTM / carry state lives in the trunk leader");
   { int rc = quiesce(h); if (rc) return rc; }
   const int T = h->T;
-  if (h->in_hz) {   // the call has no place for the resampler history: the stream's input starts as a new signal
+  if (h->rs_hist) {   // the call has no place for the resampler history: the stream's input starts as a new signal
     HIPCHK(h, hipMemset(h->rs_hist + (size_t)sid * h->rs_rec, 0, (size_t)h->rs_rec * sizeof(float)));
     HIPCHK(h, hipMemset(h->rs_started + (size_t)sid * 2, 0, 2 * sizeof(int)));
   }
@@ -1690,6 +1730,8 @@ size_t vapx_state_floats(vapx_handle h, int32_t flags) { return h ? state_floats
 
 int vapx_export_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, float* dst, int32_t flags, void* hip_stream) {
   if (!h) return VAPX_E_INVAL;
+  if (h->n_cls) return fail(h, VAPX_E_INVAL, "%s is refused on an engine with input classes: a state record has one resampler history size per engine, "
+                            "records with per-stream history sizes do not exist yet (vapx_get_state / vapx_set_state work)", "vapx_export_streams");
   { int rc = sio_check(h, "vapx_export_streams", n, stream_ids, dst, flags); if (rc) return rc; }
   hipStream_t st = (hipStream_t)hip_stream;
   int rc = sio_begin(h, st);
@@ -1719,6 +1761,8 @@ int vapx_export_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, flo
 
 int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* src, int32_t flags, void* hip_stream) {
   if (!h) return VAPX_E_INVAL;
+  if (h->n_cls) return fail(h, VAPX_E_INVAL, "%s is refused on an engine with input classes: a state record has one resampler history size per engine, "
+                            "records with per-stream history sizes do not exist yet (vapx_get_state / vapx_set_state work)", "vapx_import_streams");
   { int rc = sio_check(h, "vapx_import_streams", n, stream_ids, src, flags); if (rc) return rc; }
   const size_t rec = state_floats(h, flags);
   const bool with_cache = (flags & VAPX_STATE_CACHE) != 0, on_host = !(flags & VAPX_OUT_DEVICE);
@@ -1800,6 +1844,7 @@ int vapx_encode_audio(vapx_handle h, int32_t n, const int32_t* stream_ids, const
   if (h->trunk || h->orphaned) return fail(h, VAPX_E_INVAL, "a trunk follower has no encoder; call the leader");
   if (n < 1 || n > h->cfg.max_batch) return fail(h, VAPX_E_RANGE, "n=%d outside [1,%d]", n, h->cfg.max_batch);
   if (!frames || !e) return fail(h, VAPX_E_INVAL, "null frames/e");
+  if (h->n_cls) return fail(h, VAPX_E_INVAL, "vapx_encode_audio takes complete 16 kHz fp32 frames that carry their own carry; this engine has input classes");
   if (h->in_hz) return fail(h, VAPX_E_INVAL, "vapx_encode_audio takes complete 16 kHz frames that carry their own carry; this engine's input rate is %d Hz", h->in_hz);
   hipStream_t st = (hipStream_t)hip_stream;
   (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
@@ -1982,6 +2027,7 @@ int vapx_set_input_rate(vapx_handle h, int32_t input_hz) {
   if (input_hz != 16000 && !resample_geometry(input_hz, &g))
     return fail(h, VAPX_E_INVAL, "input rate %d Hz: supported are 8000, 16000, 32000 and 48000", input_hz);
   if (h->trunk || h->orphaned) return fail(h, VAPX_E_INVAL, "a trunk follower takes no audio: set the input rate on the leader");
+  if (h->n_cls) return fail(h, VAPX_E_INVAL, "this engine has input classes (vapx_set_input_classes): the rate is each class's own");
   if (h->tick != 0 || h->in_hz) return fail(h, VAPX_E_INVAL, "set the input rate once, on a freshly created engine, before its first step");
   if (input_hz == 16000) return VAPX_OK;
   (void)hipGetLastError();
@@ -2024,6 +2070,7 @@ int vapx_set_input_format(vapx_handle h, int32_t format) {
   if (format < VAPX_PCM_F32 || format > VAPX_PCM_ALAW)
     return fail(h, VAPX_E_INVAL, "input format %d: known are 0 (f32), 1 (s16), 2 (mulaw) and 3 (alaw)", format);
   if (h->trunk || h->orphaned) return fail(h, VAPX_E_INVAL, "a trunk follower takes no audio: set the input format on the leader");
+  if (h->n_cls) return fail(h, VAPX_E_INVAL, "this engine has input classes (vapx_set_input_classes): the format is each class's own");
   if (h->tick != 0 || h->in_fmt) return fail(h, VAPX_E_INVAL, "set the input format once, on a freshly created engine, before its first step");
   if (format == VAPX_PCM_F32) return VAPX_OK;
   (void)hipGetLastError();
@@ -2035,6 +2082,106 @@ int vapx_set_input_format(vapx_handle h, int32_t format) {
 }
 
 int32_t vapx_get_input_format(vapx_handle h) { return !h ? VAPX_E_INVAL : h->in_fmt; }
+
+int vapx_set_input_classes(vapx_handle h, int32_t n, const vapx_input_class* classes) {
+  if (!h) return VAPX_E_INVAL;
+  if (h->trunk || h->orphaned) return fail(h, VAPX_E_INVAL, "a trunk follower takes no audio: set the input classes on the leader");
+  if (h->in_hz || h->in_fmt)
+    return fail(h, VAPX_E_INVAL, "this engine has an input %s of its own (vapx_set_input_%s): input classes replace both calls, they do not combine",
+                h->in_hz ? "rate" : "format", h->in_hz ? "rate" : "format");
+  if (h->tick != 0 || h->n_cls) return fail(h, VAPX_E_INVAL, "set the input classes once, on a freshly created engine, before its first step");
+  if (n < 1 || n > VAPX_MAX_INPUT_CLASSES || !classes)
+    return fail(h, VAPX_E_INVAL, "n = %d input classes: the table holds 1 .. %d", n, VAPX_MAX_INPUT_CLASSES);
+  InputClassGeom tab[VAPX_MAX_INPUT_CLASSES] = {};
+  int Hmax = 0;
+  size_t slot_max = 0;
+  for (int i = 0; i < n; ++i) {
+    const int hz = classes[i].input_hz, fmt = classes[i].format;
+    ResampleGeom g = {};
+    if (hz != 16000 && !resample_geometry(hz, &g))
+      return fail(h, VAPX_E_INVAL, "class %d: input rate %d Hz: supported are 8000, 16000, 32000 and 48000", i, hz);
+    if (fmt < VAPX_PCM_F32 || fmt > VAPX_PCM_ALAW)
+      return fail(h, VAPX_E_INVAL, "class %d: input format %d: known are 0 (f32), 1 (s16), 2 (mulaw) and 3 (alaw)", i, fmt);
+    for (int j = 0; j < i; ++j)
+      if (classes[j].input_hz == hz && classes[j].format == fmt)
+        return fail(h, VAPX_E_INVAL, "classes %d and %d are equal (format %d at %d Hz): a duplicate entry", j, i, fmt, hz);
+    tab[i] = {g.orig, g.nnew, g.width, g.K, g.d, g.H, hz / h->cfg.frame_hz, fmt};   // 16 kHz: orig = 0, no window
+    Hmax = std::max(Hmax, g.H);
+    slot_max = std::max(slot_max, (size_t)2 * tab[i].hop_in * (size_t)pcm_bytes_per_sample(fmt));
+  }
+  if ((size_t)h->cfg.max_batch * slot_max > 0xFFFFFFFFull)
+    return fail(h, VAPX_E_INVAL, "max_batch %d x the largest slot (%zu bytes) passes 4 GiB: a slot's offset in the packed block is 32 bits", h->cfg.max_batch, slot_max);
+  (void)hipGetLastError();
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  HIPCHK(h, hipDeviceSynchronize());
+  const size_t S = h->cfg.max_streams, B = h->cfg.max_batch;
+  const int rec = std::max(4, (2 * Hmax + 3) & ~3);
+  const size_t stage_floats = B * slot_max / sizeof(float);   // staging for host audio: the largest slot in every batch slot
+  float *hist = nullptr, *rout = nullptr, *adev = nullptr, *apin = nullptr;
+  int *started = nullptr, *sdev = nullptr;
+  Staged<int> slots;
+  hipError_t e = dalloc(&hist, S * (size_t)rec);
+  if (e == hipSuccess) e = dalloc(&started, S * 2);
+  if (e == hipSuccess) e = dalloc(&rout, B * 2 * (size_t)h->hop);
+  if (e == hipSuccess) e = dalloc(&sdev, B * 2);
+  if (e == hipSuccess) e = slots.create_pinned(B * 2);
+  if (e == hipSuccess && stage_floats > B * 2 * (size_t)h->L) {
+    e = dalloc(&adev, stage_floats);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&apin, stage_floats * sizeof(float), hipHostMallocDefault);
+  }
+  if (e != hipSuccess) {   // the engine stays as it was
+    (void)hipGetLastError();
+    dfree(hist); dfree(started); dfree(rout); dfree(adev);
+    slots.dev = sdev;
+    release(slots);
+    if (apin) (void)hipHostFree(apin);
+    return fail(h, e == hipErrorOutOfMemory ? VAPX_E_NOMEM : VAPX_E_HIP, "state and staging for %d input classes: %s", n, hipGetErrorString(e));
+  }
+  if (adev) {
+    dfree(h->audio.dev); h->audio.dev = adev;
+    (void)hipHostFree(h->audio.pin); h->audio.pin = apin;
+  }
+  slots.dev = sdev;
+  h->cls_slots = slots;
+  h->cls_slots_host.assign(B, InputSlot{0, 0});
+  h->rs_hist = hist; h->rs_started = started; h->rs_out = rout; h->rs_rec = rec;
+  memcpy(h->cls, tab, sizeof tab);
+  memcpy(h->cls_pub, classes, (size_t)n * sizeof *classes);
+  h->cls_lds = input_classes_lds_floats(tab, n);
+  h->stream_cls.assign(S, 0);
+  h->n_cls = n;
+  return VAPX_OK;
+}
+
+int32_t vapx_get_input_classes(vapx_handle h, vapx_input_class* out, int32_t max) {
+  if (!h) return VAPX_E_INVAL;
+  for (int i = 0; out && i < h->n_cls && i < max; ++i) out[i] = h->cls_pub[i];
+  return h->n_cls;
+}
+
+int vapx_set_stream_class(vapx_handle h, int32_t sid, int32_t cls) {
+  if (!h) return VAPX_E_INVAL;
+  if (!h->n_cls) return fail(h, VAPX_E_INVAL, "this engine has no input classes (vapx_set_input_classes)");
+  if (sid < 0 || sid >= h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "stream id %d out of range [0,%d)", sid, h->cfg.max_streams);
+  if (cls < 0 || cls >= h->n_cls) return fail(h, VAPX_E_RANGE, "input class %d out of range [0,%d)", cls, h->n_cls);
+  // a new class is a new signal: the carry-only request of vapx_reset_carry (carry, resampler history, started flags), applied by the next
+  // step before it touches any state; that step is also the first to build a slot descriptor from the stream's class, which lives on the host
+  const int rc = vapx_reset_carry(h, sid);
+  if (rc == VAPX_OK) h->stream_cls[sid] = cls;
+  return rc;
+}
+
+int32_t vapx_get_stream_class(vapx_handle h, int32_t sid) {
+  if (!h) return VAPX_E_INVAL;
+  if (!h->n_cls) return fail(h, VAPX_E_INVAL, "this engine has no input classes (vapx_set_input_classes)");
+  if (sid < 0 || sid >= h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "stream id %d out of range [0,%d)", sid, h->cfg.max_streams);
+  return h->stream_cls[sid];
+}
+
+int64_t vapx_input_slot_bytes(vapx_handle h, int32_t cls) {
+  if (!h || cls < 0 || cls >= h->n_cls) return 0;
+  return (int64_t)h->cls_slot_bytes(cls);
+}
 
 int vapx_pcm_decode(int32_t format, int64_t n, const void* src, float* dst, void* hip_stream) {
   if (!src || !dst || n < 1 || n > ((int64_t)1 << 40) || format < VAPX_PCM_S16 || format > VAPX_PCM_ALAW) return VAPX_E_INVAL;

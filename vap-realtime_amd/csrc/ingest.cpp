@@ -8,6 +8,11 @@
 //   tick thread             batches the ready frames (ragged), vapx_step (host in / host out), hands rows to the senders
 //   tx threads              encode header / tail, sendmsg() with the echo arrays as iovecs (no copy), free the frame buffer
 //
+// Input classes (vapx_ingest_config.input_classes; vapx.h "Input classes"): one input port per class; a connection accepted on class c's port
+// makes its slot a stream of class c, whose geometry (InGeo: format, hop, packet size) every thread takes from the slot or from the queued
+// frame instead of from the front-end; the tick packs the ready frames' slots back to back, which is the packed block the engine takes.
+// A front-end without a table has one geometry, geo[0], and every slot is of it.
+//
 // A raw input format (vapx_ingest_config.input_format: s16, mulaw, alaw; vapx.h "Input format"): the receive threads only de-interleave
 // the samples into the staging as they are (no cast, no f32 staging, no f64 echo copy), the tick hands the raw block to the step, whose
 // engine decodes on the device, and a sender expands the frame's echo from the raw staging by pcm_tables.h when it encodes the packet.
@@ -57,6 +62,9 @@
 #pragma weak vapx_get_input_rate
 // the engine's input format (vapx_set_input_format): weak for the same reason; a program without it takes fp32
 #pragma weak vapx_get_input_format
+// the engine's input classes (vapx_set_input_classes): weak for the same reason; a program without them has no table
+#pragma weak vapx_get_input_classes
+#pragma weak vapx_set_stream_class
 
 namespace {
 
@@ -161,8 +169,19 @@ struct Hist {   // log2-spaced latency histogram, 8 sub-buckets per octave from 
   void clear() { for (auto& x : b) x = 0; cnt = 0; sum_us = 0; max_us = 0; }
 };
 
+// the geometry of an input port: the front-end's one, or one per input class
+struct InGeo {
+  int fmt = VAPX_PCM_F32;                  // VAPX_PCM_F32 = the reference's f64 pairs, cast to f32 on the host; S16 / MULAW / ALAW = raw samples
+  int in_hz = 16000;
+  int hop = 0;                             // sample PAIRS per frame on the wire = in_hz / frame_hz
+  int bps = 4;                             // bytes per sample of the staging
+  int pair_bytes = PAIR_BYTES;             // one sample of both channels on the wire
+  size_t frame_bytes() const { return (size_t)2 * hop * bps; }   // a frame of the staging = a slot of the step's block
+};
+
 struct Slot {
   int fd_in = -1;
+  int cls = 0;                             // index into vapx_ingest::geo; written at adoption, before the socket joins an epoll set
   std::atomic<uint32_t> gen{0};           // bumped per connection: queued frames of a dead connection are dropped (read by the tick thread)
   std::atomic<int> state[NBUF];
   double t_ready[NBUF] = {};
@@ -179,7 +198,8 @@ struct Slot {
   Slot() { for (auto& s : state) s = B_FREE; }
 };
 
-struct Ready { int slot; int buf; uint32_t gen; double t; };
+struct Ready { int slot; int buf; uint32_t gen; double t; int cls; };   // cls: the slot's class when the frame was completed
+struct ResetReq { int slot; int carry_only; int cls; };                // cls >= 0: the connection's input class (a front-end with a table)
 
 struct Job {                               // one tick's rows on their way out
   int n = 0;
@@ -212,6 +232,7 @@ struct OutPort {
 }  // namespace
 
 struct vapx_ingest {
+  vapx_ingest() { for (int& fd : cls_lsock) fd = -1; }
   vapx_ingest_config cfg;
   vapx_ingest_step_fn step = nullptr;
   vapx_ingest_reset_fn reset = nullptr;
@@ -224,6 +245,15 @@ struct vapx_ingest {
   int fmt = VAPX_PCM_F32;
   int bps = 4;                             // bytes per sample of the staging blocks
   int pair_bytes = PAIR_BYTES;             // one sample of both channels on the wire
+  // input classes: geo[c] is class c's geometry and cls_lsock / cls_port its input port; without a table n_cls = 0 and geo[0] restates the
+  // five fields above.  frame_stride / echo_stride: bytes / doubles between two frame buffers, sized for the largest class
+  int n_cls = 0;
+  InGeo geo[VAPX_MAX_INPUT_CLASSES];
+  vapx_input_class cls_pub[VAPX_MAX_INPUT_CLASSES] = {};
+  int cls_lsock[VAPX_MAX_INPUT_CLASSES], cls_port[VAPX_MAX_INPUT_CLASSES] = {};
+  size_t frame_stride = 0, echo_stride = 0;
+  std::vector<int32_t> tick_cls;           // [S] tick thread only: a stream's class as the engine (or the step function) knows it
+  void (*set_class)(void* user, int32_t stream_id, int32_t cls) = nullptr;   // tick thread: vapx_set_stream_class on the engine
   int M = 1;                               // models = output ports (> 1: a trunk group, `step` fills wire blocks)
   OutPort ports[MAX_MODELS];
   size_t row_floats = VAPX_OUT_STRIDE;     // floats per stream in a job's block, all models
@@ -253,7 +283,7 @@ struct vapx_ingest {
   std::mutex ready_mu;
   std::condition_variable ready_cv;
   std::vector<Ready> ready;                // rx -> tick
-  std::vector<std::pair<int, int>> resets; // (slot, carry_only) rx -> tick, under ready_mu
+  std::vector<ResetReq> resets;            // accept -> tick, under ready_mu
   std::vector<std::mutex> resume_mu;
   std::vector<std::vector<int>> resume;    // tick/tx -> rx: slots with a free buffer again
 
@@ -282,9 +312,9 @@ struct vapx_ingest {
   std::mutex link_mu;                      // serialises the sends (rx / tx / link threads)
   std::thread link_thread;
 
-  float* f32buf(int slot, int buf) { return stage + ((size_t)slot * NBUF + buf) * 2 * hop; }
-  double* f64buf(int slot, int buf) { return echo.data() + ((size_t)slot * NBUF + buf) * 2 * hop; }
-  uint8_t* rawbuf(int slot, int buf) { return (uint8_t*)stage + ((size_t)slot * NBUF + buf) * 2 * hop * bps; }
+  uint8_t* rawbuf(int slot, int buf) { return (uint8_t*)stage + ((size_t)slot * NBUF + buf) * frame_stride; }
+  float* f32buf(int slot, int buf) { return (float*)rawbuf(slot, buf); }
+  double* f64buf(int slot, int buf) { return echo.data() + ((size_t)slot * NBUF + buf) * echo_stride; }
 };
 
 namespace {
@@ -438,7 +468,7 @@ void frame_complete(vapx_ingest* g, int slot, Slot& s) {
   s.wbuf = -1; s.fill = 0;
   {
     std::lock_guard<std::mutex> lk(g->ready_mu);
-    g->ready.push_back({slot, b, s.gen.load(std::memory_order_relaxed), t});
+    g->ready.push_back({slot, b, s.gen.load(std::memory_order_relaxed), t, s.cls});
   }
   g->ready_cv.notify_one();
 }
@@ -447,7 +477,8 @@ void frame_complete(vapx_ingest* g, int slot, Slot& s) {
 // f32 staging, no f64 echo copy.  Same contract as feed()
 size_t feed_raw(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
   Slot& s = g->slots[slot];
-  const size_t hop = (size_t)g->hop, bps = (size_t)g->bps, pb = (size_t)g->pair_bytes;
+  const InGeo& q = g->geo[s.cls];
+  const size_t hop = (size_t)q.hop, bps = (size_t)q.bps, pb = (size_t)q.pair_bytes;
   size_t used = 0;
   while (used < n) {
     if (s.wbuf < 0) {
@@ -489,21 +520,21 @@ size_t feed_raw(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
 }
 
 // a frame of a raw format as the result packet echoes it: the decoded samples as float64, [2][hop]
-void expand_raw(const vapx_ingest* g, const uint8_t* raw, double* e) {
-  const size_t n = (size_t)2 * g->hop;
-  if (g->fmt == VAPX_PCM_S16) {
+void expand_raw(const InGeo& q, const uint8_t* raw, double* e) {
+  const size_t n = (size_t)2 * q.hop;
+  if (q.fmt == VAPX_PCM_S16) {
     for (size_t i = 0; i < n; ++i) { int16_t v; memcpy(&v, raw + 2 * i, 2); e[i] = (double)v * 0x1p-15; }
   } else {
-    const int16_t* t = g->fmt == VAPX_PCM_MULAW ? kMulaw : kAlaw;
+    const int16_t* t = q.fmt == VAPX_PCM_MULAW ? kMulaw : kAlaw;
     for (size_t i = 0; i < n; ++i) e[i] = (double)t[raw[i]] * 0x1p-15;
   }
 }
 
 // decode `n` bytes of the stream into the slot's frame buffers; returns bytes consumed (< n: no free buffer)
 size_t feed(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
-  if (g->fmt) return feed_raw(g, slot, p, n);
   Slot& s = g->slots[slot];
-  const int hop = g->hop;
+  if (g->geo[s.cls].fmt) return feed_raw(g, slot, p, n);
+  const int hop = g->geo[s.cls].hop;
   const double gain = g->cfg.gain;
   size_t used = 0;
   while (used < n) {
@@ -566,7 +597,8 @@ size_t feed(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
 // runs there (round 5: on a box with load average 60 from other tenants every front-end thread was losing ~10 ms slices).  Re-armed only
 // when the value changes: a sender that delivers whole frames never causes a setsockopt.
 void arm_lowat(vapx_ingest* g, Slot& s) {
-  long need = (long)(g->hop - (s.wbuf >= 0 ? s.fill : 0)) * (long)g->pair_bytes - s.npartial;
+  const InGeo& q = g->geo[s.cls];
+  long need = (long)(q.hop - (s.wbuf >= 0 ? s.fill : 0)) * (long)q.pair_bytes - s.npartial;
   if (need < 1) need = 1;
   if (need > 65536) need = 65536;           // (5 Hz frames are 51 KB; stay well inside the receive buffer)
   if ((int)need == s.lowat || s.fd_in < 0 || g->no_lowat) return;
@@ -657,7 +689,7 @@ int lowest_free_slot(vapx_ingest* g) {
 }
 
 // take over an accepted input connection: the lowest free stream slot gets it; false = every slot is taken (fd untouched)
-bool adopt_in(vapx_ingest* g, int fd) {
+bool adopt_in(vapx_ingest* g, int fd, int cls = -1) {
   int slot = -1;
   {
     // (round 4: this was a scan from slot 0 — 4096 dialogues connecting at once cost the accept thread ~S^2 / 2 slot visits, the output
@@ -673,11 +705,12 @@ bool adopt_in(vapx_ingest* g, int fd) {
   setsockopt(fd, IPPROTO_TCP, TCP_NODELAY, &one, sizeof one);
   Slot& s = g->slots[slot];
   s.wbuf = -1; s.fill = 0; s.npartial = 0; s.backlog.clear(); s.paused = false; s.lowat = 0;
+  s.cls = cls >= 0 ? cls : 0;   // frames of the slot's previous connection that are still queued or being sent carry their own class (Ready::cls)
   {
     // the carry restarts from zeros for every connection (vap_main.py:368-369); reset_on_connect also clears the
     // model state, which the reference keeps.  Applied by the tick thread before its next step.
     std::lock_guard<std::mutex> lk(g->ready_mu);
-    g->resets.push_back({slot, g->cfg.reset_on_connect ? 0 : 1});
+    g->resets.push_back({slot, g->cfg.reset_on_connect ? 0 : 1, cls});   // with a table: the tick thread tells the engine the stream's class first
   }
   g->in_conns.fetch_add(1);
   { const double t = mono_now(); if (g->dbg_t_in_first == 0) g->dbg_t_in_first = t; g->dbg_t_in_last = t; }
@@ -685,11 +718,12 @@ bool adopt_in(vapx_ingest* g, int fd) {
   return true;
 }
 
-void accept_in(vapx_ingest* g) {
+// cls: the input class whose port became readable (a front-end with a table), or -1: the one input port
+void accept_in(vapx_ingest* g, int cls = -1) {
   for (;;) {
-    int fd = accept4(g->lin, nullptr, nullptr, SOCK_NONBLOCK);
+    int fd = accept4(cls >= 0 ? g->cls_lsock[cls] : g->lin, nullptr, nullptr, SOCK_NONBLOCK);
     if (fd < 0) { accept_failed_for_fds(g); return; }
-    if (!adopt_in(g, fd)) close(fd);        // every stream slot is taken
+    if (!adopt_in(g, fd, cls)) close(fd);   // every stream slot is taken
   }
 }
 
@@ -758,7 +792,7 @@ bool adopt_in_at(vapx_ingest* g, int fd, int slot) {
   s.wbuf = -1; s.fill = 0; s.npartial = 0; s.backlog.clear(); s.paused = false; s.lowat = 0;
   {
     std::lock_guard<std::mutex> lk(g->ready_mu);
-    g->resets.push_back({slot, g->cfg.reset_on_connect ? 0 : 1});
+    g->resets.push_back({slot, g->cfg.reset_on_connect ? 0 : 1, -1});
   }
   g->in_conns.fetch_add(1);
   ep_add(g->ep[slot % g->R], fd, K_DATA | (uint32_t)slot);
@@ -800,7 +834,7 @@ void accept_main(vapx_ingest* g) {
     int n = epoll_wait(g->ep_accept, evs, 8, 100);
     for (int i = 0; i < n; ++i) {
       const uint64_t kind = evs[i].data.u64 & ~0xffffffffull;
-      if (kind == K_LISTEN_IN) accept_in(g);
+      if (kind == K_LISTEN_IN) accept_in(g, g->n_cls ? (int)(evs[i].data.u64 & 0xffffffffu) : -1);
       else if (kind == K_LISTEN_OUT) accept_out(g, (int)(evs[i].data.u64 & 0xffffffffu));
     }
   }
@@ -850,8 +884,10 @@ bool send_packet(int fd, iovec* iov, int niov, size_t total) {
 
 void tx_main(vapx_ingest* g, int x) {
   std::vector<uint8_t> tail(64 + 8 * 256);
-  const int hop = g->hop;
-  std::vector<double> expanded(g->fmt ? (size_t)2 * hop : 0);   // a raw format: the row's echo, decoded from the staging by the table
+  size_t raw_hop = 0;
+  for (int c = 0; c < std::max(g->n_cls, 1); ++c)
+    if (g->geo[c].fmt) raw_hop = std::max(raw_hop, (size_t)g->geo[c].hop);
+  std::vector<double> expanded(2 * raw_hop);   // a raw format: the row's echo, decoded from the staging by the table
   constexpr int MAX_R = 10;                  // 50 Hz -> 5 Hz
   int64_t next = 0;                          // the job this thread sends next: every sender walks over EVERY job, in publication order
   while (true) {
@@ -870,14 +906,16 @@ void tx_main(vapx_ingest* g, int x) {
     for (int k : job.part[x]) {
       const Ready& rd = job.rows[k];
       Slot& s = g->slots[rd.slot];
+      const InGeo& q = g->geo[rd.cls];
+      const int hop = q.hop;
       if (job.bad[k]) {   // the stream was reset (status 1 in some model): a slower model's frame in the making starts over with it
         for (int m = 0; m < g->M; ++m)
           if (g->ports[m].R > 1) g->ports[m].hist_n[rd.slot] = 0;
       } else {
         // u32 len | f64 t | u32 n | x1 | u32 n | x2 | tail   (util.py:122-143; length prefix vap_main.py:446-448); a trunk group sends one
         // packet per model, each to its own port's listeners, tail in that model's framing (bc util.py:193-211, nod :213-237)
-        double* e = g->fmt ? expanded.data() : g->f64buf(rd.slot, rd.buf);
-        if (g->fmt) expand_raw(g, g->rawbuf(rd.slot, rd.buf), e);
+        double* e = q.fmt ? expanded.data() : g->f64buf(rd.slot, rd.buf);
+        if (q.fmt) expand_raw(q, g->rawbuf(rd.slot, rd.buf), e);
         for (int m = 0; m < g->M; ++m) {
           OutPort& o = g->ports[m];
           const float* row = job.out + (size_t)job.n * o.off + (size_t)k * o.wf;
@@ -970,7 +1008,7 @@ void tick_main(vapx_ingest* g) {
   double earliest_next = 0.0;              // pacing: previous tick's start + its duration / util
   while (!g->stop.load()) {
     std::vector<Ready> fresh;
-    std::vector<std::pair<int, int>> resets;
+    std::vector<ResetReq> resets;
     {
       std::unique_lock<std::mutex> lk(g->ready_mu);
       if (g->ready.empty() && g->resets.empty()) {
@@ -983,8 +1021,13 @@ void tick_main(vapx_ingest* g) {
       fresh.swap(g->ready);
       resets.swap(g->resets);
     }
-    for (auto& rs : resets)
-      if (g->reset) g->reset(g->user, rs.second ? -(rs.first + 1) : rs.first);   // negative = carry only
+    for (auto& rs : resets) {
+      if (rs.cls >= 0) {   // a connection on a class port: the stream is of that class from its first frame on
+        g->tick_cls[rs.slot] = rs.cls;
+        if (g->set_class) g->set_class(g->user, rs.slot, rs.cls);
+      }
+      if (g->reset) g->reset(g->user, rs.carry_only ? -(rs.slot + 1) : rs.slot);   // negative = carry only
+    }
     for (auto& rd : fresh) {
       if (rd.gen != g->slots[rd.slot].gen.load(std::memory_order_acquire)) { release_buf(g, rd.slot, rd.buf); continue; }   // connection already gone
       if (pending.empty()) first_ready = rd.t;
@@ -1026,11 +1069,13 @@ void tick_main(vapx_ingest* g) {
     if (!pending.empty()) first_ready = pending.front().t;
     const int n = (int)job.rows.size();
     if (n == 0) continue;
-    const size_t fb = (size_t)2 * g->hop * g->bps;   // a frame of the staging, f32 or raw
+    size_t at = 0;   // frames of the staging, f32 or raw, back to back in batch order: with a table, the packed block of vapx.h "Input classes"
     for (int k = 0; k < n; ++k) {
       in_batch[job.rows[k].slot] = 0;
       g->batch_ids[k] = job.rows[k].slot;
-      memcpy((uint8_t*)g->batch_audio + (size_t)k * fb, g->rawbuf(job.rows[k].slot, job.rows[k].buf), fb);
+      const size_t fb = g->geo[job.rows[k].cls].frame_bytes();
+      memcpy((uint8_t*)g->batch_audio + at, g->rawbuf(job.rows[k].slot, job.rows[k].buf), fb);
+      at += fb;
     }
     const double t0 = mono_now();
     const int rc = g->step(g->user, n, g->batch_ids.data(), g->batch_audio, job.out);
@@ -1074,7 +1119,11 @@ void tick_main(vapx_ingest* g) {
 
 int engine_step(void* user, int32_t n, const int32_t* ids, const float* audio, float* out) {
   vapx_ingest* g = (vapx_ingest*)user;
-  return vapx_step(g->engine, n, ids, audio, g->hop, out, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
+  return vapx_step(g->engine, n, ids, audio, g->n_cls ? 0 : g->hop, out, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);   // a table: the classes size the slots
+}
+void engine_set_class(void* user, int32_t sid, int32_t cls) {
+  vapx_ingest* g = (vapx_ingest*)user;
+  if (vapx_set_stream_class) (void)vapx_set_stream_class(g->engine, sid, cls);
 }
 void engine_reset(void* user, int32_t sid) {
   vapx_ingest* g = (vapx_ingest*)user;
@@ -1100,9 +1149,14 @@ void pin_to(std::thread& t, const vapx_ingest_config& c, int k) {
 bool read_config(const vapx_ingest_config* cfg, vapx_ingest_config* out) {
   constexpr int32_t kFirst = (int32_t)offsetof(vapx_ingest_config, cpu_first);   // ABI 2 as first shipped: up to `reserved` (now `flags`)
   constexpr int32_t kPlaced = (int32_t)offsetof(vapx_ingest_config, input_format);   // ... with the thread placement, before the input format
-  if (!cfg || (cfg->struct_size != kFirst && cfg->struct_size != kPlaced && cfg->struct_size != (int32_t)sizeof(vapx_ingest_config))) return false;
+  // ... with the input format, before the input classes: the struct then ENDED with input_format, and its tail padding is where
+  // n_input_classes lives now: nothing past input_format is read from a struct of that size
+  constexpr int32_t kFormatEnd = (int32_t)offsetof(vapx_ingest_config, n_input_classes);
+  constexpr int32_t kFormat = (kFormatEnd + 7) & ~7;
+  if (!cfg || (cfg->struct_size != kFirst && cfg->struct_size != kPlaced && cfg->struct_size != kFormat &&
+               cfg->struct_size != (int32_t)sizeof(vapx_ingest_config))) return false;
   memset(out, 0, sizeof *out);
-  memcpy(out, cfg, (size_t)cfg->struct_size);
+  memcpy(out, cfg, cfg->struct_size == kFormat ? (size_t)kFormatEnd : (size_t)cfg->struct_size);
   out->struct_size = (int32_t)sizeof(vapx_ingest_config);
   return true;
 }
@@ -1123,11 +1177,56 @@ int check_format(const vapx_ingest_config* cfg, int engine_fmt) {
   return VAPX_OK;
 }
 
-int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt = -1) {
+InGeo make_geo(int fmt, int in_hz, int frame_hz) {
+  InGeo q;
+  q.fmt = fmt; q.in_hz = in_hz; q.hop = in_hz / frame_hz;
+  q.bps = fmt == VAPX_PCM_F32 ? 4 : fmt == VAPX_PCM_S16 ? 2 : 1;
+  q.pair_bytes = fmt ? 2 * q.bps : PAIR_BYTES;
+  return q;
+}
+
+// the class table a front-end serves: the engine's (n_engine > 0; the config's must then be empty or equal to it) or, over a step function
+// (n_engine < 0), the config's.  Sets g->n_cls / cls_pub; VAPX_OK or the refusal, with its message
+int check_classes(vapx_ingest* g, const vapx_ingest_config* cfg, int n_engine, const vapx_input_class* engine_tab) {
+  const int nc = cfg->n_input_classes;
+  if (nc < 0 || nc > VAPX_MAX_INPUT_CLASSES) return open_refused("n_input_classes: the table holds 0 (no classes) .. 16 entries");
+  for (int i = 0; i < nc; ++i) {
+    const vapx_input_class& c = cfg->input_classes[i];
+    if (c.input_hz != 8000 && c.input_hz != 16000 && c.input_hz != 32000 && c.input_hz != 48000)
+      return open_refused("input_classes: an input rate other than 8000, 16000, 32000 and 48000");
+    if (c.format < VAPX_PCM_F32 || c.format > VAPX_PCM_ALAW) return open_refused("input_classes: formats are 0 (f64 pairs on the wire), 1 (s16), 2 (mulaw) and 3 (alaw)");
+    for (int j = 0; j < i; ++j)
+      if (cfg->input_classes[j].input_hz == c.input_hz && cfg->input_classes[j].format == c.format) return open_refused("input_classes: two equal entries");
+    if (cfg->class_ports_in[i] < 0) return open_refused("class_ports_in: a class's input port must be >= 0 (0 = ephemeral)");
+  }
+  if (n_engine >= 0) {
+    if (nc && nc != n_engine)
+      return open_refused("vapx_ingest_config.input_classes differs from the engine's table (vapx_set_input_classes): leave it empty or make them equal");
+    for (int i = 0; i < nc; ++i)
+      if (cfg->input_classes[i].input_hz != engine_tab[i].input_hz || cfg->input_classes[i].format != engine_tab[i].format)
+        return open_refused("vapx_ingest_config.input_classes differs from the engine's table (vapx_set_input_classes): leave it empty or make them equal");
+  }
+  g->n_cls = n_engine >= 0 ? n_engine : nc;
+  for (int i = 0; i < g->n_cls; ++i) g->cls_pub[i] = n_engine >= 0 ? engine_tab[i] : cfg->input_classes[i];
+  if (!g->n_cls) return VAPX_OK;
+  if (cfg->input_format) return open_refused("input_format together with input classes: the format is each class's own");
+  if (cfg->port_in < 0 || cfg->port_out < 0)
+    return open_refused("a front-end with input classes cannot be a passive shard (port_in = -1): the front door has one input port, a class is known by its port");
+  if (g->M > 1) return open_refused("a trunk group's front-end takes no input classes: multi-port groups are not part of the class ports yet");
+  if (cfg->gain != 1.0 && cfg->gain != 0.0)
+    for (int i = 0; i < g->n_cls; ++i)
+      if (g->cls_pub[i].format)
+        return open_refused("gain with a raw input class: the gain is a float64 multiply in front of the f32 cast, and raw samples are never cast on the host");
+  return VAPX_OK;
+}
+
+int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt = -1, int n_engine_cls = -1,
+                const vapx_input_class* engine_tab = nullptr) {
   if (!read_config(cfg_in, &g->cfg)) return VAPX_E_INVAL;
   const vapx_ingest_config* cfg = &g->cfg;
   g->debug = getenv("VAPX_INGEST_DEBUG") != nullptr;
   g->no_lowat = getenv("VAPX_INGEST_NO_LOWAT") != nullptr;
+  { const int rc = check_classes(g, cfg, n_engine_cls, engine_tab); if (rc) return rc; }
   if (g->cfg.gain == 0.0) g->cfg.gain = 1.0;
   { const int rc = check_format(cfg, engine_fmt); if (rc) return rc; }
   g->fmt = engine_fmt >= 0 ? engine_fmt : cfg->input_format;
@@ -1137,10 +1236,17 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt
   g->X = cfg->tx_threads > 0 ? std::min(cfg->tx_threads, 16) : 2;
   g->broadcast = cfg->broadcast < 0 ? (g->S == 1) : (cfg->broadcast != 0);
   g->hop = g->in_hz / g->hz;
+  g->geo[0] = make_geo(g->fmt, g->in_hz, g->hz);   // no table: the one geometry, every slot's
+  for (int c = 0; c < g->n_cls; ++c) g->geo[c] = make_geo(g->cls_pub[c].format, g->cls_pub[c].input_hz, g->hz);
+  g->frame_stride = g->echo_stride = 0;
+  for (int c = 0; c < std::max(g->n_cls, 1); ++c) {
+    g->frame_stride = std::max(g->frame_stride, g->geo[c].frame_bytes());
+    if (!g->geo[c].fmt) g->echo_stride = std::max(g->echo_stride, (size_t)2 * g->geo[c].hop);   // a raw format keeps no f64 echo
+  }
+  g->tick_cls.assign(g->S, 0);
   g->slots.reset(new Slot[g->S]);
-  const size_t per_samples = (size_t)g->S * NBUF * 2 * g->hop;
-  const size_t per = (per_samples * g->bps + 3) / 4;                       // the staging blocks in floats: f32 samples, or raw ones of bps bytes
-  const size_t ba = ((size_t)g->max_batch * 2 * g->hop * g->bps + 3) / 4;
+  const size_t per = ((size_t)g->S * NBUF * g->frame_stride + 3) / 4;      // the staging blocks in floats: f32 samples, or raw ones of bps bytes
+  const size_t ba = ((size_t)g->max_batch * g->frame_stride + 3) / 4;
   const size_t ob = (size_t)g->max_batch * g->row_floats;
   // page-locked staging so vapx_step DMAs straight out of / into it; without a HIP device (host-logic tests over a step
   // function) plain memory does
@@ -1148,7 +1254,7 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt
   g->pinned_blocks = g->stage != nullptr;
   auto grab = [&](size_t n) { return (float*)(g->pinned_blocks ? vapx_host_alloc(n * sizeof(float)) : calloc(n, sizeof(float))); };
   if (!g->stage) g->stage = grab(per);
-  if (!g->fmt) g->echo.assign(per_samples, 0.0);
+  if (g->echo_stride) g->echo.assign((size_t)g->S * NBUF * g->echo_stride, 0.0);
   g->batch_audio = grab(ba);
   g->batch_ids.assign(g->max_batch, 0);
   for (auto& j : g->jobs) {
@@ -1177,12 +1283,18 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt
   const bool passive = cfg->port_in < 0;
   if (passive != (cfg->port_out < 0)) return VAPX_E_INVAL;   // a shard is passive on BOTH ports or on none (-1 / >= 0 mixed is a configuration error)
   if (!passive) {
-    g->lin = listen_on(cfg->port_in, cfg->bind_any != 0, &g->port_in);
+    if (g->n_cls) {   // one input port per class; port_in is ignored
+      for (int c = 0; c < g->n_cls; ++c) {
+        g->cls_lsock[c] = listen_on(cfg->class_ports_in[c], cfg->bind_any != 0, &g->cls_port[c]);
+        if (g->cls_lsock[c] < 0) return VAPX_E_INVAL;
+      }
+      g->port_in = g->cls_port[0];
+    } else g->lin = listen_on(cfg->port_in, cfg->bind_any != 0, &g->port_in);
     for (int m = 0; m < g->M; ++m) {
       g->ports[m].lsock = listen_on(m ? g->cfg_ports_out[m] : cfg->port_out, cfg->bind_any != 0, &g->ports[m].port);
       if (g->ports[m].lsock < 0) return VAPX_E_INVAL;
     }
-    if (g->lin < 0) return VAPX_E_INVAL;
+    if (!g->n_cls && g->lin < 0) return VAPX_E_INVAL;
   }
   g->resume_mu = std::vector<std::mutex>(g->R);
   g->resume.assign(g->R, {});
@@ -1194,7 +1306,8 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt
   for (int m = 0; m < g->M; ++m) g->ports[m].lcount.assign(g->S, 0);
   if (!passive) {
     g->ep_accept = epoll_create1(0);          // own thread: a connect storm must not starve the streams of a receive thread
-    ep_add(g->ep_accept, g->lin, K_LISTEN_IN);
+    if (!g->n_cls) ep_add(g->ep_accept, g->lin, K_LISTEN_IN);
+    for (int c = 0; c < g->n_cls; ++c) ep_add(g->ep_accept, g->cls_lsock[c], K_LISTEN_IN | (uint32_t)c);
     for (int m = 0; m < g->M; ++m) ep_add(g->ep_accept, g->ports[m].lsock, K_LISTEN_OUT | (uint32_t)m);
     g->accept_thread = std::thread(accept_main, g);
   }
@@ -1227,6 +1340,12 @@ int silence_byte(int fmt) { return fmt == VAPX_PCM_MULAW ? 0xFF : fmt == VAPX_PC
 int engine_input_hz(vapx_handle engine) {
   const int32_t r = vapx_get_input_rate ? vapx_get_input_rate(engine) : 16000;
   return r > 0 ? r : 16000;
+}
+
+// the engine's class table (vapx_set_input_classes): its length, 0 without one
+int engine_input_classes(vapx_handle engine, vapx_input_class* tab) {
+  const int32_t n = vapx_get_input_classes ? vapx_get_input_classes(engine, tab, VAPX_MAX_INPUT_CLASSES) : 0;
+  return n > 0 ? n : 0;
 }
 
 // a trunk group's ports: model m's framing, the geometry of its rows in the tick's wire block (vapx_step_group) and its requested port
@@ -1300,9 +1419,26 @@ int vapx_ingest_open(vapx_handle engine, const vapx_ingest_config* cfg, vapx_ing
   g->S = ec.max_streams; g->max_batch = ec.max_batch; g->hz = ec.frame_hz; g->ports[0].mode = ec.mode;
   g->in_hz = engine_input_hz(engine);
   const int efmt = engine_input_format(engine);
-  rc = check_format(&probe, efmt);   // before the warm-up: a refused open leaves the engine untouched
+  vapx_input_class etab[VAPX_MAX_INPUT_CLASSES];
+  const int ncls = engine_input_classes(engine, etab);
+  if (ncls) g->set_class = engine_set_class;
+  rc = check_classes(g, &probe, ncls, etab);   // before the warm-up: a refused open leaves the engine untouched
+  if (rc == VAPX_OK) rc = check_format(&probe, efmt);
   if (rc != VAPX_OK) { delete g; return rc; }
-  if (!(probe.flags & VAPX_INGEST_KEEP_STATE)) {
+  if (ncls && !(probe.flags & VAPX_INGEST_KEEP_STATE)) {
+    // the warm-up of an engine with a table: every stream is of class 0 still, so the packed block is max_batch slots of class 0
+    const InGeo q = make_geo(etab[0].format, etab[0].input_hz, ec.frame_hz);
+    const int nw = ec.max_batch;
+    float* a = (float*)vapx_host_alloc((size_t)nw * q.frame_bytes());
+    float* o = (float*)vapx_host_alloc((size_t)nw * VAPX_OUT_STRIDE * sizeof(float));
+    if (a && o) {
+      memset(a, silence_byte(q.fmt), (size_t)nw * q.frame_bytes());
+      for (int k = 0; k < 3; ++k) (void)vapx_step(engine, nw, nullptr, a, 0, o, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
+      for (int i = 0; i < nw; ++i) (void)vapx_reset_stream(engine, i);
+    }
+    vapx_host_free(a);
+    vapx_host_free(o);
+  } else if (!(probe.flags & VAPX_INGEST_KEEP_STATE)) {
      // warm the engine up before the first client connects: the first vapx_step of a process loads the code objects and sizes
      // the runtime's pools (hundreds of ms) — paid here on silence, then every touched stream is reset (VAPX_INGEST_KEEP_STATE: the
      // streams hold imported state and the caller has warmed the engine up before importing)
@@ -1317,10 +1453,22 @@ int vapx_ingest_open(vapx_handle engine, const vapx_ingest_config* cfg, vapx_ing
     vapx_host_free(a);
     vapx_host_free(o);
   }
-  rc = open_common(g, cfg, efmt);
+  rc = open_common(g, cfg, efmt, ncls, etab);
   if (rc != VAPX_OK) { vapx_ingest_close(g); return rc; }
   *out = g;
   return VAPX_OK;
+}
+
+int32_t vapx_ingest_class_ports(vapx_ingest_handle g, int32_t* ports, int32_t max) {
+  if (!g) return VAPX_E_INVAL;
+  for (int c = 0; ports && c < g->n_cls && c < max; ++c) ports[c] = g->cls_port[c];
+  return g->n_cls;
+}
+
+int32_t vapx_ingest_stream_class(vapx_ingest_handle g, int32_t stream_id) {
+  if (!g || !g->n_cls) return VAPX_E_INVAL;
+  if (stream_id < 0 || stream_id >= g->S) return VAPX_E_RANGE;
+  return g->tick_cls[stream_id];
 }
 
 int vapx_ingest_ports(vapx_ingest_handle g, int32_t* port_in, int32_t* port_out) {
@@ -1361,6 +1509,8 @@ int vapx_ingest_open_group_fn2(vapx_ingest_group_step_fn step, vapx_ingest_reset
     return open_refused("null argument or a vapx_ingest_config of unknown size");
   if (n_streams < 1 || max_batch < 1 || max_batch > n_streams) return open_refused("need 1 <= max_batch <= n_streams");
   if (n_models < 1 || n_models > MAX_MODELS) return open_refused("a group serves one to three models");
+  if (probe.n_input_classes)
+    return open_refused("a trunk group's front-end takes no input classes: multi-port groups are not part of the class ports yet");
   const int32_t frame_hz = frame_hzs[0];
   if (frame_hz != 5 && frame_hz != 10 && frame_hz != 20 && frame_hz != 50) return open_refused("frame_hz must be 5, 10, 20 or 50");
   vapx_ingest* g = new vapx_ingest();
@@ -1390,6 +1540,12 @@ int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int
     vapx_config fc;
     if (!followers[i] || vapx_get_config(followers[i], &fc) != VAPX_OK) return open_refused("null follower");
     modes[i + 1] = fc.mode; hzs[i + 1] = fc.frame_hz; ctxs[i + 1] = fc.ctx_frames;
+  }
+  {
+    vapx_input_class etab[VAPX_MAX_INPUT_CLASSES];
+    if (engine_input_classes(leader, etab) || probe.n_input_classes)
+      return open_refused("a trunk group's front-end takes no input classes (the leader has a table, or the config names one): multi-port "
+                          "groups are not part of the class ports yet; serve the leader alone, or the group without a table");
   }
   vapx_ingest* g = new vapx_ingest();
   g->in_hz = engine_input_hz(leader);
@@ -1498,6 +1654,7 @@ void vapx_ingest_close(vapx_ingest_handle g) {
   }
   for (auto& o : g->ports) { for (int fd : o.out_all) close(fd); if (o.lsock >= 0) close(o.lsock); }
   if (g->lin >= 0) close(g->lin);
+  for (int fd : g->cls_lsock) if (fd >= 0) close(fd);
   for (int fd : g->ep) close(fd);
   for (int fd : g->wake) close(fd);
   auto drop = [&](void* p) {

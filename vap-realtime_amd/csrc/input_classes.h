@@ -1,0 +1,28 @@
+// Input classes (vapx_set_input_classes; include/vapx.h "Input classes"): what engine.hip hands to input_classes.hip.  Plain C++.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/vapx.h"
+
+// one class as the kernel reads it: the resampler's geometry (orig = 0: the class is 16 kHz, no window), samples per channel and tick, format
+struct InputClassGeom { int orig, nnew, width, K, d, H, hop_in, fmt; };
+
+// one batch slot of a tick: where its [2][hop_in] samples start in the packed block, and its stream's class
+struct InputSlot { uint32_t byte_off; int32_t cls; };
+
+struct InputClassesArgs {
+  const unsigned char* in;   // the packed block, 16-byte aligned
+  const InputSlot* slots;    // [n]
+  const int* ids;            // [n] stream ids (device) or null = identity
+  float* hist;               // [S][rec]: per stream [2][H of its class] input samples of its earlier ticks, then padding
+  int* started;              // [S][2]: the (stream, channel) has consumed a tick since its reset
+  float* out;                // [n][2][hop] the 16 kHz samples conv0 takes
+  int rec, hop;
+  InputClassGeom cls[VAPX_MAX_INPUT_CLASSES];
+};
+
+// lds_floats: the dynamic LDS of the engine's largest class (input_classes_lds_floats over the table)
+size_t input_classes_lds_floats(const InputClassGeom* cls, int n_cls);
+hipError_t launch_input_classes(const InputClassesArgs& a, int n, size_t lds_floats, hipStream_t st);

@@ -1,0 +1,122 @@
+// Input classes: streams of different sample formats and rates in ONE batch (vapx_set_input_classes; include/vapx.h "Input classes").
+// A class is (format, rate); every stream belongs to one; a tick's audio is a packed block in which batch slot k holds
+// [2][hop_in(c_k)] samples of format(c_k).  input_classes_kernel turns the whole ragged block into the 16 kHz fp32 hops conv0 takes, in
+// one launch: one 256-thread workgroup per (batch slot, channel).  The slot's class is uniform over the workgroup; its geometry is read
+// once from the kernel arguments and lives in scalars.
+//   - load + decode: lane i reads the aligned dword at the row's base + 4 i (four G.711 codes, two s16 samples or one float) and expands
+//     it with the device functions of input_decode.h, the ones pcm_decode_kernel uses;
+//   - a 16 kHz class stores the decoded samples straight to the output with vector stores: no window, no barrier;
+//   - any other rate: the samples land in LDS behind the stream's history [H], the new history is stored back, and every output is one
+//     resample_dot chain over the same tap tables as resample_kernel, with the same `started` / "first d blocks are zero" rule.
+// One definition of each expansion and of the chain: a stream of class (f, r) equals, bit for bit, the stream of an engine with
+// vapx_set_input_format(f) + vapx_set_input_rate(r).  The tick moves about 40 MB at 4096 streams; nothing is tuned past coalesced access.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "input_classes.h"
+#include "input_decode.h"
+
+namespace {
+
+// the row's dwords -> decoded samples in LDS (scalar LDS stores: the window starts H floats in, at no particular alignment)
+template <int FMT>
+__device__ __forceinline__ void decode_to_lds(const uint32_t* __restrict__ src, float* __restrict__ dst, int dwords, int tid) {
+  for (int i = tid; i < dwords; i += 256) {
+    const uint32_t w = src[i];
+    if (FMT == VAPX_PCM_F32) {
+      dst[i] = __uint_as_float(w);
+    } else if (FMT == VAPX_PCM_S16) {
+      dst[2 * i] = pcm_value((int)(short)(w & 0xFFFFu));
+      dst[2 * i + 1] = pcm_value((int)(short)(w >> 16));
+    } else {
+      dst[4 * i] = pcm_code<FMT>(w & 0xFFu);
+      dst[4 * i + 1] = pcm_code<FMT>((w >> 8) & 0xFFu);
+      dst[4 * i + 2] = pcm_code<FMT>((w >> 16) & 0xFFu);
+      dst[4 * i + 3] = pcm_code<FMT>(w >> 24);
+    }
+  }
+}
+
+// the row's dwords -> decoded samples in global memory (a 16 kHz class); dst is 16-byte aligned: one 4-, 8- or 16-byte store per lane
+template <int FMT>
+__device__ __forceinline__ void decode_to_out(const uint32_t* __restrict__ src, float* __restrict__ dst, int dwords, int tid) {
+  for (int i = tid; i < dwords; i += 256) {
+    const uint32_t w = src[i];
+    if (FMT == VAPX_PCM_F32) {
+      dst[i] = __uint_as_float(w);
+    } else if (FMT == VAPX_PCM_S16) {
+      float2 o;
+      o.x = pcm_value((int)(short)(w & 0xFFFFu));
+      o.y = pcm_value((int)(short)(w >> 16));
+      *reinterpret_cast<float2*>(dst + 2 * i) = o;
+    } else {
+      float4 o;
+      o.x = pcm_code<FMT>(w & 0xFFu);
+      o.y = pcm_code<FMT>((w >> 8) & 0xFFu);
+      o.z = pcm_code<FMT>((w >> 16) & 0xFFu);
+      o.w = pcm_code<FMT>(w >> 24);
+      *reinterpret_cast<float4*>(dst + 4 * i) = o;
+    }
+  }
+}
+
+__device__ __forceinline__ int bytes_per_sample(int fmt) { return fmt == VAPX_PCM_F32 ? 4 : fmt == VAPX_PCM_S16 ? 2 : 1; }
+
+// One workgroup per (batch slot, channel): LDS = taps | history [H] ++ this tick's hop_in decoded samples (classes off 16 kHz only).
+__global__ __launch_bounds__(256) void input_classes_kernel(InputClassesArgs a) {
+  extern __shared__ float lds[];
+  const int tid = threadIdx.x, row = blockIdx.x, b = row >> 1, c = row & 1;
+  const InputSlot slot = a.slots[b];
+  const InputClassGeom g = a.cls[__builtin_amdgcn_readfirstlane(slot.cls)];   // uniform over the workgroup: scalars
+  const int row_bytes = g.hop_in * bytes_per_sample(g.fmt), dwords = row_bytes >> 2;   // hop_in is a multiple of 16 samples
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(a.in + slot.byte_off + (size_t)c * row_bytes);
+  float* o = a.out + (long)row * a.hop;
+
+  if (g.orig == 0) {   // 16 kHz: hop_in == hop, decode straight to the output
+    switch (g.fmt) {
+      case VAPX_PCM_F32: decode_to_out<VAPX_PCM_F32>(src, o, dwords, tid); break;
+      case VAPX_PCM_S16: decode_to_out<VAPX_PCM_S16>(src, o, dwords, tid); break;
+      case VAPX_PCM_MULAW: decode_to_out<VAPX_PCM_MULAW>(src, o, dwords, tid); break;
+      default: decode_to_out<VAPX_PCM_ALAW>(src, o, dwords, tid); break;
+    }
+    return;
+  }
+
+  float* th = lds;
+  float* buf = lds + kTapSlots;
+  const int sid = a.ids ? a.ids[b] : b;
+  const float* tp = taps_of(g.orig);
+  for (int i = tid; i < g.nnew * g.K; i += 256) th[i] = tp[i];
+  float* hs = a.hist + (long)sid * a.rec + c * g.H;
+  for (int i = tid; i < g.H; i += 256) buf[i] = hs[i];
+  switch (g.fmt) {
+    case VAPX_PCM_F32: decode_to_lds<VAPX_PCM_F32>(src, buf + g.H, dwords, tid); break;
+    case VAPX_PCM_S16: decode_to_lds<VAPX_PCM_S16>(src, buf + g.H, dwords, tid); break;
+    case VAPX_PCM_MULAW: decode_to_lds<VAPX_PCM_MULAW>(src, buf + g.H, dwords, tid); break;
+    default: decode_to_lds<VAPX_PCM_ALAW>(src, buf + g.H, dwords, tid); break;
+  }
+  const bool fresh = a.started[sid * 2 + c] == 0;   // no tick since the stream's reset: Y has no samples before its block 0
+  __syncthreads();
+  for (int i = tid; i < g.H; i += 256) hs[i] = buf[g.hop_in + i];   // hop_in >= 160 > H: the new history is all of this tick
+  if (tid == 0) a.started[sid * 2 + c] = 1;
+  for (int m = tid; m < a.hop; m += 256) {
+    const int j = m / g.nnew, p = m - j * g.nnew;
+    const float v = resample_dot(th + p * g.K, buf + g.orig * j, g.K);   // last index read: hop_in + 2 width - 1 < H + hop_in
+    o[m] = (fresh && j < g.d) ? 0.f : v;
+  }
+}
+
+}  // namespace
+
+size_t input_classes_lds_floats(const InputClassGeom* cls, int n_cls) {
+  size_t win = 0;
+  for (int i = 0; i < n_cls; ++i)
+    if (cls[i].orig && (size_t)(cls[i].H + cls[i].hop_in) > win) win = (size_t)(cls[i].H + cls[i].hop_in);
+  return win ? kTapSlots + win : 0;   // 48 + 40 + 9600 floats (about 39 KB) at 48 kHz and 5 Hz
+}
+
+hipError_t launch_input_classes(const InputClassesArgs& a, int n, size_t lds_floats, hipStream_t st) {
+  hipLaunchKernelGGL(input_classes_kernel, dim3((unsigned)n * 2), dim3(256), lds_floats * sizeof(float), st, a);
+  return hipGetLastError();
+}

@@ -4,7 +4,7 @@
 // fp32 and integer zero converts to +0.0f, so a stream stepped in a raw format equals, bit for bit, one fed the decoded floats.
 //
 // G.711 is expanded by the CLOSED FORM in integer ALU (a handful of shifts and adds per code), not by a table in LDS: no LDS, no barrier,
-// no constant-memory traffic.  The static_asserts below hold the closed forms to pcm_tables.h for all 256 codes at compile time; the host
+// no constant-memory traffic.  input_decode.h holds the closed forms to pcm_tables.h for all 256 codes at compile time; the host
 // side (the front-end's echo, csrc/ingest.cpp) reads the tables.
 //
 // One kernel for the engine's step and for vapx_pcm_decode: the block is flat, [rows][spc] samples are n = rows * spc samples in a row.
@@ -17,41 +17,10 @@
 #include <cstdint>
 
 #include "../../include/vapx.h"
-#include "pcm_tables.h"
+#include "input_decode.h"   // the closed forms, pcm_value and pcm_code: shared with input_classes.hip
 #include "vap_kernels.h"
 
 namespace {
-
-__host__ __device__ constexpr int mulaw_linear(unsigned c) {
-  c = ~c & 0xFFu;
-  const int e = (int)(c >> 4) & 7, m = (int)(c & 15u);
-  const int t = (((m << 3) + 0x84) << e) - 0x84;
-  return (c & 0x80u) ? -t : t;
-}
-
-__host__ __device__ constexpr int alaw_linear(unsigned c) {
-  c = (c ^ 0x55u) & 0xFFu;
-  const int e = (int)(c >> 4) & 7, m = (int)(c & 15u);
-  const int t = e == 0 ? (m << 4) + 8 : ((m << 4) + 0x108) << (e - 1);
-  return (c & 0x80u) ? t : -t;
-}
-
-constexpr short kMulawTable[256] = {VAPX_PCM_MULAW_TABLE};
-constexpr short kAlawTable[256] = {VAPX_PCM_ALAW_TABLE};
-constexpr bool closed_forms_match_tables() {
-  for (unsigned c = 0; c < 256; ++c)
-    if (mulaw_linear(c) != kMulawTable[c] || alaw_linear(c) != kAlawTable[c]) return false;
-  return true;
-}
-static_assert(closed_forms_match_tables(), "pcm.hip's closed forms and pcm_tables.h (vap-realtime_amd/pcm.py) disagree");
-
-// one sample: 16-bit linear -> fp32.  Exact; (float)0 is +0.0f
-__device__ __forceinline__ float pcm_value(int v) { return (float)v * 0x1p-15f; }
-
-template <int FMT>
-__device__ __forceinline__ float pcm_code(unsigned c) {
-  return pcm_value(FMT == VAPX_PCM_MULAW ? mulaw_linear(c) : alaw_linear(c));
-}
 
 // n samples at src (dword-aligned) -> n floats at dst (8-byte aligned for s16, 16-byte aligned for G.711)
 template <int FMT>

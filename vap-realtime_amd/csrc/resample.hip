@@ -10,26 +10,10 @@
 // whole-signal kernel therefore agree bit for bit.  A tick of 4096 streams moves about 40 MB: nothing here is tuned past that.
 #include <hip/hip_runtime.h>
 
-#include "resample_taps.h"
+#include "input_decode.h"   // the tap tables, taps_of and resample_dot: shared with input_classes.hip
 #include "vap_kernels.h"
 
 namespace {
-
-constexpr int kTapSlots = 48;   // floats reserved for h[new][K]: 2 x 15, 1 x 28, 1 x 41
-
-__constant__ float c_taps_8k[] = {VAPX_RESAMPLE_TAPS_8000};
-__constant__ float c_taps_32k[] = {VAPX_RESAMPLE_TAPS_32000};
-__constant__ float c_taps_48k[] = {VAPX_RESAMPLE_TAPS_48000};
-static_assert(sizeof(c_taps_8k) == 2 * 15 * 4 && sizeof(c_taps_32k) == 28 * 4 && sizeof(c_taps_48k) == 41 * 4, "tap tables");
-
-__device__ __forceinline__ const float* taps_of(int orig) { return orig == 1 ? c_taps_8k : orig == 2 ? c_taps_32k : c_taps_48k; }
-
-// one output: h = the phase's K taps, w = the K input samples under them.  The order of the chain is the definition.
-__device__ __forceinline__ float resample_dot(const float* __restrict__ h, const float* __restrict__ w, int K) {
-  float acc = 0.f;
-  for (int k = 0; k < K; ++k) acc = fmaf(h[k], w[k], acc);
-  return acc;
-}
 
 // One workgroup per (batch slot, channel): LDS = taps | history [H] ++ this tick's hop_in samples.
 __global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {

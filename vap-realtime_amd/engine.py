@@ -43,7 +43,10 @@ EXPORTS = ("vapx_abi_version", "vapx_blob_floats", "vapx_create", "vapx_destroy"
            "vapx_ingest_open_group_fn", "vapx_ingest_open_group_fn2", "vapx_ingest_group_ports", "vapx_ingest_last_open_error",
            "vapx_state_floats", "vapx_export_streams", "vapx_import_streams",
            "vapx_set_input_rate", "vapx_get_input_rate", "vapx_resample",
-           "vapx_set_input_format", "vapx_get_input_format", "vapx_pcm_decode")
+           "vapx_set_input_format", "vapx_get_input_format", "vapx_pcm_decode",
+           "vapx_set_input_classes", "vapx_get_input_classes", "vapx_set_stream_class", "vapx_get_stream_class", "vapx_input_slot_bytes",
+           "vapx_ingest_class_ports", "vapx_ingest_stream_class")
+MAX_INPUT_CLASSES = 16
 PROF_CLASSES = {0: "gemm_store", 1: "gemm_gelu", 2: "gemm_resid", 3: "gemm_resid_ln", 4: "gemm_cn_relu",
                 5: "conv_tail", 6: "ffn_block", 7: "last_row", 8: "conv0", 9: "lstm", 10: "gather_ln", 11: "attention", 12: "head",
                 13: "gemm_bias_ln_gelu", 14: "ffn_proj", 15: "trunk_collect"}
@@ -57,6 +60,77 @@ class _Config(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("device_id", C.c_int32), ("frame_hz", C.c_int32),
                 ("ctx_frames", C.c_int32), ("max_streams", C.c_int32), ("max_batch", C.c_int32),
                 ("mode", C.c_int32), ("flags", C.c_int32)]
+
+
+class _InputClass(C.Structure):
+    _fields_ = [("input_hz", C.c_int32), ("format", C.c_int32)]
+
+
+def input_class_table(classes) -> list:
+    """``[(format, rate), ...]`` as ``[(format name, rate in Hz)]``: formats by name or id ("f32" / "s16" / "mulaw" / "alaw", vapx.h VAPX_PCM_*),
+    rates 8000 / 16000 / 32000 / 48000; 1 .. 16 entries, no two equal (the rules of ``vapx_set_input_classes``)."""
+    from . import pcm
+    tab = [(pcm.format_name(f), int(hz)) for f, hz in classes]
+    if not 1 <= len(tab) <= MAX_INPUT_CLASSES:
+        raise ValueError(f"{len(tab)} input classes: the table holds 1 .. {MAX_INPUT_CLASSES}")
+    for f, hz in tab:
+        if hz not in (8000, 16000, 32000, 48000):
+            raise ValueError(f"input rate {hz} Hz: supported are 8000, 16000, 32000 and 48000")
+    if len(set(tab)) != len(tab):
+        raise ValueError("two equal input classes")
+    return tab
+
+
+def input_slot_shape(cls, frame_hz: int):
+    """``(dtype, [2, hop_in])`` of one batch slot of class ``cls = (format, rate)``."""
+    from . import pcm
+    f, hz = cls
+    return pcm.DTYPES[pcm.format_name(f)], (2, int(hz) // frame_hz)
+
+
+def input_slot_bytes(cls, frame_hz: int) -> int:
+    """Bytes of one batch slot of class ``cls``: 2 * hop_in * bytes per sample, a multiple of 16 (vapx.h, vapx_input_slot_bytes)."""
+    dt, (two, hop_in) = input_slot_shape(cls, frame_hz)
+    return two * hop_in * dt.itemsize
+
+
+def aligned_bytes(n: int, align: int = 16) -> np.ndarray:
+    """A uint8 array of n bytes whose first byte sits on a multiple of ``align``."""
+    raw = np.empty(n + align, np.uint8)
+    at = (-raw.ctypes.data) % align
+    return raw[at:at + n]
+
+
+def pack_input_classes(classes, frame_hz: int, slot_classes: Sequence[int], arrays, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """The packed audio block of one step on an engine with input classes (vapx.h "Input classes", LAYOUT): slot k holds ``arrays[k]``,
+    [2, hop_in(c_k)] samples of format(c_k) with c_k = ``slot_classes[k]``, at byte offset sum_{j<k} input_slot_bytes(c_j).  The dtype of
+    every array is checked as ``Engine.step`` checks a uniform engine's: float arrays of any width are cast for "f32", a raw format takes
+    its own dtype only.  Returns a 16-byte aligned uint8 block (``out``, e.g. a view of a ``pinned_empty`` block, if given)."""
+    tab = input_class_table(classes)
+    if len(slot_classes) != len(arrays):
+        raise ValueError(f"{len(arrays)} arrays for {len(slot_classes)} batch slots")
+    sizes = [input_slot_bytes(tab[c], frame_hz) for c in slot_classes]
+    total = int(sum(sizes))
+    if out is None:
+        out = aligned_bytes(total)
+    block = out.reshape(-1).view(np.uint8)[:total]
+    if block.size != total or block.ctypes.data % 16:
+        raise ValueError("the packed block must hold every slot and start on a 16-byte boundary")
+    at = 0
+    for k, (c, a, nb) in enumerate(zip(slot_classes, arrays, sizes)):
+        dt, shape = input_slot_shape(tab[c], frame_hz)
+        if hasattr(a, "detach") and hasattr(a, "numpy"):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if tab[c][0] == "f32":
+            a = np.ascontiguousarray(a, dtype=np.float32)
+        elif a.dtype != dt:
+            raise TypeError(f"batch slot {k}: class {c} ({tab[c][0]} at {tab[c][1]} Hz) takes {dt.name} samples, not {a.dtype.name}")
+        if a.shape != shape:
+            raise ValueError(f"batch slot {k}: class {c} ({tab[c][0]} at {tab[c][1]} Hz) takes {list(shape)} samples, not {list(a.shape)}")
+        block[at:at + nb] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+        at += nb
+    return block
 
 
 _lib = None
@@ -115,6 +189,16 @@ def load_library(path: Optional[str] = None):
     lib.vapx_get_input_format.argtypes = [vp]
     lib.vapx_pcm_decode.restype = i32
     lib.vapx_pcm_decode.argtypes = [i32, C.c_int64, vp, f32p, vp]
+    lib.vapx_set_input_classes.restype = i32
+    lib.vapx_set_input_classes.argtypes = [vp, i32, vp]
+    lib.vapx_get_input_classes.restype = i32
+    lib.vapx_get_input_classes.argtypes = [vp, vp, i32]
+    lib.vapx_set_stream_class.restype = i32
+    lib.vapx_set_stream_class.argtypes = [vp, i32, i32]
+    lib.vapx_get_stream_class.restype = i32
+    lib.vapx_get_stream_class.argtypes = [vp, i32]
+    lib.vapx_input_slot_bytes.restype = C.c_int64
+    lib.vapx_input_slot_bytes.argtypes = [vp, i32]
     lib.vapx_encode_audio.restype = i32
     lib.vapx_encode_audio.argtypes = [vp, i32, i32p, f32p, f32p, vp]
     lib.vapx_transformer.restype = i32
@@ -147,6 +231,10 @@ def load_library(path: Optional[str] = None):
     lib.vapx_ingest_open_fn.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, C.POINTER(vp)]
     lib.vapx_ingest_ports.restype = i32
     lib.vapx_ingest_ports.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    lib.vapx_ingest_class_ports.restype = i32
+    lib.vapx_ingest_class_ports.argtypes = [vp, vp, i32]
+    lib.vapx_ingest_stream_class.restype = i32
+    lib.vapx_ingest_stream_class.argtypes = [vp, i32]
     lib.vapx_ingest_stats_read.restype = i32
     lib.vapx_ingest_stats_read.argtypes = [vp, vp, i32]
     lib.vapx_ingest_late_read.restype = i32
@@ -247,8 +335,13 @@ class Engine:
                  groups: int = 0, full_last_layer: bool = False, unfused_conv: bool = False,
                  materialize_x0: bool = False, unfused_last_row: bool = False, split_f16: bool = False,
                  unfused_proj: bool = False, split_qkv_in_ffn: bool = False, input_hz: int = 16000,
-                 input_format: str = "f32"):
+                 input_format: str = "f32", input_classes=None):
         from . import pcm
+        self.input_classes = None                           # [(format name, rate)]: every stream has a class of its own (vapx.h "Input classes")
+        if input_classes is not None:
+            if int(input_hz) != 16000 or pcm.format_name(input_format) != "f32":
+                raise ValueError("input_classes replaces input_hz / input_format: give the table alone")
+            self.input_classes = input_class_table(input_classes)
         self.lib = load_library()
         self.input_format = pcm.format_name(input_format)   # sample format of the audio ``step`` takes (vapx.h, vapx_set_input_format)
         self.frame_hz = frame_hz
@@ -284,6 +377,61 @@ class Engine:
                 msg = self.lib.vapx_last_error(h).decode()
                 self.close()
                 raise VapxError(f"vapx_set_input_format failed ({rc}): {msg}")
+        if self.input_classes is not None:
+            tab = (_InputClass * len(self.input_classes))(*[_InputClass(hz, pcm.FORMATS[f]) for f, hz in self.input_classes])
+            rc = self.lib.vapx_set_input_classes(h, len(self.input_classes), C.cast(tab, C.c_void_p))
+            if rc != 0:
+                msg = self.lib.vapx_last_error(h).decode()
+                self.close()
+                raise VapxError(f"vapx_set_input_classes failed ({rc}): {msg}")
+            self._mirror_input_classes()
+
+    # -- input classes ---------------------------------------------------------------------------
+    def _mirror_input_classes(self):
+        """The host's copy of every stream's class and every class's slot size: a step sizes its packed block without a library call per slot."""
+        self._cls = np.zeros(self.max_streams, np.int64)
+        self._cls_bytes = np.array([input_slot_bytes(c, self.frame_hz) for c in self.input_classes], np.int64)
+
+    def set_stream_class(self, sid: int, cls: int):
+        """Move stream ``sid`` to input class ``cls``: queued like ``reset_carry``; the next step zeroes the stream's carry and resampler
+        history first (a new class is a new signal) and keeps its LSTM and context window."""
+        self._check(self.lib.vapx_set_stream_class(self._h, sid, cls), "vapx_set_stream_class")
+        self._cls[sid] = cls
+
+    def stream_class(self, sid: int) -> int:
+        return self._check(self.lib.vapx_get_stream_class(self._h, sid), "vapx_get_stream_class")
+
+    def refresh_stream_classes(self):
+        """Re-read every stream's class from the library: after somebody else moved streams (a ``NativeServer`` does for every connection)."""
+        for s in range(self.max_streams):
+            self._cls[s] = self.stream_class(s)
+
+    def input_slot_bytes(self, cls: int) -> int:
+        return int(self.lib.vapx_input_slot_bytes(self._h, cls))
+
+    def pack_input(self, stream_ids: Optional[Sequence[int]], arrays, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The packed block ``step`` takes for these streams in this batch order (``stream_ids`` None = 0 .. n-1): array k is
+        [2, hop_in] samples in the class of ``stream_ids[k]`` (``pack_input_classes``)."""
+        if self.input_classes is None:
+            raise VapxError("this engine has no input classes")
+        ids = np.arange(len(arrays)) if stream_ids is None else np.asarray(stream_ids, dtype=np.int64)
+        return pack_input_classes(self.input_classes, self.frame_hz, self._cls[ids].tolist(), arrays, out)
+
+    def _packed_audio(self, audio, stream_ids):
+        """``(block, n)`` of a step on an engine with input classes: ``audio`` is a list of per-slot arrays (packed here) or one packed
+        uint8 block, whose size must be what the streams' classes add up to."""
+        if isinstance(audio, np.ndarray) and audio.dtype == np.uint8 and audio.ndim == 1:
+            if stream_ids is None:
+                raise ValueError("a packed block needs stream_ids: its slots are sized by their streams' classes")
+            need = int(self._cls_bytes[self._cls[np.asarray(stream_ids, dtype=np.int64)]].sum())
+            if audio.size != need:
+                raise ValueError(f"the packed block has {audio.size} bytes, the classes of these {len(stream_ids)} streams add up to {need}")
+            if not audio.flags.c_contiguous or audio.ctypes.data % 16:
+                aligned = aligned_bytes(audio.size)
+                aligned[:] = audio
+                audio = aligned
+            return audio, len(stream_ids)
+        return self.pack_input(stream_ids, audio), len(audio)
 
     # -- lifecycle -------------------------------------------------------------------------------
     def close(self):
@@ -350,9 +498,13 @@ class Engine:
         ``pinned_empty`` block).  A stream with non-finite results (VAPX_E_NUMERIC) raises by default; with
         ``on_numeric="status"`` the block is returned — every other row is valid, the bad rows have column OUT_STATUS = 1
         and ``bad_slots()`` lists them."""
-        audio = self._host_audio(audio)
-        n, two, spc = audio.shape
-        assert two == 2
+        if self.input_classes is not None:   # a list of per-slot arrays, [2, hop_in] each in its stream's class, or one packed uint8 block
+            audio, n = self._packed_audio(audio, stream_ids)
+            spc = 0
+        else:
+            audio = self._host_audio(audio)
+            n, two, spc = audio.shape
+            assert two == 2
         ids = None if stream_ids is None else np.ascontiguousarray(stream_ids, dtype=np.int32)
         if ids is not None:
             assert ids.shape == (n,)
@@ -401,6 +553,13 @@ class Engine:
         flags = AUDIO_DEVICE | OUT_DEVICE | (IDS_DEVICE if ids_ptr else 0) | (8 if defer_join else 0)
         self._check(self.lib.vapx_step(self._h, n, ids_ptr or None, audio_ptr, spc, out_ptr, flags, stream or None), "vapx_step")
 
+    def step_packed_device(self, stream_ids: Optional[Sequence[int]], audio_ptr: int, out_ptr: int, stream: int = 0, n: Optional[int] = None):
+        """Device path of an engine with input classes: ``audio_ptr`` is the packed block in device memory (16-byte aligned), the stream
+        ids stay on the host (``None`` = 0 .. n-1): the engine computes every slot's offset from them."""
+        ids = None if stream_ids is None else np.ascontiguousarray(stream_ids, dtype=np.int32)
+        n = len(ids) if ids is not None else int(n)
+        self._check(self.lib.vapx_step(self._h, n, _np_ptr(ids), audio_ptr, 0, out_ptr, AUDIO_DEVICE | OUT_DEVICE, stream or None), "vapx_step")
+
     # -- the whole trunk group in one call (this engine leads) -----------------------------------------
     def group_wire_floats(self) -> int:
         """Wire floats per stream of this leader and its followers together (vapx.h, vapx_group_wire_floats)."""
@@ -411,9 +570,13 @@ class Engine:
         """Host path of ``vapx_step_group``: steps this leader and every follower and returns the tick's wire block, flat float32
         [n * group_wire_floats()], model-major (``TrunkGroup.step_wire`` slices it).  ``out``: e.g. a ``pinned_empty`` block.
         ``on_numeric`` as in ``step``; ``group_bad()`` lists the (slot, model) pairs."""
-        audio = self._host_audio(audio)
-        n, two, spc = audio.shape
-        assert two == 2
+        if self.input_classes is not None:
+            audio, n = self._packed_audio(audio, stream_ids)
+            spc = 0
+        else:
+            audio = self._host_audio(audio)
+            n, two, spc = audio.shape
+            assert two == 2
         ids = None if stream_ids is None else np.ascontiguousarray(stream_ids, dtype=np.int32)
         if ids is not None:
             assert ids.shape == (n,)
@@ -611,25 +774,26 @@ class TrunkGroup:
     n rows in the batch order, rows without a frame are zero with column OUT_STATUS = STATUS_NO_FRAME (``due`` masks them)."""
 
     def __init__(self, blobs: dict, frame_hz=20, context_len_sec=2.5, max_streams: int = 1,
-                 max_batch: Optional[int] = None, device_id: int = 0, input_hz: int = 16000, input_format: str = "f32", **engine_kw):
+                 max_batch: Optional[int] = None, device_id: int = 0, input_hz: int = 16000, input_format: str = "f32", input_classes=None, **engine_kw):
         self.modes = list(blobs)
         plan = trunk_plan(self.modes, frame_hz, context_len_sec)
         self.hz, self.ctx, self.hop_of, self.L_of, self.T_of, self.R = (plan[k] for k in ("hz", "ctx", "hop", "L", "T", "R"))
         self.order = plan["order"]                             # model order of vapx_step_group's wire block: leader, then followers
         self.engines = {}
         for m in self.order:                                   # engine_kw: groups / split_f16 / ... — the same for every weight set
-            kw = dict(engine_kw, input_hz=input_hz, input_format=input_format) if m == self.order[0] else engine_kw      # the leader owns the audio
+            kw = dict(engine_kw, input_hz=input_hz, input_format=input_format, input_classes=input_classes) if m == self.order[0] else engine_kw      # the leader owns the audio
             self.engines[m] = Engine(blobs[m], self.hz[m], self.ctx[m], max_streams, max_batch, m, device_id, **kw)
         self.leader = self.engines[self.order[0]]
         for m in self.order[1:]:
             self.engines[m].attach_trunk(self.leader)
         self.hop, self.L, self.T = self.leader.hop, self.leader.L, self.leader.T
         self.input_hz, self.hop_in, self.input_format = self.leader.input_hz, self.leader.hop_in, self.leader.input_format
+        self.input_classes = self.leader.input_classes     # a table: ``step`` / ``step_wire`` take per-slot arrays or a packed block, as the leader does
 
     def step(self, audio: np.ndarray, stream_ids: Optional[Sequence[int]] = None) -> dict:
         res = {self.order[0]: self.leader.step(audio, stream_ids)}
         for m in self.order[1:]:
-            res[m] = self.engines[m].step_follow(len(audio))
+            res[m] = self.engines[m].step_follow(len(res[self.order[0]]))
         return {m: res[m] for m in self.modes}
 
     @staticmethod
@@ -645,7 +809,7 @@ class TrunkGroup:
         """One ``vapx_step_group`` call for the whole group: ``{mode: wire rows [n, wire_floats(mode)]}`` (views of one block; name
         the columns with ``split_wire``).  One compact device-to-host copy and one synchronisation per tick, where ``step`` pays a
         full [n, OUT_STRIDE] copy and a synchronisation per model."""
-        n = len(audio)
+        n = len(stream_ids) if stream_ids is not None else len(audio)
         block = self.leader.step_group(audio, stream_ids, out, on_numeric)
         res, at = {}, 0
         for m in self.order:

@@ -21,11 +21,35 @@ from . import engine as _engine
 MODE = _engine.MODE
 
 
+_CONFIG_FIELDS = [("struct_size", C.c_int32), ("port_in", C.c_int32), ("port_out", C.c_int32), ("rx_threads", C.c_int32),
+                  ("tx_threads", C.c_int32), ("max_wait_us", C.c_int32), ("min_batch", C.c_int32), ("reset_on_connect", C.c_int32),
+                  ("broadcast", C.c_int32), ("bind_any", C.c_int32), ("gain", C.c_double), ("target_util_pct", C.c_int32),
+                  ("flags", C.c_int32), ("cpu_first", C.c_int32), ("cpu_count", C.c_int32), ("input_format", C.c_int32)]
+
+
+class _IngestConfigNoClasses(C.Structure):
+    """vapx_ingest_config as it was before the input classes (it ended with input_format): the library still takes it, as "no classes"."""
+    _fields_ = _CONFIG_FIELDS
+
+
 class _IngestConfig(C.Structure):
-    _fields_ = [("struct_size", C.c_int32), ("port_in", C.c_int32), ("port_out", C.c_int32), ("rx_threads", C.c_int32),
-                ("tx_threads", C.c_int32), ("max_wait_us", C.c_int32), ("min_batch", C.c_int32), ("reset_on_connect", C.c_int32),
-                ("broadcast", C.c_int32), ("bind_any", C.c_int32), ("gain", C.c_double), ("target_util_pct", C.c_int32),
-                ("flags", C.c_int32), ("cpu_first", C.c_int32), ("cpu_count", C.c_int32), ("input_format", C.c_int32)]
+    _fields_ = _CONFIG_FIELDS + [("n_input_classes", C.c_int32), ("input_classes", _engine._InputClass * _engine.MAX_INPUT_CLASSES),
+                                 ("class_ports_in", C.c_int32 * _engine.MAX_INPUT_CLASSES)]
+
+
+def class_table(classes) -> list:
+    """An input-class table for a front-end: ``engine.input_class_table`` with the wire's name "f64" (the reference's framing: f64 pairs,
+    cast to the engine's f32 on the host) accepted for "f32"."""
+    return _engine.input_class_table([("f32" if f == "f64" else f, hz) for f, hz in classes])
+
+
+def parse_input_class(text: str):
+    """``FORMAT@RATE[:PORT]`` (``serve --input_class``, the load tools) -> ((engine format name, rate), port or 0)."""
+    spec, _, port = text.partition(":")
+    fmt, at, rate = spec.partition("@")
+    if not at or not rate.isdigit() or (port and not port.isdigit()):
+        raise ValueError(f"input class {text!r}: expected FORMAT@RATE[:PORT], e.g. mulaw@8000:50017")
+    return class_table([(fmt, int(rate))])[0], int(port or 0)
 
 
 WIRE_FORMATS = {"f64": 0, "s16": 1, "mulaw": 2, "alaw": 3}      # wire format of the input port; f64 = the reference's framing (engine format f32)
@@ -65,8 +89,11 @@ class NativeServer:
     def __init__(self, eng: "_engine.Engine", port_in: int = 50007, port_out: int = 50008, gain: float = 1.0, max_wait_s: float = 0.002,
                  min_batch: int = 0, reset_on_connect: bool = True, broadcast: Optional[bool] = None, rx_threads: int = 0,
                  tx_threads: int = 0, bind_any: bool = False, target_util: float = 0.9, cores: Optional[tuple] = None,
-                 keep_nofile: bool = False, core_set: bool = False, keep_state: bool = False, input_format: Optional[str] = None):
-        """``input_format``: wire format of the input port, "f64" (the reference's framing) / "s16" / "mulaw" / "alaw"; it is the engine's
+                 keep_nofile: bool = False, core_set: bool = False, keep_state: bool = False, input_format: Optional[str] = None,
+                 class_ports=None):
+        """``class_ports``: with an engine that has input classes (``Engine(input_classes=...)``) the input port of every class, in table
+        order (default: all ephemeral; ``.class_ports`` lists the bound ones); ``port_in`` is then ignored.
+        ``input_format``: wire format of the input port, "f64" (the reference's framing) / "s16" / "mulaw" / "alaw"; it is the engine's
         (``Engine(input_format=...)``, "f32" there is "f64" here) and may be left out; one that disagrees with the engine's is refused.
         ``cores`` = (first, count): pin the front-end's tick / receive / sender threads to that core range (the GPU's NUMA node; keep
         load generators and other tenants off it), one core each — or, with ``core_set``, all of them to the range as one affinity set.  ``keep_nofile``: never raise the process's RLIMIT_NOFILE (include/vapx.h).
@@ -76,7 +103,7 @@ class NativeServer:
         self._keep = [eng]
         self._check_format(getattr(eng, "input_format", "f32"), input_format)
         cfg = self._cfg(port_in, port_out, gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, bind_any, target_util,
-                        cores, keep_nofile, core_set, keep_state, input_format)
+                        cores, keep_nofile, core_set, keep_state, input_format, getattr(eng, "input_classes", None), class_ports)
         h = C.c_void_p()
         rc = self.lib.vapx_ingest_open(eng._h, C.byref(cfg), C.byref(h))
         if rc != 0:
@@ -92,30 +119,52 @@ class NativeServer:
 
     @staticmethod
     def _cfg(port_in, port_out, gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, bind_any, target_util=0.9,
-             cores=None, keep_nofile=False, core_set=False, keep_state=False, input_format=None):
+             cores=None, keep_nofile=False, core_set=False, keep_state=False, input_format=None, input_classes=None, class_ports=None):
         first, count = (int(cores[0]), int(cores[1])) if cores else (0, 0)
-        return _IngestConfig(C.sizeof(_IngestConfig), port_in, port_out, rx_threads, tx_threads, int(max_wait_s * 1e6), min_batch,
-                             1 if reset_on_connect else 0, -1 if broadcast is None else int(bool(broadcast)), int(bool(bind_any)), gain,
-                             int(round(target_util * 100)), (1 if keep_nofile else 0) | (2 if core_set else 0) | (4 if keep_state else 0), first, count,
-                             wire_format_id(input_format))
+        cfg = _IngestConfig(C.sizeof(_IngestConfig), port_in, port_out, rx_threads, tx_threads, int(max_wait_s * 1e6), min_batch,
+                            1 if reset_on_connect else 0, -1 if broadcast is None else int(bool(broadcast)), int(bool(bind_any)), gain,
+                            int(round(target_util * 100)), (1 if keep_nofile else 0) | (2 if core_set else 0) | (4 if keep_state else 0), first, count,
+                            wire_format_id(input_format))
+        if input_classes:
+            from . import pcm
+            tab = class_table(input_classes)
+            ports = list(class_ports) if class_ports is not None else [0] * len(tab)
+            if len(ports) != len(tab):
+                raise ValueError(f"{len(tab)} input classes need {len(tab)} input ports, got {len(ports)}")
+            cfg.n_input_classes = len(tab)
+            for i, ((f, hz), port) in enumerate(zip(tab, ports)):
+                cfg.input_classes[i] = _engine._InputClass(hz, pcm.FORMATS[f])
+                cfg.class_ports_in[i] = int(port)
+        elif class_ports:
+            raise ValueError("class_ports without input classes")
+        return cfg
 
     @classmethod
     def over_function(cls, step: Callable, n_streams: int, frame_hz: int = 20, mode: str = "vap", max_batch: Optional[int] = None,
                       reset: Optional[Callable] = None, port_in: int = 0, port_out: int = 0, gain: float = 1.0, max_wait_s: float = 0.002,
                       min_batch: int = 0, reset_on_connect: bool = True, broadcast: Optional[bool] = None, rx_threads: int = 0,
-                      tx_threads: int = 0, target_util: float = 1.0, input_format: Optional[str] = None):
+                      tx_threads: int = 0, target_util: float = 1.0, input_format: Optional[str] = None, input_classes=None,
+                      class_ports=None):
         """``step(ids int32[n], audio float32[n,2,hop], out float32[n,OUT_STRIDE]) -> int`` fills ``out`` in place;
         ``reset(stream_id)`` gets negative ids (``-(id+1)``) for carry-only resets.  With ``input_format`` "s16" / "mulaw" / "alaw" the
-        input port takes packets of that format and ``audio`` is the de-interleaved raw block, int16 or uint8 [n,2,hop]."""
+        input port takes packets of that format and ``audio`` is the de-interleaved raw block, int16 or uint8 [n,2,hop].
+        With ``input_classes`` (and ``class_ports``, default ephemeral) there is one input port per class and ``audio`` is the packed block
+        exactly as an engine with that table takes it, a uint8 array: slot k holds [2, hop_in] samples of the class
+        ``self.stream_class(ids[k])`` (valid inside ``step``), the slots back to back in batch order."""
         self = cls.__new__(cls)
         self.lib = _engine.load_library()
         hop = 16000 // frame_hz
         fmt_id = wire_format_id(input_format)
+        tab = class_table(input_classes) if input_classes else None
 
         def _step(_user, n, ids, audio, out):
             try:
                 i = np.ctypeslib.as_array(ids, shape=(n,))
-                a = _raw_view(audio, n, hop, fmt_id)
+                if tab:
+                    nbytes = sum(_engine.input_slot_bytes(tab[self.stream_class(int(s))], frame_hz) for s in i)
+                    a = np.frombuffer((C.c_char * nbytes).from_address(C.addressof(audio.contents)), dtype=np.uint8)
+                else:
+                    a = _raw_view(audio, n, hop, fmt_id)
                 o = np.ctypeslib.as_array(out, shape=(n, _engine.OUT_STRIDE))
                 o[:, _engine.OUT_STATUS] = 0.0
                 return int(step(i, a, o) or 0)
@@ -130,7 +179,7 @@ class NativeServer:
 
         self._keep = [_STEP_FN(_step), _RESET_FN(_reset)]
         cfg = cls._cfg(port_in, port_out, gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, False, target_util,
-                       input_format=fmt_id)
+                       input_format=fmt_id, input_classes=tab, class_ports=class_ports)
         h = C.c_void_p()
         rc = self.lib.vapx_ingest_open_fn(C.cast(self._keep[0], C.c_void_p), C.cast(self._keep[1], C.c_void_p), None, n_streams,
                                           max_batch or n_streams, frame_hz, MODE[mode], C.byref(cfg), C.byref(h))
@@ -279,6 +328,16 @@ class NativeServer:
         a, b = C.c_int32(0), C.c_int32(0)
         self.lib.vapx_ingest_ports(self._h, C.byref(a), C.byref(b))
         self.port_in, self.port_out = a.value, b.value
+        arr = (C.c_int32 * _engine.MAX_INPUT_CLASSES)()
+        n = self.lib.vapx_ingest_class_ports(self._h, arr, _engine.MAX_INPUT_CLASSES)
+        self.class_ports = [int(arr[c]) for c in range(max(n, 0))]      # the bound input port of every input class; [] without a table
+
+    def stream_class(self, sid: int) -> int:
+        """The input class of stream ``sid`` as the tick thread knows it: for a step function of ``over_function(input_classes=...)``."""
+        c = self.lib.vapx_ingest_stream_class(self._h, int(sid))
+        if c < 0:
+            raise _engine.VapxError(f"vapx_ingest_stream_class failed ({c}): no input classes, or a bad stream id")
+        return c
 
     def stats(self, reset_latency_window: bool = False) -> dict:
         """Counters + the latency window (frame complete on the host -> packet handed to the kernel); ``late_over_10ms`` / ``answered`` are the
@@ -295,6 +354,9 @@ class NativeServer:
         if getattr(self, "_h", None):
             self.lib.vapx_ingest_close(self._h)
             self._h = None
+            for e in self._keep:                               # an engine with input classes: the front-end moved its streams between classes
+                if getattr(e, "input_classes", None) and hasattr(e, "refresh_stream_classes") and getattr(e, "_h", None):
+                    e.refresh_stream_classes()
 
     stop = close
 

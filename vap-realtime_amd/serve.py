@@ -113,9 +113,28 @@ def save_state(path, target, tag: str = "") -> bool:
     return True
 
 
+def input_class_refusal(args, names=None):
+    """Why ``--input_class`` cannot be served with the other options given, one line - or None.  ``names``: the models of ``--mode a+b``."""
+    if not getattr(args, "input_class", None):
+        return None
+    if args.input_rate != 16000:
+        return "--input_class with --input_rate: every class names its own rate (FORMAT@RATE)"
+    if args.input_format != "f64":
+        return "--input_class with --input_format: every class names its own format (FORMAT@RATE)"
+    if names is not None:
+        return f"--input_class with --mode {args.mode}: the group front-end has one input port, class ports serve one model"
+    if args.gpus > 1 or args.worker_procs == "on" or args.worker_link is not None:
+        return "--input_class with --gpus N > 1 (or worker processes): the front door has one input port, class ports serve one GPU"
+    if args.load_state or args.save_state:
+        return "--input_class with --save_state / --load_state: state records of an engine with input classes do not exist yet"
+    return None
+
+
 def rate_kw(args) -> dict:
     """``--input_rate`` and ``--input_format`` as ``Engine`` / ``TrunkGroup`` keywords; nothing at 16000 / f64, so such engines are built
-    exactly as before.  The front-end reads both from the engine."""
+    exactly as before.  The front-end reads both from the engine.  ``--input_class``: the table instead (``args.input_classes``)."""
+    if getattr(args, "input_classes", None):
+        return {"input_classes": args.input_classes}
     kw = {"input_hz": args.input_rate} if getattr(args, "input_rate", 16000) != 16000 else {}
     if getattr(args, "input_format", "f64") != "f64":
         kw["input_format"] = args.input_format
@@ -296,7 +315,8 @@ def build(args):
                 taken[node_key] = taken.get(node_key, 0) + nthr
             shards.append(ingest.NativeServer(eng, port_in=-1 if passive else args.port_num_in, port_out=-1 if passive else args.port_num_out,
                                               gain=args.audio_gain, max_wait_s=args.max_wait_ms * 1e-3, bind_any=args.bind_any,
-                                              rx_threads=args.rx_threads, tx_threads=args.tx_threads, cores=cores, reset_on_connect=not warm, keep_state=warm))
+                                              rx_threads=args.rx_threads, tx_threads=args.tx_threads, cores=cores, reset_on_connect=not warm, keep_state=warm,
+                                              class_ports=getattr(args, "class_ports", None)))
         if n > 1:
             door = ingest.FrontDoor(shards, args.port_num_in, args.port_num_out, bind_any=args.bind_any)
     except Exception:
@@ -437,6 +457,10 @@ def main(argv=None) -> int:
                     help="sample format of the clients' audio on the input port: f64 (default) is the reference's framing, 160 x {f64, f64} per "
                          "10 ms; s16 (16-bit little-endian PCM) and mulaw / alaw (G.711) packets carry input_rate / 100 interleaved (ch1, ch2) pairs "
                          "of 2 or 1 bytes per sample and are decoded on the GPU; result packets are unchanged.  Not with --audio_gain")
+    ap.add_argument("--input_class", action="append", default=None, metavar="FORMAT@RATE[:PORT]",
+                    help="repeatable: one INPUT PORT per kind of client on ONE engine, e.g. --input_class f64@16000:50007 --input_class mulaw@8000:50017 "
+                         "--input_class s16@48000:50027 (formats and rates as --input_format / --input_rate; PORT 0 or left out = ephemeral); "
+                         "--port_num_in is then ignored.  Not with --input_rate / --input_format, --mode a+b, --gpus N > 1, --save_state / --load_state")
     ap.add_argument("--streams", type=int, default=1, help="dialogue slots per GPU (the reference serves exactly one)")
     ap.add_argument("--max_batch", type=int, default=1024)
     ap.add_argument("--gpus", type=int, default=1)
@@ -480,8 +504,17 @@ def main(argv=None) -> int:
             args.context_len_sec = per_model(args.context_len_sec, 1, float, "--context_len_sec")[0]
         else:
             args.group_plan = group_plan(args, names)
+        args.input_classes = args.class_ports = None
+        if args.input_class:
+            from . import ingest
+            parsed = [ingest.parse_input_class(t) for t in args.input_class]
+            args.input_classes = ingest.class_table([c for c, _ in parsed])
+            args.class_ports = [port for _, port in parsed]
     except ValueError as e:
         ap.error(str(e))
+    why = input_class_refusal(args, names)
+    if why:
+        ap.error(why)
     if names is not None:
         if args.gpus > 1 or args.worker_procs == "on" or args.worker_link is not None:
             print(f"[vapx] --mode {args.mode} serves one GPU from one process: the front door (--gpus > 1, --worker-procs on) is single-model",
@@ -504,7 +537,12 @@ def main(argv=None) -> int:
         print(f"[vapx] start-up failed: {e}", file=sys.stderr, flush=True)
         return 1
     pin, pout = (door.port_in, door.port_out) if door else (shards[0].port_in, shards[0].port_out)
-    print(f"[vapx] {len(engines)} GPU(s) x {args.streams} dialogue slots, mode {mode}, {args.precision} arithmetic, {args.vap_process_rate} Hz / {args.context_len_sec} s, audio at {args.input_rate} Hz ({args.input_format}) — "
+    if args.input_classes:
+        audio = "input classes " + ", ".join(f"{t.split(':')[0]} :{port}" for t, port in zip(args.input_class, shards[0].class_ports))
+        print(f"[vapx] 1 GPU(s) x {args.streams} dialogue slots, mode {mode}, {args.precision} arithmetic, {args.vap_process_rate} Hz / {args.context_len_sec} s, "
+              f"{audio} — output :{pout}", flush=True)
+    else:
+        print(f"[vapx] {len(engines)} GPU(s) x {args.streams} dialogue slots, mode {mode}, {args.precision} arithmetic, {args.vap_process_rate} Hz / {args.context_len_sec} s, audio at {args.input_rate} Hz ({args.input_format}) — "
           f"input :{pin}, output :{pout}" + (" (front door: dialogue k -> GPU k mod N)" if door else ""), flush=True)
     last = time.time()
     while not stop["now"]:
