@@ -196,8 +196,9 @@ int vapx_resample(int32_t input_hz, int64_t rows, int64_t n_in, const float* x, 
  *     `const float*` and is reinterpreted.  samples_per_ch keeps its meaning and its checks (hop or hop + 320 at 16 kHz, hop_in with an
  *     input rate); every legal value is a multiple of 16, so rows stay dword-aligned.  The block's base address must be 4-byte aligned
  *     (VAPX_E_INVAL otherwise).  VAPX_AUDIO_HOST (page-locked or pageable, staged as before but in bytes) and VAPX_AUDIO_DEVICE both work;
- *   - one launch per step decodes the whole batch into an engine buffer [max_batch][2][max(hop_in, hop + 320)], before the resampler
- *     and before the overlap groups fork; the resampler or conv0 then reads fp32 as before;
+ *   - the engine's one input launch per step (csrc/input_classes.hip, the launch of an input rate) decodes the whole batch, and with an
+ *     input rate resamples it in the same pass: there is no decoded intermediate.  Its output, 16 kHz fp32 rows in an engine buffer
+ *     ([max_batch][2][hop + 320] at 16 kHz, [max_batch][2][hop] with an input rate), is what conv0 reads, before the overlap groups fork;
  *   - vapx_encode_audio always takes fp32 frames and is unaffected; state records, snapshots and vapx_reset_* are untouched (the decoder
  *     has no state: a record moves freely between engines of different input formats);
  *   - VAPX_DEFER_JOIN is not honoured (the decoded hops of a tick live in one buffer).
@@ -216,8 +217,9 @@ int vapx_pcm_decode(int32_t format, int64_t n, const void* src, float* dst, void
  * vapx_set_input_format hold for every stream of an engine; a service that faces telephone gateways (8 kHz mu-law), WebRTC peers (48 kHz
  * s16) and clients with the reference's f64 framing at once would need one engine - weights, state, scratch, ports - per combination.  An
  * input class is a pair (sample format, sample rate); an engine gets a table of classes once, every stream belongs to one class, and ONE
- * kernel launch per step decodes and resamples the whole ragged batch.  An engine that never gets a table behaves bit for bit as before,
- * on the kernels and code paths it had.
+ * kernel launch per step decodes and resamples the whole ragged batch.  It is the launch of vapx_set_input_rate / _format too: inside
+ * the engine those are a table of one class without slot descriptors, with their own rules for the step (above).  An engine with neither
+ * a rate, a format nor a table launches no input kernel.
  *
  * vapx_set_input_classes: the rules of vapx_set_input_rate - allowed once, on a freshly created engine with no step yet; refused
  * (VAPX_E_INVAL, with a message) on a trunk follower, together with vapx_set_input_rate / vapx_set_input_format in either order, for n
@@ -239,8 +241,8 @@ int vapx_pcm_decode(int32_t format, int64_t n, const void* src, float* dst, void
  * input rate.  The engine computes the offsets from the ids, so they must be on the host: VAPX_IDS_DEVICE is VAPX_E_INVAL (the rule a
  * slower trunk follower already has).  VAPX_AUDIO_HOST (page-locked or pageable, staged in bytes) and VAPX_AUDIO_DEVICE both work;
  * VAPX_DEFER_JOIN is not honoured (the hops of a tick live in one buffer).  Followers of such a leader work unchanged: the leader owns the
- * audio.  A class (f, r) stream equals, bit for bit, the stream of an engine with vapx_set_input_format(f) and vapx_set_input_rate(r): the
- * kernels share one definition of each expansion and of the resampler's chain (csrc/input_decode.h).
+ * audio.  A class (f, r) stream equals, bit for bit, the stream of an engine with vapx_set_input_format(f) and vapx_set_input_rate(r): one
+ * kernel, one definition of each expansion and of the resampler's chain (csrc/input_decode.h), shared with vapx_pcm_decode and vapx_resample.
  *
  * Other calls: vapx_encode_audio is refused, as with an input rate.  vapx_get_state / vapx_set_state behave as with an input rate (the
  * history restarts).  DELIBERATE GAPS: vapx_export_streams / vapx_import_streams are REFUSED (VAPX_E_INVAL) - a state record has one history

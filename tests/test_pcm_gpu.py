@@ -133,6 +133,7 @@ def _step_a(a, mode, raw, ids, bufs):
 CASES = [("s16", 20, False, False, "pageable"), ("s16", 20, False, False, "pinned"), ("s16", 20, False, False, "device"),
          ("mulaw", 50, False, False, "pageable"), ("mulaw", 50, False, False, "pinned"), ("mulaw", 50, False, False, "device"),
          ("s16", 20, True, False, "pageable"), ("s16", 20, True, False, "device"),
+         ("mulaw", 50, True, False, "device"),                             # L = 640: rows of 160 dwords, 16-byte stores at an output stride of L
          ("s16", 20, False, True, "pinned"), ("alaw", 20, False, True, "device")]
 
 
@@ -180,7 +181,21 @@ def test_raw_stepping_equals_float_stepping_bit_for_bit(fmt, frame_hz, full_fram
         assert odd.ctypes.data % 4 == 2
         with pytest.raises(engine.VapxError, match="4-byte aligned"):
             a.step(odd, [0])
+        out1 = np.zeros((1, engine.OUT_STRIDE), np.float32)                  # samples_per_ch = 0 is the rule of a table, not of this engine
+        assert a.lib.vapx_step(a._h, 1, None, raw[[0], :, :hop].ctypes.data, 0, out1.ctypes.data, 0, None) == -1
+        msg = a.lib.vapx_last_error(a._h).decode()
+        assert "samples_per_ch must be" in msg and "input classes" not in msg, msg
+        # to the class calls a uniform engine has no classes
+        assert a.lib.vapx_get_input_classes(a._h, None, 0) == 0 and a.lib.vapx_input_slot_bytes(a._h, 0) == 0
+        assert a.lib.vapx_set_stream_class(a._h, 0, 0) == -1 and b"no input classes" in a.lib.vapx_last_error(a._h)
+        assert a.lib.vapx_get_stream_class(a._h, 0) == -1 and b"no input classes" in a.lib.vapx_last_error(a._h)
         assert np.array_equal(a.step(np.ascontiguousarray(raw[[0], :, :hop]), [0]), b.step(flt[[0], :, :hop], [0]))
+        buf = np.zeros(2 * hop + 8, np.int16)                               # a block at an address that is 4 mod 16: dwords are all it needs
+        off = ((4 - buf.ctypes.data) % 16) // 2
+        four = buf[off:off + 2 * hop].reshape(1, 2, hop)
+        four[:] = raw[[0], :, hop:2 * hop]
+        assert four.ctypes.data % 16 == 4
+        assert np.array_equal(a.step(four, [0]), b.step(flt[[0], :, hop:2 * hop], [0]))
     a.close()
     b.close()
 
@@ -201,27 +216,41 @@ def _z(hz, x, n_out):
     return resample.delayed(yd.cpu().numpy(), hz, n_out).reshape(x.shape[:-1] + (n_out,))
 
 
-@pytest.mark.parametrize("fmt,hz,frame_hz,format_first", [("mulaw", 8000, 20, False), ("mulaw", 8000, 50, False), ("alaw", 48000, 10, True)],
-                         ids=["mulaw_8k_20hz", "mulaw_8k_50hz", "alaw_48k_10hz_format_first"])
-def test_raw_input_at_an_input_rate_equals_the_resampled_floats(fmt, hz, frame_hz, format_first):
+@pytest.mark.parametrize("fmt,hz,frame_hz,format_first,device_ids",
+                         [("mulaw", 8000, 20, False, False), ("mulaw", 8000, 50, False, False), ("alaw", 48000, 10, True, False),
+                          ("mulaw", 8000, 50, False, True)],
+                         ids=["mulaw_8k_20hz", "mulaw_8k_50hz", "alaw_48k_10hz_format_first", "mulaw_8k_50hz_device_ids"])
+def test_raw_input_at_an_input_rate_equals_the_resampled_floats(fmt, hz, frame_hz, format_first, device_ids):
     from vap_realtime_amd import pcm
     frames, hop_in, hop = 10, hz // frame_hz, 16000 // frame_hz
     assert (hz, frame_hz, hop_in) in ((8000, 20, 400), (8000, 50, 160), (48000, 10, 4800))
-    raw = _raw(fmt, (3, 2, frames * hop_in), seed=hz + frame_hz)
+    S = 6 if device_ids else 3
+    raw = _raw(fmt, (S, 2, frames * hop_in), seed=hz + frame_hz)
     z = _z(hz, _decode_gpu(fmt, raw), frames * hop)
     if format_first:                                                        # the two calls in the other order: format, then rate
-        a = _engine(frame_hz, max_streams=3)
+        a = _engine(frame_hz, max_streams=S)
         assert a.lib.vapx_set_input_format(a._h, pcm.FORMATS[fmt]) == 0 and a.lib.vapx_set_input_rate(a._h, hz) == 0
         a.input_format, a.input_hz, a.hop_in = fmt, hz, hop_in
     else:
-        a = _engine(frame_hz, max_streams=3, input_hz=hz, input_format=fmt)
+        a = _engine(frame_hz, max_streams=S, input_hz=hz, input_format=fmt)
     assert a.lib.vapx_get_input_rate(a._h) == hz and a.lib.vapx_get_input_format(a._h) == pcm.FORMATS[fmt]
-    b = _engine(frame_hz, max_streams=3)
-    for t in range(frames):
-        got = a.step(raw[:, :, t * hop_in:(t + 1) * hop_in])
-        want = b.step(z[:, :, t * hop:(t + 1) * hop])
-        assert np.array_equal(got, want), f"frame {t}: {np.abs(got - want).max()}"
-    assert got[0, 10] >= 8.0 and np.abs(got[:, :6]).max() > 0
+    b = _engine(frame_hz, max_streams=S)
+    # device_ids: device audio and device stream ids in permuted, ragged batches, rows of 40 dwords (less than a wave): the input kernel
+    # without slot descriptors, with ids that are not the identity and a history behind every stream
+    plan = _schedule(frames) if device_ids else [list(range(S))] * frames
+    done = [0] * S                                                          # a stream's k-th step takes its k-th hop: its signal has no gaps
+    for t, ids in enumerate(plan):
+        seg = np.stack([raw[s, :, done[s] * hop_in:(done[s] + 1) * hop_in] for s in ids])
+        zs = np.stack([z[s, :, done[s] * hop:(done[s] + 1) * hop] for s in ids])
+        for s in ids:
+            done[s] += 1
+        got = _step_a(a, "device", seg, ids, {}) if device_ids else a.step(seg)
+        want = b.step(zs, ids if device_ids else None)
+        assert np.array_equal(got, want), f"frame {t}, ids {ids}: {np.abs(got - want).max()}"
+    if device_ids:
+        assert np.isfinite(got).all() and np.abs(got[:, :6]).max() > 0 and min(len(i) for i in plan) < 3
+    else:
+        assert got[0, 10] >= 8.0 and np.abs(got[:, :6]).max() > 0
     a.close()
     b.close()
 
@@ -262,6 +291,11 @@ def test_trunk_group_with_a_format_on_the_leader_and_the_refusals():
         f.attach_trunk(_CACHE.setdefault("lead", _engine(20, max_streams=1)))
     with pytest.raises(ValueError, match="g722"):
         _engine(20, input_format="g722")
+    import torch
+    fr, emb = torch.zeros((1, 2, 1120), device="cuda"), torch.full((1, 2, 256), float("nan"), device="cuda")
+    e.encode_audio_device(1, fr.data_ptr(), emb.data_ptr())                 # always fp32 frames: a format alone does not refuse it
+    torch.cuda.synchronize()
+    assert torch.isfinite(emb).all()
     for x in (e, f, _CACHE.pop("lead")):
         x.close()
 

@@ -2,9 +2,12 @@
 """What input classes cost per step, in ONE process on ONE board (vapx_set_input_classes, csrc/input_classes.hip).  Legs run in
 alternating blocks, the block order reversed every block, after a warm-up that fills the context window.
 
-  --part a   a ONE-CLASS table against the existing two-launch path: three engines of the same shape - `table` (input_classes =
-             [(format, rate)]: input_classes_kernel), `uniform` (input_hz + input_format: pcm_decode_kernel + resample_kernel) and `unset`
-             (fp32 at 16 kHz, no input kernel at all, whose spread between blocks is the noise a difference has to beat).  The second
+  --part a   a ONE-CLASS table against input_hz + input_format: three engines of the same shape - `table` (input_classes =
+             [(format, rate)]), `uniform` (input_hz + input_format) and `unset` (fp32 at 16 kHz, no input kernel at all, whose spread
+             between blocks is the noise a difference has to beat).  Since the engine has one input path these are two spellings of the
+             SAME launch of input_classes_kernel: the table leg adds the slot descriptors the host builds and uploads per tick, the
+             uniform leg computes its offsets in the kernel (profiles/input_classes holds the record of when `uniform` was two launches,
+             a decoder and a resampler).  The second
              engine a process creates steps slower whatever it is (profiles/pcm_input/README.md), so a DISCARDED one-stream engine is
              created second and kept alive; --first names the leg created first.
   --part b   ONE mixed engine of S streams, split evenly over the classes, against one uniform engine of S / n streams per class,

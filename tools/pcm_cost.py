@@ -4,7 +4,8 @@ mulaw and alaw, all at 16 kHz — stepped in alternating blocks after a warm-up 
 signal, encoded for its format.
 
   device legs   audio already on the device (VAPX_AUDIO_DEVICE | VAPX_OUT_DEVICE): HIP events around each block of steps; the difference
-                to the unset engine is pcm_decode_kernel (one launch per step)
+                to the unset engine is input_classes_kernel (the engine's one input launch per step, here decoding at 16 kHz: one
+                workgroup per row, straight to the rows conv0 reads)
   host legs     audio in page-locked host memory, output in page-locked host memory (the serving path): host clock around a step, which
                 ends in a stream synchronise inside the library; the H2D bytes per tick are printed next to each leg: this is where a
                 smaller sample shows

@@ -3,7 +3,8 @@
 48000 — stepped in alternating blocks after a warm-up that fills the context window.
 
   device legs   audio already on the device (VAPX_AUDIO_DEVICE | VAPX_OUT_DEVICE): HIP events around each block of steps; the difference
-                to the unset engine is resample_kernel (one launch per step) plus what the different input size does to the tick
+                to the unset engine is input_classes_kernel (the engine's one input launch per step, here resampling fp32 input) plus
+                what the different input size does to the tick
   host legs     audio in page-locked host memory, output in page-locked host memory (the serving path): host clock around a step, which
                 ends in a stream synchronise inside the library; the H2D bytes per tick are printed next to each leg
 

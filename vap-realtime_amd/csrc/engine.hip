@@ -19,6 +19,7 @@
 #include "fused_blocks.h"
 #include "gemm_f32.h"
 #include "input_classes.h"
+#include "input_decode.h"   // pcm_bytes_per_sample
 #include "vap_kernels.h"
 #include "vapx_layout.h"
 
@@ -117,26 +118,30 @@ struct vapx_engine : Geometry {
   size_t ffn_trace_wgs = 0, attn_trace_wgs = 0;
   std::string ffn_trace_path, attn_trace_path;
 #endif
-  // input at 8 / 32 / 48 kHz (vapx_set_input_rate; resample.hip): resample_kernel turns the tick's hop_in samples into rs_out [max_batch][2][hop],
-  // which takes the place of the caller's audio in front of conv0
-  int in_hz = 0;                          // 0: the input is 16 kHz, nothing below exists
-  ResampleGeom rs = {};
-  int hop_in = 0, rs_rec = 0;             // input samples per channel and tick; floats of a stream's history [2][H], padded to a multiple of 4
-  float *rs_hist = nullptr, *rs_out = nullptr;   // [max_streams][rs_rec], [max_batch][2][hop]
-  int* rs_started = nullptr;              // [max_streams * 2] the (stream, channel) has consumed a tick since its reset
-  // input as 16-bit PCM or G.711 (vapx_set_input_format; pcm.hip): one launch decodes the tick's raw samples into pcm_out, which takes the
-  // place of the caller's audio in front of the resampler or conv0
-  int in_fmt = VAPX_PCM_F32;              // VAPX_PCM_F32: the input is fp32, pcm_out does not exist
-  float* pcm_out = nullptr;               // [max_batch][2][max(hop_in, L)]
-  size_t pcm_floats() const { return (size_t)cfg.max_batch * 2 * (size_t)std::max(hop_in, L); }
-  // input classes (vapx_set_input_classes; input_classes.hip): every stream has a (format, rate) of its own; ONE launch turns the tick's packed
-  // block into rs_out.  rs_hist (a record for the largest H of the table), rs_started and rs_out above serve it; in_hz and in_fmt stay unset
-  int n_cls = 0;                          // 0: no table, nothing below exists
+  // the engine's input (input_classes.hip): n_cls = 0, the caller's audio is 16 kHz fp32 and goes to conv0 as it is, nothing below exists.
+  // Otherwise ONE launch of input_classes_kernel turns the tick's block into rs_out, which takes the place of the caller's audio in front of
+  // conv0.  A uniform engine (vapx_set_input_rate and / or vapx_set_input_format) is the one class cls[0]; an engine with a table
+  // (vapx_set_input_classes, cls_table) gives every stream a class of its own
+  int n_cls = 0;
+  bool cls_table = false;
   InputClassGeom cls[VAPX_MAX_INPUT_CLASSES] = {};
-  vapx_input_class cls_pub[VAPX_MAX_INPUT_CLASSES] = {};   // the table as the caller gave it
-  size_t cls_lds = 0;                     // floats of dynamic LDS: the largest window of the table
-  std::vector<int32_t> stream_cls;        // [max_streams] a stream's class; the host builds the slot descriptors from it
-  Staged<int> cls_slots;                  // [max_batch] InputSlot {byte_off, cls} of a step
+  int tab_cls() const { return cls_table ? n_cls : 0; }               // what the public class calls see: a uniform engine has no classes
+  int in_fmt() const { return n_cls && !cls_table ? cls[0].fmt : VAPX_PCM_F32; }
+  int in_hz() const {                                                 // 0: no rate of the engine's own (16 kHz, or each class's)
+    static const int hz[4] = {0, 8000, 32000, 48000};                 // by ResampleGeom::orig
+    return n_cls && !cls_table ? hz[cls[0].orig] : 0;
+  }
+  int hop_in() const { return cls[0].hop_in; }                        // a uniform engine's samples per channel and tick
+  size_t cls_lds = 0;                     // floats of dynamic LDS: the largest window of cls[]
+  int rs_rec = 0;                         // floats of a stream's history [2][largest H of cls[]], padded to a multiple of 4; 0: every class is 16 kHz
+  float* rs_hist = nullptr;               // [max_streams][rs_rec], null with rs_rec = 0
+  int* rs_started = nullptr;              // [max_streams * 2] the (stream, channel) has consumed a tick since its reset
+  int rs_row = 0;                         // floats of a row of rs_out: hop; L on a uniform 16 kHz engine, which may be stepped with full frames
+  float* rs_out = nullptr;                // [max_batch][2][rs_row]
+  size_t audio_floats = 0;                // what `audio` (device and pinned) holds: [max_batch][2][L], more where the largest slot needs it
+  vapx_input_class cls_pub[VAPX_MAX_INPUT_CLASSES] = {};   // a table as the caller gave it
+  std::vector<int32_t> stream_cls;        // a table: [max_streams] a stream's class; the host builds the slot descriptors from it
+  Staged<int> cls_slots;                  // a table: [max_batch] InputSlot {byte_off, cls} of a step
   std::vector<InputSlot> cls_slots_host;
   size_t cls_slot_bytes(int c) const { return (size_t)2 * cls[c].hop_in * (size_t)pcm_bytes_per_sample(cls[c].fmt); }
   float* out_pinned = nullptr;
@@ -964,7 +969,6 @@ void vapx_destroy(vapx_handle h) {
   release_scratch(h->sc, /*encoder_only=*/false);
   release(h->audio); release(h->ids); release(h->mix); release(h->sio_ids); release(h->cls_slots);
   dfree(h->rs_hist); dfree(h->rs_out); dfree(h->rs_started);
-  dfree(h->pcm_out);
   dfree(h->gw_dev);
   dfree(h->acc); dfree(h->mixA); dfree(h->out_c);
   dfree(h->sio_dev);
@@ -1125,6 +1129,7 @@ int vapx_create(const vapx_config* cfg, const float* blob, size_t n_floats, vapx
   CR(hipHostMalloc((void**)&h->out_pinned, B * VAPX_OUT_STRIDE * sizeof(float), hipHostMallocDefault));
   CR(h->ids.create_pinned(B));
   CR(h->audio.create_pinned(B * 2 * h->L));
+  h->audio_floats = B * 2 * h->L;
   CR(dalloc(&h->sio_ids.dev, S));
   CR(h->sio_ids.create_pinned(S));
   h->id_stamp.assign(S, 0u);
@@ -1160,6 +1165,29 @@ int vapx_create(const vapx_config* cfg, const float* blob, size_t n_floats, vapx
   return VAPX_OK;
 }
 
+// what a step's audio block must be, by the engine's input: the rules of include/vapx.h "Input rate", "Input format" and "Input classes"
+static int check_audio(vapx_engine* h, const int32_t* stream_ids, const void* audio, int spc, int flags) {
+  if (h->cls_table) {
+    if (spc != 0)
+      return fail(h, VAPX_E_INVAL, "samples_per_ch must be 0 on an engine with input classes: every slot's size is its stream's class's "
+                  "(vapx_input_slot_bytes); a full frame with the caller's carry is defined at 16 kHz fp32 only");
+    if (stream_ids && (flags & VAPX_IDS_DEVICE))
+      return fail(h, VAPX_E_INVAL, "an engine with input classes needs host stream ids (VAPX_IDS_DEVICE is refused): the host computes every "
+                  "slot's offset in the packed block from its stream's class");
+    if ((uintptr_t)audio & 15) return fail(h, VAPX_E_INVAL, "the packed audio block of an engine with input classes must be 16-byte aligned");
+  } else if (h->in_hz()) {
+    if (spc != h->hop_in())
+      return fail(h, VAPX_E_INVAL, "samples_per_ch must be %d (the hop at the engine's input rate of %d Hz); a full frame with the caller's carry "
+                  "is defined at 16 kHz only", h->hop_in(), h->in_hz());
+  } else if (spc != h->hop && spc != h->L) return fail(h, VAPX_E_INVAL, "samples_per_ch must be %d (hop) or %d (full frame)", h->hop, h->L);
+  if (h->in_fmt()) {   // lane i of the input kernel reads the dword at base + 4 i
+    const size_t bps = (size_t)pcm_bytes_per_sample(h->in_fmt());
+    if ((uintptr_t)audio & 3) return fail(h, VAPX_E_INVAL, "audio in a raw input format must be 4-byte aligned");
+    if (((size_t)spc * bps) & 3) return fail(h, VAPX_E_INVAL, "samples_per_ch = %d: a row of %zu-byte samples is not a whole number of dwords", spc, bps);
+  }
+  return VAPX_OK;
+}
+
 int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* audio, int32_t spc, float* out,
               int32_t flags, void* hip_stream) {
   if (!h) return VAPX_E_INVAL;
@@ -1177,26 +1205,10 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
                   "needs host ids (or none), the host decides which streams have a frame due", h->R);
   } else {
     if (!audio) return fail(h, VAPX_E_INVAL, "null audio");
-    if (h->n_cls) {
-      if (spc != 0)
-        return fail(h, VAPX_E_INVAL, "samples_per_ch must be 0 on an engine with input classes: every slot's size is its stream's class's "
-                    "(vapx_input_slot_bytes); a full frame with the caller's carry is defined at 16 kHz fp32 only");
-      if (stream_ids && (flags & VAPX_IDS_DEVICE))
-        return fail(h, VAPX_E_INVAL, "an engine with input classes needs host stream ids (VAPX_IDS_DEVICE is refused): the host computes every "
-                    "slot's offset in the packed block from its stream's class");
-      if ((uintptr_t)audio & 15) return fail(h, VAPX_E_INVAL, "the packed audio block of an engine with input classes must be 16-byte aligned");
-    } else if (h->in_hz) {
-      if (spc != h->hop_in)
-        return fail(h, VAPX_E_INVAL, "samples_per_ch must be %d (the hop at the engine's input rate of %d Hz); a full frame with the caller's carry "
-                    "is defined at 16 kHz only", h->hop_in, h->in_hz);
-    } else if (spc != h->hop && spc != h->L) return fail(h, VAPX_E_INVAL, "samples_per_ch must be %d (hop) or %d (full frame)", h->hop, h->L);
+    const int rc0 = check_audio(h, stream_ids, audio, spc, flags);
+    if (rc0) return rc0;
   }
   if (!stream_ids && n > h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "n exceeds max_streams");
-  const size_t bps = h->in_fmt ? (size_t)pcm_bytes_per_sample(h->in_fmt) : sizeof(float);   // bytes per sample of `audio`
-  if (!lead && h->in_fmt) {   // lane i of the decoder reads the dword at base + 4 i
-    if ((uintptr_t)audio & 3) return fail(h, VAPX_E_INVAL, "audio in a raw input format must be 4-byte aligned");
-    if (((size_t)spc * bps) & 3) return fail(h, VAPX_E_INVAL, "samples_per_ch = %d: a row of %zu-byte samples is not a whole number of dwords", spc, bps);
-  }
   hipStream_t st = (hipStream_t)hip_stream;
   (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -1214,7 +1226,7 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
   // free-running groups are only safe when nothing of this step is staged through engine-owned buffers on `st`
   // (host audio / host ids would be overwritten under a still-running group of the previous tick)
   const bool all_device = (flags & VAPX_OUT_DEVICE) && (lead || (flags & VAPX_AUDIO_DEVICE)) && (!stream_ids || (flags & VAPX_IDS_DEVICE));
-  const bool defer_join = G > 1 && (flags & VAPX_DEFER_JOIN) && all_device && !slower && !h->in_hz && !h->in_fmt && !h->n_cls;   // rs_out / pcm_out is one buffer: the next tick's resampler / decoder must not overtake a running group
+  const bool defer_join = G > 1 && (flags & VAPX_DEFER_JOIN) && all_device && !slower && !h->n_cls;   // rs_out is one buffer: the next tick's input launch must not overtake a running group
   int rc = VAPX_OK;
   // a different batch split re-slices the shared scratch, and a reset touches state a running group may still use:
   // in both cases the previous tick's groups are joined first
@@ -1228,8 +1240,7 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     for (const ScratchRow& r : kScratchTable)
       if (r.poison && !(r.encoder && lead))   // a follower has released its encoder scratch
         HIPCHK(h, hipMemsetAsync(scratch_ptr(r, h->sc), 0xFF, (size_t)h->cfg.max_batch * r.per_slot(*h) * sizeof(float), st));
-    if (h->rs_out) HIPCHK(h, hipMemsetAsync(h->rs_out, 0xFF, (size_t)h->cfg.max_batch * 2 * h->hop * sizeof(float), st));
-    if (h->pcm_out) HIPCHK(h, hipMemsetAsync(h->pcm_out, 0xFF, h->pcm_floats() * sizeof(float), st));
+    if (h->n_cls) HIPCHK(h, hipMemsetAsync(h->rs_out, 0xFF, (size_t)h->cfg.max_batch * 2 * h->rs_row * sizeof(float), st));
   }
   if (!lead) { rc = flush_resets(h, st); if (rc) return rc; }
   const int* ids = nullptr;
@@ -1267,46 +1278,35 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     ids = h->mix.dev;   // the due streams' ids, in compact order
   }
   const float* ad = audio;
-  if (h->n_cls) {   // a packed block of per-class slots -> 16 kHz fp32 hops, one launch for the whole ragged batch before the overlap groups fork
-    size_t bytes = 0;
-    for (int i = 0; i < n; ++i) {
-      const int c = h->stream_cls[stream_ids ? stream_ids[i] : i];
-      h->cls_slots_host[i] = {(uint32_t)bytes, c};
-      bytes += h->cls_slot_bytes(c);   // below 2^32: vapx_set_input_classes refused a table whose largest slot x max_batch is not
+  if (!lead) {
+    // bytes of the tick's block: [n][2][spc] samples of the engine's format, or a table's packed slots, whose descriptors the host builds
+    size_t bytes = (size_t)n * 2 * spc * (size_t)pcm_bytes_per_sample(h->in_fmt());
+    if (h->cls_table) {
+      bytes = 0;
+      for (int i = 0; i < n; ++i) {
+        const int c = h->stream_cls[stream_ids ? stream_ids[i] : i];
+        h->cls_slots_host[i] = {(uint32_t)bytes, c};
+        bytes += h->cls_slot_bytes(c);   // below 2^32: vapx_set_input_classes refused a table whose largest slot x max_batch is not
+      }
+      HIPCHK(h, h->cls_slots.upload((const int*)h->cls_slots_host.data(), (size_t)2 * n, st));
     }
-    HIPCHK(h, h->cls_slots.upload((const int*)h->cls_slots_host.data(), (size_t)2 * n, st));
-    if (!(flags & VAPX_AUDIO_DEVICE)) {   // as below, in bytes: every slot is a multiple of 16
+    if (!(flags & VAPX_AUDIO_DEVICE)) {
+      // pageable memory: stage through the engine's pinned buffer (an async copy from pageable memory is a hidden synchronous staging
+      // copy inside the runtime); vapx_host_alloc memory: copy straight from the caller.  `bytes` is a whole number of dwords
+      // (check_audio; a table's slots are multiples of 16) and never more than `audio` holds (build_input)
       if (is_pinned_host(audio)) HIPCHK(h, hipMemcpyAsync(h->audio.dev, audio, bytes, hipMemcpyHostToDevice, st));
       else HIPCHK(h, h->audio.upload(audio, bytes / sizeof(float), st));
       ad = h->audio.dev;
     }
-    InputClassesArgs ia;
-    ia.in = (const unsigned char*)ad; ia.slots = (const InputSlot*)h->cls_slots.dev; ia.ids = ids; ia.hist = h->rs_hist; ia.started = h->rs_started;
-    ia.out = h->rs_out; ia.rec = h->rs_rec; ia.hop = h->hop;
-    memcpy(ia.cls, h->cls, sizeof ia.cls);
-    HIPCHK(h, launch_input_classes(ia, n, h->cls_lds, st));
-    ad = h->rs_out;
-    spc = h->hop;
-  } else if (!lead && !(flags & VAPX_AUDIO_DEVICE)) {
-    const size_t bytes = (size_t)n * 2 * spc * bps;   // a raw format: a whole number of dwords (checked above), never more than the fp32 block
-    // pageable memory: stage through the engine's pinned buffer (an async copy from pageable memory is a hidden synchronous staging
-    // copy inside the runtime); vapx_host_alloc memory: copy straight from the caller
-    if (is_pinned_host(audio)) HIPCHK(h, hipMemcpyAsync(h->audio.dev, audio, bytes, hipMemcpyHostToDevice, st));
-    else HIPCHK(h, h->audio.upload(audio, bytes / sizeof(float), st));
-    ad = h->audio.dev;
-  }
-  if (!lead && h->in_fmt) {   // raw samples -> fp32, one launch for the whole batch; the resampler or conv0 reads fp32 as ever
-    HIPCHK(h, launch_pcm_decode(h->in_fmt, (long)n * 2 * spc, ad, h->pcm_out, st));
-    ad = h->pcm_out;
-  }
-  if (h->in_hz) {   // input rate -> 16 kHz, one launch for the whole batch before the overlap groups fork; conv0 and its carry see plain hops
-    ResampleArgs ra;
-    ra.in = ad; ra.ids = ids; ra.hist = h->rs_hist; ra.started = h->rs_started; ra.out = h->rs_out;
-    ra.orig = h->rs.orig; ra.nnew = h->rs.nnew; ra.K = h->rs.K; ra.d = h->rs.d; ra.H = h->rs.H; ra.rec = h->rs_rec;
-    ra.hop_in = h->hop_in; ra.hop = h->hop;
-    HIPCHK(h, launch_resample(ra, n, st));
-    ad = h->rs_out;
-    spc = h->hop;
+    if (h->n_cls) {   // the block -> 16 kHz fp32 rows, one launch for the whole batch before the overlap groups fork; conv0 and its carry see plain rows
+      if (h->rs_row == h->hop) spc = h->hop;   // else a uniform 16 kHz engine: hop or full frame, as stepped
+      InputClassesArgs ia;
+      ia.in = (const unsigned char*)ad; ia.slots = h->cls_table ? (const InputSlot*)h->cls_slots.dev : nullptr; ia.ids = ids;
+      ia.hist = h->rs_hist; ia.started = h->rs_started; ia.out = h->rs_out; ia.rec = h->rs_rec; ia.out_row = spc;
+      memcpy(ia.cls, h->cls, sizeof ia.cls);
+      HIPCHK(h, launch_input_classes(ia, n, h->cls_lds, st));
+      ad = h->rs_out;
+    }
   }
   float* od = (flags & VAPX_OUT_DEVICE) ? out : h->sc.out_dev;
   float* orows = slower ? h->out_c : od;   // a slower follower's kernels write compact rows; one scatter places them in `od`
@@ -1480,9 +1480,11 @@ int vapx_attach_trunk(vapx_handle f, vapx_handle lead) {
   if (f == lead || lead->trunk || f->trunk || !f->followers.empty())
     return fail(f, VAPX_E_INVAL, "attach a stand-alone engine to a leader that is not itself a follower");
   if (f->tick != 0 || lead->tick != 0) return fail(f, VAPX_E_INVAL, "attach before the first step of either engine");
-  if (f->in_hz) return fail(f, VAPX_E_INVAL, "this engine has an input rate of its own (%d Hz): a follower takes no audio, set the rate on the leader", f->in_hz);
-  if (f->n_cls) return fail(f, VAPX_E_INVAL, "this engine has input classes of its own: a follower takes no audio, set the table on the leader");
-  if (f->in_fmt) return fail(f, VAPX_E_INVAL, "this engine has an input format of its own (%d): a follower takes no audio, set the format on the leader", f->in_fmt);
+  if (f->n_cls) {
+    if (f->in_hz()) return fail(f, VAPX_E_INVAL, "this engine has an input rate of its own (%d Hz): a follower takes no audio, set the rate on the leader", f->in_hz());
+    if (f->cls_table) return fail(f, VAPX_E_INVAL, "this engine has input classes of its own: a follower takes no audio, set the table on the leader");
+    return fail(f, VAPX_E_INVAL, "this engine has an input format of its own (%d): a follower takes no audio, set the format on the leader", f->in_fmt());
+  }
   if (f->cfg.device_id != lead->cfg.device_id || f->cfg.max_streams != lead->cfg.max_streams || f->cfg.max_batch != lead->cfg.max_batch)
     return fail(f, VAPX_E_INVAL, "device, max_streams and max_batch must match the leader's");
   // window and rate may differ: the follower's frame is R consecutive leader ticks (a CPC frame is a function of real samples only)
@@ -1717,8 +1719,8 @@ StateIoArgs sio_args(vapx_engine* h, int flags, float* rec, const int* ids, int 
   a.frames_seen = h->frames_seen; a.T = h->T; a.n = n;
   a.with_state = sio_follower(h) ? 0 : 1; a.with_cache = (flags & VAPX_STATE_CACHE) ? 1 : 0;
   a.hdr[0] = VAPX_STATE_MAGIC; a.hdr[1] = h->T; a.hdr[2] = h->cfg.frame_hz;
-  a.rs_hist = h->rs_hist; a.rs_started = h->rs_started; a.rs_rec = h->rs_rec; a.hdr[6] = h->in_hz;
-  a.hdr[3] = (a.with_state ? VAPX_STATE_HAS_LSTM : 0) | (h->in_hz ? VAPX_STATE_HAS_RESAMPLE : 0) |
+  a.rs_hist = h->rs_hist; a.rs_started = h->rs_started; a.rs_rec = h->rs_rec; a.hdr[6] = h->in_hz();
+  a.hdr[3] = (a.with_state ? VAPX_STATE_HAS_LSTM : 0) | (h->in_hz() ? VAPX_STATE_HAS_RESAMPLE : 0) |
              (a.with_cache ? VAPX_STATE_HAS_CACHE | ((h->cfg.flags & VAPX_FLAG_SPLIT_F16) ? VAPX_STATE_CACHE_SPLIT : 0) : 0);
   a.hdr[5] = h->cfg.mode;
   return a;
@@ -1730,7 +1732,7 @@ size_t vapx_state_floats(vapx_handle h, int32_t flags) { return h ? state_floats
 
 int vapx_export_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, float* dst, int32_t flags, void* hip_stream) {
   if (!h) return VAPX_E_INVAL;
-  if (h->n_cls) return fail(h, VAPX_E_INVAL, "%s is refused on an engine with input classes: a state record has one resampler history size per engine, "
+  if (h->cls_table) return fail(h, VAPX_E_INVAL, "%s is refused on an engine with input classes: a state record has one resampler history size per engine, "
                             "records with per-stream history sizes do not exist yet (vapx_get_state / vapx_set_state work)", "vapx_export_streams");
   { int rc = sio_check(h, "vapx_export_streams", n, stream_ids, dst, flags); if (rc) return rc; }
   hipStream_t st = (hipStream_t)hip_stream;
@@ -1761,7 +1763,7 @@ int vapx_export_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, flo
 
 int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* src, int32_t flags, void* hip_stream) {
   if (!h) return VAPX_E_INVAL;
-  if (h->n_cls) return fail(h, VAPX_E_INVAL, "%s is refused on an engine with input classes: a state record has one resampler history size per engine, "
+  if (h->cls_table) return fail(h, VAPX_E_INVAL, "%s is refused on an engine with input classes: a state record has one resampler history size per engine, "
                             "records with per-stream history sizes do not exist yet (vapx_get_state / vapx_set_state work)", "vapx_import_streams");
   { int rc = sio_check(h, "vapx_import_streams", n, stream_ids, src, flags); if (rc) return rc; }
   const size_t rec = state_floats(h, flags);
@@ -1780,10 +1782,10 @@ int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, con
         return fail(h, VAPX_E_INVAL, "record %d: content bits 0x%x: %s", k, hd[3],
                     sio_follower(h) ? "a leader / stand-alone record (LSTM + carry) offered to a trunk follower"
                                     : "a trunk follower's record (no LSTM + carry) offered to a leader / stand-alone engine");
-      if (((hd[3] & VAPX_STATE_HAS_RESAMPLE) != 0) != (h->in_hz != 0) || hd[6] != h->in_hz)
+      if (((hd[3] & VAPX_STATE_HAS_RESAMPLE) != 0) != (h->in_hz() != 0) || hd[6] != h->in_hz())
         return fail(h, VAPX_E_INVAL, "record %d: input_hz %d (content bits 0x%x) differs from this engine's %d: the record %s a resampler history, "
-                    "this engine %s", k, hd[6] ? hd[6] : 16000, hd[3], h->in_hz ? h->in_hz : 16000,
-                    (hd[3] & VAPX_STATE_HAS_RESAMPLE) ? "carries" : "carries no", h->in_hz ? "keeps one" : "keeps none");
+                    "this engine %s", k, hd[6] ? hd[6] : 16000, hd[3], h->in_hz() ? h->in_hz() : 16000,
+                    (hd[3] & VAPX_STATE_HAS_RESAMPLE) ? "carries" : "carries no", h->in_hz() ? "keeps one" : "keeps none");
       if ((hd[3] & VAPX_STATE_HAS_CACHE) != (want_bits & VAPX_STATE_HAS_CACHE))
         return fail(h, VAPX_E_INVAL, "record %d: content bits 0x%x: the record %s a Q|K|V cache, the call's flags say it %s", k, hd[3],
                     (hd[3] & VAPX_STATE_HAS_CACHE) ? "carries" : "carries no", with_cache ? "does" : "does not");
@@ -1844,8 +1846,8 @@ int vapx_encode_audio(vapx_handle h, int32_t n, const int32_t* stream_ids, const
   if (h->trunk || h->orphaned) return fail(h, VAPX_E_INVAL, "a trunk follower has no encoder; call the leader");
   if (n < 1 || n > h->cfg.max_batch) return fail(h, VAPX_E_RANGE, "n=%d outside [1,%d]", n, h->cfg.max_batch);
   if (!frames || !e) return fail(h, VAPX_E_INVAL, "null frames/e");
-  if (h->n_cls) return fail(h, VAPX_E_INVAL, "vapx_encode_audio takes complete 16 kHz fp32 frames that carry their own carry; this engine has input classes");
-  if (h->in_hz) return fail(h, VAPX_E_INVAL, "vapx_encode_audio takes complete 16 kHz frames that carry their own carry; this engine's input rate is %d Hz", h->in_hz);
+  if (h->cls_table) return fail(h, VAPX_E_INVAL, "vapx_encode_audio takes complete 16 kHz fp32 frames that carry their own carry; this engine has input classes");
+  if (h->in_hz()) return fail(h, VAPX_E_INVAL, "vapx_encode_audio takes complete 16 kHz frames that carry their own carry; this engine's input rate is %d Hz", h->in_hz());
   hipStream_t st = (hipStream_t)hip_stream;
   (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -2008,162 +2010,153 @@ int vapx_aux_head(vapx_handle h, int32_t which, int64_t rows, const float* x, fl
   return VAPX_OK;
 }
 
-// (re)allocate the decoder's output for an engine whose format is `format` and whose input hop is `hop_in` (0: 16 kHz); on failure the engine stays as it was
-static int alloc_pcm_out(vapx_engine* h, int format, int hop_in) {
-  float* p = nullptr;
-  const hipError_t e = dalloc(&p, (size_t)h->cfg.max_batch * 2 * (size_t)std::max(hop_in, h->L));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(h, e == hipErrorOutOfMemory ? VAPX_E_NOMEM : VAPX_E_HIP, "decoded-input buffer for input format %d: %s", format, hipGetErrorString(e));
+// one class as the input kernel reads it; false: a rate or format that does not exist, named in the engine's error text
+static bool input_class_geom(vapx_engine* h, int hz, int fmt, const char* who, InputClassGeom* out) {
+  ResampleGeom g = {};   // 16 kHz: orig = 0, no window
+  if (hz != 16000 && !resample_geometry(hz, &g)) {
+    fail(h, VAPX_E_INVAL, "%sinput rate %d Hz: supported are 8000, 16000, 32000 and 48000", who, hz);
+    return false;
   }
-  dfree(h->pcm_out);
-  h->pcm_out = p;
+  if (fmt < VAPX_PCM_F32 || fmt > VAPX_PCM_ALAW) {
+    fail(h, VAPX_E_INVAL, "%sinput format %d: known are 0 (f32), 1 (s16), 2 (mulaw) and 3 (alaw)", who, fmt);
+    return false;
+  }
+  *out = {g.orig, g.nnew, g.width, g.K, g.d, g.H, hz / h->cfg.frame_hz, fmt};
+  return true;
+}
+
+// (Re)build the engine's input state for the classes tab[0 .. n): the history and the `started` flags for the largest H, the 16 kHz output,
+// staging for host audio where the largest slot exceeds what `audio` holds, and the slot descriptors of a caller's table.  A buffer whose
+// size does not change is kept with its contents: a format set after a rate keeps the history.  On an allocation failure the engine stays
+// as it was and nothing leaks.  `what` names the state in the error text.
+static int build_input(vapx_engine* h, const InputClassGeom* tab, int n, bool table, const char* what) {
+  (void)hipGetLastError();
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  HIPCHK(h, hipDeviceSynchronize());
+  const size_t S = h->cfg.max_streams, B = h->cfg.max_batch;
+  int Hmax = 0;
+  size_t slot_max = 0;
+  for (int i = 0; i < n; ++i) {
+    Hmax = std::max(Hmax, tab[i].H);
+    slot_max = std::max(slot_max, (size_t)2 * tab[i].hop_in * (size_t)pcm_bytes_per_sample(tab[i].fmt));
+  }
+  const int rec = (2 * Hmax + 3) & ~3;
+  const int row = !table && tab[0].orig == 0 ? h->L : h->hop;   // a uniform 16 kHz engine may be stepped with full frames (never a larger block than `audio` holds)
+  const size_t stage_floats = B * slot_max / sizeof(float);     // staging for host audio: the largest slot in every batch slot
+  float *hist = nullptr, *rout = nullptr, *adev = nullptr, *apin = nullptr;
+  int* started = nullptr;
+  Staged<int> slots;
+  hipError_t e = hipSuccess;
+  if (rec != h->rs_rec) {
+    e = dalloc(&hist, S * (size_t)rec);
+    if (e == hipSuccess) e = dalloc(&started, S * 2);
+  }
+  if (e == hipSuccess && row != h->rs_row) e = dalloc(&rout, B * 2 * (size_t)row);
+  if (e == hipSuccess && stage_floats > h->audio_floats) {
+    e = dalloc(&adev, stage_floats);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&apin, stage_floats * sizeof(float), hipHostMallocDefault);
+  }
+  if (e == hipSuccess && table) {
+    e = dalloc(&slots.dev, B * 2);
+    if (e == hipSuccess) e = slots.create_pinned(B * 2);
+  }
+  if (e != hipSuccess) {   // the engine stays as it was
+    (void)hipGetLastError();
+    dfree(hist); dfree(started); dfree(rout); dfree(adev);
+    if (apin) (void)hipHostFree(apin);
+    release(slots);
+    return fail(h, e == hipErrorOutOfMemory ? VAPX_E_NOMEM : VAPX_E_HIP, "%s: %s", what, hipGetErrorString(e));
+  }
+  if (hist) { dfree(h->rs_hist); dfree(h->rs_started); h->rs_hist = hist; h->rs_started = started; h->rs_rec = rec; }
+  if (rout) { dfree(h->rs_out); h->rs_out = rout; h->rs_row = row; }
+  if (adev) {
+    dfree(h->audio.dev); h->audio.dev = adev;
+    (void)hipHostFree(h->audio.pin); h->audio.pin = apin;
+    h->audio_floats = stage_floats;
+  }
+  if (table) {
+    h->cls_slots = slots;
+    h->cls_slots_host.assign(B, InputSlot{0, 0});
+    h->stream_cls.assign(S, 0);
+  }
+  memcpy(h->cls, tab, (size_t)n * sizeof *tab);
+  h->cls_lds = input_classes_lds_floats(tab, n);
+  h->n_cls = n;
+  h->cls_table = table;
   return VAPX_OK;
 }
 
 int vapx_set_input_rate(vapx_handle h, int32_t input_hz) {
   if (!h) return VAPX_E_INVAL;
-  ResampleGeom g = {};
-  if (input_hz != 16000 && !resample_geometry(input_hz, &g))
-    return fail(h, VAPX_E_INVAL, "input rate %d Hz: supported are 8000, 16000, 32000 and 48000", input_hz);
+  InputClassGeom g;
+  if (!input_class_geom(h, input_hz, h->in_fmt(), "", &g)) return VAPX_E_INVAL;   // the class of a uniform engine: this rate, the format it has
   if (h->trunk || h->orphaned) return fail(h, VAPX_E_INVAL, "a trunk follower takes no audio: set the input rate on the leader");
-  if (h->n_cls) return fail(h, VAPX_E_INVAL, "this engine has input classes (vapx_set_input_classes): the rate is each class's own");
-  if (h->tick != 0 || h->in_hz) return fail(h, VAPX_E_INVAL, "set the input rate once, on a freshly created engine, before its first step");
+  if (h->cls_table) return fail(h, VAPX_E_INVAL, "this engine has input classes (vapx_set_input_classes): the rate is each class's own");
+  if (h->tick != 0 || h->in_hz()) return fail(h, VAPX_E_INVAL, "set the input rate once, on a freshly created engine, before its first step");
   if (input_hz == 16000) return VAPX_OK;
-  (void)hipGetLastError();
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  HIPCHK(h, hipDeviceSynchronize());
-  const size_t S = h->cfg.max_streams, B = h->cfg.max_batch;
-  const int hop_in = input_hz / h->cfg.frame_hz, rec = (2 * g.H + 3) & ~3;
-  float *hist = nullptr, *rout = nullptr, *adev = nullptr, *apin = nullptr;
-  int* started = nullptr;
-  hipError_t e = dalloc(&hist, S * (size_t)rec);
-  if (e == hipSuccess) e = dalloc(&started, S * 2);
-  if (e == hipSuccess) e = dalloc(&rout, B * 2 * (size_t)h->hop);
-  if (e == hipSuccess && hop_in > h->L) {   // staging for host audio at the input rate
-    e = dalloc(&adev, B * 2 * (size_t)hop_in);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&apin, B * 2 * (size_t)hop_in * sizeof(float), hipHostMallocDefault);
-  }
-  if (e != hipSuccess) {   // the engine stays as it was
-    (void)hipGetLastError();
-    dfree(hist); dfree(started); dfree(rout); dfree(adev);
-    if (apin) (void)hipHostFree(apin);
-    return fail(h, e == hipErrorOutOfMemory ? VAPX_E_NOMEM : VAPX_E_HIP, "resampler state for %d Hz: %s", input_hz, hipGetErrorString(e));
-  }
-  if (h->in_fmt && hop_in > h->L) {   // the format came first: its buffer has to hold hop_in samples now
-    const int rc = alloc_pcm_out(h, h->in_fmt, hop_in);
-    if (rc) { dfree(hist); dfree(started); dfree(rout); dfree(adev); if (apin) (void)hipHostFree(apin); return rc; }
-  }
-  if (adev) {
-    dfree(h->audio.dev); h->audio.dev = adev;
-    (void)hipHostFree(h->audio.pin); h->audio.pin = apin;
-  }
-  h->rs_hist = hist; h->rs_started = started; h->rs_out = rout;
-  h->rs = g; h->hop_in = hop_in; h->rs_rec = rec; h->in_hz = input_hz;
-  return VAPX_OK;
+  char what[64];
+  snprintf(what, sizeof what, "resampler state for %d Hz", input_hz);
+  return build_input(h, &g, 1, false, what);
 }
 
-int32_t vapx_get_input_rate(vapx_handle h) { return !h ? VAPX_E_INVAL : (h->in_hz ? h->in_hz : 16000); }
+int32_t vapx_get_input_rate(vapx_handle h) { return !h ? VAPX_E_INVAL : (h->in_hz() ? h->in_hz() : 16000); }
 
 int vapx_set_input_format(vapx_handle h, int32_t format) {
   if (!h) return VAPX_E_INVAL;
-  if (format < VAPX_PCM_F32 || format > VAPX_PCM_ALAW)
-    return fail(h, VAPX_E_INVAL, "input format %d: known are 0 (f32), 1 (s16), 2 (mulaw) and 3 (alaw)", format);
+  InputClassGeom g;
+  if (!input_class_geom(h, h->in_hz() ? h->in_hz() : 16000, format, "", &g)) return VAPX_E_INVAL;   // this format, the rate it has
   if (h->trunk || h->orphaned) return fail(h, VAPX_E_INVAL, "a trunk follower takes no audio: set the input format on the leader");
-  if (h->n_cls) return fail(h, VAPX_E_INVAL, "this engine has input classes (vapx_set_input_classes): the format is each class's own");
-  if (h->tick != 0 || h->in_fmt) return fail(h, VAPX_E_INVAL, "set the input format once, on a freshly created engine, before its first step");
+  if (h->cls_table) return fail(h, VAPX_E_INVAL, "this engine has input classes (vapx_set_input_classes): the format is each class's own");
+  if (h->tick != 0 || h->in_fmt()) return fail(h, VAPX_E_INVAL, "set the input format once, on a freshly created engine, before its first step");
   if (format == VAPX_PCM_F32) return VAPX_OK;
-  (void)hipGetLastError();
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  HIPCHK(h, hipDeviceSynchronize());
-  const int rc = alloc_pcm_out(h, format, h->hop_in);
-  if (rc == VAPX_OK) h->in_fmt = format;
-  return rc;
+  char what[64];
+  snprintf(what, sizeof what, "decoded-input buffer for input format %d", format);
+  return build_input(h, &g, 1, false, what);
 }
 
-int32_t vapx_get_input_format(vapx_handle h) { return !h ? VAPX_E_INVAL : h->in_fmt; }
+int32_t vapx_get_input_format(vapx_handle h) { return !h ? VAPX_E_INVAL : h->in_fmt(); }
 
 int vapx_set_input_classes(vapx_handle h, int32_t n, const vapx_input_class* classes) {
   if (!h) return VAPX_E_INVAL;
   if (h->trunk || h->orphaned) return fail(h, VAPX_E_INVAL, "a trunk follower takes no audio: set the input classes on the leader");
-  if (h->in_hz || h->in_fmt)
+  if (h->n_cls && !h->cls_table)
     return fail(h, VAPX_E_INVAL, "this engine has an input %s of its own (vapx_set_input_%s): input classes replace both calls, they do not combine",
-                h->in_hz ? "rate" : "format", h->in_hz ? "rate" : "format");
-  if (h->tick != 0 || h->n_cls) return fail(h, VAPX_E_INVAL, "set the input classes once, on a freshly created engine, before its first step");
+                h->in_hz() ? "rate" : "format", h->in_hz() ? "rate" : "format");
+  if (h->tick != 0 || h->cls_table) return fail(h, VAPX_E_INVAL, "set the input classes once, on a freshly created engine, before its first step");
   if (n < 1 || n > VAPX_MAX_INPUT_CLASSES || !classes)
     return fail(h, VAPX_E_INVAL, "n = %d input classes: the table holds 1 .. %d", n, VAPX_MAX_INPUT_CLASSES);
   InputClassGeom tab[VAPX_MAX_INPUT_CLASSES] = {};
-  int Hmax = 0;
   size_t slot_max = 0;
   for (int i = 0; i < n; ++i) {
     const int hz = classes[i].input_hz, fmt = classes[i].format;
-    ResampleGeom g = {};
-    if (hz != 16000 && !resample_geometry(hz, &g))
-      return fail(h, VAPX_E_INVAL, "class %d: input rate %d Hz: supported are 8000, 16000, 32000 and 48000", i, hz);
-    if (fmt < VAPX_PCM_F32 || fmt > VAPX_PCM_ALAW)
-      return fail(h, VAPX_E_INVAL, "class %d: input format %d: known are 0 (f32), 1 (s16), 2 (mulaw) and 3 (alaw)", i, fmt);
+    char who[16];
+    snprintf(who, sizeof who, "class %d: ", i);
+    if (!input_class_geom(h, hz, fmt, who, &tab[i])) return VAPX_E_INVAL;
     for (int j = 0; j < i; ++j)
       if (classes[j].input_hz == hz && classes[j].format == fmt)
         return fail(h, VAPX_E_INVAL, "classes %d and %d are equal (format %d at %d Hz): a duplicate entry", j, i, fmt, hz);
-    tab[i] = {g.orig, g.nnew, g.width, g.K, g.d, g.H, hz / h->cfg.frame_hz, fmt};   // 16 kHz: orig = 0, no window
-    Hmax = std::max(Hmax, g.H);
     slot_max = std::max(slot_max, (size_t)2 * tab[i].hop_in * (size_t)pcm_bytes_per_sample(fmt));
   }
   if ((size_t)h->cfg.max_batch * slot_max > 0xFFFFFFFFull)
     return fail(h, VAPX_E_INVAL, "max_batch %d x the largest slot (%zu bytes) passes 4 GiB: a slot's offset in the packed block is 32 bits", h->cfg.max_batch, slot_max);
-  (void)hipGetLastError();
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  HIPCHK(h, hipDeviceSynchronize());
-  const size_t S = h->cfg.max_streams, B = h->cfg.max_batch;
-  const int rec = std::max(4, (2 * Hmax + 3) & ~3);
-  const size_t stage_floats = B * slot_max / sizeof(float);   // staging for host audio: the largest slot in every batch slot
-  float *hist = nullptr, *rout = nullptr, *adev = nullptr, *apin = nullptr;
-  int *started = nullptr, *sdev = nullptr;
-  Staged<int> slots;
-  hipError_t e = dalloc(&hist, S * (size_t)rec);
-  if (e == hipSuccess) e = dalloc(&started, S * 2);
-  if (e == hipSuccess) e = dalloc(&rout, B * 2 * (size_t)h->hop);
-  if (e == hipSuccess) e = dalloc(&sdev, B * 2);
-  if (e == hipSuccess) e = slots.create_pinned(B * 2);
-  if (e == hipSuccess && stage_floats > B * 2 * (size_t)h->L) {
-    e = dalloc(&adev, stage_floats);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&apin, stage_floats * sizeof(float), hipHostMallocDefault);
-  }
-  if (e != hipSuccess) {   // the engine stays as it was
-    (void)hipGetLastError();
-    dfree(hist); dfree(started); dfree(rout); dfree(adev);
-    slots.dev = sdev;
-    release(slots);
-    if (apin) (void)hipHostFree(apin);
-    return fail(h, e == hipErrorOutOfMemory ? VAPX_E_NOMEM : VAPX_E_HIP, "state and staging for %d input classes: %s", n, hipGetErrorString(e));
-  }
-  if (adev) {
-    dfree(h->audio.dev); h->audio.dev = adev;
-    (void)hipHostFree(h->audio.pin); h->audio.pin = apin;
-  }
-  slots.dev = sdev;
-  h->cls_slots = slots;
-  h->cls_slots_host.assign(B, InputSlot{0, 0});
-  h->rs_hist = hist; h->rs_started = started; h->rs_out = rout; h->rs_rec = rec;
-  memcpy(h->cls, tab, sizeof tab);
-  memcpy(h->cls_pub, classes, (size_t)n * sizeof *classes);
-  h->cls_lds = input_classes_lds_floats(tab, n);
-  h->stream_cls.assign(S, 0);
-  h->n_cls = n;
-  return VAPX_OK;
+  char what[64];
+  snprintf(what, sizeof what, "state and staging for %d input classes", n);
+  const int rc = build_input(h, tab, n, true, what);
+  if (rc == VAPX_OK) memcpy(h->cls_pub, classes, (size_t)n * sizeof *classes);
+  return rc;
 }
 
 int32_t vapx_get_input_classes(vapx_handle h, vapx_input_class* out, int32_t max) {
   if (!h) return VAPX_E_INVAL;
-  for (int i = 0; out && i < h->n_cls && i < max; ++i) out[i] = h->cls_pub[i];
-  return h->n_cls;
+  for (int i = 0; out && i < h->tab_cls() && i < max; ++i) out[i] = h->cls_pub[i];
+  return h->tab_cls();
 }
 
 int vapx_set_stream_class(vapx_handle h, int32_t sid, int32_t cls) {
   if (!h) return VAPX_E_INVAL;
-  if (!h->n_cls) return fail(h, VAPX_E_INVAL, "this engine has no input classes (vapx_set_input_classes)");
+  if (!h->cls_table) return fail(h, VAPX_E_INVAL, "this engine has no input classes (vapx_set_input_classes)");
   if (sid < 0 || sid >= h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "stream id %d out of range [0,%d)", sid, h->cfg.max_streams);
-  if (cls < 0 || cls >= h->n_cls) return fail(h, VAPX_E_RANGE, "input class %d out of range [0,%d)", cls, h->n_cls);
+  if (cls < 0 || cls >= h->tab_cls()) return fail(h, VAPX_E_RANGE, "input class %d out of range [0,%d)", cls, h->tab_cls());
   // a new class is a new signal: the carry-only request of vapx_reset_carry (carry, resampler history, started flags), applied by the next
   // step before it touches any state; that step is also the first to build a slot descriptor from the stream's class, which lives on the host
   const int rc = vapx_reset_carry(h, sid);
@@ -2173,13 +2166,13 @@ int vapx_set_stream_class(vapx_handle h, int32_t sid, int32_t cls) {
 
 int32_t vapx_get_stream_class(vapx_handle h, int32_t sid) {
   if (!h) return VAPX_E_INVAL;
-  if (!h->n_cls) return fail(h, VAPX_E_INVAL, "this engine has no input classes (vapx_set_input_classes)");
+  if (!h->cls_table) return fail(h, VAPX_E_INVAL, "this engine has no input classes (vapx_set_input_classes)");
   if (sid < 0 || sid >= h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "stream id %d out of range [0,%d)", sid, h->cfg.max_streams);
   return h->stream_cls[sid];
 }
 
 int64_t vapx_input_slot_bytes(vapx_handle h, int32_t cls) {
-  if (!h || cls < 0 || cls >= h->n_cls) return 0;
+  if (!h || cls < 0 || cls >= h->tab_cls()) return 0;
   return (int64_t)h->cls_slot_bytes(cls);
 }
 

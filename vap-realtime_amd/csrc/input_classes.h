@@ -1,4 +1,5 @@
-// Input classes (vapx_set_input_classes; include/vapx.h "Input classes"): what engine.hip hands to input_classes.hip.  Plain C++.
+// The engine's input launch (vapx_set_input_rate / _format / _classes; include/vapx.h "Input rate", "Input format", "Input classes"):
+// what engine.hip hands to input_classes.hip.  Plain C++.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,13 +14,15 @@ struct InputClassGeom { int orig, nnew, width, K, d, H, hop_in, fmt; };
 struct InputSlot { uint32_t byte_off; int32_t cls; };
 
 struct InputClassesArgs {
-  const unsigned char* in;   // the packed block, 16-byte aligned
-  const InputSlot* slots;    // [n]
+  const unsigned char* in;   // the block: packed slots, 16-byte aligned (a table), or [n][2][row] samples of class 0, dword-aligned (slots == null)
+  const InputSlot* slots;    // [n], or null: a uniform engine, slot b is class 0 at b * (bytes of its two rows)
   const int* ids;            // [n] stream ids (device) or null = identity
   float* hist;               // [S][rec]: per stream [2][H of its class] input samples of its earlier ticks, then padding
   int* started;              // [S][2]: the (stream, channel) has consumed a tick since its reset
-  float* out;                // [n][2][hop] the 16 kHz samples conv0 takes
-  int rec, hop;
+  float* out;                // [n][2][out_row] the 16 kHz samples conv0 takes
+  int rec;
+  int out_row;               // samples of an output row, and of a 16 kHz class's input row: the hop; a uniform 16 kHz engine stepped with
+                             // full frames: L (the caller's carry in front).  A multiple of 16
   InputClassGeom cls[VAPX_MAX_INPUT_CLASSES];
 };
 

@@ -1,15 +1,18 @@
-// Input classes: streams of different sample formats and rates in ONE batch (vapx_set_input_classes; include/vapx.h "Input classes").
-// A class is (format, rate); every stream belongs to one; a tick's audio is a packed block in which batch slot k holds
-// [2][hop_in(c_k)] samples of format(c_k).  input_classes_kernel turns the whole ragged block into the 16 kHz fp32 hops conv0 takes, in
-// one launch: one 256-thread workgroup per (batch slot, channel).  The slot's class is uniform over the workgroup; its geometry is read
-// once from the kernel arguments and lives in scalars.
+// The engine's one input path: whatever the caller's audio is, input_classes_kernel turns a tick's block into the 16 kHz fp32 rows conv0
+// takes, in one launch.  A class is (format, rate).  An engine with a table (vapx_set_input_classes; include/vapx.h "Input classes") gives
+// every stream a class of its own; its tick is a packed block in which batch slot k holds [2][hop_in(c_k)] samples of format(c_k), described
+// by slot descriptors the host builds.  A uniform engine (vapx_set_input_rate and / or vapx_set_input_format) is a table of ONE class with
+// no descriptors: slot b is class 0 at b x (bytes of its two rows), computed here.
+// One 256-thread workgroup per (batch slot, channel).  The slot's class is uniform over the workgroup; its geometry is read once from the
+// kernel arguments and lives in scalars.
 //   - load + decode: lane i reads the aligned dword at the row's base + 4 i (four G.711 codes, two s16 samples or one float) and expands
-//     it with the device functions of input_decode.h, the ones pcm_decode_kernel uses;
+//     it with the device functions of input_decode.h, the ones pcm_decode_kernel (vapx_pcm_decode) uses;
 //   - a 16 kHz class stores the decoded samples straight to the output with vector stores: no window, no barrier;
 //   - any other rate: the samples land in LDS behind the stream's history [H], the new history is stored back, and every output is one
-//     resample_dot chain over the same tap tables as resample_kernel, with the same `started` / "first d blocks are zero" rule.
-// One definition of each expansion and of the chain: a stream of class (f, r) equals, bit for bit, the stream of an engine with
-// vapx_set_input_format(f) + vapx_set_input_rate(r).  The tick moves about 40 MB at 4096 streams; nothing is tuned past coalesced access.
+//     resample_dot chain over the tap tables resample_whole_kernel (vapx_resample) reads.  A stream has no future samples, so its 16 kHz
+//     stream is the whole-signal Y delayed by d blocks (resample.hip): the first d blocks after a reset (`started` clear) are zero.
+// One definition of each expansion and of the chain: a stream of class (f, r) in a table equals, bit for bit, the stream of a uniform
+// engine of (f, r).  The tick moves about 40 MB at 4096 streams; nothing is tuned past coalesced access.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -38,7 +41,8 @@ __device__ __forceinline__ void decode_to_lds(const uint32_t* __restrict__ src, 
   }
 }
 
-// the row's dwords -> decoded samples in global memory (a 16 kHz class); dst is 16-byte aligned: one 4-, 8- or 16-byte store per lane
+// the row's dwords -> decoded samples in global memory (a 16 kHz class): one 4-, 8- or 16-byte store per lane.  dst is 16-byte aligned:
+// the output buffer is, and a row (out_row: the hop, or L = hop + 320 for full frames) is a multiple of 16 samples
 template <int FMT>
 __device__ __forceinline__ void decode_to_out(const uint32_t* __restrict__ src, float* __restrict__ dst, int dwords, int tid) {
   for (int i = tid; i < dwords; i += 256) {
@@ -61,19 +65,18 @@ __device__ __forceinline__ void decode_to_out(const uint32_t* __restrict__ src, 
   }
 }
 
-__device__ __forceinline__ int bytes_per_sample(int fmt) { return fmt == VAPX_PCM_F32 ? 4 : fmt == VAPX_PCM_S16 ? 2 : 1; }
-
 // One workgroup per (batch slot, channel): LDS = taps | history [H] ++ this tick's hop_in decoded samples (classes off 16 kHz only).
 __global__ __launch_bounds__(256) void input_classes_kernel(InputClassesArgs a) {
   extern __shared__ float lds[];
   const int tid = threadIdx.x, row = blockIdx.x, b = row >> 1, c = row & 1;
-  const InputSlot slot = a.slots[b];
-  const InputClassGeom g = a.cls[__builtin_amdgcn_readfirstlane(slot.cls)];   // uniform over the workgroup: scalars
-  const int row_bytes = g.hop_in * bytes_per_sample(g.fmt), dwords = row_bytes >> 2;   // hop_in is a multiple of 16 samples
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(a.in + slot.byte_off + (size_t)c * row_bytes);
-  float* o = a.out + (long)row * a.hop;
+  const InputClassGeom g = a.cls[a.slots ? __builtin_amdgcn_readfirstlane(a.slots[b].cls) : 0];   // uniform over the workgroup: scalars
+  const int n_in = g.orig ? g.hop_in : a.out_row;   // a 16 kHz row is as long as the row stepped
+  const int row_bytes = n_in * pcm_bytes_per_sample(g.fmt), dwords = row_bytes >> 2;   // every row is a multiple of 16 samples
+  const size_t byte_off = a.slots ? a.slots[b].byte_off : (size_t)b * 2 * row_bytes;   // no descriptors: a uniform engine, rows back to back
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(a.in + byte_off + (size_t)c * row_bytes);
+  float* o = a.out + (long)row * a.out_row;
 
-  if (g.orig == 0) {   // 16 kHz: hop_in == hop, decode straight to the output
+  if (g.orig == 0) {   // 16 kHz: decode straight to the output
     switch (g.fmt) {
       case VAPX_PCM_F32: decode_to_out<VAPX_PCM_F32>(src, o, dwords, tid); break;
       case VAPX_PCM_S16: decode_to_out<VAPX_PCM_S16>(src, o, dwords, tid); break;
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(256) void input_classes_kernel(InputClassesArgs a) 
   __syncthreads();
   for (int i = tid; i < g.H; i += 256) hs[i] = buf[g.hop_in + i];   // hop_in >= 160 > H: the new history is all of this tick
   if (tid == 0) a.started[sid * 2 + c] = 1;
-  for (int m = tid; m < a.hop; m += 256) {
+  for (int m = tid; m < a.out_row; m += 256) {   // out_row is the hop: full frames are a 16 kHz engine's
     const int j = m / g.nnew, p = m - j * g.nnew;
     const float v = resample_dot(th + p * g.K, buf + g.orig * j, g.K);   // last index read: hop_in + 2 width - 1 < H + hop_in
     o[m] = (fresh && j < g.d) ? 0.f : v;

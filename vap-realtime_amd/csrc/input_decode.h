@@ -1,6 +1,7 @@
 // The device functions every input kernel shares: the G.711 / s16 expansions of pcm.hip and the resampler's tap tables and fmaf chain of
-// resample.hip.  pcm_decode_kernel, resample_kernel, resample_whole_kernel and input_classes_kernel (input_classes.hip) all include this
-// header, so there is ONE definition of each expansion and ONE of the chain: a stream stepped through any of them sees the same bits.
+// resample.hip.  pcm_decode_kernel, resample_whole_kernel and input_classes_kernel (input_classes.hip, the engine's one input launch) all
+// include this header, so there is ONE definition of each expansion and ONE of the chain: a stream stepped through any of them sees the
+// same bits.
 // The definitions are vap-realtime_amd/pcm.py (tables of pcm_tables.h) and vap-realtime_amd/resample.py (taps of resample_taps.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,6 +13,11 @@
 namespace {
 
 // ---- sample formats -----------------------------------------------------------------------------------------------------------------
+// bytes of one sample, on the host and in the kernels; 0: unknown format id
+__host__ __device__ constexpr int pcm_bytes_per_sample(int format) {
+  return format == VAPX_PCM_F32 ? 4 : format == VAPX_PCM_S16 ? 2 : (format == VAPX_PCM_MULAW || format == VAPX_PCM_ALAW) ? 1 : 0;
+}
+
 // G.711 is expanded by the CLOSED FORM in integer ALU (a handful of shifts and adds per code), not by a table in LDS: no LDS, no barrier,
 // no constant-memory traffic.  The static_assert below holds the closed forms to pcm_tables.h for all 256 codes at compile time.
 __host__ __device__ constexpr int mulaw_linear(unsigned c) {

@@ -1,5 +1,6 @@
 // Input in the sample format it already has: 16-bit linear PCM and G.711 mu-law / A-law -> the fp32 the model computes in, on the device
-// (vapx_set_input_format, vapx_pcm_decode; include/vapx.h "Input format").  The definition is vap-realtime_amd/pcm.py, which also writes
+// (include/vapx.h "Input format").  This file is vapx_pcm_decode, a block of samples of any length; an engine with an input format
+// (vapx_set_input_format) decodes its ticks in input_classes_kernel (input_classes.hip), with the same device functions of input_decode.h.  The definition is vap-realtime_amd/pcm.py, which also writes
 // the two 256-entry tables of pcm_tables.h:  s16: float(v) * 2^-15;  mulaw / alaw: float(table[c]) * 2^-15.  Every value is exact in
 // fp32 and integer zero converts to +0.0f, so a stream stepped in a raw format equals, bit for bit, one fed the decoded floats.
 //
@@ -7,11 +8,10 @@
 // no constant-memory traffic.  input_decode.h holds the closed forms to pcm_tables.h for all 256 codes at compile time; the host
 // side (the front-end's echo, csrc/ingest.cpp) reads the tables.
 //
-// One kernel for the engine's step and for vapx_pcm_decode: the block is flat, [rows][spc] samples are n = rows * spc samples in a row.
-// Lane i reads the aligned dword at base + 4 i (two s16 samples or four codes) and writes its outputs with one 8-byte or one 16-byte
-// store.  A tick of 4096 streams moves at most about 40 MB; the kernel is bound by that traffic and nothing is tuned past the access
-// pattern.  A sample count that does not fill the last dword (vapx_pcm_decode only: every row of a step is a multiple of 16 samples) is
-// finished by that dword's lane with single loads and stores, so nothing is read or written past n samples.
+// The block is flat: n samples in a row.  Lane i reads the aligned dword at base + 4 i (two s16 samples or four codes) and writes its
+// outputs with one 8-byte or one 16-byte store; the kernel is bound by that traffic and nothing is tuned past the access pattern.  A
+// sample count that does not fill the last dword is finished by that dword's lane with single loads and stores, so nothing is read or
+// written past n samples.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -53,15 +53,6 @@ __global__ __launch_bounds__(256) void pcm_decode_kernel(const uint32_t* __restr
 }
 
 }  // namespace
-
-int pcm_bytes_per_sample(int format) {
-  switch (format) {
-    case VAPX_PCM_F32: return 4;
-    case VAPX_PCM_S16: return 2;
-    case VAPX_PCM_MULAW: case VAPX_PCM_ALAW: return 1;
-  }
-  return 0;
-}
 
 hipError_t launch_pcm_decode(int format, long n, const void* src, float* dst, hipStream_t st) {
   const int per = format == VAPX_PCM_S16 ? 2 : 4;

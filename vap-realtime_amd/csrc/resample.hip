@@ -2,43 +2,19 @@
 // The filter is torchaudio.functional.resample's default (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99), restated in
 // vap-realtime_amd/resample.py, which also writes the fp32 tap tables of resample_taps.h.  With orig = in_hz / g, new = 16000 / g:
 //   Y[new*i + p] = sum_k h[p][k] * x[orig*i + k - width],  k = 0 .. K-1,  x = 0 outside the signal
-// A stream has no future samples: the engine's 16 kHz stream is Y delayed by d = ceil(width / orig) = 7 blocks (0.875 ms at 8 kHz,
-// 0.4375 ms at 32 and 48 kHz), z[m] = Y[m - new*d] and zero for m < new*d; a tick needs the last H = orig*d + width input samples
-// of the stream's earlier ticks.
-// Both kernels stage their input window in LDS with coalesced 4-byte loads (lane i at base + 4 i), keep the taps in LDS (copied from
-// constant memory) and produce every output with resample_dot: one fmaf chain over k = 0 .. K-1.  The streaming kernel and the
-// whole-signal kernel therefore agree bit for bit.  A tick of 4096 streams moves about 40 MB: nothing here is tuned past that.
+// vapx_resample turns whole signals into Y.  An engine's stream has no future samples: its 16 kHz stream is Y delayed by
+// d = ceil(width / orig) = 7 blocks (0.875 ms at 8 kHz, 0.4375 ms at 32 and 48 kHz), z[m] = Y[m - new*d] and zero for m < new*d; a tick
+// needs the last H = orig*d + width input samples of the stream's earlier ticks.  That streaming form is input_classes_kernel
+// (input_classes.hip), the engine's one input launch; this file keeps the geometry both share and the whole-signal kernel.
+// Both stage their input window in LDS with coalesced 4-byte loads (lane i at base + 4 i), keep the taps in LDS (copied from constant
+// memory) and produce every output with resample_dot: one fmaf chain over k = 0 .. K-1.  The streaming launch and the whole-signal
+// kernel therefore agree bit for bit.
 #include <hip/hip_runtime.h>
 
 #include "input_decode.h"   // the tap tables, taps_of and resample_dot: shared with input_classes.hip
 #include "vap_kernels.h"
 
 namespace {
-
-// One workgroup per (batch slot, channel): LDS = taps | history [H] ++ this tick's hop_in samples.
-__global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {
-  extern __shared__ float lds[];
-  float* th = lds;
-  float* buf = lds + kTapSlots;
-  const int tid = threadIdx.x, row = blockIdx.x, b = row >> 1, c = row & 1;
-  const int sid = a.ids ? a.ids[b] : b;
-  const float* tp = taps_of(a.orig);
-  for (int i = tid; i < a.nnew * a.K; i += 256) th[i] = tp[i];
-  float* hs = a.hist + (long)sid * a.rec + c * a.H;
-  const float* in = a.in + (long)row * a.hop_in;
-  for (int i = tid; i < a.H; i += 256) buf[i] = hs[i];
-  for (int i = tid; i < a.hop_in; i += 256) buf[a.H + i] = in[i];
-  const bool fresh = a.started[sid * 2 + c] == 0;   // no tick since the stream's reset: Y has no samples before its block 0
-  __syncthreads();
-  for (int i = tid; i < a.H; i += 256) hs[i] = buf[a.hop_in + i];   // hop_in >= 160 > H: the new history is all of this tick
-  if (tid == 0) a.started[sid * 2 + c] = 1;
-  float* o = a.out + (long)row * a.hop;
-  for (int m = tid; m < a.hop; m += 256) {
-    const int j = m / a.nnew, p = m - j * a.nnew;
-    const float v = resample_dot(th + p * a.K, buf + a.orig * j, a.K);   // last index read: hop_in + 2 width - 1 < H + hop_in
-    o[m] = (fresh && j < a.d) ? 0.f : v;
-  }
-}
 
 // Whole signals: a workgroup makes 256 output blocks (256 * new outputs) of one row from a window of orig * 255 + K inputs.
 constexpr int kWholeBlocks = 256;
@@ -75,12 +51,6 @@ bool resample_geometry(int in_hz, ResampleGeom* g) {
     case 48000: *g = {3, 1, 19, 41, 7, 40}; return true;
   }
   return false;
-}
-
-hipError_t launch_resample(const ResampleArgs& a, int n, hipStream_t st) {
-  const size_t lds = (size_t)(kTapSlots + a.H + a.hop_in) * sizeof(float);
-  hipLaunchKernelGGL(resample_kernel, dim3((unsigned)n * 2), dim3(256), lds, st, a);
-  return hipGetLastError();
 }
 
 hipError_t launch_resample_whole(const ResampleGeom& g, long rows, long n_in, const float* x, float* y, hipStream_t st) {

@@ -167,20 +167,10 @@ struct StateIoArgs {    // state_io.hip: bulk stream-state export / import (vapx
 };
 
 struct ResampleGeom { int orig, nnew, width, K, d, H; };   // resample.hip: in_hz / g, 16000 / g, filter half width, taps per phase, delay blocks, history
-struct ResampleArgs {   // resample.hip: one tick of the streaming resampler (vapx_set_input_rate)
-  const float* in;      // [n][2][hop_in] this tick's samples at the input rate
-  const int* ids;       // [n] stream ids (device) or null = identity
-  float* hist;          // [S][rec]: per stream [2][H] input samples of its earlier ticks, then padding
-  int* started;         // [S*2] 0 until the (stream, channel) has consumed a tick since its reset
-  float* out;           // [n][2][hop] the 16 kHz samples conv0 takes
-  int orig, nnew, K, d, H, rec, hop_in, hop;
-};
 bool resample_geometry(int in_hz, ResampleGeom* g);   // false: not 8000 / 32000 / 48000
-hipError_t launch_resample(const ResampleArgs& a, int n, hipStream_t st);
 hipError_t launch_resample_whole(const ResampleGeom& g, long rows, long n_in, const float* x, float* y, hipStream_t st);
 
-// pcm.hip: n raw samples (VAPX_PCM_S16 / _MULAW / _ALAW; src dword-aligned) -> n floats (dst 16-byte aligned), the engine's step and vapx_pcm_decode alike
-int pcm_bytes_per_sample(int format);   // 0: unknown format id
+// pcm.hip: n raw samples (VAPX_PCM_S16 / _MULAW / _ALAW; src dword-aligned) -> n floats (dst 16-byte aligned): vapx_pcm_decode
 hipError_t launch_pcm_decode(int format, long n, const void* src, float* dst, hipStream_t st);
 
 hipError_t launch_state_export(const StateIoArgs& a, hipStream_t st);
