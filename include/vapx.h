@@ -249,7 +249,27 @@ int vapx_pcm_decode(int32_t format, int64_t n, const void* src, float* dst, void
  * size per engine, records with per-stream history sizes are a follow-up (the precedent of the mixed-rate follower); the group and door front-ends
  * (vapx_ingest_open_group*, passive shards behind vapx_frontdoor_*) refuse a table - vapx_ingest_open and vapx_ingest_open_fn serve one, with an
  * input port per class (vapx_ingest_config.input_classes); offline.py keeps
- * its one engine per rate (its 16 kHz pairs use full frames with a real carry, which a class engine refuses by design). */
+ * its one engine per rate (its 16 kHz pairs use full frames with a real carry, which a class engine refuses by design).
+ *
+ * CHANNEL CLASSES: a class belongs to a (stream, channel).  A contact-centre dialogue has an agent leg from a softphone (48 kHz s16) and a
+ * customer leg from the PSTN (8 kHz G.711); a gateway that forks both legs has them in two codecs.  vapx_set_stream_class(sid, c) means
+ * (c, c), and everything above holds for such a stream as it stands.
+ * vapx_set_stream_channel_classes(sid, c1, c2): the rules of vapx_set_stream_class - queued, applied by the next step before it touches any
+ * state; the carry, the history and the `started` flags of BOTH channels are zeroed, the LSTM and the ring stay.  VAPX_E_RANGE for a bad
+ * stream id or class; VAPX_E_INVAL on an engine without a table.  A reset of one channel alone, where only one leg's class changes, is
+ * deliberately not built: the 320-sample carry and the reset list are per stream, and a leg that changes codec in mid-call is a new call.
+ * vapx_get_stream_channel_classes: out[0], out[1] = the classes of channel 1 and channel 2.  vapx_get_stream_class returns c where both
+ * are c and VAPX_E_INVAL (with a message naming this call) where they differ.
+ * vapx_input_row_bytes: bytes of ONE channel's row of class cls, hop_in(cls) * bytes_per_sample(cls), a multiple of 16; 0 for a bad class
+ * or an engine without a table.  vapx_input_slot_bytes(c) = 2 * vapx_input_row_bytes(c), unchanged.
+ * LAYOUT: slot k of the packed block holds channel 1's row, hop_in(c1) samples of format(c1), followed by channel 2's row, hop_in(c2)
+ * samples of format(c2): vapx_input_row_bytes(c1) + vapx_input_row_bytes(c2) bytes, at the sum of the earlier slots' sizes.  For c1 == c2
+ * this is the layout above byte for byte; every row is a multiple of 16 bytes, so every alignment rule stays.  A mixed slot is never
+ * larger than the largest same-class slot of the table, so the staging, the LDS window and the 4 GiB rule of vapx_set_input_classes
+ * stand.  Each channel's history lives in its own half of the stream's record, whatever the other channel's class.
+ * SKEW: each channel reaches the model with its own class's delay (DELAY under "Input rate"), d = 7 blocks of `new` 16 kHz samples: 0.875 ms
+ * at 8 kHz, 0.4375 ms at 32 and at 48 kHz, none at 16 kHz.  Two legs of different classes are therefore up to 0.875 ms apart, against a frame
+ * of 20 - 100 ms. */
 #define VAPX_MAX_INPUT_CLASSES 16      /* 4 formats x 4 rates: every combination fits */
 typedef struct vapx_input_class { int32_t input_hz; int32_t format; } vapx_input_class;   /* 8000|16000|32000|48000, VAPX_PCM_* */
 int vapx_set_input_classes(vapx_handle h, int32_t n, const vapx_input_class* classes);
@@ -257,6 +277,9 @@ int32_t vapx_get_input_classes(vapx_handle h, vapx_input_class* out, int32_t max
 int vapx_set_stream_class(vapx_handle h, int32_t stream_id, int32_t cls);
 int32_t vapx_get_stream_class(vapx_handle h, int32_t stream_id);
 int64_t vapx_input_slot_bytes(vapx_handle h, int32_t cls);
+int vapx_set_stream_channel_classes(vapx_handle h, int32_t stream_id, int32_t cls_ch1, int32_t cls_ch2);
+int vapx_get_stream_channel_classes(vapx_handle h, int32_t stream_id, int32_t out[2]);
+int64_t vapx_input_row_bytes(vapx_handle h, int32_t cls);
 
 /* Batch slots (row indices of `out`) of the latest host-output vapx_step whose results were not finite; returns their number
  * (writes at most max_slots of them; slots may be NULL to just count). */
@@ -564,7 +587,21 @@ typedef struct vapx_ingest_config {
   int32_t n_input_classes;
   vapx_input_class input_classes[VAPX_MAX_INPUT_CLASSES];
   int32_t class_ports_in[VAPX_MAX_INPUT_CLASSES];
+  /* PAIR PORTS (struct_size = the whole struct; every earlier size, the one that ended with class_ports_in included, means "no pair ports"):
+     input ports for dialogues whose two legs arrive in different classes of the table ("Input classes", CHANNEL CLASSES): a media gateway
+     that forks an agent leg (48 kHz s16) and a customer leg (8 kHz G.711) sends both on ONE connection.  A connection accepted on pair port
+     p takes the lowest free slot; the front-end calls vapx_set_stream_channel_classes(slot, cls_ch1, cls_ch2) and then receives PLANAR
+     10 ms packets: channel 1's 10 ms in cls_ch1's wire form (input_hz / 100 samples: f64 for VAPX_PCM_F32, cast on the host; raw s16 /
+     G.711 otherwise), followed by channel 2's 10 ms in cls_ch2's.  Samples cannot be interleaved across rates; a pair port takes planar
+     packets also where cls_ch1 == cls_ch2.  A connection that ends inside a frame loses that part of a frame, as on every port.  Result
+     packets keep their framing: x1 carries hop_in(cls_ch1) decoded samples and x2 hop_in(cls_ch2), each block with its own count.  The
+     tick packs such a slot as the engine takes it: channel 1's row, then channel 2's.  Pair ports need a table (the engine's, or
+     input_classes here); what a table refuses (a passive shard, a group, a gain with a raw class) stays refused.  port_in: 0 = ephemeral,
+     see vapx_ingest_pair_ports. */
+  int32_t n_pair_ports;                  /* 0 .. VAPX_MAX_PAIR_PORTS */
+  struct { int32_t cls_ch1, cls_ch2, port_in; } pair_ports[16];
 } vapx_ingest_config;
+#define VAPX_MAX_PAIR_PORTS 16
 #define VAPX_INGEST_CORE_SET 2      /* with cpu_count > 0: every front-end thread may run on ANY core of the range (one affinity set) instead of
                                        one core each: keeps other processes' work off the range without nailing a thread to a core that the
                                        kernel then borrows for softirq work */
@@ -607,6 +644,12 @@ int vapx_ingest_ports(vapx_ingest_handle g, int32_t* port_in, int32_t* port_out)
  * thread owns the answer); VAPX_E_INVAL without a table, VAPX_E_RANGE for a bad id. */
 int32_t vapx_ingest_class_ports(vapx_ingest_handle g, int32_t* ports, int32_t max);
 int32_t vapx_ingest_stream_class(vapx_ingest_handle g, int32_t stream_id);
+/* Pair ports (vapx_ingest_config.pair_ports).  vapx_ingest_pair_ports: the bound input port of every pair port (at most max), returns their
+ * number.  vapx_ingest_stream_channel_classes: out[0], out[1] = the classes of the stream's two channels, for the step function of the _fn
+ * variant: slot k of its packed block holds channel 1's row, hop_in(out[0]) samples of format(out[0]), then channel 2's row of out[1]'s;
+ * valid inside the step function.  vapx_ingest_stream_class answers VAPX_E_INVAL for a stream whose two classes differ. */
+int32_t vapx_ingest_pair_ports(vapx_ingest_handle g, int32_t* ports, int32_t max);
+int vapx_ingest_stream_channel_classes(vapx_ingest_handle g, int32_t stream_id, int32_t out[2]);
 /* One front-end for a trunk group (vapx_attach_trunk): the reference's deployment of vap_main.py, vap_bc_main.py and vap_nod_main.py
  * side by side on one cpc_model file, with ONE input port and the audio encoded once.
  *   - input: cfg->port_in; every accepted connection is a dialogue exactly as with vapx_ingest_open (lowest free slot, carry re-zeroed,

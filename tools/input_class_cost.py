@@ -13,6 +13,11 @@ alternating blocks, the block order reversed every block, after a warm-up that f
   --part b   ONE mixed engine of S streams, split evenly over the classes, against one uniform engine of S / n streams per class,
              stepped back to back in the same process on the same audio; ms per tick of audio for both and the device memory each holds.
 
+  --part c   a class per CHANNEL against a class per stream, same table, same bytes per tick: `split` (half the streams of --pair's first
+             class, half of its second, set by vapx_set_stream_class: the path of before), `pair` (every stream (first, second), set by
+             vapx_set_stream_channel_classes) and `unset`.  --tree DIR imports the package (and its library) from another checkout, e.g.
+             the parent commit's, which has no `pair` leg; --first and the discarded second engine as in part a.
+
   device legs   audio already on the device: HIP events around each block of steps
   host legs     audio and output in page-locked host memory (the serving path): host clock around a step (a tick of part b's uniform
                 side is the sum of its engines' steps)
@@ -21,6 +26,7 @@ Prints one JSON line, with the board's watts and shader clock during the timed b
 
     python tools/input_class_cost.py --part a [--streams 4096] [--hz 20] [--ctx-sec 2.5] [--class mulaw@8000] [--first table]
     python tools/input_class_cost.py --part b [--classes f64@16000,mulaw@8000,s16@16000,s16@48000]
+    python tools/input_class_cost.py --part c [--pair mulaw@8000+s16@48000] [--first pair] [--tree ../parent] [--kinds dev]
 """
 import argparse
 import contextlib
@@ -38,7 +44,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--part", choices=["a", "b"], required=True)
+    ap.add_argument("--part", choices=["a", "b", "c"], required=True)
     ap.add_argument("--streams", type=int, default=4096)
     ap.add_argument("--hz", type=int, default=20)
     ap.add_argument("--ctx-sec", type=float, default=2.5)
@@ -46,9 +52,15 @@ def main():
     ap.add_argument("--blocks", type=int, default=4, help="timed blocks per leg")
     ap.add_argument("--steps", type=int, default=50, help="steps per block")
     ap.add_argument("--class", dest="cls", default="mulaw@8000", help="part a: the one class")
-    ap.add_argument("--first", choices=["table", "uniform", "unset"], default="table", help="part a: the leg whose engine is created first")
+    ap.add_argument("--first", choices=["table", "uniform", "unset", "split", "pair"], default=None,
+                    help="parts a and c: the leg whose engine is created first (default: table, split)")
+    ap.add_argument("--pair", default="mulaw@8000+s16@48000", help="part c: the two classes")
+    ap.add_argument("--tree", default=None, help="part c: import vap_realtime_amd from this checkout instead of the tool's own")
+    ap.add_argument("--kinds", default="dev,host", help="which legs to time: dev, host or both")
     ap.add_argument("--classes", default="f64@16000,mulaw@8000,s16@16000,s16@48000", help="part b: the mix, evenly split")
     args = ap.parse_args()
+    if args.tree:
+        sys.path.insert(0, os.path.abspath(args.tree))
     import torch
     from vap_realtime_amd import engine, ingest, pcm, weights as W
     S, pool, hz = args.streams, 4, args.hz
@@ -75,7 +87,8 @@ def main():
     if args.part == "a":
         cls = ingest.parse_input_class(args.cls)[0]
         f, r = cls
-        order = [args.first] + [x for x in ("table", "uniform", "unset") if x != args.first]
+        first = args.first or "table"
+        order = [first] + [x for x in ("table", "uniform", "unset") if x != first]
         for i, name in enumerate(order):
             kw = {"table": {"input_classes": [cls]}, "uniform": {"input_hz": r, "input_format": f}, "unset": {}}[name]
             e, mem = make(S, **kw)
@@ -92,6 +105,43 @@ def main():
                 dfn = lambda t, e=e, dev=dev, out_d=out_d, c=c: e.step_device(S, dev[t % pool].data_ptr(), c[1] // hz, out_d.data_ptr())
                 hfn = lambda t, e=e, host=host, out_h=out_h: e.step(host[t % pool], out=out_h)
             legs[name] = {"dev": dfn, "host": hfn, "mem": mem, "bytes": int(host[0].nbytes), "eng": [e]}
+    elif args.part == "c":
+        pair = [ingest.parse_input_class(t)[0] for t in args.pair.split("+")]
+        assert len(pair) == 2 and pair[0] != pair[1] and S % 2 == 0, "--pair names two different classes, --streams is even"
+        names_c = ["split", "pair", "unset"] if hasattr(engine.Engine, "set_stream_channel_classes") else ["split", "unset"]
+        first = args.first or "split"
+        assert first in names_c, f"--first {first}: this tree has the legs {names_c}"
+        ids = np.arange(S, dtype=np.int32)
+        for i, name in enumerate([first] + [x for x in names_c if x != first]):
+            e, mem = make(S, **({} if name == "unset" else {"input_classes": pair}))
+            if i == 0:
+                keep.append(make(1)[0])                    # the discarded second engine of the process
+            out_h, out_d = engine.pinned_empty((S, engine.OUT_STRIDE)), torch.empty((S, engine.OUT_STRIDE), device="cuda")
+            if name == "unset":
+                host, dev = audio(("f32", 16000), S)
+                dfn = lambda t, e=e, dev=dev, out_d=out_d: e.step_device(S, dev[t % pool].data_ptr(), 16000 // hz, out_d.data_ptr())
+                hfn = lambda t, e=e, host=host, out_h=out_h: e.step(host[t % pool], out=out_h)
+                nbytes = int(host[0].nbytes)
+            else:
+                if name == "split":                        # S / 2 slots of [2][hop_in] of the first class, then S / 2 of the second
+                    for s_ in range(S):
+                        e.set_stream_class(s_, s_ // (S // 2))
+                    parts = [audio(c, S // 2)[0] for c in pair]
+                    rows = [np.concatenate([h[p_].reshape(-1).view(np.uint8) for h in parts]) for p_ in range(pool)]
+                else:                                      # S slots of the first class's row, then the second's
+                    for s_ in range(S):
+                        e.set_stream_channel_classes(s_, 0, 1)
+                    parts = [audio(c, S)[0][:, :, 0, :] for c in pair]
+                    rows = [np.concatenate([np.ascontiguousarray(h[p_]).view(np.uint8).reshape(S, -1) for h in parts], axis=1).reshape(-1)
+                            for p_ in range(pool)]
+                nbytes = int(rows[0].size)
+                packed_h = engine.pinned_empty((pool, nbytes), np.uint8)
+                for p_ in range(pool):
+                    packed_h[p_] = rows[p_]
+                packed_d = torch.from_numpy(np.array(packed_h)).cuda()
+                dfn = lambda t, e=e, d=packed_d, out_d=out_d: e.step_packed_device(ids, d[t % pool].data_ptr(), out_d.data_ptr())
+                hfn = lambda t, e=e, h=packed_h, out_h=out_h: e.step(h[t % pool], ids, out=out_h)
+            legs[name] = {"dev": dfn, "host": hfn, "mem": mem, "bytes": nbytes, "eng": [e]}
     else:
         classes = [ingest.parse_input_class(t)[0] for t in args.classes.split(",")]
         n_c = len(classes)
@@ -163,9 +213,12 @@ def main():
            "second_engine_of_the_process": "a discarded 1-stream engine, kept alive"}
     if args.part == "a":
         res["class"] = args.cls
+    elif args.part == "c":
+        res["pair"], res["tree"] = args.pair, os.path.basename(os.path.abspath(args.tree)) if args.tree else "."
+        res["library"] = os.path.relpath(os.path.realpath(engine.load_library()._name), os.path.realpath(args.tree or ROOT))
     else:
         res["classes"] = args.classes.split(",")
-    for kind in ("dev", "host"):
+    for kind in [k for k in ("dev", "host") if k in args.kinds.split(",")]:
         blocks = {n: [] for n in names}
         with (watch if watch is not None else contextlib.nullcontext()):
             for b in range(args.blocks):
@@ -178,6 +231,11 @@ def main():
                       "block_spread_ms": round(max(meds) - min(meds), 4), "input_bytes_per_tick": legs[n]["bytes"], "device_memory_mib": legs[n]["mem"]}
         if args.part == "a":
             out["table_minus_uniform_ms"] = round(out["table"]["ms_per_tick"] - out["uniform"]["ms_per_tick"], 4)
+            out["noise_unset_block_spread_ms"] = out["unset"]["block_spread_ms"]
+        elif args.part == "c":
+            for n in names:
+                if n != "unset":
+                    out[n + "_minus_unset_ms"] = round(out[n]["ms_per_tick"] - out["unset"]["ms_per_tick"], 4)
             out["noise_unset_block_spread_ms"] = out["unset"]["block_spread_ms"]
         else:
             out["mixed_over_uniform"] = round(out[names[0]]["ms_per_tick"] / out[names[1]]["ms_per_tick"], 4)

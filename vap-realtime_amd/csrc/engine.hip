@@ -133,17 +133,19 @@ struct vapx_engine : Geometry {
   }
   int hop_in() const { return cls[0].hop_in; }                        // a uniform engine's samples per channel and tick
   size_t cls_lds = 0;                     // floats of dynamic LDS: the largest window of cls[]
-  int rs_rec = 0;                         // floats of a stream's history [2][largest H of cls[]], padded to a multiple of 4; 0: every class is 16 kHz
+  int rs_rec = 0;                         // floats of a stream's history [2][largest H of cls[]], padded to a multiple of 4; 0: every class is 16 kHz.
+                                          // Channel 2 starts H floats in on a uniform engine and at half the record with a table (input_classes.h)
   float* rs_hist = nullptr;               // [max_streams][rs_rec], null with rs_rec = 0
   int* rs_started = nullptr;              // [max_streams * 2] the (stream, channel) has consumed a tick since its reset
   int rs_row = 0;                         // floats of a row of rs_out: hop; L on a uniform 16 kHz engine, which may be stepped with full frames
   float* rs_out = nullptr;                // [max_batch][2][rs_row]
   size_t audio_floats = 0;                // what `audio` (device and pinned) holds: [max_batch][2][L], more where the largest slot needs it
   vapx_input_class cls_pub[VAPX_MAX_INPUT_CLASSES] = {};   // a table as the caller gave it
-  std::vector<int32_t> stream_cls;        // a table: [max_streams] a stream's class; the host builds the slot descriptors from it
+  std::vector<int32_t> stream_cls;        // a table: [max_streams][2] a (stream, channel)'s class; the host builds the slot descriptors from it
   Staged<int> cls_slots;                  // a table: [max_batch] InputSlot {byte_off, cls} of a step
   std::vector<InputSlot> cls_slots_host;
-  size_t cls_slot_bytes(int c) const { return (size_t)2 * cls[c].hop_in * (size_t)pcm_bytes_per_sample(cls[c].fmt); }
+  size_t cls_row_bytes(int c) const { return (size_t)cls[c].hop_in * (size_t)pcm_bytes_per_sample(cls[c].fmt); }   // one channel's row
+  size_t cls_slot_bytes(int c) const { return 2 * cls_row_bytes(c); }
   float* out_pinned = nullptr;
   int last_B = 0, last_G = 1;
   bool last_tail_fused = false;           // some overlap group of the latest encoder pass ran conv_tail_kernel: h2 / h3 were not written
@@ -1284,9 +1286,11 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
     if (h->cls_table) {
       bytes = 0;
       for (int i = 0; i < n; ++i) {
-        const int c = h->stream_cls[stream_ids ? stream_ids[i] : i];
-        h->cls_slots_host[i] = {(uint32_t)bytes, c};
-        bytes += h->cls_slot_bytes(c);   // below 2^32: vapx_set_input_classes refused a table whose largest slot x max_batch is not
+        const int32_t* c = &h->stream_cls[(size_t)2 * (stream_ids ? stream_ids[i] : i)];
+        h->cls_slots_host[i] = {(uint32_t)bytes, input_slot_classes(c[0], c[1])};
+        // channel 1's row, then channel 2's.  Below 2^32: vapx_set_input_classes refused a table whose largest same-class slot x max_batch
+        // is not, and row(c1) + row(c2) <= 2 max(row) = the largest same-class slot
+        bytes += h->cls_row_bytes(c[0]) + h->cls_row_bytes(c[1]);
       }
       HIPCHK(h, h->cls_slots.upload((const int*)h->cls_slots_host.data(), (size_t)2 * n, st));
     }
@@ -2077,7 +2081,7 @@ static int build_input(vapx_engine* h, const InputClassGeom* tab, int n, bool ta
   if (table) {
     h->cls_slots = slots;
     h->cls_slots_host.assign(B, InputSlot{0, 0});
-    h->stream_cls.assign(S, 0);
+    h->stream_cls.assign(S * 2, 0);
   }
   memcpy(h->cls, tab, (size_t)n * sizeof *tab);
   h->cls_lds = input_classes_lds_floats(tab, n);
@@ -2160,7 +2164,7 @@ int vapx_set_stream_class(vapx_handle h, int32_t sid, int32_t cls) {
   // a new class is a new signal: the carry-only request of vapx_reset_carry (carry, resampler history, started flags), applied by the next
   // step before it touches any state; that step is also the first to build a slot descriptor from the stream's class, which lives on the host
   const int rc = vapx_reset_carry(h, sid);
-  if (rc == VAPX_OK) h->stream_cls[sid] = cls;
+  if (rc == VAPX_OK) h->stream_cls[(size_t)2 * sid] = h->stream_cls[(size_t)2 * sid + 1] = cls;
   return rc;
 }
 
@@ -2168,7 +2172,40 @@ int32_t vapx_get_stream_class(vapx_handle h, int32_t sid) {
   if (!h) return VAPX_E_INVAL;
   if (!h->cls_table) return fail(h, VAPX_E_INVAL, "this engine has no input classes (vapx_set_input_classes)");
   if (sid < 0 || sid >= h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "stream id %d out of range [0,%d)", sid, h->cfg.max_streams);
-  return h->stream_cls[sid];
+  const int32_t* c = &h->stream_cls[(size_t)2 * sid];
+  if (c[0] != c[1])
+    return fail(h, VAPX_E_INVAL, "stream %d has channel classes (%d, %d), not one class: ask vapx_get_stream_channel_classes", sid, c[0], c[1]);
+  return c[0];
+}
+
+int vapx_set_stream_channel_classes(vapx_handle h, int32_t sid, int32_t c1, int32_t c2) {
+  if (!h) return VAPX_E_INVAL;
+  if (!h->cls_table) return fail(h, VAPX_E_INVAL, "this engine has no input classes (vapx_set_input_classes)");
+  if (sid < 0 || sid >= h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "stream id %d out of range [0,%d)", sid, h->cfg.max_streams);
+  for (int c = 0; c < 2; ++c) {
+    const int cls = c ? c2 : c1;
+    if (cls < 0 || cls >= h->tab_cls()) return fail(h, VAPX_E_RANGE, "input class %d of channel %d out of range [0,%d)", cls, c + 1, h->tab_cls());
+  }
+  // the request of vapx_set_stream_class: the carry, the history and the started flags of BOTH channels restart, also where only one leg's
+  // class changes (the 320-sample carry and the reset list are per stream)
+  const int rc = vapx_reset_carry(h, sid);
+  if (rc == VAPX_OK) { h->stream_cls[(size_t)2 * sid] = c1; h->stream_cls[(size_t)2 * sid + 1] = c2; }
+  return rc;
+}
+
+int vapx_get_stream_channel_classes(vapx_handle h, int32_t sid, int32_t out[2]) {
+  if (!h) return VAPX_E_INVAL;
+  if (!out) return fail(h, VAPX_E_INVAL, "null out");
+  if (!h->cls_table) return fail(h, VAPX_E_INVAL, "this engine has no input classes (vapx_set_input_classes)");
+  if (sid < 0 || sid >= h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "stream id %d out of range [0,%d)", sid, h->cfg.max_streams);
+  out[0] = h->stream_cls[(size_t)2 * sid];
+  out[1] = h->stream_cls[(size_t)2 * sid + 1];
+  return VAPX_OK;
+}
+
+int64_t vapx_input_row_bytes(vapx_handle h, int32_t cls) {
+  if (!h || cls < 0 || cls >= h->tab_cls()) return 0;
+  return (int64_t)h->cls_row_bytes(cls);
 }
 
 int64_t vapx_input_slot_bytes(vapx_handle h, int32_t cls) {

@@ -12,6 +12,10 @@
 // makes its slot a stream of class c, whose geometry (InGeo: format, hop, packet size) every thread takes from the slot or from the queued
 // frame instead of from the front-end; the tick packs the ready frames' slots back to back, which is the packed block the engine takes.
 // A front-end without a table has one geometry, geo[0], and every slot is of it.
+// Pair ports (vapx_ingest_config.pair_ports; vapx.h CHANNEL CLASSES): a connection on pair port (c1, c2) is a dialogue whose channel 1 is of
+// class c1 and whose channel 2 of c2.  Its packets are planar (channel 1's 10 ms, then channel 2's: feed_planar), its frame buffer holds
+// channel 1's row and then channel 2's, each in its own class's staging form, which is the engine's slot.  A slot of any other port is
+// the case c1 == c2 of that layout.
 //
 // A raw input format (vapx_ingest_config.input_format: s16, mulaw, alaw; vapx.h "Input format"): the receive threads only de-interleave
 // the samples into the staging as they are (no cast, no f32 staging, no f64 echo copy), the tick hands the raw block to the step, whose
@@ -65,6 +69,7 @@
 // the engine's input classes (vapx_set_input_classes): weak for the same reason; a program without them has no table
 #pragma weak vapx_get_input_classes
 #pragma weak vapx_set_stream_class
+#pragma weak vapx_set_stream_channel_classes
 
 namespace {
 
@@ -176,12 +181,16 @@ struct InGeo {
   int hop = 0;                             // sample PAIRS per frame on the wire = in_hz / frame_hz
   int bps = 4;                             // bytes per sample of the staging
   int pair_bytes = PAIR_BYTES;             // one sample of both channels on the wire
+  size_t row_bytes() const { return (size_t)hop * bps; }         // one channel's row of the staging
   size_t frame_bytes() const { return (size_t)2 * hop * bps; }   // a frame of the staging = a slot of the step's block
+  int wire_bps() const { return fmt ? bps : 8; }                 // bytes per sample on the wire: f64 for an F32 class
 };
 
 struct Slot {
   int fd_in = -1;
   int cls = 0;                             // index into vapx_ingest::geo; written at adoption, before the socket joins an epoll set
+  int cls2 = 0;                            // channel 2's class: cls unless the connection came in on a pair port
+  bool planar = false;                     // a pair port's connection: planar packets (feed_planar); `fill` then counts the frame's wire bytes
   std::atomic<uint32_t> gen{0};           // bumped per connection: queued frames of a dead connection are dropped (read by the tick thread)
   std::atomic<int> state[NBUF];
   double t_ready[NBUF] = {};
@@ -198,8 +207,8 @@ struct Slot {
   Slot() { for (auto& s : state) s = B_FREE; }
 };
 
-struct Ready { int slot; int buf; uint32_t gen; double t; int cls; };   // cls: the slot's class when the frame was completed
-struct ResetReq { int slot; int carry_only; int cls; };                // cls >= 0: the connection's input class (a front-end with a table)
+struct Ready { int slot; int buf; uint32_t gen; double t; int cls, cls2; };   // the slot's channel classes when the frame was completed
+struct ResetReq { int slot; int carry_only; int cls, cls2; };          // cls >= 0: the connection's input classes (a front-end with a table)
 
 struct Job {                               // one tick's rows on their way out
   int n = 0;
@@ -232,7 +241,7 @@ struct OutPort {
 }  // namespace
 
 struct vapx_ingest {
-  vapx_ingest() { for (int& fd : cls_lsock) fd = -1; }
+  vapx_ingest() { for (int& fd : cls_lsock) fd = -1; for (int& fd : pair_lsock) fd = -1; }
   vapx_ingest_config cfg;
   vapx_ingest_step_fn step = nullptr;
   vapx_ingest_reset_fn reset = nullptr;
@@ -252,8 +261,15 @@ struct vapx_ingest {
   vapx_input_class cls_pub[VAPX_MAX_INPUT_CLASSES] = {};
   int cls_lsock[VAPX_MAX_INPUT_CLASSES], cls_port[VAPX_MAX_INPUT_CLASSES] = {};
   size_t frame_stride = 0, echo_stride = 0;
-  std::vector<int32_t> tick_cls;           // [S] tick thread only: a stream's class as the engine (or the step function) knows it
-  void (*set_class)(void* user, int32_t stream_id, int32_t cls) = nullptr;   // tick thread: vapx_set_stream_class on the engine
+  int n_pair = 0;                          // pair ports: pair_cls[p] = the classes of channel 1 and channel 2
+  int pair_cls[VAPX_MAX_PAIR_PORTS][2] = {};
+  int pair_lsock[VAPX_MAX_PAIR_PORTS], pair_port[VAPX_MAX_PAIR_PORTS] = {};
+  std::vector<int32_t> tick_cls;           // [S][2] tick thread only: a stream's channel classes as the engine (or the step function) knows them
+  void (*set_class)(void* user, int32_t stream_id, int32_t cls, int32_t cls2) = nullptr;   // tick thread: vapx_set_stream_class / _channel_classes on the engine
+  size_t frame_bytes(int c1, int c2) const { return geo[c1].row_bytes() + geo[c2].row_bytes(); }   // a slot of the step's block
+  // where channel 2's f64 echo starts in a frame's echo buffer: behind channel 1's [hop] for one class; half the buffer (the largest f64
+  // hop) where the classes differ, whatever channel 1's class is
+  size_t echo_ch2(int c1, int c2) const { return c1 == c2 ? (size_t)geo[c1].hop : echo_stride / 2; }
   int M = 1;                               // models = output ports (> 1: a trunk group, `step` fills wire blocks)
   OutPort ports[MAX_MODELS];
   size_t row_floats = VAPX_OUT_STRIDE;     // floats per stream in a job's block, all models
@@ -468,7 +484,7 @@ void frame_complete(vapx_ingest* g, int slot, Slot& s) {
   s.wbuf = -1; s.fill = 0;
   {
     std::lock_guard<std::mutex> lk(g->ready_mu);
-    g->ready.push_back({slot, b, s.gen.load(std::memory_order_relaxed), t, s.cls});
+    g->ready.push_back({slot, b, s.gen.load(std::memory_order_relaxed), t, s.cls, s.cls2});
   }
   g->ready_cv.notify_one();
 }
@@ -519,9 +535,9 @@ size_t feed_raw(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
   return used;
 }
 
-// a frame of a raw format as the result packet echoes it: the decoded samples as float64, [2][hop]
+// a channel's row of a raw format as the result packet echoes it: the decoded samples as float64, [hop]
 void expand_raw(const InGeo& q, const uint8_t* raw, double* e) {
-  const size_t n = (size_t)2 * q.hop;
+  const size_t n = (size_t)q.hop;
   if (q.fmt == VAPX_PCM_S16) {
     for (size_t i = 0; i < n; ++i) { int16_t v; memcpy(&v, raw + 2 * i, 2); e[i] = (double)v * 0x1p-15; }
   } else {
@@ -530,9 +546,75 @@ void expand_raw(const InGeo& q, const uint8_t* raw, double* e) {
   }
 }
 
+// wire bytes of a whole frame of a pair port's connection: 100 / frame_hz planar packets of (channel 1's 10 ms, channel 2's 10 ms)
+size_t planar_frame_bytes(const vapx_ingest* g, const Slot& s) {
+  return (size_t)g->geo[s.cls].hop * g->geo[s.cls].wire_bps() + (size_t)g->geo[s.cls2].hop * g->geo[s.cls2].wire_bps();
+}
+
+// a pair port's connection: planar 10 ms packets, channel 1's samples in its class's wire form, then channel 2's in its own.  Raw samples
+// are copied into the channel's row as they are, f64 samples are cast (and echoed) as feed() does.  `fill` is the position in the frame's
+// wire bytes; a sample split across two reads waits in `partial`.  Same contract as feed()
+size_t feed_planar(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
+  Slot& s = g->slots[slot];
+  const InGeo* q[2] = {&g->geo[s.cls], &g->geo[s.cls2]};
+  const size_t pk = (size_t)(100 / g->hz);                                    // packets per frame
+  const size_t seg[2] = {(size_t)q[0]->hop * q[0]->wire_bps() / pk, (size_t)q[1]->hop * q[1]->wire_bps() / pk};   // a channel's bytes of a packet
+  const size_t pkt = seg[0] + seg[1], total = pkt * pk;
+  const double gain = g->cfg.gain;
+  size_t used = 0;
+  while (used < n) {
+    if (s.wbuf < 0) {
+      s.wbuf = pick_free(s);
+      if (s.wbuf < 0) return used;
+      s.fill = 0;
+    }
+    const size_t k = (size_t)s.fill / pkt, in_pkt = (size_t)s.fill % pkt;   // (a partial sample's bytes are not counted in fill yet)
+    const int c = in_pkt >= seg[0];
+    const size_t in_seg = in_pkt - (c ? seg[0] : 0);
+    const size_t wb = (size_t)q[c]->wire_bps();
+    const size_t i0 = (k * seg[c] + in_seg) / wb;                            // the channel's sample index in the frame
+    const size_t left = seg[c] - in_seg;                                     // wire bytes to the end of this channel's part of the packet
+    uint8_t* row = g->rawbuf(slot, s.wbuf) + (c ? q[0]->row_bytes() : 0);
+    if (q[c]->fmt) {                                                         // raw: bytes as they are (a split s16 sample is just two copies)
+      const size_t take = std::min(left, n - used);
+      memcpy(row + k * seg[c] + in_seg, p + used, take);
+      used += take; s.fill += (int)take;
+    } else {
+      double* d = g->f64buf(slot, s.wbuf) + (c ? g->echo_ch2(s.cls, s.cls2) : 0);
+      float* f = (float*)row;
+      size_t done = 0;                                                       // whole samples taken
+      if (s.npartial || n - used < 8) {
+        const size_t take = std::min<size_t>(8 - s.npartial, n - used);
+        memcpy(s.partial + s.npartial, p + used, take);
+        s.npartial += (int)take; used += take;
+        if (s.npartial < 8) break;
+        double v;
+        memcpy(&v, s.partial, 8);
+        s.npartial = 0;
+        if (gain != 1.0) v *= gain;
+        d[i0] = v; f[i0] = (float)v;
+        done = 1;
+      } else {
+        done = std::min(left, n - used) / 8;
+        for (size_t i = 0; i < done; ++i) {
+          double v;
+          memcpy(&v, p + used + 8 * i, 8);
+          if (gain != 1.0) v *= gain;                                        // float64 multiply BEFORE the f32 cast, as in feed()
+          d[i0 + i] = v; f[i0 + i] = (float)v;
+        }
+        used += done * 8;
+      }
+      s.fill += (int)(done * 8);
+    }
+    if ((size_t)s.fill == total) frame_complete(g, slot, s);
+  }
+  return used;
+}
+
 // decode `n` bytes of the stream into the slot's frame buffers; returns bytes consumed (< n: no free buffer)
 size_t feed(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
   Slot& s = g->slots[slot];
+  if (s.planar) return feed_planar(g, slot, p, n);
   if (g->geo[s.cls].fmt) return feed_raw(g, slot, p, n);
   const int hop = g->geo[s.cls].hop;
   const double gain = g->cfg.gain;
@@ -598,7 +680,8 @@ size_t feed(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
 // when the value changes: a sender that delivers whole frames never causes a setsockopt.
 void arm_lowat(vapx_ingest* g, Slot& s) {
   const InGeo& q = g->geo[s.cls];
-  long need = (long)(q.hop - (s.wbuf >= 0 ? s.fill : 0)) * (long)q.pair_bytes - s.npartial;
+  long need = s.planar ? (long)planar_frame_bytes(g, s) - (s.wbuf >= 0 ? s.fill : 0) - s.npartial
+                       : (long)(q.hop - (s.wbuf >= 0 ? s.fill : 0)) * (long)q.pair_bytes - s.npartial;
   if (need < 1) need = 1;
   if (need > 65536) need = 65536;           // (5 Hz frames are 51 KB; stay well inside the receive buffer)
   if ((int)need == s.lowat || s.fd_in < 0 || g->no_lowat) return;
@@ -689,7 +772,7 @@ int lowest_free_slot(vapx_ingest* g) {
 }
 
 // take over an accepted input connection: the lowest free stream slot gets it; false = every slot is taken (fd untouched)
-bool adopt_in(vapx_ingest* g, int fd, int cls = -1) {
+bool adopt_in(vapx_ingest* g, int fd, int cls = -1, int cls2 = -1) {
   int slot = -1;
   {
     // (round 4: this was a scan from slot 0 — 4096 dialogues connecting at once cost the accept thread ~S^2 / 2 slot visits, the output
@@ -706,11 +789,13 @@ bool adopt_in(vapx_ingest* g, int fd, int cls = -1) {
   Slot& s = g->slots[slot];
   s.wbuf = -1; s.fill = 0; s.npartial = 0; s.backlog.clear(); s.paused = false; s.lowat = 0;
   s.cls = cls >= 0 ? cls : 0;   // frames of the slot's previous connection that are still queued or being sent carry their own class (Ready::cls)
+  s.planar = cls2 >= 0;         // a pair port
+  s.cls2 = cls2 >= 0 ? cls2 : s.cls;
   {
     // the carry restarts from zeros for every connection (vap_main.py:368-369); reset_on_connect also clears the
     // model state, which the reference keeps.  Applied by the tick thread before its next step.
     std::lock_guard<std::mutex> lk(g->ready_mu);
-    g->resets.push_back({slot, g->cfg.reset_on_connect ? 0 : 1, cls});   // with a table: the tick thread tells the engine the stream's class first
+    g->resets.push_back({slot, g->cfg.reset_on_connect ? 0 : 1, cls, s.cls2});   // with a table: the tick thread tells the engine the stream's classes first
   }
   g->in_conns.fetch_add(1);
   { const double t = mono_now(); if (g->dbg_t_in_first == 0) g->dbg_t_in_first = t; g->dbg_t_in_last = t; }
@@ -718,12 +803,15 @@ bool adopt_in(vapx_ingest* g, int fd, int cls = -1) {
   return true;
 }
 
-// cls: the input class whose port became readable (a front-end with a table), or -1: the one input port
+// cls: the input class whose port became readable (a front-end with a table), kPairKey + p: pair port p, or -1: the one input port
+constexpr int kPairKey = 0x100;
 void accept_in(vapx_ingest* g, int cls = -1) {
+  const int pair = cls >= kPairKey ? cls - kPairKey : -1;
   for (;;) {
-    int fd = accept4(cls >= 0 ? g->cls_lsock[cls] : g->lin, nullptr, nullptr, SOCK_NONBLOCK);
+    int fd = accept4(pair >= 0 ? g->pair_lsock[pair] : cls >= 0 ? g->cls_lsock[cls] : g->lin, nullptr, nullptr, SOCK_NONBLOCK);
     if (fd < 0) { accept_failed_for_fds(g); return; }
-    if (!adopt_in(g, fd, cls)) close(fd);   // every stream slot is taken
+    const bool ok = pair >= 0 ? adopt_in(g, fd, g->pair_cls[pair][0], g->pair_cls[pair][1]) : adopt_in(g, fd, cls);
+    if (!ok) close(fd);   // every stream slot is taken
   }
 }
 
@@ -887,7 +975,7 @@ void tx_main(vapx_ingest* g, int x) {
   size_t raw_hop = 0;
   for (int c = 0; c < std::max(g->n_cls, 1); ++c)
     if (g->geo[c].fmt) raw_hop = std::max(raw_hop, (size_t)g->geo[c].hop);
-  std::vector<double> expanded(2 * raw_hop);   // a raw format: the row's echo, decoded from the staging by the table
+  std::vector<double> expanded(2 * raw_hop);   // a raw format: the echo of a row's channels, decoded from the staging by the table
   constexpr int MAX_R = 10;                  // 50 Hz -> 5 Hz
   int64_t next = 0;                          // the job this thread sends next: every sender walks over EVERY job, in publication order
   while (true) {
@@ -907,6 +995,7 @@ void tx_main(vapx_ingest* g, int x) {
       const Ready& rd = job.rows[k];
       Slot& s = g->slots[rd.slot];
       const InGeo& q = g->geo[rd.cls];
+      const InGeo* qc[2] = {&q, &g->geo[rd.cls2]};   // channel 2's class differs on a pair port's stream (M = 1, R = 1 there: check_classes)
       const int hop = q.hop;
       if (job.bad[k]) {   // the stream was reset (status 1 in some model): a slower model's frame in the making starts over with it
         for (int m = 0; m < g->M; ++m)
@@ -914,8 +1003,14 @@ void tx_main(vapx_ingest* g, int x) {
       } else {
         // u32 len | f64 t | u32 n | x1 | u32 n | x2 | tail   (util.py:122-143; length prefix vap_main.py:446-448); a trunk group sends one
         // packet per model, each to its own port's listeners, tail in that model's framing (bc util.py:193-211, nod :213-237)
-        double* e = q.fmt ? expanded.data() : g->f64buf(rd.slot, rd.buf);
-        if (q.fmt) expand_raw(q, g->rawbuf(rd.slot, rd.buf), e);
+        double* ec[2];                              // the echo of channel 1 and of channel 2: [hop of its class] f64
+        for (int c = 0; c < 2; ++c) {
+          if (qc[c]->fmt) {
+            ec[c] = expanded.data() + (size_t)c * raw_hop;
+            expand_raw(*qc[c], g->rawbuf(rd.slot, rd.buf) + (c ? qc[0]->row_bytes() : 0), ec[c]);
+          } else ec[c] = g->f64buf(rd.slot, rd.buf) + (c ? g->echo_ch2(rd.cls, rd.cls2) : 0);
+        }
+        double* e = ec[0];                          // (R > 1: one class, [2][hop] contiguous in either case)
         for (int m = 0; m < g->M; ++m) {
           OutPort& o = g->ports[m];
           const float* row = job.out + (size_t)job.n * o.off + (size_t)k * o.wf;
@@ -939,19 +1034,19 @@ void tx_main(vapx_ingest* g, int x) {
             // samples to echo for the frame's head: that one frame goes unanswered
             if (held != o.R - 1) continue;
           }
-          const uint32_t ns = (uint32_t)(hop * o.R);
+          const uint32_t ns = (uint32_t)(hop * o.R), ns2 = (uint32_t)(qc[1]->hop * o.R);
           const int tb = encode_tail(o.mode, row, tail.data(), std::min(256, o.wf - VAPX_OUT_LOGITS));
-          const uint32_t plen = 8 + 2 * (4 + 8 * ns) + (uint32_t)tb;
+          const uint32_t plen = 8 + (4 + 8 * ns) + (4 + 8 * ns2) + (uint32_t)tb;
           uint8_t* p = head;
           put_u32(p, plen); put_f64(p, job.t_unix); put_u32(p, ns);
-          p = mid; put_u32(p, ns);
+          p = mid; put_u32(p, ns2);
           iovec iov[2 * MAX_R + 3];
           int niov = 0;
           iov[niov++] = {head, 16};
           for (int c = 0; c < 2; ++c) {
             if (c) iov[niov++] = {mid, 4};
             for (int q = 0; q < held; ++q) iov[niov++] = {hb + ((size_t)q * 2 + c) * hop, (size_t)hop * 8};
-            iov[niov++] = {e + (size_t)c * hop, (size_t)hop * 8};
+            iov[niov++] = {ec[c], (size_t)qc[c]->hop * 8};
           }
           iov[niov++] = {tail.data(), (size_t)tb};
           const size_t total = 4 + plen;
@@ -1022,9 +1117,10 @@ void tick_main(vapx_ingest* g) {
       resets.swap(g->resets);
     }
     for (auto& rs : resets) {
-      if (rs.cls >= 0) {   // a connection on a class port: the stream is of that class from its first frame on
-        g->tick_cls[rs.slot] = rs.cls;
-        if (g->set_class) g->set_class(g->user, rs.slot, rs.cls);
+      if (rs.cls >= 0) {   // a connection on a class or pair port: the stream is of those classes from its first frame on
+        g->tick_cls[(size_t)2 * rs.slot] = rs.cls;
+        g->tick_cls[(size_t)2 * rs.slot + 1] = rs.cls2;
+        if (g->set_class) g->set_class(g->user, rs.slot, rs.cls, rs.cls2);
       }
       if (g->reset) g->reset(g->user, rs.carry_only ? -(rs.slot + 1) : rs.slot);   // negative = carry only
     }
@@ -1073,7 +1169,7 @@ void tick_main(vapx_ingest* g) {
     for (int k = 0; k < n; ++k) {
       in_batch[job.rows[k].slot] = 0;
       g->batch_ids[k] = job.rows[k].slot;
-      const size_t fb = g->geo[job.rows[k].cls].frame_bytes();
+      const size_t fb = g->frame_bytes(job.rows[k].cls, job.rows[k].cls2);
       memcpy((uint8_t*)g->batch_audio + at, g->rawbuf(job.rows[k].slot, job.rows[k].buf), fb);
       at += fb;
     }
@@ -1121,9 +1217,11 @@ int engine_step(void* user, int32_t n, const int32_t* ids, const float* audio, f
   vapx_ingest* g = (vapx_ingest*)user;
   return vapx_step(g->engine, n, ids, audio, g->n_cls ? 0 : g->hop, out, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);   // a table: the classes size the slots
 }
-void engine_set_class(void* user, int32_t sid, int32_t cls) {
+void engine_set_class(void* user, int32_t sid, int32_t cls, int32_t cls2) {
   vapx_ingest* g = (vapx_ingest*)user;
-  if (vapx_set_stream_class) (void)vapx_set_stream_class(g->engine, sid, cls);
+  if (cls != cls2) {
+    if (vapx_set_stream_channel_classes) (void)vapx_set_stream_channel_classes(g->engine, sid, cls, cls2);
+  } else if (vapx_set_stream_class) (void)vapx_set_stream_class(g->engine, sid, cls);
 }
 void engine_reset(void* user, int32_t sid) {
   vapx_ingest* g = (vapx_ingest*)user;
@@ -1153,7 +1251,9 @@ bool read_config(const vapx_ingest_config* cfg, vapx_ingest_config* out) {
   // n_input_classes lives now: nothing past input_format is read from a struct of that size
   constexpr int32_t kFormatEnd = (int32_t)offsetof(vapx_ingest_config, n_input_classes);
   constexpr int32_t kFormat = (kFormatEnd + 7) & ~7;
-  if (!cfg || (cfg->struct_size != kFirst && cfg->struct_size != kPlaced && cfg->struct_size != kFormat &&
+  constexpr int32_t kClasses = (int32_t)offsetof(vapx_ingest_config, n_pair_ports);   // ... with the input classes, before the pair ports (no padding: a multiple of 8)
+  static_assert(kClasses % 8 == 0, "the struct that ended with class_ports_in had no tail padding");
+  if (!cfg || (cfg->struct_size != kFirst && cfg->struct_size != kPlaced && cfg->struct_size != kFormat && cfg->struct_size != kClasses &&
                cfg->struct_size != (int32_t)sizeof(vapx_ingest_config))) return false;
   memset(out, 0, sizeof *out);
   memcpy(out, cfg, cfg->struct_size == kFormat ? (size_t)kFormatEnd : (size_t)cfg->struct_size);
@@ -1208,6 +1308,16 @@ int check_classes(vapx_ingest* g, const vapx_ingest_config* cfg, int n_engine, c
   }
   g->n_cls = n_engine >= 0 ? n_engine : nc;
   for (int i = 0; i < g->n_cls; ++i) g->cls_pub[i] = n_engine >= 0 ? engine_tab[i] : cfg->input_classes[i];
+  const int np = cfg->n_pair_ports;
+  if (np < 0 || np > VAPX_MAX_PAIR_PORTS) return open_refused("n_pair_ports: 0 (no pair ports) .. 16 entries");
+  if (np && !g->n_cls) return open_refused("pair_ports without input classes: a pair port names two classes of the table (vapx_set_input_classes, or input_classes here)");
+  for (int i = 0; i < np; ++i) {
+    if (cfg->pair_ports[i].cls_ch1 < 0 || cfg->pair_ports[i].cls_ch1 >= g->n_cls || cfg->pair_ports[i].cls_ch2 < 0 || cfg->pair_ports[i].cls_ch2 >= g->n_cls)
+      return open_refused("pair_ports: a channel's class is not an index into the table of input classes");
+    if (cfg->pair_ports[i].port_in < 0) return open_refused("pair_ports: a pair port's input port must be >= 0 (0 = ephemeral)");
+  }
+  g->n_pair = np;
+  for (int i = 0; i < np; ++i) { g->pair_cls[i][0] = cfg->pair_ports[i].cls_ch1; g->pair_cls[i][1] = cfg->pair_ports[i].cls_ch2; }
   if (!g->n_cls) return VAPX_OK;
   if (cfg->input_format) return open_refused("input_format together with input classes: the format is each class's own");
   if (cfg->port_in < 0 || cfg->port_out < 0)
@@ -1243,7 +1353,7 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt
     g->frame_stride = std::max(g->frame_stride, g->geo[c].frame_bytes());
     if (!g->geo[c].fmt) g->echo_stride = std::max(g->echo_stride, (size_t)2 * g->geo[c].hop);   // a raw format keeps no f64 echo
   }
-  g->tick_cls.assign(g->S, 0);
+  g->tick_cls.assign((size_t)g->S * 2, 0);
   g->slots.reset(new Slot[g->S]);
   const size_t per = ((size_t)g->S * NBUF * g->frame_stride + 3) / 4;      // the staging blocks in floats: f32 samples, or raw ones of bps bytes
   const size_t ba = ((size_t)g->max_batch * g->frame_stride + 3) / 4;
@@ -1288,6 +1398,10 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt
         g->cls_lsock[c] = listen_on(cfg->class_ports_in[c], cfg->bind_any != 0, &g->cls_port[c]);
         if (g->cls_lsock[c] < 0) return VAPX_E_INVAL;
       }
+      for (int p = 0; p < g->n_pair; ++p) {
+        g->pair_lsock[p] = listen_on(cfg->pair_ports[p].port_in, cfg->bind_any != 0, &g->pair_port[p]);
+        if (g->pair_lsock[p] < 0) return VAPX_E_INVAL;
+      }
       g->port_in = g->cls_port[0];
     } else g->lin = listen_on(cfg->port_in, cfg->bind_any != 0, &g->port_in);
     for (int m = 0; m < g->M; ++m) {
@@ -1308,6 +1422,7 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt
     g->ep_accept = epoll_create1(0);          // own thread: a connect storm must not starve the streams of a receive thread
     if (!g->n_cls) ep_add(g->ep_accept, g->lin, K_LISTEN_IN);
     for (int c = 0; c < g->n_cls; ++c) ep_add(g->ep_accept, g->cls_lsock[c], K_LISTEN_IN | (uint32_t)c);
+    for (int p = 0; p < g->n_pair; ++p) ep_add(g->ep_accept, g->pair_lsock[p], K_LISTEN_IN | (uint32_t)(kPairKey + p));
     for (int m = 0; m < g->M; ++m) ep_add(g->ep_accept, g->ports[m].lsock, K_LISTEN_OUT | (uint32_t)m);
     g->accept_thread = std::thread(accept_main, g);
   }
@@ -1468,7 +1583,22 @@ int32_t vapx_ingest_class_ports(vapx_ingest_handle g, int32_t* ports, int32_t ma
 int32_t vapx_ingest_stream_class(vapx_ingest_handle g, int32_t stream_id) {
   if (!g || !g->n_cls) return VAPX_E_INVAL;
   if (stream_id < 0 || stream_id >= g->S) return VAPX_E_RANGE;
-  return g->tick_cls[stream_id];
+  const int32_t* c = &g->tick_cls[(size_t)2 * stream_id];
+  return c[0] == c[1] ? c[0] : VAPX_E_INVAL;   // a pair port's stream: vapx_ingest_stream_channel_classes
+}
+
+int32_t vapx_ingest_pair_ports(vapx_ingest_handle g, int32_t* ports, int32_t max) {
+  if (!g) return VAPX_E_INVAL;
+  for (int p = 0; ports && p < g->n_pair && p < max; ++p) ports[p] = g->pair_port[p];
+  return g->n_pair;
+}
+
+int vapx_ingest_stream_channel_classes(vapx_ingest_handle g, int32_t stream_id, int32_t out[2]) {
+  if (!g || !g->n_cls || !out) return VAPX_E_INVAL;
+  if (stream_id < 0 || stream_id >= g->S) return VAPX_E_RANGE;
+  out[0] = g->tick_cls[(size_t)2 * stream_id];
+  out[1] = g->tick_cls[(size_t)2 * stream_id + 1];
+  return VAPX_OK;
 }
 
 int vapx_ingest_ports(vapx_ingest_handle g, int32_t* port_in, int32_t* port_out) {
@@ -1655,6 +1785,7 @@ void vapx_ingest_close(vapx_ingest_handle g) {
   for (auto& o : g->ports) { for (int fd : o.out_all) close(fd); if (o.lsock >= 0) close(o.lsock); }
   if (g->lin >= 0) close(g->lin);
   for (int fd : g->cls_lsock) if (fd >= 0) close(fd);
+  for (int fd : g->pair_lsock) if (fd >= 0) close(fd);
   for (int fd : g->ep) close(fd);
   for (int fd : g->wake) close(fd);
   auto drop = [&](void* p) {

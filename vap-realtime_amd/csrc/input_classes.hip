@@ -1,10 +1,11 @@
 // The engine's one input path: whatever the caller's audio is, input_classes_kernel turns a tick's block into the 16 kHz fp32 rows conv0
 // takes, in one launch.  A class is (format, rate).  An engine with a table (vapx_set_input_classes; include/vapx.h "Input classes") gives
-// every stream a class of its own; its tick is a packed block in which batch slot k holds [2][hop_in(c_k)] samples of format(c_k), described
+// every (stream, channel) a class of its own; its tick is a packed block in which batch slot k holds a row per channel, described
 // by slot descriptors the host builds.  A uniform engine (vapx_set_input_rate and / or vapx_set_input_format) is a table of ONE class with
 // no descriptors: slot b is class 0 at b x (bytes of its two rows), computed here.
-// One 256-thread workgroup per (batch slot, channel).  The slot's class is uniform over the workgroup; its geometry is read once from the
-// kernel arguments and lives in scalars.
+// One 256-thread workgroup per (batch slot, channel).  With a table a class belongs to a (stream, channel): the slot holds channel 1's row
+// of its class, then channel 2's of its own, and the two workgroups of a slot may take different paths.  A workgroup's class is uniform
+// over it; its geometry is read once from the kernel arguments and lives in scalars.
 //   - load + decode: lane i reads the aligned dword at the row's base + 4 i (four G.711 codes, two s16 samples or one float) and expands
 //     it with the device functions of input_decode.h, the ones pcm_decode_kernel (vapx_pcm_decode) uses;
 //   - a 16 kHz class stores the decoded samples straight to the output with vector stores: no window, no barrier;
@@ -69,11 +70,18 @@ __device__ __forceinline__ void decode_to_out(const uint32_t* __restrict__ src, 
 __global__ __launch_bounds__(256) void input_classes_kernel(InputClassesArgs a) {
   extern __shared__ float lds[];
   const int tid = threadIdx.x, row = blockIdx.x, b = row >> 1, c = row & 1;
-  const InputClassGeom g = a.cls[a.slots ? __builtin_amdgcn_readfirstlane(a.slots[b].cls) : 0];   // uniform over the workgroup: scalars
+  const int pair = a.slots ? __builtin_amdgcn_readfirstlane(a.slots[b].cls) : 0;   // uniform over the workgroup: scalars
+  const InputClassGeom g = a.cls[(pair >> (8 * c)) & 0xFF];                        // this channel's class
   const int n_in = g.orig ? g.hop_in : a.out_row;   // a 16 kHz row is as long as the row stepped
   const int row_bytes = n_in * pcm_bytes_per_sample(g.fmt), dwords = row_bytes >> 2;   // every row is a multiple of 16 samples
-  const size_t byte_off = a.slots ? a.slots[b].byte_off : (size_t)b * 2 * row_bytes;   // no descriptors: a uniform engine, rows back to back
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(a.in + byte_off + (size_t)c * row_bytes);
+  size_t byte_off;
+  if (a.slots) {   // channel 2's row follows channel 1's, which is of channel 1's class (a table's 16 kHz row is the hop: hop_in)
+    const InputClassGeom g1 = a.cls[pair & 0xFF];
+    byte_off = (size_t)a.slots[b].byte_off + (c ? (size_t)g1.hop_in * pcm_bytes_per_sample(g1.fmt) : 0);
+  } else {
+    byte_off = ((size_t)b * 2 + c) * row_bytes;   // no descriptors: a uniform engine, rows back to back
+  }
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(a.in + byte_off);
   float* o = a.out + (long)row * a.out_row;
 
   if (g.orig == 0) {   // 16 kHz: decode straight to the output
@@ -91,7 +99,7 @@ __global__ __launch_bounds__(256) void input_classes_kernel(InputClassesArgs a) 
   const int sid = a.ids ? a.ids[b] : b;
   const float* tp = taps_of(g.orig);
   for (int i = tid; i < g.nnew * g.K; i += 256) th[i] = tp[i];
-  float* hs = a.hist + (long)sid * a.rec + c * g.H;
+  float* hs = a.hist + (long)sid * a.rec + c * (a.slots ? a.rec >> 1 : g.H);   // a table: half the record, whatever the other channel's H
   for (int i = tid; i < g.H; i += 256) buf[i] = hs[i];
   switch (g.fmt) {
     case VAPX_PCM_F32: decode_to_lds<VAPX_PCM_F32>(src, buf + g.H, dwords, tid); break;

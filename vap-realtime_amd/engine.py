@@ -45,7 +45,9 @@ EXPORTS = ("vapx_abi_version", "vapx_blob_floats", "vapx_create", "vapx_destroy"
            "vapx_set_input_rate", "vapx_get_input_rate", "vapx_resample",
            "vapx_set_input_format", "vapx_get_input_format", "vapx_pcm_decode",
            "vapx_set_input_classes", "vapx_get_input_classes", "vapx_set_stream_class", "vapx_get_stream_class", "vapx_input_slot_bytes",
-           "vapx_ingest_class_ports", "vapx_ingest_stream_class")
+           "vapx_ingest_class_ports", "vapx_ingest_stream_class",
+           "vapx_set_stream_channel_classes", "vapx_get_stream_channel_classes", "vapx_input_row_bytes",
+           "vapx_ingest_pair_ports", "vapx_ingest_stream_channel_classes")
 MAX_INPUT_CLASSES = 16
 PROF_CLASSES = {0: "gemm_store", 1: "gemm_gelu", 2: "gemm_resid", 3: "gemm_resid_ln", 4: "gemm_cn_relu",
                 5: "conv_tail", 6: "ffn_block", 7: "last_row", 8: "conv0", 9: "lstm", 10: "gather_ln", 11: "attention", 12: "head",
@@ -101,35 +103,68 @@ def aligned_bytes(n: int, align: int = 16) -> np.ndarray:
     return raw[at:at + n]
 
 
-def pack_input_classes(classes, frame_hz: int, slot_classes: Sequence[int], arrays, out: Optional[np.ndarray] = None) -> np.ndarray:
-    """The packed audio block of one step on an engine with input classes (vapx.h "Input classes", LAYOUT): slot k holds ``arrays[k]``,
-    [2, hop_in(c_k)] samples of format(c_k) with c_k = ``slot_classes[k]``, at byte offset sum_{j<k} input_slot_bytes(c_j).  The dtype of
-    every array is checked as ``Engine.step`` checks a uniform engine's: float arrays of any width are cast for "f32", a raw format takes
-    its own dtype only.  Returns a 16-byte aligned uint8 block (``out``, e.g. a view of a ``pinned_empty`` block, if given)."""
+def input_row_bytes(cls, frame_hz: int) -> int:
+    """Bytes of one channel's row of class ``cls``: hop_in * bytes per sample, a multiple of 16 (vapx.h, vapx_input_row_bytes)."""
+    return input_slot_bytes(cls, frame_hz) // 2
+
+
+def _slot_pair(c):
+    """A batch slot's classes as ``(c1, c2)``: a class index means both channels."""
+    if isinstance(c, (tuple, list, np.ndarray)):
+        if len(c) != 2:
+            raise ValueError(f"a batch slot's classes are one index or a pair (c1, c2), not {c!r}")
+        return int(c[0]), int(c[1])
+    return int(c), int(c)
+
+
+def pack_input_classes(classes, frame_hz: int, slot_classes: Sequence, arrays, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """The packed audio block of one step on an engine with input classes (vapx.h "Input classes", LAYOUT).  ``slot_classes[k]`` is a class
+    index c_k, and ``arrays[k]`` [2, hop_in(c_k)] samples of format(c_k); or a pair (c1, c2), the classes of the stream's two channels, and
+    ``arrays[k]`` a pair of 1-D arrays: hop_in(c1) samples of format(c1), then hop_in(c2) of format(c2) (a class index takes such a pair
+    too).  Slot k starts at the sum of the earlier slots' bytes, channel 1's row first; a pair (c, c) is the block of the index c byte for
+    byte.  The dtype of every array is checked as ``Engine.step`` checks a uniform engine's: float arrays of any width are cast for "f32",
+    a raw format takes its own dtype only.  Returns a 16-byte aligned uint8 block (``out``, e.g. a view of a ``pinned_empty`` block, if
+    given)."""
     tab = input_class_table(classes)
     if len(slot_classes) != len(arrays):
         raise ValueError(f"{len(arrays)} arrays for {len(slot_classes)} batch slots")
-    sizes = [input_slot_bytes(tab[c], frame_hz) for c in slot_classes]
-    total = int(sum(sizes))
+    pairs = [_slot_pair(c) for c in slot_classes]
+    total = int(sum(input_row_bytes(tab[c], frame_hz) for p in pairs for c in p))
     if out is None:
         out = aligned_bytes(total)
     block = out.reshape(-1).view(np.uint8)[:total]
     if block.size != total or block.ctypes.data % 16:
         raise ValueError("the packed block must hold every slot and start on a 16-byte boundary")
     at = 0
-    for k, (c, a, nb) in enumerate(zip(slot_classes, arrays, sizes)):
-        dt, shape = input_slot_shape(tab[c], frame_hz)
+    for k, (pair, a) in enumerate(zip(pairs, arrays)):
         if hasattr(a, "detach") and hasattr(a, "numpy"):
             a = a.detach().cpu().numpy()
-        a = np.asarray(a)
-        if tab[c][0] == "f32":
-            a = np.ascontiguousarray(a, dtype=np.float32)
-        elif a.dtype != dt:
-            raise TypeError(f"batch slot {k}: class {c} ({tab[c][0]} at {tab[c][1]} Hz) takes {dt.name} samples, not {a.dtype.name}")
-        if a.shape != shape:
-            raise ValueError(f"batch slot {k}: class {c} ({tab[c][0]} at {tab[c][1]} Hz) takes {list(shape)} samples, not {list(a.shape)}")
-        block[at:at + nb] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
-        at += nb
+        planar = isinstance(a, (tuple, list))
+        if planar and len(a) != 2:
+            raise ValueError(f"batch slot {k}: a pair of per-channel arrays has two entries, not {len(a)}")
+        if not planar:
+            if pair[0] != pair[1]:
+                raise TypeError(f"batch slot {k}: channel classes {pair} take a pair of 1-D arrays, one per channel")
+            a = np.asarray(a)
+            if a.ndim != 2 or a.shape[0] != 2:
+                dt, shape = input_slot_shape(tab[pair[0]], frame_hz)
+                raise ValueError(f"batch slot {k}: class {pair[0]} ({tab[pair[0]][0]} at {tab[pair[0]][1]} Hz) takes {list(shape)} samples, not {list(a.shape)}")
+        for ch, c in enumerate(pair):
+            dt, (_, hop_in) = input_slot_shape(tab[c], frame_hz)
+            r = a[ch]
+            if hasattr(r, "detach") and hasattr(r, "numpy"):
+                r = r.detach().cpu().numpy()
+            r = np.asarray(r)
+            if tab[c][0] == "f32":
+                r = np.ascontiguousarray(r, dtype=np.float32)
+            elif r.dtype != dt:
+                raise TypeError(f"batch slot {k}: class {c} ({tab[c][0]} at {tab[c][1]} Hz) takes {dt.name} samples, not {r.dtype.name}")
+            if r.shape != (hop_in,):
+                shape = [hop_in] if planar else [2, hop_in]
+                raise ValueError(f"batch slot {k}: class {c} ({tab[c][0]} at {tab[c][1]} Hz) takes {shape} samples, not {list(r.shape if planar else a.shape)}")
+            nb = hop_in * dt.itemsize
+            block[at:at + nb] = np.ascontiguousarray(r).view(np.uint8)
+            at += nb
     return block
 
 
@@ -199,6 +234,12 @@ def load_library(path: Optional[str] = None):
     lib.vapx_get_stream_class.argtypes = [vp, i32]
     lib.vapx_input_slot_bytes.restype = C.c_int64
     lib.vapx_input_slot_bytes.argtypes = [vp, i32]
+    lib.vapx_set_stream_channel_classes.restype = i32
+    lib.vapx_set_stream_channel_classes.argtypes = [vp, i32, i32, i32]
+    lib.vapx_get_stream_channel_classes.restype = i32
+    lib.vapx_get_stream_channel_classes.argtypes = [vp, i32, vp]
+    lib.vapx_input_row_bytes.restype = C.c_int64
+    lib.vapx_input_row_bytes.argtypes = [vp, i32]
     lib.vapx_encode_audio.restype = i32
     lib.vapx_encode_audio.argtypes = [vp, i32, i32p, f32p, f32p, vp]
     lib.vapx_transformer.restype = i32
@@ -235,6 +276,10 @@ def load_library(path: Optional[str] = None):
     lib.vapx_ingest_class_ports.argtypes = [vp, vp, i32]
     lib.vapx_ingest_stream_class.restype = i32
     lib.vapx_ingest_stream_class.argtypes = [vp, i32]
+    lib.vapx_ingest_pair_ports.restype = i32
+    lib.vapx_ingest_pair_ports.argtypes = [vp, vp, i32]
+    lib.vapx_ingest_stream_channel_classes.restype = i32
+    lib.vapx_ingest_stream_channel_classes.argtypes = [vp, i32, vp]
     lib.vapx_ingest_stats_read.restype = i32
     lib.vapx_ingest_stats_read.argtypes = [vp, vp, i32]
     lib.vapx_ingest_late_read.restype = i32
@@ -388,9 +433,10 @@ class Engine:
 
     # -- input classes ---------------------------------------------------------------------------
     def _mirror_input_classes(self):
-        """The host's copy of every stream's class and every class's slot size: a step sizes its packed block without a library call per slot."""
-        self._cls = np.zeros(self.max_streams, np.int64)
-        self._cls_bytes = np.array([input_slot_bytes(c, self.frame_hz) for c in self.input_classes], np.int64)
+        """The host's copy of every (stream, channel)'s class and every class's row size: a step sizes its packed block without a library
+        call per slot."""
+        self._cls = np.zeros((self.max_streams, 2), np.int64)
+        self._row_bytes = np.array([input_row_bytes(c, self.frame_hz) for c in self.input_classes], np.int64)
 
     def set_stream_class(self, sid: int, cls: int):
         """Move stream ``sid`` to input class ``cls``: queued like ``reset_carry``; the next step zeroes the stream's carry and resampler
@@ -401,21 +447,37 @@ class Engine:
     def stream_class(self, sid: int) -> int:
         return self._check(self.lib.vapx_get_stream_class(self._h, sid), "vapx_get_stream_class")
 
+    def set_stream_channel_classes(self, sid: int, c1: int, c2: int):
+        """Give the two channels of stream ``sid`` the input classes ``c1`` and ``c2`` (a dialogue whose legs arrive in different codecs):
+        the rules of ``set_stream_class``, and the carry and the history of both channels restart."""
+        self._check(self.lib.vapx_set_stream_channel_classes(self._h, sid, c1, c2), "vapx_set_stream_channel_classes")
+        self._cls[sid] = (c1, c2)
+
+    def stream_channel_classes(self, sid: int) -> tuple:
+        out = (C.c_int32 * 2)()
+        self._check(self.lib.vapx_get_stream_channel_classes(self._h, sid, out), "vapx_get_stream_channel_classes")
+        return int(out[0]), int(out[1])
+
     def refresh_stream_classes(self):
-        """Re-read every stream's class from the library: after somebody else moved streams (a ``NativeServer`` does for every connection)."""
+        """Re-read every channel's class from the library: after somebody else moved streams (a ``NativeServer`` does for every connection)."""
         for s in range(self.max_streams):
-            self._cls[s] = self.stream_class(s)
+            self._cls[s] = self.stream_channel_classes(s)
 
     def input_slot_bytes(self, cls: int) -> int:
         return int(self.lib.vapx_input_slot_bytes(self._h, cls))
 
+    def input_row_bytes(self, cls: int) -> int:
+        return int(self.lib.vapx_input_row_bytes(self._h, cls))
+
     def pack_input(self, stream_ids: Optional[Sequence[int]], arrays, out: Optional[np.ndarray] = None) -> np.ndarray:
         """The packed block ``step`` takes for these streams in this batch order (``stream_ids`` None = 0 .. n-1): array k is
-        [2, hop_in] samples in the class of ``stream_ids[k]`` (``pack_input_classes``)."""
+        [2, hop_in] samples in the class of ``stream_ids[k]``, or a pair of 1-D arrays in its two channels' classes
+        (``pack_input_classes``)."""
         if self.input_classes is None:
             raise VapxError("this engine has no input classes")
         ids = np.arange(len(arrays)) if stream_ids is None else np.asarray(stream_ids, dtype=np.int64)
-        return pack_input_classes(self.input_classes, self.frame_hz, self._cls[ids].tolist(), arrays, out)
+        slot_classes = [int(c1) if c1 == c2 else (int(c1), int(c2)) for c1, c2 in self._cls[ids]]
+        return pack_input_classes(self.input_classes, self.frame_hz, slot_classes, arrays, out)
 
     def _packed_audio(self, audio, stream_ids):
         """``(block, n)`` of a step on an engine with input classes: ``audio`` is a list of per-slot arrays (packed here) or one packed
@@ -423,7 +485,7 @@ class Engine:
         if isinstance(audio, np.ndarray) and audio.dtype == np.uint8 and audio.ndim == 1:
             if stream_ids is None:
                 raise ValueError("a packed block needs stream_ids: its slots are sized by their streams' classes")
-            need = int(self._cls_bytes[self._cls[np.asarray(stream_ids, dtype=np.int64)]].sum())
+            need = int(self._row_bytes[self._cls[np.asarray(stream_ids, dtype=np.int64)]].sum())
             if audio.size != need:
                 raise ValueError(f"the packed block has {audio.size} bytes, the classes of these {len(stream_ids)} streams add up to {need}")
             if not audio.flags.c_contiguous or audio.ctypes.data % 16:

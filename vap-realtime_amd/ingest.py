@@ -37,6 +37,18 @@ class _IngestConfig(C.Structure):
                                  ("class_ports_in", C.c_int32 * _engine.MAX_INPUT_CLASSES)]
 
 
+MAX_PAIR_PORTS = 16
+
+
+class _PairPort(C.Structure):
+    _fields_ = [("cls_ch1", C.c_int32), ("cls_ch2", C.c_int32), ("port_in", C.c_int32)]
+
+
+class _IngestConfigPairs(C.Structure):
+    """vapx_ingest_config with the pair ports at its end; ``_IngestConfig`` keeps the size it had before them, which still means "none"."""
+    _fields_ = _IngestConfig._fields_ + [("n_pair_ports", C.c_int32), ("pair_ports", _PairPort * MAX_PAIR_PORTS)]
+
+
 def class_table(classes) -> list:
     """An input-class table for a front-end: ``engine.input_class_table`` with the wire's name "f64" (the reference's framing: f64 pairs,
     cast to the engine's f32 on the host) accepted for "f32"."""
@@ -50,6 +62,43 @@ def parse_input_class(text: str):
     if not at or not rate.isdigit() or (port and not port.isdigit()):
         raise ValueError(f"input class {text!r}: expected FORMAT@RATE[:PORT], e.g. mulaw@8000:50017")
     return class_table([(fmt, int(rate))])[0], int(port or 0)
+
+
+def parse_input_port(text: str):
+    """``FORMAT@RATE[:PORT]`` or ``FORMAT@RATE+FORMAT@RATE[:PORT]`` (a pair port: channel 1's class, then channel 2's) ->
+    ([class] or [class of channel 1, class of channel 2], port or 0)."""
+    spec, _, port = text.partition(":")
+    legs = spec.split("+")
+    if len(legs) == 1:
+        c, p = parse_input_class(text)
+        return [c], p
+    if len(legs) != 2 or (port and not port.isdigit()):
+        raise ValueError(f"input class {text!r}: expected FORMAT@RATE[:PORT] or FORMAT@RATE+FORMAT@RATE[:PORT], e.g. s16@48000+mulaw@8000:50027")
+    return [parse_input_class(leg)[0] for leg in legs], int(port or 0)
+
+
+def input_ports(specs):
+    """The ``--input_class`` arguments of a server -> (table, class_ports, pair_ports): the table is the distinct classes named anywhere, in
+    order of first appearance; ``class_ports[c]`` is the port of class c's own port (0 = ephemeral: also for a class that only pair ports
+    name); ``pair_ports`` is ``[(c1, c2, port)]`` with indices into the table.  A class or a pair named twice is refused."""
+    table, class_ports, pair_ports, seen = [], [], [], set()
+    for text in specs:
+        legs, port = parse_input_port(text)
+        if tuple(legs) in seen:
+            raise ValueError(f"two equal input classes: {text.partition(':')[0]!r} is named twice")
+        seen.add(tuple(legs))
+        for c in legs:
+            if c not in table:
+                table.append(c)
+                class_ports.append(0)
+        if len(legs) == 1:
+            class_ports[table.index(legs[0])] = port
+        else:
+            pair_ports.append((table.index(legs[0]), table.index(legs[1]), port))
+    class_table(table)      # at most 16
+    if len(pair_ports) > MAX_PAIR_PORTS:
+        raise ValueError(f"{len(pair_ports)} pair ports: at most {MAX_PAIR_PORTS}")
+    return table, class_ports, pair_ports
 
 
 WIRE_FORMATS = {"f64": 0, "s16": 1, "mulaw": 2, "alaw": 3}      # wire format of the input port; f64 = the reference's framing (engine format f32)
@@ -90,9 +139,11 @@ class NativeServer:
                  min_batch: int = 0, reset_on_connect: bool = True, broadcast: Optional[bool] = None, rx_threads: int = 0,
                  tx_threads: int = 0, bind_any: bool = False, target_util: float = 0.9, cores: Optional[tuple] = None,
                  keep_nofile: bool = False, core_set: bool = False, keep_state: bool = False, input_format: Optional[str] = None,
-                 class_ports=None):
+                 class_ports=None, pair_ports=None):
         """``class_ports``: with an engine that has input classes (``Engine(input_classes=...)``) the input port of every class, in table
         order (default: all ephemeral; ``.class_ports`` lists the bound ones); ``port_in`` is then ignored.
+        ``pair_ports``: ``[(c1, c2, port)]``, input ports for dialogues whose channel 1 is of class c1 and channel 2 of class c2; they take
+        planar 10 ms packets (``wire.encode_input_planar``; ``.pair_ports`` lists the bound ports).
         ``input_format``: wire format of the input port, "f64" (the reference's framing) / "s16" / "mulaw" / "alaw"; it is the engine's
         (``Engine(input_format=...)``, "f32" there is "f64" here) and may be left out; one that disagrees with the engine's is refused.
         ``cores`` = (first, count): pin the front-end's tick / receive / sender threads to that core range (the GPU's NUMA node; keep
@@ -103,7 +154,7 @@ class NativeServer:
         self._keep = [eng]
         self._check_format(getattr(eng, "input_format", "f32"), input_format)
         cfg = self._cfg(port_in, port_out, gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, bind_any, target_util,
-                        cores, keep_nofile, core_set, keep_state, input_format, getattr(eng, "input_classes", None), class_ports)
+                        cores, keep_nofile, core_set, keep_state, input_format, getattr(eng, "input_classes", None), class_ports, pair_ports)
         h = C.c_void_p()
         rc = self.lib.vapx_ingest_open(eng._h, C.byref(cfg), C.byref(h))
         if rc != 0:
@@ -119,9 +170,11 @@ class NativeServer:
 
     @staticmethod
     def _cfg(port_in, port_out, gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, bind_any, target_util=0.9,
-             cores=None, keep_nofile=False, core_set=False, keep_state=False, input_format=None, input_classes=None, class_ports=None):
+             cores=None, keep_nofile=False, core_set=False, keep_state=False, input_format=None, input_classes=None, class_ports=None,
+             pair_ports=None):
         first, count = (int(cores[0]), int(cores[1])) if cores else (0, 0)
-        cfg = _IngestConfig(C.sizeof(_IngestConfig), port_in, port_out, rx_threads, tx_threads, int(max_wait_s * 1e6), min_batch,
+        struct = _IngestConfigPairs if pair_ports else _IngestConfig
+        cfg = struct(C.sizeof(struct), port_in, port_out, rx_threads, tx_threads, int(max_wait_s * 1e6), min_batch,
                             1 if reset_on_connect else 0, -1 if broadcast is None else int(bool(broadcast)), int(bool(bind_any)), gain,
                             int(round(target_util * 100)), (1 if keep_nofile else 0) | (2 if core_set else 0) | (4 if keep_state else 0), first, count,
                             wire_format_id(input_format))
@@ -137,6 +190,12 @@ class NativeServer:
                 cfg.class_ports_in[i] = int(port)
         elif class_ports:
             raise ValueError("class_ports without input classes")
+        if pair_ports:
+            if len(pair_ports) > MAX_PAIR_PORTS:
+                raise ValueError(f"{len(pair_ports)} pair ports: at most {MAX_PAIR_PORTS}")
+            cfg.n_pair_ports = len(pair_ports)
+            for i, (c1, c2, port) in enumerate(pair_ports):
+                cfg.pair_ports[i] = _PairPort(int(c1), int(c2), int(port))
         return cfg
 
     @classmethod
@@ -144,13 +203,14 @@ class NativeServer:
                       reset: Optional[Callable] = None, port_in: int = 0, port_out: int = 0, gain: float = 1.0, max_wait_s: float = 0.002,
                       min_batch: int = 0, reset_on_connect: bool = True, broadcast: Optional[bool] = None, rx_threads: int = 0,
                       tx_threads: int = 0, target_util: float = 1.0, input_format: Optional[str] = None, input_classes=None,
-                      class_ports=None):
+                      class_ports=None, pair_ports=None):
         """``step(ids int32[n], audio float32[n,2,hop], out float32[n,OUT_STRIDE]) -> int`` fills ``out`` in place;
         ``reset(stream_id)`` gets negative ids (``-(id+1)``) for carry-only resets.  With ``input_format`` "s16" / "mulaw" / "alaw" the
         input port takes packets of that format and ``audio`` is the de-interleaved raw block, int16 or uint8 [n,2,hop].
         With ``input_classes`` (and ``class_ports``, default ephemeral) there is one input port per class and ``audio`` is the packed block
         exactly as an engine with that table takes it, a uint8 array: slot k holds [2, hop_in] samples of the class
-        ``self.stream_class(ids[k])`` (valid inside ``step``), the slots back to back in batch order."""
+        ``self.stream_class(ids[k])`` (valid inside ``step``), the slots back to back in batch order.  With ``pair_ports`` a slot holds
+        channel 1's row and then channel 2's, in the classes ``self.stream_channel_classes(ids[k])``."""
         self = cls.__new__(cls)
         self.lib = _engine.load_library()
         hop = 16000 // frame_hz
@@ -161,7 +221,7 @@ class NativeServer:
             try:
                 i = np.ctypeslib.as_array(ids, shape=(n,))
                 if tab:
-                    nbytes = sum(_engine.input_slot_bytes(tab[self.stream_class(int(s))], frame_hz) for s in i)
+                    nbytes = sum(_engine.input_row_bytes(tab[c], frame_hz) for s in i for c in self.stream_channel_classes(int(s)))
                     a = np.frombuffer((C.c_char * nbytes).from_address(C.addressof(audio.contents)), dtype=np.uint8)
                 else:
                     a = _raw_view(audio, n, hop, fmt_id)
@@ -179,7 +239,7 @@ class NativeServer:
 
         self._keep = [_STEP_FN(_step), _RESET_FN(_reset)]
         cfg = cls._cfg(port_in, port_out, gain, max_wait_s, min_batch, reset_on_connect, broadcast, rx_threads, tx_threads, False, target_util,
-                       input_format=fmt_id, input_classes=tab, class_ports=class_ports)
+                       input_format=fmt_id, input_classes=tab, class_ports=class_ports, pair_ports=pair_ports)
         h = C.c_void_p()
         rc = self.lib.vapx_ingest_open_fn(C.cast(self._keep[0], C.c_void_p), C.cast(self._keep[1], C.c_void_p), None, n_streams,
                                           max_batch or n_streams, frame_hz, MODE[mode], C.byref(cfg), C.byref(h))
@@ -331,13 +391,24 @@ class NativeServer:
         arr = (C.c_int32 * _engine.MAX_INPUT_CLASSES)()
         n = self.lib.vapx_ingest_class_ports(self._h, arr, _engine.MAX_INPUT_CLASSES)
         self.class_ports = [int(arr[c]) for c in range(max(n, 0))]      # the bound input port of every input class; [] without a table
+        arr = (C.c_int32 * MAX_PAIR_PORTS)()
+        n = self.lib.vapx_ingest_pair_ports(self._h, arr, MAX_PAIR_PORTS)
+        self.pair_ports = [int(arr[p]) for p in range(max(n, 0))]       # the bound input port of every pair port
 
     def stream_class(self, sid: int) -> int:
         """The input class of stream ``sid`` as the tick thread knows it: for a step function of ``over_function(input_classes=...)``."""
         c = self.lib.vapx_ingest_stream_class(self._h, int(sid))
         if c < 0:
-            raise _engine.VapxError(f"vapx_ingest_stream_class failed ({c}): no input classes, or a bad stream id")
+            raise _engine.VapxError(f"vapx_ingest_stream_class failed ({c}): no input classes, a bad stream id, or a stream whose channels differ")
         return c
+
+    def stream_channel_classes(self, sid: int) -> tuple:
+        """The input classes of the two channels of stream ``sid`` as the tick thread knows them (a pair port's stream has two)."""
+        out = (C.c_int32 * 2)()
+        rc = self.lib.vapx_ingest_stream_channel_classes(self._h, int(sid), out)
+        if rc < 0:
+            raise _engine.VapxError(f"vapx_ingest_stream_channel_classes failed ({rc}): no input classes, or a bad stream id")
+        return int(out[0]), int(out[1])
 
     def stats(self, reset_latency_window: bool = False) -> dict:
         """Counters + the latency window (frame complete on the host -> packet handed to the kernel); ``late_over_10ms`` / ``answered`` are the

@@ -316,7 +316,7 @@ def build(args):
             shards.append(ingest.NativeServer(eng, port_in=-1 if passive else args.port_num_in, port_out=-1 if passive else args.port_num_out,
                                               gain=args.audio_gain, max_wait_s=args.max_wait_ms * 1e-3, bind_any=args.bind_any,
                                               rx_threads=args.rx_threads, tx_threads=args.tx_threads, cores=cores, reset_on_connect=not warm, keep_state=warm,
-                                              class_ports=getattr(args, "class_ports", None)))
+                                              class_ports=getattr(args, "class_ports", None), pair_ports=getattr(args, "pair_ports", None)))
         if n > 1:
             door = ingest.FrontDoor(shards, args.port_num_in, args.port_num_out, bind_any=args.bind_any)
     except Exception:
@@ -457,9 +457,11 @@ def main(argv=None) -> int:
                     help="sample format of the clients' audio on the input port: f64 (default) is the reference's framing, 160 x {f64, f64} per "
                          "10 ms; s16 (16-bit little-endian PCM) and mulaw / alaw (G.711) packets carry input_rate / 100 interleaved (ch1, ch2) pairs "
                          "of 2 or 1 bytes per sample and are decoded on the GPU; result packets are unchanged.  Not with --audio_gain")
-    ap.add_argument("--input_class", action="append", default=None, metavar="FORMAT@RATE[:PORT]",
+    ap.add_argument("--input_class", action="append", default=None, metavar="FORMAT@RATE[+FORMAT@RATE][:PORT]",
                     help="repeatable: one INPUT PORT per kind of client on ONE engine, e.g. --input_class f64@16000:50007 --input_class mulaw@8000:50017 "
                          "--input_class s16@48000:50027 (formats and rates as --input_format / --input_rate; PORT 0 or left out = ephemeral); "
+                         "A+B, e.g. s16@48000+mulaw@8000:50037, is a PAIR port for dialogues whose channel 1 arrives as A and channel 2 as B, in planar "
+                         "10 ms packets (channel 1's 10 ms, then channel 2's); the engine's classes are the distinct ones named anywhere; "
                          "--port_num_in is then ignored.  Not with --input_rate / --input_format, --mode a+b, --gpus N > 1, --save_state / --load_state")
     ap.add_argument("--streams", type=int, default=1, help="dialogue slots per GPU (the reference serves exactly one)")
     ap.add_argument("--max_batch", type=int, default=1024)
@@ -504,12 +506,10 @@ def main(argv=None) -> int:
             args.context_len_sec = per_model(args.context_len_sec, 1, float, "--context_len_sec")[0]
         else:
             args.group_plan = group_plan(args, names)
-        args.input_classes = args.class_ports = None
+        args.input_classes = args.class_ports = args.pair_ports = None
         if args.input_class:
             from . import ingest
-            parsed = [ingest.parse_input_class(t) for t in args.input_class]
-            args.input_classes = ingest.class_table([c for c, _ in parsed])
-            args.class_ports = [port for _, port in parsed]
+            args.input_classes, args.class_ports, args.pair_ports = ingest.input_ports(args.input_class)
     except ValueError as e:
         ap.error(str(e))
     why = input_class_refusal(args, names)
@@ -538,7 +538,9 @@ def main(argv=None) -> int:
         return 1
     pin, pout = (door.port_in, door.port_out) if door else (shards[0].port_in, shards[0].port_out)
     if args.input_classes:
-        audio = "input classes " + ", ".join(f"{t.split(':')[0]} :{port}" for t, port in zip(args.input_class, shards[0].class_ports))
+        name = lambda c: f"{'f64' if args.input_classes[c][0] == 'f32' else args.input_classes[c][0]}@{args.input_classes[c][1]}"      # noqa: E731
+        audio = "input classes " + ", ".join([f"{name(c)} :{port}" for c, port in enumerate(shards[0].class_ports)] +
+                                             [f"{name(c1)}+{name(c2)} :{port}" for (c1, c2, _), port in zip(args.pair_ports, shards[0].pair_ports)])
         print(f"[vapx] 1 GPU(s) x {args.streams} dialogue slots, mode {mode}, {args.precision} arithmetic, {args.vap_process_rate} Hz / {args.context_len_sec} s, "
               f"{audio} — output :{pout}", flush=True)
     else:

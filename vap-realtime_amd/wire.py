@@ -31,6 +31,26 @@ def input_packet_bytes(fmt: str = "f64", input_hz: int = 16000) -> int:
     return PAIR_BYTES[fmt] * (input_hz // 100)
 
 
+def encode_input_planar(x1, cls1, x2, cls2) -> bytes:
+    """What a client of a PAIR port sends (vapx.h, vapx_ingest_config.pair_ports): planar 10 ms packets, channel 1's ``rate / 100`` samples in
+    its class's wire form followed by channel 2's in its own.  ``cls`` = (format, rate), "f64" (or "f32": the engine's name for it) /
+    "s16" / "mulaw" / "alaw"; the samples as ``encode_input`` takes them: floats are encoded, raw arrays are sent as they are.  Both
+    signals must span the same whole number of packets."""
+    legs = []
+    for x, (fmt, hz) in ((x1, cls1), (x2, cls2)):
+        fmt = "f64" if fmt == "f32" else fmt
+        per = int(hz) // 100
+        one = encode_input(x, x, fmt)                       # interleaved with itself: every second sample is the leg's
+        wb = PAIR_BYTES[fmt] // 2
+        leg = np.frombuffer(one, np.uint8).reshape(-1, 2, wb)[:, 0, :]
+        if leg.shape[0] % per:
+            raise ValueError(f"{leg.shape[0]} samples at {hz} Hz are not a whole number of 10 ms packets")
+        legs.append(leg.reshape(-1, per * wb))
+    if legs[0].shape[0] != legs[1].shape[0]:
+        raise ValueError(f"the channels span {legs[0].shape[0]} and {legs[1].shape[0]} packets of 10 ms")
+    return np.concatenate(legs, axis=1).tobytes()
+
+
 def decode_input(data: bytes, fmt: str = "f64") -> Tuple[np.ndarray, np.ndarray]:
     """bytes (multiple of 16) -> (x1, x2) float64 arrays; == util.conv_bytearray_2_2floatarray.  ``fmt`` "s16" / "mulaw" / "alaw": packets of
     interleaved raw pairs -> the decoded samples (``pcm.decode``), float64 as the result packet echoes them."""
