@@ -497,7 +497,8 @@ int vapx_aggregate(int64_t rows, const float* probs, int32_t from_bin, int32_t t
  * "comb": nod mode only, [n][ctx_frames][256], the combinator of every window row (rows >= a stream's n undefined); refused in
  * the other modes and when the latest step ran in more than one overlap group (the groups' blocks are not contiguous).
  * Debug: "guard_violations" writes one float, the number of canary bytes overwritten around the process's engine allocations (-1 unless
- * the library was started with VAPX_GUARD_ZONES=1; INTEGRATION.md "Debug and experiment knobs"). */
+ * the library was started with VAPX_GUARD_ZONES=1; INTEGRATION.md "Debug and experiment knobs"); "guard_selftest" changes one canary
+ * byte of an allocation of its own and writes what that counter then says: 1 (-1 without the variable). */
 int64_t vapx_peek(vapx_handle h, const char* name, float* dst, size_t max_floats);
 
 /* Standalone fp32-MFMA GEMM used by every dense contraction of the path (kernel unit tests):

@@ -1927,6 +1927,21 @@ int64_t vapx_peek(vapx_handle h, const char* name, float* dst, size_t max_floats
     dst[0] = guard_enabled() ? (float)guard_violations() : -1.f;
     return 1;
   }
+  if (!strcmp(name, "guard_selftest")) {   // debug: the counter above can count.  One byte of an allocation's own trailing canary is changed
+    // (inside its hipMalloc: nothing faults), guard_violations() must then say exactly 1; -1 without VAPX_GUARD_ZONES
+    dst[0] = -1.f;
+    if (!guard_enabled()) return 1;
+    unsigned char* probe = nullptr;
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    HIPCHK(h, dalloc(&probe, 8));
+    hipError_t e = hipMemset(probe + 8, 0x5A, 1);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    const long seen = e == hipSuccess ? guard_violations() : -1;
+    dfree(probe);
+    HIPCHK(h, e);
+    dst[0] = (float)seen;
+    return 1;
+  }
   // what exists after the latest step depends on the path it took: refuse what was not written
   const bool full_last = (h->cfg.flags & VAPX_FLAG_FULL_LAST_LAYER) || h->cfg.mode == VAPX_MODE_NOD;
   if ((!strcmp(name, "h2") || !strcmp(name, "h3")) && h->last_tail_fused)
