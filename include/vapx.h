@@ -444,6 +444,45 @@ size_t vapx_state_floats(vapx_handle h, int32_t flags);
 int vapx_export_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, float* dst, int32_t flags, void* hip_stream);
 int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* src, int32_t flags, void* hip_stream);
 
+/* Prefill: attach to a call in progress - fill the context window from buffered AUDIO in one call (INTEGRATION.md "Attaching to a call in
+ * progress").  A stream that starts from zeros is blind for the length of its window and its LSTM never matches the uninterrupted one
+ * (above); a snapshot helps only where another engine holds the state.  Where only the audio exists - a call transferred in, a recorder's
+ * last seconds, a restart without a snapshot - the one way in was `frames` calls of vapx_step, each running the whole transformer for rows
+ * nobody reads.  The CPC CNN is independent per frame and only h . W_hh of the LSTM is sequential; the window needs the embeddings and
+ * their layer-0 Q|K|V rows and no transformer pass at all.
+ *
+ *   n          : 1 .. max_batch
+ *   stream_ids : as in vapx_step: host ids are checked (VAPX_E_RANGE out of range, VAPX_E_INVAL for a duplicate), device ids
+ *                (VAPX_IDS_DEVICE) are the caller's responsibility; NULL means 0..n-1
+ *   audio      : fp32 [n][2][frames * hop], contiguous 16 kHz NEW samples (hop = 16000 / frame_hz), 16-byte aligned;
+ *                host (VAPX_AUDIO_HOST, page-locked or pageable) or device (VAPX_AUDIO_DEVICE) memory
+ *   frames     : >= 1, no upper bound: the work proceeds in chunks of floor(max_batch / n) frames (at least one) through the step's scratch
+ *   flags      : VAPX_AUDIO_HOST | VAPX_AUDIO_DEVICE, VAPX_IDS_DEVICE
+ *
+ * Meaning: the state of every named stream is what `frames` consecutive calls of vapx_step(..., samples_per_ch = hop, ...) on that audio
+ * would have left, except that NO output row is produced and NO transformer layer runs:
+ *   - LSTM (h, c) advanced through frames * n_cpc steps; the first frame's 320-sample prefix is the stream's current carry, as in a step,
+ *     and the carry becomes the block's last 320 samples;
+ *   - frame j lands in ring slot (frames_seen + j) mod T; for frames > T only the last T rows are written (the LSTM still runs every
+ *     frame); frames_seen += frames;
+ *   - the layer-0 Q|K|V cache rows of the written slots are made as the step makes them: LN0 of the embedding (inside the LSTM kernel),
+ *     then the engine's own GEMM dispatch on Wqkv - on a VAPX_FLAG_SPLIT_F16 engine the split product, like a step's;
+ *   - the next vapx_step continues as if the frames had been stepped.  The arithmetic is the step's; a GEMM over another number of rows
+ *     may pick another tile, so the state agrees with the stepped one to rounding (tests/test_prefill_gpu.py holds it against float64 at
+ *     twice the stepped engine's own error), not bit for bit.
+ * Ordering: as vapx_export_streams.  The call makes hip_stream wait for overlap groups a VAPX_DEFER_JOIN step left running, applies queued
+ * vapx_reset_stream / vapx_reset_carry requests, then enqueues on hip_stream; no device-wide synchronisation.  Device audio is read where it
+ * lies: no copy, no synchronisation at all.  Host audio travels chunk by chunk through the step's own audio staging (one strided copy per
+ * chunk from vapx_host_alloc memory; pageable memory through the pinned block, one event wait per chunk) - never a second full-size pinned
+ * copy - and the call synchronises hip_stream ONCE, at its end.  Streams not named are not touched, not by a single byte.  vapx_peek names
+ * buffers of the latest STEP: after a prefill the encoder buffers hold its last chunk.
+ * Refused in this version (VAPX_E_INVAL, vapx_last_error names the reason; validation happens before anything is enqueued, a refused call
+ * modifies nothing): an engine with an input rate, an input format or an input-class table (the resampler history would have to be
+ * advanced over a long block); a trunk leader or follower (the followers' windows and collect state would have to advance too);
+ * n > max_batch; frames < 1; an audio block that is not 16-byte aligned.  Ragged `frames` per stream: group equal lengths. */
+int vapx_prefill(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* audio, int32_t frames, int32_t flags,
+                 void* hip_stream);
+
 /* Stage-level entry points: the model-attribute surface process_vap calls (SURVEY.md §8b level 1).
  * All pointers are DEVICE memory, fp32, contiguous.  They use the handle's weights and scratch
  * but touch no stream state except vapx_encode_audio (LSTM h/c of the given stream ids). */

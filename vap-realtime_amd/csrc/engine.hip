@@ -349,18 +349,11 @@ GemmArgs gemm_args(const float* A, RowMap am, const float* W, int M, int N, int 
   return g;
 }
 
-// ---- the CPC encoder on B streams: frames -> e [B*2][256] -------------------------------------
-int run_encoder(vapx_engine* h, const Scratch& sc, const StateView& sv, int B, const int* ids_dev, const float* audio,
-                int spc, bool use_state_meta, hipStream_t st) {
+// ---- the CPC encoder between conv0 and the LSTM on B entries: h0 -> gx [B*2][ncpc][1024] (conv1 .. conv4, the LSTM input projection).
+// An entry is a stream of a step, or a (frame, stream) pair of vapx_prefill: nothing here knows the difference
+int run_conv_chain(vapx_engine* h, const Scratch& sc, int B, hipStream_t st) {
   const int* P = h->P;
   const Weights& w = h->wt;
-  Conv0Args c0;
-  c0.audio = audio; c0.ids = ids_dev; c0.carry = use_state_meta ? sv.carry : nullptr;
-  c0.h0 = sc.h0; c0.w = w.conv[0].w; c0.bias = w.conv[0].b; c0.gamma = w.conv[0].g; c0.beta = w.conv[0].beta;
-  c0.frames_seen = use_state_meta ? sv.frames_seen : nullptr; c0.bn = sc.bn; c0.bhead = sc.bhead;
-  c0.L = h->L; c0.spc = spc; c0.T = h->T;
-  { ProfScope ps(h, CLS_CONV0, st); HIPCHK(h, launch_conv0(c0, B, st)); }
-
   struct ConvSpec { const float* in; int Pin, guard_in, k, s; float* out; int Pout, guard_out; };
   const ConvSpec cs[3] = {   // conv1 .. conv3
       {sc.h0, P[0], 2, 8, 4, sc.h1, P[1], 1},
@@ -401,13 +394,34 @@ int run_encoder(vapx_engine* h, const Scratch& sc, const StateView& sv, int B, c
     g.W16 = w.lstm_wih16; g.bias = w.lstm_b;
     HIPCHK(h, gemm(h, g, EPI_STORE, st));
   }
-  LstmArgs la;
-  la.gx = sc.gx; la.ids = ids_dev; la.h_state = sv.h_state; la.c_state = sv.c_state;
-  la.wfrag = w.lstm_whh; la.out = sc.lstm_out; la.M = B * 2; la.ncpc = h->ncpc;
+  return VAPX_OK;
+}
+
+// the LSTM's arguments but its batch (M, ids, en): the weights and the buffers of `sc`
+void lstm_args(const vapx_engine* h, const Scratch& sc, const StateView& sv, LstmArgs& la) {
+  const Weights& w = h->wt;
+  la.gx = sc.gx; la.h_state = sv.h_state; la.c_state = sv.c_state;
+  la.wfrag = w.lstm_whh; la.out = sc.lstm_out; la.ncpc = h->ncpc;
   // downsample (single-output Conv1d == dense [ncpc*256 -> 256]) + LN + GELU fused into the LSTM kernel
   la.down_wf = w.down_wf; la.down_b = w.down_b; la.down_g = w.down_g; la.down_beta = w.down_beta;
   la.e = sc.e;
-  la.ln0_g = h->layer[0].ln_self_g; la.ln0_b = h->layer[0].ln_self_b; la.en = use_state_meta ? sc.en : nullptr;
+  la.ln0_g = h->layer[0].ln_self_g; la.ln0_b = h->layer[0].ln_self_b;
+}
+
+// ---- the CPC encoder on B streams: frames -> e [B*2][256] -------------------------------------
+int run_encoder(vapx_engine* h, const Scratch& sc, const StateView& sv, int B, const int* ids_dev, const float* audio,
+                int spc, bool use_state_meta, hipStream_t st) {
+  const Weights& w = h->wt;
+  Conv0Args c0;
+  c0.audio = audio; c0.ids = ids_dev; c0.carry = use_state_meta ? sv.carry : nullptr;
+  c0.h0 = sc.h0; c0.w = w.conv[0].w; c0.bias = w.conv[0].b; c0.gamma = w.conv[0].g; c0.beta = w.conv[0].beta;
+  c0.frames_seen = use_state_meta ? sv.frames_seen : nullptr; c0.bn = sc.bn; c0.bhead = sc.bhead;
+  c0.L = h->L; c0.spc = spc; c0.T = h->T;
+  { ProfScope ps(h, CLS_CONV0, st); HIPCHK(h, launch_conv0(c0, B, st)); }
+  { int rc = run_conv_chain(h, sc, B, st); if (rc) return rc; }
+  LstmArgs la;
+  lstm_args(h, sc, sv, la);
+  la.ids = ids_dev; la.M = B * 2; la.en = use_state_meta ? sc.en : nullptr;
   { ProfScope ps(h, CLS_LSTM, st); HIPCHK(h, launch_lstm(la, st)); }
   return VAPX_OK;
 }
@@ -1842,6 +1856,101 @@ int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, con
     }
   }
   if (on_host) HIPCHK(h, hipStreamSynchronize(st));
+  return VAPX_OK;
+}
+
+// Attach to a call in progress: the encoder half of `frames` steps in one call (vapx.h "Prefill").  Per chunk of floor(max_batch / n)
+// frames: conv0 over (frame, stream) pairs, the step's conv chain and gx GEMM on that virtual batch, ONE LSTM launch that walks the
+// chunk's frames, the layer-0 Q|K|V GEMM of every frame's row and one ring fill.  No transformer layer, no head, no output row.
+int vapx_prefill(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* audio, int32_t frames, int32_t flags, void* hip_stream) {
+  if (!h) return VAPX_E_INVAL;
+  const char* later = "in this version";
+  if (h->trunk || h->orphaned)
+    return fail(h, VAPX_E_INVAL, "vapx_prefill is refused on a trunk follower %s: it has no encoder, and its leader's prefill would have to advance "
+                "every follower's window and collect state too", later);
+  if (!h->followers.empty())
+    return fail(h, VAPX_E_INVAL, "vapx_prefill is refused on a trunk leader %s: its followers' windows and collect state would have to advance "
+                "over the same frames", later);
+  if (h->cls_table)
+    return fail(h, VAPX_E_INVAL, "vapx_prefill is refused on an engine with an input-class table %s: every class's resampler history would have to "
+                "be advanced over a long block", later);
+  if (h->in_hz())
+    return fail(h, VAPX_E_INVAL, "vapx_prefill is refused on an engine with an input rate (%d Hz) %s: the resampler history would have to be advanced "
+                "over a long block", h->in_hz(), later);
+  if (h->n_cls)
+    return fail(h, VAPX_E_INVAL, "vapx_prefill is refused on an engine with an input format %s: it takes 16 kHz fp32 samples", later);
+  if (n < 1) return fail(h, VAPX_E_RANGE, "vapx_prefill: n=%d outside [1,%d]", n, h->cfg.max_batch);
+  if (n > h->cfg.max_batch)
+    return fail(h, VAPX_E_INVAL, "vapx_prefill: n=%d exceeds max_batch=%d: a chunk holds at least one frame of every named stream", n, h->cfg.max_batch);
+  if (frames < 1) return fail(h, VAPX_E_INVAL, "vapx_prefill: frames=%d, at least one frame is needed", frames);
+  if (!audio) return fail(h, VAPX_E_INVAL, "vapx_prefill: null audio");
+  if ((uintptr_t)audio & 15) return fail(h, VAPX_E_INVAL, "vapx_prefill: the audio block must be 16-byte aligned");
+  if (flags & ~(VAPX_AUDIO_DEVICE | VAPX_IDS_DEVICE)) return fail(h, VAPX_E_INVAL, "vapx_prefill: unknown flag bits 0x%x", flags);
+  if (!stream_ids && n > h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "vapx_prefill: n exceeds max_streams");
+  const bool host_ids = stream_ids && !(flags & VAPX_IDS_DEVICE);
+  if (host_ids) { int rc = check_ids(h, n, stream_ids); if (rc) return rc; }   // before anything is enqueued
+  hipStream_t st = (hipStream_t)hip_stream;
+  (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  int rc = join_deferred(h, st);
+  if (rc) return rc;
+  if ((rc = flush_resets(h, st))) return rc;
+  const int* ids = stream_ids;
+  if (host_ids) { HIPCHK(h, h->ids.upload(stream_ids, n, st)); ids = h->ids.dev; }
+
+  const int hop = h->hop, T = h->T, Fc = prefill_chunk_frames(h->cfg.max_batch, n);
+  const bool on_dev = (flags & VAPX_AUDIO_DEVICE) != 0, direct = !on_dev && is_pinned_host(audio);
+  const size_t row = (size_t)frames * hop;   // floats of one (stream, channel) row of the caller's block
+  const Scratch& sc = h->sc;
+  const StateView sv{h->ring, h->ring_qkv, h->h_state, h->c_state, h->carry, h->frames_seen};
+  const Weights& w = h->wt;
+  for (int f0 = 0; f0 < frames; f0 += Fc) {
+    const int fc = std::min(Fc, frames - f0), V = n * fc;
+    // the chunk's samples: a device block is read where it lies; host audio travels as [n * 2] rows of [320 | fc * hop] through the
+    // step's own staging ([max_batch][2][hop + 320] holds it: n * fc <= max_batch), every row with the 320 samples in front of it -
+    // but a call's first chunk, whose prefix is the carry
+    const float* src = audio + (size_t)f0 * hop;
+    size_t stride = row;
+    if (!on_dev) {
+      const size_t wrow = VAPX_PAD + (size_t)fc * hop, pre = f0 ? VAPX_PAD : 0, wcopy = pre + (size_t)fc * hop;
+      if (direct) {
+        HIPCHK(h, hipMemcpy2DAsync(h->audio.dev + (VAPX_PAD - pre), wrow * sizeof(float), src - pre, row * sizeof(float), wcopy * sizeof(float),
+                                   (size_t)n * 2, hipMemcpyHostToDevice, st));
+      } else {
+        HIPCHK(h, hipEventSynchronize(h->audio.evt));   // the previous chunk has left the pinned block
+        for (size_t r = 0; r < (size_t)n * 2; ++r)
+          memcpy(h->audio.pin + r * wrow + (VAPX_PAD - pre), src - pre + r * row, wcopy * sizeof(float));
+        if (!pre)   // the unused prefix slots: defined bytes for the copy
+          for (size_t r = 0; r < (size_t)n * 2; ++r) memset(h->audio.pin + r * wrow, 0, VAPX_PAD * sizeof(float));
+        HIPCHK(h, hipMemcpyAsync(h->audio.dev, h->audio.pin, (size_t)n * 2 * wrow * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipEventRecord(h->audio.evt, st));
+      }
+      src = h->audio.dev + VAPX_PAD;
+      stride = wrow;
+    }
+    Conv0PrefillArgs c0;
+    c0.audio = src; c0.row_stride = (long)stride; c0.ids = ids; c0.carry = sv.carry; c0.prefix_in_audio = f0 ? 1 : 0;
+    c0.h0 = sc.h0; c0.w = w.conv[0].w; c0.bias = w.conv[0].b; c0.gamma = w.conv[0].g; c0.beta = w.conv[0].beta;
+    c0.frames_seen = sv.frames_seen; c0.bhead = f0 ? nullptr : sc.bhead; c0.L = h->L; c0.n = n; c0.T = T;
+    { ProfScope ps(h, CLS_CONV0, st); HIPCHK(h, launch_conv0_prefill(c0, V, st)); }
+    if ((rc = run_conv_chain(h, sc, V, st))) return rc;
+    LstmPrefillArgs la;
+    lstm_args(h, sc, sv, la);
+    la.ids = ids; la.M = n * 2; la.en = sc.en; la.frames = fc;
+    { ProfScope ps(h, CLS_LSTM, st); HIPCHK(h, launch_lstm_prefill(la, st)); }
+    if ((long)f0 + fc + T <= frames) continue;   // every frame of this chunk is overwritten by a later one: the LSTM alone had to see it
+    {  // layer-0 Q|K|V of every frame's row, as the step makes qkv_new
+      GemmArgs g = gemm_args(sc.en, contiguous_rows(256), h->layer[0].wqkv, V * 2, 768, 256, sc.qkv_new, contiguous_rows(768));
+      g.W16 = w.l0_wqkv16;
+      HIPCHK(h, gemm(h, g, EPI_STORE, st));
+    }
+    PrefillFillArgs fa;
+    fa.ring = sv.ring; fa.ring_qkv = sv.ring_qkv; fa.e = sc.e; fa.qkv_new = sc.qkv_new; fa.ids = ids; fa.bhead = sc.bhead;
+    fa.n = n; fa.T = T; fa.fc = fc; fa.f0 = f0; fa.frames = frames;
+    fa.frames_seen = sv.frames_seen; fa.carry = sv.carry; fa.tail = src + (size_t)fc * hop - VAPX_PAD; fa.row_stride = (long)stride;
+    { ProfScope ps(h, CLS_GATHER, st); HIPCHK(h, launch_prefill_fill(fa, st)); }
+  }
+  if (!on_dev) HIPCHK(h, hipStreamSynchronize(st));   // the caller's block (and the engine's staging) is free again on return
   return VAPX_OK;
 }
 

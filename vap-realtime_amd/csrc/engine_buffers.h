@@ -32,6 +32,14 @@ inline Geometry geometry(int hz, int T = 0) {
   return g;
 }
 
+// vapx_prefill: frames of n streams that one pass through the step's scratch holds.  Every encoder buffer is sized for max_batch entries and
+// a (stream, frame) pair is an entry, so floor(max_batch / n) frames fit; n > max_batch / 2 leaves one frame per pass
+// (engine.prefill_chunks in ../engine.py restates the plan for the host-side tests)
+inline int prefill_chunk_frames(int max_batch, int n) {
+  const int fc = n > 0 ? max_batch / n : 0;
+  return fc < 1 ? 1 : fc;
+}
+
 struct Scratch {
   float* out_dev = nullptr;   // [B][VAPX_OUT_STRIDE] the step's output rows before they leave (or the caller's device block instead)
   int *bn = nullptr, *bhead = nullptr, *rot = nullptr;

@@ -35,6 +35,44 @@ struct LstmArgs {
   int M, ncpc;
 };
 
+// vapx_prefill: the encoder over a CONTIGUOUS block of audio, frames_in_chunk frames of n streams per pass.  The passes' virtual batch is
+// frame-major: entry v = j * n + k is frame j (of the chunk) of batch slot k, so a frame's rows of every per-entry buffer (h0 .. gx, e, en,
+// qkv_new) are one contiguous [n * 2] block and the LSTM walks the frames by advancing its pointers.
+struct Conv0PrefillArgs {
+  const float* audio;   // row (k, c) = audio + (k * 2 + c) * row_stride: the chunk's new samples, frame j at + j * hop; 16-byte aligned
+  long row_stride;      // floats, a multiple of 4
+  const int* ids;       // [n] stream ids (device) or null = identity
+  const float* carry;   // [S][2][320]: what precedes frame 0 of the chunk unless prefix_in_audio
+  int prefix_in_audio;  // the 320 samples in front of every row are in the block itself (every chunk but a call's first)
+  float* h0;            // [V*2][P0+4][256] as Conv0Args
+  const float* w;
+  const float* bias;
+  const float* gamma;
+  const float* beta;
+  const int* frames_seen;   // [S]; with bhead (a call's first chunk): bhead[k] = frames_seen % T, the ring slot of the call's first frame
+  int* bhead;           // [n] or null
+  int L, n, T;
+};
+
+struct LstmPrefillArgs : LstmArgs {   // M = n * 2 rows; gx, e and en hold `frames` blocks of M rows each; `out` is not written
+  int frames;
+};
+
+struct PrefillFillArgs {   // ring fill of a chunk: frame g = f0 + j of the call goes to ring slot (bhead + g) % T
+  float* ring;             // [S*2][T][256]
+  float* ring_qkv;         // [S*2][T][768]
+  const float* e;          // [fc][n*2][256]
+  const float* qkv_new;    // [fc][n*2][768]
+  const int* ids;
+  const int* bhead;        // [n] ring slot of the call's first frame (Conv0PrefillArgs)
+  int n, T, fc, f0, frames;   // a frame with g + T < frames is skipped: a later frame of the call owns its slot
+  // the waves of the call's last frame (g == frames - 1, always in the last chunk) also finish the call:
+  int* frames_seen;        // [S] += frames
+  float* carry;            // [S][2][320] <- the last 320 samples of each row
+  const float* tail;       // row (k, c)'s last 320 samples at tail + (k * 2 + c) * row_stride; 16-byte aligned
+  long row_stride;
+};
+
 struct GatherArgs {
   float* ring;          // [S*2][T][256] or null (then xin is used)
   float* ring_qkv;      // [S*2][T][768] cached layer-0 Q|K|V per ring row, or null
@@ -182,6 +220,9 @@ hipError_t launch_state_cache_scatter(const float* qkv, const int* ids, int id0,
 hipError_t launch_conv0(const Conv0Args& a, int B, hipStream_t st);
 hipError_t launch_lstm(const LstmArgs& a, hipStream_t st);
 hipError_t launch_ring_append(const GatherArgs& a, hipStream_t st);
+hipError_t launch_conv0_prefill(const Conv0PrefillArgs& a, int V, hipStream_t st);   // V = n * frames_in_chunk virtual entries
+hipError_t launch_lstm_prefill(const LstmPrefillArgs& a, hipStream_t st);
+hipError_t launch_prefill_fill(const PrefillFillArgs& a, hipStream_t st);
 hipError_t launch_gather_ln(const GatherArgs& a, hipStream_t st);
 hipError_t launch_attention(const AttnArgs& a, int B, hipStream_t st, bool force_xl);   // force_xl: attention_xl_kernel for any T (tests)
 hipError_t launch_attention_f16x3(const AttnArgs& a, int B, hipStream_t st);   // split-precision variant (attention_f16x3.hip), same arguments

@@ -13,6 +13,37 @@ namespace {
 //    K = 10 is too thin for MFMA: one wave computes one output position (256 channels, 4 per lane)
 //    with the 40 taps*channels weights held in registers; the channel reduction is a wave butterfly.
 // ------------------------------------------------------------------------------------------------
+// the P0 output positions of one assembled frame xs[L] -> outb[P0][256] (one wave per position)
+__device__ __forceinline__ void conv0_positions(const float* xs, int L, const float* __restrict__ cw, const float* __restrict__ cbias,
+                                                const float* __restrict__ cgamma, const float* __restrict__ cbeta, float* outb, int lane, int wave) {
+  const int ch = lane * 4;
+  f32x4 w[10];
+#pragma unroll
+  for (int t = 0; t < 10; ++t) w[t] = *(const f32x4*)(cw + t * 256 + ch);
+  const f32x4 bias = *(const f32x4*)(cbias + ch);
+  const f32x4 gam = *(const f32x4*)(cgamma + ch);
+  const f32x4 bet = *(const f32x4*)(cbeta + ch);
+  const int P0 = L / 5;
+  for (int p = wave; p < P0; p += 4) {
+    f32x4 v = bias;
+    const int x0 = p * 5 - 3;
+#pragma unroll
+    for (int t = 0; t < 10; ++t) {
+      int xi = x0 + t;
+      float xv = (xi >= 0 && xi < L) ? xs[xi] : 0.f;
+      v += w[t] * xv;
+    }
+    float s = wave_sum(v[0] + v[1] + v[2] + v[3]);
+    float mean = s * (1.0f / 256.0f);
+    f32x4 d = v - mean;
+    float ss = wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]);
+    float rstd = rsqrtf(ss * (1.0f / 255.0f) + 1e-5f);
+    f32x4 y = d * rstd * gam + bet;
+    y[0] = relu_nanprop(y[0]); y[1] = relu_nanprop(y[1]); y[2] = relu_nanprop(y[2]); y[3] = relu_nanprop(y[3]);
+    *(f32x4*)(outb + (long)p * 256 + ch) = y;
+  }
+}
+
 __global__ __launch_bounds__(256) void conv0_kernel(Conv0Args a) {
   extern __shared__ __attribute__((aligned(16))) float xs[];  // [L]
   const int bc = blockIdx.x, b = bc >> 1, c = bc & 1;
@@ -37,33 +68,26 @@ __global__ __launch_bounds__(256) void conv0_kernel(Conv0Args a) {
     a.bhead[b] = fs % a.T;
   }
 
-  const int ch = lane * 4;
-  f32x4 w[10];
-#pragma unroll
-  for (int t = 0; t < 10; ++t) w[t] = *(const f32x4*)(a.w + t * 256 + ch);
-  const f32x4 bias = *(const f32x4*)(a.bias + ch);
-  const f32x4 gam = *(const f32x4*)(a.gamma + ch);
-  const f32x4 bet = *(const f32x4*)(a.beta + ch);
-  const int P0 = L / 5;
-  float* outb = a.h0 + (long)bc * (P0 + 4) * 256 + 2 * 256;
-  for (int p = wave; p < P0; p += 4) {
-    f32x4 v = bias;
-    const int x0 = p * 5 - 3;
-#pragma unroll
-    for (int t = 0; t < 10; ++t) {
-      int xi = x0 + t;
-      float xv = (xi >= 0 && xi < L) ? xs[xi] : 0.f;
-      v += w[t] * xv;
-    }
-    float s = wave_sum(v[0] + v[1] + v[2] + v[3]);
-    float mean = s * (1.0f / 256.0f);
-    f32x4 d = v - mean;
-    float ss = wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]);
-    float rstd = rsqrtf(ss * (1.0f / 255.0f) + 1e-5f);
-    f32x4 y = d * rstd * gam + bet;
-    y[0] = relu_nanprop(y[0]); y[1] = relu_nanprop(y[1]); y[2] = relu_nanprop(y[2]); y[3] = relu_nanprop(y[3]);
-    *(f32x4*)(outb + (long)p * 256 + ch) = y;
-  }
+  conv0_positions(xs, L, a.w, a.bias, a.gamma, a.beta, a.h0 + (long)bc * (L / 5 + 4) * 256 + 2 * 256, lane, wave);
+}
+
+// vapx_prefill: the same conv0 over (frame, stream) pairs cut from a contiguous block.  Frame j of a row starts hop * j samples in and is
+// prefixed by the 320 samples in front of it - the block's own, or for the call's very first frame the stream's carry.  Nothing is written
+// but h0 and, by a call's first chunk, the ring slot of the call's first frame (bhead, as the step's conv0 publishes it): the carry and the
+// frame counter move once, in the ring fill of the call's last chunk - no launch both reads and writes either.
+__global__ __launch_bounds__(256) void conv0_kernel(Conv0PrefillArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // [L]
+  const int vc = blockIdx.x, v = vc >> 1, c = vc & 1, j = v / a.n, k = v - j * a.n;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int L = a.L, hop = L - VAPX_PAD;
+  const float* row = a.audio + ((long)k * 2 + c) * a.row_stride + (long)j * hop;
+  const float* pre = row - VAPX_PAD;
+  if (j == 0 && !a.prefix_in_audio) pre = a.carry + ((long)(a.ids ? a.ids[k] : k) * 2 + c) * VAPX_PAD;
+  for (int i = tid; i < VAPX_PAD / 4; i += 256) ((f32x4*)xs)[i] = ((const f32x4*)pre)[i];
+  for (int i = tid; i < hop / 4; i += 256) ((f32x4*)(xs + VAPX_PAD))[i] = ((const f32x4*)row)[i];
+  if (a.bhead && j == 0 && c == 0 && tid == 0) a.bhead[k] = a.frames_seen[a.ids ? a.ids[k] : k] % a.T;
+  __syncthreads();
+  conv0_positions(xs, L, a.w, a.bias, a.gamma, a.beta, a.h0 + (long)vc * (L / 5 + 4) * 256 + 2 * 256, lane, wave);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -83,7 +107,14 @@ __global__ __launch_bounds__(256) void conv0_kernel(Conv0Args a) {
 constexpr int H_LD = 260;  // 256 + 4 pad floats
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
-__global__ __launch_bounds__(512) void lstm_kernel(LstmArgs a) {
+// One source for the step (kPrefill = false: lstm_kernel, the code it always was) and for vapx_prefill (kPrefill = true): the same cell
+// step walks a.frames frames in one launch - h stays in LDS and c in registers across the frame boundaries, both register rings wrap
+// into the next frame as they wrap between steps, and the downsample + LN + GELU (+ LN0) epilogue runs once per frame on that frame's
+// block of e / en.  State is written once, after the last frame.  The arguments travel by value and the frame loop is a do-while
+// whose condition the step folds away: with a reference or a counted loop the step's instantiation came out with other SGPR and
+// instruction counts than the kernel it replaces (now 216 VGPRs, 56 SGPRs, 2 104 instructions, as before; profiles/prefill/README.md).
+template <bool kPrefill, typename Args>
+__device__ __forceinline__ void lstm_body(const Args a) {
   __shared__ __attribute__((aligned(16))) float hbuf[16 * H_LD];
   __shared__ float red[8 * 16];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -128,7 +159,7 @@ __global__ __launch_bounds__(512) void lstm_kernel(LstmArgs a) {
   f32x4v dacc[2] = {f32x4v{0.f, 0.f, 0.f, 0.f}, f32x4v{0.f, 0.f, 0.f, 0.f}};
   auto down_step = [&](int t) {   // dacc += h_t (in hbuf) . Wd_t^T for this wave's 32 output columns
     const f32x4* d = df + (long)t * 8 * 16 * 2 * 64;
-    const f32x4* dn = df + (long)(t + 1 < a.ncpc ? t + 1 : t) * 8 * 16 * 2 * 64;
+    const f32x4* dn = df + (long)(t + 1 < a.ncpc ? t + 1 : (kPrefill ? 0 : t)) * 8 * 16 * 2 * 64;   // prefill: on into the next frame's step 0
 #pragma unroll 1
     for (int kp = 0; kp < 8; ++kp) {
 #pragma unroll
@@ -147,6 +178,13 @@ __global__ __launch_bounds__(512) void lstm_kernel(LstmArgs a) {
       }
     }
   };
+  int n_frames = 1;
+  if constexpr (kPrefill) n_frames = a.frames;
+  const float* gxf = a.gx;   // this frame's blocks of gx / e / en
+  float *ef = a.e, *enf = a.en;
+  int f = 0;
+  do {   // frames: one pass in the step, whose loop condition is a constant false
+  if constexpr (kPrefill) dacc[0] = dacc[1] = f32x4v{0.f, 0.f, 0.f, 0.f};
   for (int t = 0; t < a.ncpc; ++t) {
     // this step's input projection (issued early: in flight under the MFMAs)
     float gxr[4][8];
@@ -154,7 +192,7 @@ __global__ __launch_bounds__(512) void lstm_kernel(LstmArgs a) {
     for (int reg = 0; reg < 4; ++reg) {
       int m = m0 + kq * 4 + reg;
       m = m < a.M ? m : a.M - 1;
-      const float* gx = a.gx + ((long)m * a.ncpc + t) * 1024 + w * 128 + l15;
+      const float* gx = gxf + ((long)m * a.ncpc + t) * 1024 + w * 128 + l15;
 #pragma unroll
       for (int c8 = 0; c8 < 8; ++c8) gxr[reg][c8] = gx[c8 * 16];
     }
@@ -197,11 +235,12 @@ __global__ __launch_bounds__(512) void lstm_kernel(LstmArgs a) {
         float hn = og * fast_tanh(cn);
         const int j = w * 32 + q * 16 + l15;
         hbuf[row * H_LD + j] = hn;
-        if (live) a.out[((long)m * a.ncpc + t) * 256 + j] = hn;
+        if (!kPrefill && live) a.out[((long)m * a.ncpc + t) * 256 + j] = hn;
       }
     }
   }
   __syncthreads();
+  if (!kPrefill || f + 1 == n_frames) {
 #pragma unroll
   for (int reg = 0; reg < 4; ++reg) {
     const int row = kq * 4 + reg;
@@ -213,6 +252,7 @@ __global__ __launch_bounds__(512) void lstm_kernel(LstmArgs a) {
         a.h_state[srow[reg] * 256 + j] = hbuf[row * H_LD + j];
       }
     }
+  }
   }
   if (!a.down_wf) return;
   // ---- downsample epilogue: + bias, LayerNorm over 256 outputs (8 waves), exact GELU -> e ----
@@ -265,8 +305,8 @@ __global__ __launch_bounds__(512) void lstm_kernel(LstmArgs a) {
     ev[0][reg] = gelu_erf((dacc[0][reg] - mean[reg]) * rstd * g0 + be0);
     ev[1][reg] = gelu_erf((dacc[1][reg] - mean[reg]) * rstd * g1 + be1);
     if (m < a.M) {
-      a.e[(long)m * 256 + oc] = ev[0][reg];
-      a.e[(long)m * 256 + oc + 16] = ev[1][reg];
+      ef[(long)m * 256 + oc] = ev[0][reg];
+      ef[(long)m * 256 + oc + 16] = ev[1][reg];
     }
   }
   if (!a.en) return;
@@ -309,11 +349,20 @@ __global__ __launch_bounds__(512) void lstm_kernel(LstmArgs a) {
     const float rstd = rsqrtf(sv[reg] * (1.0f / 256.0f) + 1e-5f);
     const int m = m0 + kq * 4 + reg;
     if (m < a.M) {
-      a.en[(long)m * 256 + oc] = (ev[0][reg] - sm[reg]) * rstd * lg0 + lb0;
-      a.en[(long)m * 256 + oc + 16] = (ev[1][reg] - sm[reg]) * rstd * lg1 + lb1;
+      enf[(long)m * 256 + oc] = (ev[0][reg] - sm[reg]) * rstd * lg0 + lb0;
+      enf[(long)m * 256 + oc + 16] = (ev[1][reg] - sm[reg]) * rstd * lg1 + lb1;
     }
   }
+  if constexpr (kPrefill) {
+    gxf += (long)a.M * a.ncpc * 1024;
+    ef += (long)a.M * 256;
+    enf += (long)a.M * 256;
+  }
+  } while (kPrefill && ++f < n_frames);
 }
+
+__global__ __launch_bounds__(512) void lstm_kernel(LstmArgs a) { lstm_body<false>(a); }
+__global__ __launch_bounds__(512) void lstm_kernel(LstmPrefillArgs a) { lstm_body<true>(a); }
 
 // ------------------------------------------------------------------------------------------------
 // 3. context-ring append + chronological gather + LayerNorm(ln_self of layer 0)
@@ -341,6 +390,36 @@ __global__ __launch_bounds__(256) void ring_append_kernel(GatherArgs a) {
     int rot = head + 1 - n;           // slot of the oldest row
     a.rot[b] = rot < 0 ? rot + a.T : rot;
   }
+}
+
+// vapx_prefill: a chunk's embeddings and layer-0 Q|K|V rows into their ring slots, one wave per (frame, stream, channel) row, 16 bytes per
+// lane and access.  Frame g of the call goes to slot (bhead + g) % T, bhead being the slot of the call's first frame (conv0 of the first
+// chunk).  Within a call the slots of the written frames are distinct (a frame that a later one overwrites is skipped, here or as a
+// whole chunk on the host), so no two waves of a launch meet.  The waves of the call's last frame also move the carry (the block's last
+// 320 samples) and the frame counter, which no other wave of this launch reads.
+__global__ __launch_bounds__(256) void ring_append_kernel(PrefillFillArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= a.fc * a.n * 2) return;
+  const int c = r & 1, v = r >> 1;
+  const int j = v / a.n, k = v - j * a.n;
+  const int g = a.f0 + j;
+  if ((long)g + a.T < a.frames) return;
+  const int sid = a.ids ? a.ids[k] : k;
+  const int slot = (int)(((long)a.bhead[k] + g) % a.T);
+  float* rb = a.ring + (((long)sid * 2 + c) * a.T + slot) * 256 + lane * 4;
+  float* qs = a.ring_qkv + (((long)sid * 2 + c) * a.T + slot) * 768 + lane * 4;
+  *(f32x4*)rb = *(const f32x4*)(a.e + (long)r * 256 + lane * 4);
+  const float* qn = a.qkv_new + (long)r * 768 + lane * 4;
+  *(f32x4*)(qs) = *(const f32x4*)(qn);
+  *(f32x4*)(qs + 256) = *(const f32x4*)(qn + 256);
+  *(f32x4*)(qs + 512) = *(const f32x4*)(qn + 512);
+  if (g + 1 != a.frames) return;
+  const f32x4* src = (const f32x4*)(a.tail + ((long)k * 2 + c) * a.row_stride);
+  f32x4* dst = (f32x4*)(a.carry + ((long)sid * 2 + c) * VAPX_PAD);
+  dst[lane] = src[lane];
+  if (lane < VAPX_PAD / 4 - 64) dst[64 + lane] = src[64 + lane];
+  if (c == 0 && lane == 0) a.frames_seen[sid] += a.frames;
 }
 
 __global__ __launch_bounds__(256) void gather_ln_kernel(GatherArgs a) {
@@ -1113,6 +1192,18 @@ hipError_t launch_conv0(const Conv0Args& a, int B, hipStream_t st) {
 }
 hipError_t launch_lstm(const LstmArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(lstm_kernel, dim3((a.M + 15) / 16), dim3(512), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_conv0_prefill(const Conv0PrefillArgs& a, int V, hipStream_t st) {
+  hipLaunchKernelGGL(conv0_kernel, dim3(V * 2), dim3(256), a.L * sizeof(float), st, a);
+  return hipGetLastError();
+}
+hipError_t launch_lstm_prefill(const LstmPrefillArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(lstm_kernel, dim3((a.M + 15) / 16), dim3(512), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_prefill_fill(const PrefillFillArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(ring_append_kernel, dim3((a.fc * a.n * 2 + 3) / 4), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 hipError_t launch_ring_append(const GatherArgs& a, hipStream_t st) {

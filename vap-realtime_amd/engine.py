@@ -47,7 +47,8 @@ EXPORTS = ("vapx_abi_version", "vapx_blob_floats", "vapx_create", "vapx_destroy"
            "vapx_set_input_classes", "vapx_get_input_classes", "vapx_set_stream_class", "vapx_get_stream_class", "vapx_input_slot_bytes",
            "vapx_ingest_class_ports", "vapx_ingest_stream_class",
            "vapx_set_stream_channel_classes", "vapx_get_stream_channel_classes", "vapx_input_row_bytes",
-           "vapx_ingest_pair_ports", "vapx_ingest_stream_channel_classes")
+           "vapx_ingest_pair_ports", "vapx_ingest_stream_channel_classes",
+           "vapx_prefill")
 MAX_INPUT_CLASSES = 16
 PROF_CLASSES = {0: "gemm_store", 1: "gemm_gelu", 2: "gemm_resid", 3: "gemm_resid_ln", 4: "gemm_cn_relu",
                 5: "conv_tail", 6: "ffn_block", 7: "last_row", 8: "conv0", 9: "lstm", 10: "gather_ln", 11: "attention", 12: "head",
@@ -212,6 +213,9 @@ def load_library(path: Optional[str] = None):
     lib.vapx_export_streams.argtypes = [vp, i32, i32p, f32p, i32, vp]
     lib.vapx_import_streams.restype = i32
     lib.vapx_import_streams.argtypes = [vp, i32, i32p, f32p, i32, vp]
+    if hasattr(lib, "vapx_prefill"):   # absent from an older build named by VAPX_LIBRARY for an A/B run (tools/ab_lib.sh); build() checks EXPORTS
+        lib.vapx_prefill.restype = i32
+        lib.vapx_prefill.argtypes = [vp, i32, i32p, f32p, i32, i32, vp]
     lib.vapx_set_input_rate.restype = i32
     lib.vapx_set_input_rate.argtypes = [vp, i32]
     lib.vapx_get_input_rate.restype = i32
@@ -578,6 +582,53 @@ class Engine:
             self._check(rc, "vapx_step")
         return out.reshape(-1, OUT_STRIDE)[:n]
 
+    # -- attach to a call in progress ------------------------------------------------------------------
+    def _prefill_shape(self, shape, dtype_ok: bool, n_ids: Optional[int]) -> tuple:
+        """(n, frames) of a prefill block of ``shape``; raises before any library call."""
+        if not dtype_ok:
+            raise TypeError("prefill takes float32 samples (16 kHz new samples as the step takes them)")
+        if len(shape) != 3 or shape[1] != 2:
+            raise ValueError(f"prefill audio must be [n, 2, frames * hop], got shape {tuple(shape)}")
+        n, _, samples = (int(x) for x in shape)
+        if n < 1 or samples < self.hop or samples % self.hop:
+            raise ValueError(f"prefill audio {tuple(shape)}: n >= 1 and a whole number (>= 1) of {self.hop}-sample frames per channel are needed")
+        if n_ids is not None and n_ids != n:
+            raise ValueError(f"{n_ids} stream ids for {n} audio rows")
+        return n, samples // self.hop
+
+    def prefill(self, audio, stream_ids: Optional[Sequence[int]] = None):
+        """Attach to a call in progress (vapx.h, vapx_prefill): ``audio`` float32 [n, 2, frames * hop], the streams' buffered 16 kHz
+        history, as a numpy array (host: page-locked ``pinned_empty`` blocks are copied from directly, others staged in bounded blocks)
+        or a torch CUDA tensor (read where it lies, enqueued on the current torch stream, no synchronisation).  Afterwards the streams'
+        LSTM, carry, context window and layer-0 Q|K|V cache are what ``frames`` calls of ``step`` would have left; no output rows are
+        made and no transformer layer runs.  ``stream_ids``: as in ``step`` (None: slots 0 .. n-1).  Returns the number of frames."""
+        ids = None if stream_ids is None else np.ascontiguousarray(stream_ids, dtype=np.int32).reshape(-1)
+        n_ids = None if ids is None else int(ids.size)
+        if hasattr(audio, "data_ptr") and hasattr(audio, "is_cuda"):          # a torch tensor
+            import torch
+            n, frames = self._prefill_shape(tuple(audio.shape), audio.dtype == torch.float32, n_ids)
+            if audio.is_cuda:
+                if not audio.is_contiguous():
+                    raise ValueError("a device prefill block must be contiguous")
+                stream = torch.cuda.current_stream(audio.device).cuda_stream or None
+                self._check(self.lib.vapx_prefill(self._h, n, _np_ptr(ids), audio.data_ptr(), frames, AUDIO_DEVICE, stream), "vapx_prefill")
+                return frames
+            audio = audio.detach().numpy()
+        audio = np.asarray(audio)
+        n, frames = self._prefill_shape(audio.shape, audio.dtype == np.float32, n_ids)
+        audio = np.ascontiguousarray(audio)
+        if audio.ctypes.data % 16:                                            # the block must be 16-byte aligned (vapx.h)
+            block = aligned_bytes(audio.nbytes).view(np.float32).reshape(audio.shape)
+            block[...] = audio
+            audio = block
+        self._check(self.lib.vapx_prefill(self._h, n, _np_ptr(ids), _np_ptr(audio), frames, 0, None), "vapx_prefill")
+        return frames
+
+    def prefill_device(self, n: int, audio_ptr: int, frames: int, ids_ptr: int = 0, stream: int = 0):
+        """Device twin of ``prefill``: raw device pointers, enqueued on ``stream``, no synchronisation."""
+        flags = AUDIO_DEVICE | (IDS_DEVICE if ids_ptr else 0)
+        self._check(self.lib.vapx_prefill(self._h, n, ids_ptr or None, audio_ptr, frames, flags, stream or None), "vapx_prefill")
+
     def bad_slots(self) -> list:
         """Batch slots of the latest host-path step whose results were not finite."""
         n = self.lib.vapx_bad_slots(self._h, None, 0)
@@ -903,6 +954,16 @@ class TrunkGroup:
     def close(self):
         for m in reversed(self.order):                     # followers before their leader
             self.engines[m].close()
+
+
+def prefill_chunks(max_batch: int, n: int, frames: int, ctx_frames: int) -> list:
+    """The plan of one ``vapx_prefill`` call, as the engine walks it (csrc/engine_buffers.h prefill_chunk_frames): a list of
+    (first frame, frames in the chunk, fills the ring).  A chunk holds floor(max_batch / n) frames, at least one; a chunk all of whose
+    frames a later frame of the call overwrites (frames > ctx_frames) runs the encoder alone."""
+    if not 1 <= n <= max_batch or frames < 1 or ctx_frames < 1:
+        raise ValueError("prefill_chunks: 1 <= n <= max_batch, frames >= 1 and ctx_frames >= 1 are needed")
+    fc = max(1, max_batch // n)
+    return [(f0, min(fc, frames - f0), f0 + min(fc, frames - f0) + ctx_frames > frames) for f0 in range(0, frames, fc)]
 
 
 def split_outputs(out: np.ndarray) -> dict:

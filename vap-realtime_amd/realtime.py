@@ -210,6 +210,12 @@ class ManyStreamVAP:
             res["p_bc"] = [res["logits"][k, :int(res["n"][k])] for k in range(len(res["n"]))]
         return res
 
+    def prefill(self, history, stream_ids: Optional[Sequence[int]] = None) -> int:
+        """Attach to calls in progress: ``history`` float32 [n,2,frames*hop], each stream's buffered 16 kHz audio (numpy, or a torch CUDA
+        tensor), goes through the encoder in one call - LSTM, carry and the whole context window, no transformer pass, no results
+        (``Engine.prefill``).  ``process`` then continues as if those frames had been processed.  Returns the number of frames."""
+        return self.engine.prefill(history, stream_ids)
+
     def reset(self, stream_id: int):
         self.engine.reset_stream(stream_id)
 
