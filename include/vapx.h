@@ -468,14 +468,18 @@ int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, con
  *   - the layer-0 Q|K|V cache rows of the written slots are made as the step makes them: LN0 of the embedding (inside the LSTM kernel),
  *     then the engine's own GEMM dispatch on Wqkv - on a VAPX_FLAG_SPLIT_F16 engine the split product, like a step's;
  *   - the next vapx_step continues as if the frames had been stepped.  The arithmetic is the step's; a GEMM over another number of rows
- *     may pick another tile, so the state agrees with the stepped one to rounding (tests/test_prefill_gpu.py holds it against float64 at
- *     twice the stepped engine's own error), not bit for bit.
+ *     may pick another tile, so the state agrees with the stepped one to rounding, not bit for bit: tests/test_prefill_gpu.py holds small
+ *     chunks (every GEMM in the 32-row tile) against float64 at twice the stepped engine's own error, tests/test_prefill_classes_gpu.py
+ *     holds chunks of hundreds to 1840 entries (64- and 128-row tiles, the GEMM chain, chunks longer than the window, 50 / 20 / 10 / 5 Hz)
+ *     against float64 at the encoder-stage bound.
  * Ordering: as vapx_export_streams.  The call makes hip_stream wait for overlap groups a VAPX_DEFER_JOIN step left running, applies queued
  * vapx_reset_stream / vapx_reset_carry requests, then enqueues on hip_stream; no device-wide synchronisation.  Device audio is read where it
  * lies: no copy, no synchronisation at all.  Host audio travels chunk by chunk through the step's own audio staging (one strided copy per
  * chunk from vapx_host_alloc memory; pageable memory through the pinned block, one event wait per chunk) - never a second full-size pinned
- * copy - and the call synchronises hip_stream ONCE, at its end.  Streams not named are not touched, not by a single byte.  vapx_peek names
- * buffers of the latest STEP: after a prefill the encoder buffers hold its last chunk.
+ * copy - and the call synchronises hip_stream ONCE, at its end.  Streams not named are not touched, not by a single byte.  vapx_peek after
+ * a prefill names the buffers of its LAST CHUNK until the next step: "h0", "h1", "z", "e" - and "h2", "h3" unless that chunk ran the fused
+ * conv tail - as [V * 2] blocks of V = n * frames_in_chunk entries, frame-major (entry v = j * n + k is frame j of the chunk and stream k of
+ * the call); "lstm_out" (the prefill's LSTM launch does not write it) and every transformer buffer are refused (VAPX_E_INVAL).
  * Refused in this version (VAPX_E_INVAL, vapx_last_error names the reason; validation happens before anything is enqueued, a refused call
  * modifies nothing): an engine with an input rate, an input format or an input-class table (the resampler history would have to be
  * advanced over a long block); a trunk leader or follower (the followers' windows and collect state would have to advance too);
@@ -529,7 +533,8 @@ int vapx_aggregate(int64_t rows, const float* probs, int32_t from_bin, int32_t t
  * name: "h0".."h3","z","lstm_out","e","x0","o","stereo0".."stereo2","last","comb"; returns the number of
  * floats written (<= max_floats) or a negative error.  "h2"/"h3" are refused when any overlap group of that step ran the
  * fused conv tail (VAPX_FLAG_UNFUSED_CONV always materialises them), "stereo2" needs VAPX_FLAG_FULL_LAST_LAYER, and a trunk
- * follower refuses the encoder buffers it released (peek its leader).
+ * follower refuses the encoder buffers it released (peek its leader).  After a vapx_prefill and until the next step the encoder buffers are
+ * those of the prefill's last chunk and everything else is refused ("Prefill" above).
  * "last": [n*2][256], the last layer's output for the newest row of every (stream, channel), where that layer runs on the newest
  * row alone (the default fused block and VAPX_FLAG_UNFUSED_LAST_ROW; one peek spans the overlap groups); with
  * VAPX_FLAG_FULL_LAST_LAYER or in nod mode it is refused: take row n - 1 of "stereo2".
@@ -547,6 +552,10 @@ int64_t vapx_peek(vapx_handle h, const char* name, float* dst, size_t max_floats
 int vapx_gemm(void* hip_stream, int32_t M, int32_t N, int32_t K, const float* A, const float* W, float* C,
               int32_t epi, const float* bias, const float* gamma, const float* beta, const float* resid,
               float* C2, int32_t tile_rows);
+
+/* Rows per workgroup (32, 64 or 128) that tile_rows = 0 means for a GEMM of this shape and epilogue: the engine's own dispatch rule, for
+ * tests that must know which tile class a shape reaches.  Host arithmetic only: no device, no handle. */
+int vapx_gemm_tile_rows(int32_t M, int32_t N, int32_t K, int32_t epi);
 
 /* Per-kernel-class timing with HIP events recorded on the launch stream (bench.py's roofline leg).
  * class ids: 0..4 = the GEMM by epilogue (vapx_gemm's epi 0..4), 5 fused conv2-4 tail, 6 fused FFN block,

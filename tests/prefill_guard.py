@@ -1,7 +1,8 @@
 """Child process of tests/test_prefill_gpu.py::test_engine_buffers_keep_their_canaries: vapx_prefill under VAPX_GUARD_ZONES=1 (4 KiB
 canaries round every device allocation of the engine; the library reads the variable once per process, hence a child).  Prefills that fill
 the scratch to its last entry (n * frames_in_chunk = max_batch), leave a remainder chunk, wrap the ring inside the call and name the
-engine's last slot, over pageable, page-locked and device audio; prints one JSON line."""
+engine's last slot, over pageable, page-locked and device audio; then the large-chunk shapes of tests/prefill_classes.py (cases C and G);
+prints one JSON line."""
 import json
 import os
 import sys
@@ -41,6 +42,26 @@ def main() -> int:
                 run.finite(out, f"{hz} Hz n={n} {route}")
                 recs.append(e.export_streams(cache=True))
             agree = agree and all(np.array_equal(r, recs[0]) for r in recs[1:])
+    # the chunk shapes of tests/prefill_classes.py: case C (8 streams x 230 frames = 1840 entries = max_batch exactly: the GEMM chain with
+    # conv1 in 128-row tiles, every scratch buffer and the audio staging filled to the last entry; device and pageable audio) and case G
+    # (5 Hz, 40 frames of one stream in one chunk: the largest per-entry buffers)
+    for hz, T, n, max_batch, frames, routes in ((20, 12, 8, 1840, 230, ("device", "pageable")), (5, 4, 1, 64, 40, ("device",))):
+        hop = 16000 // hz
+        slots = [n + 2, 0, 5, 3, 1, 7, 9, 4][:n]
+        block = mb.noise(rng, (n, 2, frames * hop))
+        recs = []
+        for route in routes:
+            e = run.engine(mb.blob(hz), hz, mb.ctx_sec(T, hz), max_streams=max(max_batch, n + 3), max_batch=max_batch)
+            e.step(mb.noise(np.random.default_rng(3), (1, 2, hop)), [n + 2])               # the last slot holds a carry and a ring position of 1
+            if route == "device":
+                g, gi = mb.Guarded.of(block, what="prefill audio"), mb.Guarded.of(np.array(slots, np.int32), what="prefill ids")
+                e.prefill_device(n, g.ptr(), frames, ids_ptr=gi.ptr(), stream=torch.cuda.current_stream().cuda_stream)
+                g.check(); gi.check()
+            else:
+                e.prefill(block, slots)
+            run.finite(e.step(mb.noise(np.random.default_rng(5), (n, 2, hop)), slots), f"{hz} Hz n={n} max_batch={max_batch} {route}")
+            recs.append(e.export_streams(cache=True))
+        agree = agree and all(np.array_equal(r, recs[0]) for r in recs[1:])
     selftest = float(run.live[0].peek("guard_selftest", (1,))[0])
     run.close()
     print(json.dumps({"guard_selftest": selftest, "guard_violations": run.violations, "launches": run.launches, "routes_agree": agree}))

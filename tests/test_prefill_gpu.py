@@ -16,7 +16,7 @@ arithmetic in both engines - conv0 and the LSTM by construction, and every GEMM 
 count (gemm_f32.hip: M < 12000), in which an element's sum runs over K in the same order wherever its row lies.  So the test asserts
 equality of the whole records, which implies the bar; the errors against float64 stay in as printed figures and as a sanity bound.  An
 engine whose virtual batch crosses a tile threshold that its step does not (thousands of streams) is promised agreement to rounding
-only (vapx.h)."""
+only (vapx.h); tests/test_prefill_classes_gpu.py holds those engines - chunks of hundreds to 1840 entries - against float64."""
 import json
 import os
 import subprocess

@@ -149,6 +149,8 @@ struct vapx_engine : Geometry {
   float* out_pinned = nullptr;
   int last_B = 0, last_G = 1;
   bool last_tail_fused = false;           // some overlap group of the latest encoder pass ran conv_tail_kernel: h2 / h3 were not written
+  bool last_prefill = false;              // the latest encoder pass was a vapx_prefill chunk: last_B (frame, stream) entries, frame-major; no
+                                          // lstm_out, no transformer buffer (vapx_peek refuses them)
   bool deferred_pending = false;          // the latest step left its overlap groups un-joined (VAPX_DEFER_JOIN)
   std::vector<int32_t> pending_resets;    // vapx_reset_stream requests, applied stream-ordered by the next step
   std::vector<uint32_t> id_stamp;         // duplicate-id check: id_stamp[sid] == id_gen <=> sid already in this batch
@@ -1357,6 +1359,7 @@ int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* 
   h->deferred_pending = defer_join;
   h->last_G = G;
   h->last_B = n;
+  h->last_prefill = false;
   h->last_ids = ids;
   if (lead) h->followed_tick = lead->tick; else ++h->tick;
   if (!(flags & VAPX_OUT_DEVICE)) {
@@ -1933,6 +1936,9 @@ int vapx_prefill(vapx_handle h, int32_t n, const int32_t* stream_ids, const floa
     c0.h0 = sc.h0; c0.w = w.conv[0].w; c0.bias = w.conv[0].b; c0.gamma = w.conv[0].g; c0.beta = w.conv[0].beta;
     c0.frames_seen = sv.frames_seen; c0.bhead = f0 ? nullptr : sc.bhead; c0.L = h->L; c0.n = n; c0.T = T;
     { ProfScope ps(h, CLS_CONV0, st); HIPCHK(h, launch_conv0_prefill(c0, V, st)); }
+    // what vapx_peek finds afterwards is this chunk: V entries in one group, h2 / h3 only where the chain ran
+    h->last_tail_fused = false;
+    h->last_B = V; h->last_G = 1; h->last_prefill = true;
     if ((rc = run_conv_chain(h, sc, V, st))) return rc;
     LstmPrefillArgs la;
     lstm_args(h, sc, sv, la);
@@ -1977,6 +1983,7 @@ int vapx_encode_audio(vapx_handle h, int32_t n, const int32_t* stream_ids, const
   if (rc) return rc;
   HIPCHK(h, hipMemcpyAsync(e, h->sc.e, (size_t)n * 2 * 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
   h->last_B = n;
+  h->last_prefill = false;
   return VAPX_OK;
 }
 
@@ -2026,6 +2033,7 @@ int vapx_transformer_maps(vapx_handle h, int32_t n, int32_t rows, const float* x
   }
   HIPCHK(h, hipGetLastError());
   h->last_B = n;
+  h->last_prefill = false;
   return VAPX_OK;
 }
 
@@ -2052,6 +2060,10 @@ int64_t vapx_peek(vapx_handle h, const char* name, float* dst, size_t max_floats
     return 1;
   }
   // what exists after the latest step depends on the path it took: refuse what was not written
+  if (h->last_prefill && strcmp(name, "h0") && strcmp(name, "h1") && strcmp(name, "h2") && strcmp(name, "h3") && strcmp(name, "z") &&
+      strcmp(name, "e"))
+    return fail(h, VAPX_E_INVAL, "\"%s\" is not written by vapx_prefill (its LSTM launch keeps lstm_out to itself and no transformer layer runs): "
+                "after a prefill only h0 .. h3, z and e of its last chunk exist; step to peek \"%s\"", name, name);
   const bool full_last = (h->cfg.flags & VAPX_FLAG_FULL_LAST_LAYER) || h->cfg.mode == VAPX_MODE_NOD;
   if ((!strcmp(name, "h2") || !strcmp(name, "h3")) && h->last_tail_fused)
     // what run_encoder ran for the latest step, not a guess from last_B: the 512-stream limit holds per overlap group, so a batch of
@@ -2379,5 +2391,7 @@ int vapx_gemm(void* hip_stream, int32_t M, int32_t N, int32_t K, const float* A,
   if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? VAPX_E_INVAL : VAPX_E_HIP, "vapx_gemm: %s", hipGetErrorString(e));
   return VAPX_OK;
 }
+
+int vapx_gemm_tile_rows(int32_t M, int32_t N, int32_t K, int32_t epi) { return gemm_tile_rows(M, N, K, epi); }
 
 }  // extern "C"

@@ -30,5 +30,8 @@ struct GemmArgs {
                       // of 2^8 w) — staged as it is instead of converting W in every k-tile of every workgroup; null: convert on the fly
 };
 
-// tile_rows: 0 = choose from M, else 32 / 64 / 128 rows per workgroup.
+// Rows per workgroup that launch_gemm_f32 picks for tile_rows = 0: the one definition of the rule (host only, no device call).
+int gemm_tile_rows(int M, int N, int K, int epi);
+
+// tile_rows: 0 = gemm_tile_rows(M, N, K, epi), else 32 / 64 / 128 rows per workgroup.
 hipError_t launch_gemm_f32(const GemmArgs& g, int epi, int tile_rows, hipStream_t stream);

@@ -307,19 +307,21 @@ hipError_t launch_wm(const GemmArgs& g, int epi, hipStream_t st) {
 
 }  // namespace
 
+// The tile rule, in one place (vapx_gemm_tile_rows exports it to the tests).  Measured on MI355X (tools/gemm_sweep.py,
+// profiles/r01_gemm_sweep.txt): 64-row tiles win for N = 256 (more workgroups -> less tile quantisation, 3 waves/SIMD), 128-row tiles
+// for the plain-store wide GEMMs, 32-row tiles when M is too small to fill 256 CUs otherwise.
+int gemm_tile_rows(int M, int N, int K, int epi) {
+  if (M < 12000) return 32;
+  if (N >= 512 && epi == EPI_STORE) return 128;
+  if (K >= 2048 && M >= 200000) return 128;
+  return 64;
+}
+
 hipError_t launch_gemm_f32(const GemmArgs& g, int epi, int tile_rows, hipStream_t stream) {
   if (g.M <= 0) return hipSuccess;
   if ((g.N & 255) || (g.K & 31) || g.K <= 0) return hipErrorInvalidValue;
   if ((epi == EPI_RESID_LN || epi == EPI_CN_RELU || epi == EPI_BIAS_LN_GELU) && g.N != 256) return hipErrorInvalidValue;
-  if (tile_rows == 0) {
-    // measured on MI355X (tools/gemm_sweep.py, profiles/r01_gemm_sweep.txt): 64-row tiles win for
-    // N = 256 (more workgroups -> less tile quantisation, 3 waves/SIMD), 128-row tiles for the
-    // plain-store wide GEMMs, 32-row tiles when M is too small to fill 256 CUs otherwise.
-    if (g.M < 12000) tile_rows = 32;
-    else if (g.N >= 512 && epi == EPI_STORE) tile_rows = 128;
-    else if (g.K >= 2048 && g.M >= 200000) tile_rows = 128;
-    else tile_rows = 64;
-  }
+  if (tile_rows == 0) tile_rows = gemm_tile_rows(g.M, g.N, g.K, epi);
   if (g.split) {
     switch (tile_rows) {
       case 128: return launch_wm<4, 1, true>(g, epi, stream);

@@ -48,7 +48,7 @@ EXPORTS = ("vapx_abi_version", "vapx_blob_floats", "vapx_create", "vapx_destroy"
            "vapx_ingest_class_ports", "vapx_ingest_stream_class",
            "vapx_set_stream_channel_classes", "vapx_get_stream_channel_classes", "vapx_input_row_bytes",
            "vapx_ingest_pair_ports", "vapx_ingest_stream_channel_classes",
-           "vapx_prefill")
+           "vapx_prefill", "vapx_gemm_tile_rows")
 MAX_INPUT_CLASSES = 16
 PROF_CLASSES = {0: "gemm_store", 1: "gemm_gelu", 2: "gemm_resid", 3: "gemm_resid_ln", 4: "gemm_cn_relu",
                 5: "conv_tail", 6: "ffn_block", 7: "last_row", 8: "conv0", 9: "lstm", 10: "gather_ln", 11: "attention", 12: "head",
@@ -254,6 +254,9 @@ def load_library(path: Optional[str] = None):
     lib.vapx_peek.argtypes = [vp, C.c_char_p, f32p, C.c_size_t]
     lib.vapx_gemm.restype = i32
     lib.vapx_gemm.argtypes = [vp, i32, i32, i32, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, f32p, i32]
+    if hasattr(lib, "vapx_gemm_tile_rows"):   # absent from an older build named by VAPX_LIBRARY, as vapx_prefill below
+        lib.vapx_gemm_tile_rows.restype = i32
+        lib.vapx_gemm_tile_rows.argtypes = [i32, i32, i32, i32]
     lib.vapx_profile_enable.restype = i32
     lib.vapx_profile_enable.argtypes = [vp, C.c_uint32]
     lib.vapx_profile_read.restype = i32
@@ -807,7 +810,9 @@ class Engine:
 
     def peek(self, name: str, shape) -> np.ndarray:
         """A scratch buffer of the latest step (vapx.h, vapx_peek): the encoder stages, ``x0``, ``o``, ``stereo0`` .. ``stereo2`` [n,2,T,256],
-        ``last`` [n,2,256] (the last layer's newest row where that layer runs on the newest row alone) and, nod only, ``comb`` [n,T,256]."""
+        ``last`` [n,2,256] (the last layer's newest row where that layer runs on the newest row alone) and, nod only, ``comb`` [n,T,256].
+        After a ``prefill`` and until the next step: ``h0`` .. ``h3``, ``z``, ``e`` of its last chunk, [V, 2, ...] with entry
+        v = j * n + k = frame j of the chunk, stream k of the call; everything else is refused."""
         buf = np.empty(int(np.prod(shape)), np.float32)
         got = self._check(self.lib.vapx_peek(self._h, name.encode(), _np_ptr(buf), buf.size), "vapx_peek")
         assert got == buf.size, (name, got, buf.size)
@@ -954,6 +959,11 @@ class TrunkGroup:
     def close(self):
         for m in reversed(self.order):                     # followers before their leader
             self.engines[m].close()
+
+
+def gemm_tile_rows(M: int, N: int, K: int, epi: int) -> int:
+    """Rows per workgroup the library's GEMM dispatch picks for this shape and epilogue (vapx.h, vapx_gemm_tile_rows)."""
+    return int(load_library().vapx_gemm_tile_rows(int(M), int(N), int(K), int(epi)))
 
 
 def prefill_chunks(max_batch: int, n: int, frames: int, ctx_frames: int) -> list:
