@@ -352,6 +352,128 @@ def test_random_segmentation_and_reconnects_keep_every_stream_exact():
         srv.close()
 
 
+# The connection kinds beside the f64 pairs above, one stream each: (open arguments, which input port, the two channels' classes, planar).
+# Over a step function a front-end without a table runs at 16 kHz; uniform mu-law at 8 kHz needs an engine's rate and is the same three
+# cuttings in tests/native/pcm_open_check.cpp.
+_SEG_TABLE = [("f64", 16000), ("s16", 8000), ("mulaw", 8000)]          # class 0 is the largest: the others sit in strides sized for it
+_SEG_KINDS = {
+    "uniform-s16": (dict(input_format="s16"), None, (("s16", 16000), ("s16", 16000)), False),
+    "uniform-mulaw": (dict(input_format="mulaw"), None, (("mulaw", 16000), ("mulaw", 16000)), False),
+    "class-port": (dict(input_classes=_SEG_TABLE), ("class", 1), (("s16", 8000), ("s16", 8000)), False),
+    "pair-port": (dict(input_classes=_SEG_TABLE, pair_ports=[(0, 2, 0)]), ("pair", 0), (("f64", 16000), ("mulaw", 8000)), True),
+    # the gain (a float64 multiply before the f32 cast) on the interleaved and on the planar f64 path; a raw class refuses one
+    "f64-gain": (dict(gain=1.5), None, (("f64", 16000), ("f64", 16000)), False),
+    "pair-port-f64-gain": (dict(gain=1.5, input_classes=[("f64", 16000), ("f64", 8000)], pair_ports=[(1, 0, 0)]), ("pair", 0),
+                           (("f64", 8000), ("f64", 16000)), True),
+}
+
+
+def _seg_leg(cls, n_frames, rng):
+    fmt, hz = cls
+    n = n_frames * (hz // 50)
+    if fmt == "f64":
+        return rng.standard_normal(n) * 0.1
+    if fmt == "s16":
+        return rng.integers(-32768, 32768, n).astype(np.int16)      # every bit pattern: a split sample shows in either byte
+    return rng.integers(0, 256, n).astype(np.uint8)
+
+
+@pytest.mark.parametrize("cutting", ["bytes", "random", "frames"])
+@pytest.mark.parametrize("kind", list(_SEG_KINDS))
+def test_every_connection_kind_is_exact_under_every_cutting(kind, cutting, monkeypatch):
+    """The frame assembler for raw, class-port and pair-port connections, at the smallest shape that reaches every state of it: 50 Hz
+    frames, 3 frames, one stream.  The wire bytes are cut (1) one byte per send: every split position of every sample, every packet and
+    frame boundary, (2) at seeded random places, with a connection that hangs up in the middle of a frame before the one that is checked,
+    (3) into whole frames.  In (1) and (2) the next piece is sent when the front-end has read the last one (and SO_RCVLOWAT is off, or
+    it would wait for the whole frame), so the parser is entered once per piece.  The step function must see exactly the staged bytes,
+    and every result packet must equal, byte for byte, the one the Python codec (wire.py / pcm.py) makes from the same samples."""
+    from vap_realtime_amd import pcm
+    kw, port, legs, planar = _SEG_KINDS[kind]
+    frames, rng = 3, np.random.default_rng(sum(map(ord, kind + cutting)))
+    if cutting != "frames":
+        monkeypatch.setenv("VAPX_INGEST_NO_LOWAT", "1")
+    blocks = []
+
+    def step(ids, audio, out):
+        blocks.append(audio.tobytes())
+        out[:, 0:6] = np.arange(6, dtype=np.float32) + 8.0 * len(blocks)
+        return 0
+
+    def wire_bytes(x):
+        if planar:
+            return wire.encode_input_planar(x[0], legs[0], x[1], legs[1])
+        return wire.encode_input(x[0], x[1], legs[0][0])
+
+    srv = ingest.NativeServer.over_function(step, 1, 50, max_wait_s=0.02, **kw)
+    try:
+        p_in = srv.port_in if port is None else (srv.class_ports if port[0] == "class" else srv.pair_ports)[port[1]]
+        sent, st = [0], ingest._IngestStats()
+
+        def read_bytes():
+            srv.lib.vapx_ingest_stats_read(srv._h, C.byref(st), 0)
+            return st.rx_bytes
+
+        def connect():
+            c = socket.create_connection(("127.0.0.1", p_in))
+            c.setsockopt(socket.IPPROTO_TCP, socket.TCP_NODELAY, 1)
+            _wait(lambda: srv.stats()["in_connections"] == 1)
+            return c
+
+        def send(c, data, sizes):
+            at = 0
+            while at < len(data):
+                n = next(sizes)
+                c.sendall(data[at:at + n])
+                sent[0] += len(data[at:at + n])
+                at += n
+                t0 = time.time()
+                while cutting != "frames" and read_bytes() != sent[0]:       # (spinning: a piece is read within microseconds)
+                    assert time.time() - t0 < 5, "the front-end stopped reading"
+
+        x = [_seg_leg(c, frames, rng) for c in legs]
+        data = wire_bytes(x)
+        frame_len = len(data) // frames
+        out = socket.create_connection(("127.0.0.1", srv.port_out))
+        _wait(lambda: srv.stats()["out_connections"] == 1)
+        out.settimeout(10)
+        expect, packets = [], []                                           # per answered frame: the two channels' samples; the packets read
+
+        def read_packet():
+            ln = _recv_exact(out, 4)
+            return ln + _recv_exact(out, struct.unpack("<I", ln)[0])
+
+        if cutting == "random":                                            # a connection that ends inside its second frame comes first
+            y = [_seg_leg(c, 2, rng) for c in legs]
+            first = connect()
+            send(first, wire_bytes(y)[:frame_len + frame_len // 2 + 3], iter(lambda: int(rng.choice([1, 2, 3, 5, 8, 13, 100, 333])), 0))
+            packets.append(read_packet())          # its whole frame is answered first: a frame still queued when its connection ends is dropped
+            first.close()
+            _wait(lambda: srv.stats()["in_connections"] == 0)
+            expect.append([y[ch][:len(y[ch]) // 2] for ch in range(2)])
+        c = connect()
+        sizes = {"bytes": iter(lambda: 1, 0), "random": iter(lambda: int(rng.choice([1, 2, 3, 5, 8, 13, 100, 333, 1000])), 0),
+                 "frames": iter(lambda: frame_len, 0)}[cutting]
+        send(c, data, sizes)
+        for f in range(frames):
+            expect.append([x[ch][f * len(x[ch]) // frames:(f + 1) * len(x[ch]) // frames] for ch in range(2)])
+        packets += [read_packet() for _ in range(frames)]
+        for k, legs_k in enumerate(expect):
+            got = packets[k][4:]
+            legs_k = [v * kw.get("gain", 1.0) if cls[0] == "f64" else v for cls, v in zip(legs, legs_k)]
+            echo = [v if cls[0] == "f64" else pcm.decode(cls[0], v, np.float64) for cls, v in zip(legs, legs_k)]
+            heads = np.arange(6, dtype=np.float64) + 8.0 * (k + 1)
+            want = wire.frame_result({"t": struct.unpack_from("<d", got, 0)[0], "x1": echo[0], "x2": echo[1], "p_now": heads[0:2],
+                                      "p_future": heads[2:4], "vad": heads[4:6]})
+            assert packets[k] == want, (kind, cutting, k)
+            staged = b"".join((v.astype(np.float32) if cls[0] == "f64" else v).tobytes() for cls, v in zip(legs, legs_k))
+            assert blocks[k] == staged, (kind, cutting, k)
+        assert len(blocks) == len(expect) and srv.stats()["frames_done"] == len(expect)
+        c.close()
+        out.close()
+    finally:
+        srv.close()
+
+
 def test_many_streams_four_senders_every_stream_sees_its_frames_in_order():
     """Per-stream order with several sender threads (advisor r04): 384 dialogues, 4 senders, 4 receivers, ticks back to back (the step
     function is instant, so consecutive ticks overlap on their way out).  A stream's packets always leave through sender slot % 4, which walks

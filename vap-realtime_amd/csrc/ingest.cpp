@@ -11,9 +11,10 @@
 // Input classes (vapx_ingest_config.input_classes; vapx.h "Input classes"): one input port per class; a connection accepted on class c's port
 // makes its slot a stream of class c, whose geometry (InGeo: format, hop, packet size) every thread takes from the slot or from the queued
 // frame instead of from the front-end; the tick packs the ready frames' slots back to back, which is the packed block the engine takes.
-// A front-end without a table has one geometry, geo[0], and every slot is of it.
+// A front-end without a table is the one-class case: one geometry, geo[0], one input port, and every slot is of it; only the public calls
+// tell it from a table of one (vapx_ingest::cls_table).
 // Pair ports (vapx_ingest_config.pair_ports; vapx.h CHANNEL CLASSES): a connection on pair port (c1, c2) is a dialogue whose channel 1 is of
-// class c1 and whose channel 2 of c2.  Its packets are planar (channel 1's 10 ms, then channel 2's: feed_planar), its frame buffer holds
+// class c1 and whose channel 2 of c2.  Its packets are planar (channel 1's 10 ms, then channel 2's), its frame buffer holds
 // channel 1's row and then channel 2's, each in its own class's staging form, which is the engine's slot.  A slot of any other port is
 // the case c1 == c2 of that layout.
 //
@@ -174,28 +175,37 @@ struct Hist {   // log2-spaced latency histogram, 8 sub-buckets per octave from 
   void clear() { for (auto& x : b) x = 0; cnt = 0; sum_us = 0; max_us = 0; }
 };
 
-// the geometry of an input port: the front-end's one, or one per input class
+// the geometry of an input class (a front-end without a table has one).  The sample sizes are derived here and nowhere else
 struct InGeo {
-  int fmt = VAPX_PCM_F32;                  // VAPX_PCM_F32 = the reference's f64 pairs, cast to f32 on the host; S16 / MULAW / ALAW = raw samples
+  // wire format: VAPX_PCM_F32 = the reference's f64 pairs, cast to f32 on the host (the engine's format is f32); S16 / MULAW / ALAW = raw
+  // samples, staged as they are and handed to the step as they are (the engine decodes: vapx_set_input_format)
+  int fmt = VAPX_PCM_F32;
   int in_hz = 16000;
-  int hop = 0;                             // sample PAIRS per frame on the wire = in_hz / frame_hz
-  int bps = 4;                             // bytes per sample of the staging
-  int pair_bytes = PAIR_BYTES;             // one sample of both channels on the wire
-  size_t row_bytes() const { return (size_t)hop * bps; }         // one channel's row of the staging
-  size_t frame_bytes() const { return (size_t)2 * hop * bps; }   // a frame of the staging = a slot of the step's block
-  int wire_bps() const { return fmt ? bps : 8; }                 // bytes per sample on the wire: f64 for an F32 class
+  int hop = 0;                             // samples per channel and frame on the wire = in_hz / frame_hz (the engine resamples: vapx_set_input_rate)
+  int bps() const { return fmt == VAPX_PCM_F32 ? 4 : fmt == VAPX_PCM_S16 ? 2 : 1; }   // bytes per sample of the staging
+  int wire_bps() const { return fmt ? bps() : 8; }                 // bytes per sample on the wire: f64 for an F32 class
+  size_t row_bytes() const { return (size_t)hop * bps(); }         // one channel's row of the staging
+  size_t frame_bytes() const { return 2 * row_bytes(); }           // a frame of the staging = a slot of the step's block
+  size_t wire_row() const { return (size_t)hop * wire_bps(); }     // one channel's samples of a frame on the wire
+};
+
+// an input port: its listen socket (-1: a passive shard listens on nothing), the port bound, and what a connection accepted on it is
+struct InPort {
+  int lsock = -1, port = 0;
+  int cls = 0, cls2 = 0;                   // the classes of channel 1 and channel 2: equal but on a pair port
+  bool planar = false;                     // a pair port: planar 10 ms packets
 };
 
 struct Slot {
   int fd_in = -1;
   int cls = 0;                             // index into vapx_ingest::geo; written at adoption, before the socket joins an epoll set
   int cls2 = 0;                            // channel 2's class: cls unless the connection came in on a pair port
-  bool planar = false;                     // a pair port's connection: planar packets (feed_planar); `fill` then counts the frame's wire bytes
+  bool planar = false;                     // a pair port's connection: planar 10 ms packets
   std::atomic<uint32_t> gen{0};           // bumped per connection: queued frames of a dead connection are dropped (read by the tick thread)
   std::atomic<int> state[NBUF];
   double t_ready[NBUF] = {};
-  int wbuf = -1, fill = 0;                // rx thread only
-  uint8_t partial[PAIR_BYTES]; int npartial = 0;
+  int wbuf = -1, fill = 0;                // rx thread only: the frame buffer being filled and the wire bytes of its frame taken so far
+  uint8_t partial[PAIR_BYTES];            // the head of an f64 sample (pair) split across two reads; its bytes are counted in `fill`
   std::vector<uint8_t> backlog;           // bytes received while no buffer was free
   int lowat = 0;                          // rx thread only: SO_RCVLOWAT currently set on fd_in (0 = the kernel default)
   std::atomic<bool> paused{false};        // written by the slot's rx / accept thread, read by whoever frees a buffer
@@ -241,29 +251,23 @@ struct OutPort {
 }  // namespace
 
 struct vapx_ingest {
-  vapx_ingest() { for (int& fd : cls_lsock) fd = -1; for (int& fd : pair_lsock) fd = -1; }
   vapx_ingest_config cfg;
   vapx_ingest_step_fn step = nullptr;
   vapx_ingest_reset_fn reset = nullptr;
   void* user = nullptr;
   vapx_handle engine = nullptr;
-  int S = 0, max_batch = 0, hop = 0, hz = 0;   // hop: sample PAIRS per frame on the wire = in_hz / hz (the engine resamples: vapx_set_input_rate)
-  int in_hz = 16000;
-  // wire format of the input port: VAPX_PCM_F32 = the reference's f64 pairs, cast to f32 on the host (the engine's format is f32); S16 / MULAW /
-  // ALAW = raw samples, staged as they are and handed to the step as they are (the engine decodes: vapx_set_input_format)
-  int fmt = VAPX_PCM_F32;
-  int bps = 4;                             // bytes per sample of the staging blocks
-  int pair_bytes = PAIR_BYTES;             // one sample of both channels on the wire
-  // input classes: geo[c] is class c's geometry and cls_lsock / cls_port its input port; without a table n_cls = 0 and geo[0] restates the
-  // five fields above.  frame_stride / echo_stride: bytes / doubles between two frame buffers, sized for the largest class
-  int n_cls = 0;
+  int S = 0, max_batch = 0, hz = 0;
+  // The input: geo[c] is class c's geometry, n_cls >= 1 of them.  cls_table: the caller (or the engine) gave a table; without one the
+  // engine's rate and format are the one class, and the public calls report no classes (tab_cls).  in_ports: one per class, then the pair
+  // ports; without a table the one input port.  frame_stride / echo_stride: bytes / doubles between two frame buffers, sized for the largest class
+  bool cls_table = false;
+  int n_cls = 1;
+  int tab_cls() const { return cls_table ? n_cls : 0; }
   InGeo geo[VAPX_MAX_INPUT_CLASSES];
   vapx_input_class cls_pub[VAPX_MAX_INPUT_CLASSES] = {};
-  int cls_lsock[VAPX_MAX_INPUT_CLASSES], cls_port[VAPX_MAX_INPUT_CLASSES] = {};
+  int n_in = 0;
+  InPort in_ports[VAPX_MAX_INPUT_CLASSES + VAPX_MAX_PAIR_PORTS];
   size_t frame_stride = 0, echo_stride = 0;
-  int n_pair = 0;                          // pair ports: pair_cls[p] = the classes of channel 1 and channel 2
-  int pair_cls[VAPX_MAX_PAIR_PORTS][2] = {};
-  int pair_lsock[VAPX_MAX_PAIR_PORTS], pair_port[VAPX_MAX_PAIR_PORTS] = {};
   std::vector<int32_t> tick_cls;           // [S][2] tick thread only: a stream's channel classes as the engine (or the step function) knows them
   void (*set_class)(void* user, int32_t stream_id, int32_t cls, int32_t cls2) = nullptr;   // tick thread: vapx_set_stream_class / _channel_classes on the engine
   size_t frame_bytes(int c1, int c2) const { return geo[c1].row_bytes() + geo[c2].row_bytes(); }   // a slot of the step's block
@@ -284,8 +288,6 @@ struct vapx_ingest {
   std::vector<int32_t> batch_ids;
   Job jobs[2];
 
-  int lin = -1;
-  int port_in = 0;
   std::vector<int> ep;                     // epoll fd per rx thread
   std::vector<int> wake;                   // eventfd per rx thread (resume / stop)
   std::vector<std::thread> rx_threads, tx_threads;
@@ -463,7 +465,7 @@ void drop_input(vapx_ingest* g, int r, int slot) {
   epoll_ctl(g->ep[r], EPOLL_CTL_DEL, s.fd_in, nullptr);
   close(s.fd_in);
   if (s.wbuf >= 0) { s.state[s.wbuf].store(B_FREE); s.wbuf = -1; }
-  s.fill = 0; s.npartial = 0; s.backlog.clear(); s.paused = false;
+  s.fill = 0; s.backlog.clear(); s.paused = false;
   {
     std::lock_guard<std::mutex> lk(g->slots_mu);
     s.fd_in = -1;
@@ -489,52 +491,6 @@ void frame_complete(vapx_ingest* g, int slot, Slot& s) {
   g->ready_cv.notify_one();
 }
 
-// a raw input format: interleaved (ch1, ch2) samples of bps bytes are de-interleaved into the slot's staging as they are: no cast, no
-// f32 staging, no f64 echo copy.  Same contract as feed()
-size_t feed_raw(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
-  Slot& s = g->slots[slot];
-  const InGeo& q = g->geo[s.cls];
-  const size_t hop = (size_t)q.hop, bps = (size_t)q.bps, pb = (size_t)q.pair_bytes;
-  size_t used = 0;
-  while (used < n) {
-    if (s.wbuf < 0) {
-      s.wbuf = pick_free(s);
-      if (s.wbuf < 0) return used;
-      s.fill = 0;
-    }
-    uint8_t* d = g->rawbuf(slot, s.wbuf);
-    if (s.npartial) {                       // finish a sample pair split across two reads
-      const size_t take = std::min<size_t>(pb - s.npartial, n - used);
-      memcpy(s.partial + s.npartial, p + used, take);
-      s.npartial += (int)take; used += take;
-      if ((size_t)s.npartial < pb) break;
-      s.npartial = 0;
-      memcpy(d + (size_t)s.fill * bps, s.partial, bps);
-      memcpy(d + (hop + s.fill) * bps, s.partial + bps, bps);
-      ++s.fill;
-    } else {
-      const size_t pairs = std::min<size_t>((n - used) / pb, hop - (size_t)s.fill);
-      if (pairs == 0) {                     // less than a pair left: keep it for the next read
-        const size_t rest = n - used;
-        memcpy(s.partial, p + used, rest); s.npartial = (int)rest; used = n;
-        break;
-      }
-      const uint8_t* q = p + used;
-      if (bps == 2) {
-        uint8_t *d1 = d + (size_t)s.fill * 2, *d2 = d + (hop + s.fill) * 2;
-        for (size_t i = 0; i < pairs; ++i) { memcpy(d1 + 2 * i, q + 4 * i, 2); memcpy(d2 + 2 * i, q + 4 * i + 2, 2); }
-      } else {
-        uint8_t *d1 = d + s.fill, *d2 = d + hop + s.fill;
-        for (size_t i = 0; i < pairs; ++i) { d1[i] = q[2 * i]; d2[i] = q[2 * i + 1]; }
-      }
-      s.fill += (int)pairs;
-      used += pairs * pb;
-    }
-    if ((size_t)s.fill == hop) frame_complete(g, slot, s);
-  }
-  return used;
-}
-
 // a channel's row of a raw format as the result packet echoes it: the decoded samples as float64, [hop]
 void expand_raw(const InGeo& q, const uint8_t* raw, double* e) {
   const size_t n = (size_t)q.hop;
@@ -546,77 +502,77 @@ void expand_raw(const InGeo& q, const uint8_t* raw, double* e) {
   }
 }
 
-// wire bytes of a whole frame of a pair port's connection: 100 / frame_hz planar packets of (channel 1's 10 ms, channel 2's 10 ms)
-size_t planar_frame_bytes(const vapx_ingest* g, const Slot& s) {
-  return (size_t)g->geo[s.cls].hop * g->geo[s.cls].wire_bps() + (size_t)g->geo[s.cls2].hop * g->geo[s.cls2].wire_bps();
-}
+// wire bytes of a whole frame of the slot's connection: both channels' samples, interleaved or in planar packets
+size_t frame_wire_bytes(const vapx_ingest* g, const Slot& s) { return g->geo[s.cls].wire_row() + g->geo[s.cls2].wire_row(); }
 
-// a pair port's connection: planar 10 ms packets, channel 1's samples in its class's wire form, then channel 2's in its own.  Raw samples
-// are copied into the channel's row as they are, f64 samples are cast (and echoed) as feed() does.  `fill` is the position in the frame's
-// wire bytes; a sample split across two reads waits in `partial`.  Same contract as feed()
-size_t feed_planar(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
-  Slot& s = g->slots[slot];
-  const InGeo* q[2] = {&g->geo[s.cls], &g->geo[s.cls2]};
-  const size_t pk = (size_t)(100 / g->hz);                                    // packets per frame
-  const size_t seg[2] = {(size_t)q[0]->hop * q[0]->wire_bps() / pk, (size_t)q[1]->hop * q[1]->wire_bps() / pk};   // a channel's bytes of a packet
-  const size_t pkt = seg[0] + seg[1], total = pkt * pk;
-  const double gain = g->cfg.gain;
-  size_t used = 0;
-  while (used < n) {
-    if (s.wbuf < 0) {
-      s.wbuf = pick_free(s);
-      if (s.wbuf < 0) return used;
-      s.fill = 0;
+// The f64 move, the only one: `n` groups of CH consecutive f64 samples (2: interleaved pairs, 1: a run of one channel) -> sample c of group
+// i goes to the f64 echo d[c][i] and, cast, to the f32 staging f[c][i].  The gain is a float64 multiply BEFORE the f32 cast
+// (vap_main.py:393-395); without one the cast is torch.tensor(float64).float() (vap_main.py:266-270)
+template <int CH, bool GAIN>
+inline void move_f64_run(const uint8_t* src, size_t n, double gain, double* const* d, float* const* f) {
+  for (size_t i = 0; i < n; ++i) {
+    double v[CH];
+    memcpy(v, src + i * 8 * CH, 8 * CH);
+    for (int c = 0; c < CH; ++c) {
+      const double a = GAIN ? v[c] * gain : v[c];
+      d[c][i] = a; f[c][i] = (float)a;
     }
-    const size_t k = (size_t)s.fill / pkt, in_pkt = (size_t)s.fill % pkt;   // (a partial sample's bytes are not counted in fill yet)
-    const int c = in_pkt >= seg[0];
-    const size_t in_seg = in_pkt - (c ? seg[0] : 0);
-    const size_t wb = (size_t)q[c]->wire_bps();
-    const size_t i0 = (k * seg[c] + in_seg) / wb;                            // the channel's sample index in the frame
-    const size_t left = seg[c] - in_seg;                                     // wire bytes to the end of this channel's part of the packet
-    uint8_t* row = g->rawbuf(slot, s.wbuf) + (c ? q[0]->row_bytes() : 0);
-    if (q[c]->fmt) {                                                         // raw: bytes as they are (a split s16 sample is just two copies)
-      const size_t take = std::min(left, n - used);
-      memcpy(row + k * seg[c] + in_seg, p + used, take);
-      used += take; s.fill += (int)take;
-    } else {
-      double* d = g->f64buf(slot, s.wbuf) + (c ? g->echo_ch2(s.cls, s.cls2) : 0);
-      float* f = (float*)row;
-      size_t done = 0;                                                       // whole samples taken
-      if (s.npartial || n - used < 8) {
-        const size_t take = std::min<size_t>(8 - s.npartial, n - used);
-        memcpy(s.partial + s.npartial, p + used, take);
-        s.npartial += (int)take; used += take;
-        if (s.npartial < 8) break;
-        double v;
-        memcpy(&v, s.partial, 8);
-        s.npartial = 0;
-        if (gain != 1.0) v *= gain;
-        d[i0] = v; f[i0] = (float)v;
-        done = 1;
-      } else {
-        done = std::min(left, n - used) / 8;
-        for (size_t i = 0; i < done; ++i) {
-          double v;
-          memcpy(&v, p + used + 8 * i, 8);
-          if (gain != 1.0) v *= gain;                                        // float64 multiply BEFORE the f32 cast, as in feed()
-          d[i0 + i] = v; f[i0 + i] = (float)v;
-        }
-        used += done * 8;
-      }
-      s.fill += (int)(done * 8);
-    }
-    if ((size_t)s.fill == total) frame_complete(g, slot, s);
   }
-  return used;
+}
+template <int CH>
+inline void move_f64(const uint8_t* src, size_t n, double gain, double* const* d, float* const* f) {
+  if (gain != 1.0) move_f64_run<CH, true>(src, n, gain, d, f);
+  else move_f64_run<CH, false>(src, n, gain, d, f);
 }
 
-// decode `n` bytes of the stream into the slot's frame buffers; returns bytes consumed (< n: no free buffer)
+// f64 samples of a frame buffer: `at` = wire bytes of this run (a frame's interleaved pairs, or one channel's part of a planar frame) already
+// taken, `room` = wire bytes to the end of the run, d / f = where the run's first group goes.  A group split across two reads waits in
+// s.partial.  Returns the bytes taken from p[0, n)
+template <int CH>
+size_t take_f64(Slot& s, size_t at, size_t room, const uint8_t* p, size_t n, double gain, double* const* d0, float* const* f0) {
+  constexpr size_t U = 8 * CH;
+  const size_t i0 = at / U, held = at % U;
+  double* d[CH]; float* f[CH];
+  for (int c = 0; c < CH; ++c) { d[c] = d0[c] + i0; f[c] = f0[c] + i0; }
+  if (held || n < U) {                      // finish (or begin) a group split across two reads
+    const size_t take = std::min(U - held, n);
+    memcpy(s.partial + held, p, take);
+    if (held + take == U) move_f64<CH>(s.partial, 1, gain, d, f);
+    return take;
+  }
+  const size_t groups = std::min(room, n) / U;
+  move_f64<CH>(p, groups, gain, d, f);
+  return groups * U;
+}
+
+// raw interleaved (ch1, ch2) samples of bps bytes are de-interleaved into the two rows of the staging `d` as they are: no cast, no f32
+// staging, no f64 echo copy.  `at` = wire bytes of the frame already taken; a pair split across two reads is placed byte by byte
+size_t take_raw_pairs(uint8_t* d, size_t hop, size_t bps, size_t at, const uint8_t* p, size_t n) {
+  const size_t pb = 2 * bps, i0 = at / pb, o = at % pb;
+  if (o || n < pb) {
+    const size_t take = std::min(pb - o, n);
+    for (size_t k = 0; k < take; ++k) d[(((o + k) / bps) * hop + i0) * bps + (o + k) % bps] = p[k];
+    return take;
+  }
+  const size_t pairs = std::min(n / pb, hop - i0);
+  if (bps == 2) {
+    uint8_t *d1 = d + i0 * 2, *d2 = d + (hop + i0) * 2;
+    for (size_t i = 0; i < pairs; ++i) { memcpy(d1 + 2 * i, p + 4 * i, 2); memcpy(d2 + 2 * i, p + 4 * i + 2, 2); }
+  } else {
+    uint8_t *d1 = d + i0, *d2 = d + hop + i0;
+    for (size_t i = 0; i < pairs; ++i) { d1[i] = p[2 * i]; d2[i] = p[2 * i + 1]; }
+  }
+  return pairs * pb;
+}
+
+// Decode `n` bytes of the stream into the slot's frame buffers; returns bytes consumed (< n: no free buffer).  The frame buffer, the
+// position in the frame (s.fill, in wire bytes for every kind of connection) and the hand-over of a complete frame are here; what differs
+// is the framing - interleaved (ch1, ch2) pairs, or a pair port's planar 10 ms packets: channel 1's samples in its class's wire form, then
+// channel 2's in its own - and the move of a run of samples: f64 (take_f64), or raw bytes as they are
 size_t feed(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
   Slot& s = g->slots[slot];
-  if (s.planar) return feed_planar(g, slot, p, n);
-  if (g->geo[s.cls].fmt) return feed_raw(g, slot, p, n);
-  const int hop = g->geo[s.cls].hop;
+  const InGeo* q[2] = {&g->geo[s.cls], &g->geo[s.cls2]};
+  const size_t total = frame_wire_bytes(g, s), hop = (size_t)q[0]->hop;
   const double gain = g->cfg.gain;
   size_t used = 0;
   while (used < n) {
@@ -625,50 +581,36 @@ size_t feed(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
       if (s.wbuf < 0) return used;          // engine is two frames behind this sender
       s.fill = 0;
     }
-    if (s.npartial) {                       // finish a sample pair split across two reads
-      size_t take = std::min<size_t>(PAIR_BYTES - s.npartial, n - used);
-      memcpy(s.partial + s.npartial, p + used, take);
-      s.npartial += (int)take; used += take;
-      if (s.npartial < PAIR_BYTES) break;
-      double v[2];
-      memcpy(v, s.partial, PAIR_BYTES);
-      s.npartial = 0;
-      float* f = g->f32buf(slot, s.wbuf);
-      double* d = g->f64buf(slot, s.wbuf);
-      const double a = gain != 1.0 ? v[0] * gain : v[0], b = gain != 1.0 ? v[1] * gain : v[1];
-      d[s.fill] = a; d[hop + s.fill] = b;
-      f[s.fill] = (float)a; f[hop + s.fill] = (float)b;
-      ++s.fill;
+    uint8_t* st = g->rawbuf(slot, s.wbuf);
+    double* e = g->f64buf(slot, s.wbuf);
+    const uint8_t* src = p + used;
+    const size_t at = (size_t)s.fill, left = n - used;
+    size_t took;
+    if (!s.planar) {
+      if (q[0]->fmt) took = take_raw_pairs(st, hop, (size_t)q[0]->bps(), at, src, left);
+      else {
+        double* d[2] = {e, e + hop};
+        float* f[2] = {(float*)st, (float*)st + hop};
+        took = take_f64<2>(s, at, total - at, src, left, gain, d, f);
+      }
     } else {
-      size_t pairs = std::min<size_t>((n - used) / PAIR_BYTES, (size_t)(hop - s.fill));
-      if (pairs == 0) {                     // fewer than 16 bytes left: keep them for the next read
-        size_t rest = n - used;
-        if (rest >= (size_t)PAIR_BYTES) { /* frame full, handled below */ }
-        else { memcpy(s.partial, p + used, rest); s.npartial = (int)rest; used = n; break; }
-      }
-      float* f = g->f32buf(slot, s.wbuf) + s.fill;
-      double* d = g->f64buf(slot, s.wbuf) + s.fill;
-      const uint8_t* q = p + used;
-      if (gain != 1.0) {
-        for (size_t i = 0; i < pairs; ++i) {
-          double v[2];
-          memcpy(v, q + i * PAIR_BYTES, PAIR_BYTES);
-          const double a = v[0] * gain, b = v[1] * gain;     // float64 multiply BEFORE the f32 cast (vap_main.py:393-395)
-          d[i] = a; d[hop + i] = b;
-          f[i] = (float)a; f[hop + i] = (float)b;
-        }
+      const size_t pk = (size_t)(100 / g->hz);                                 // packets per frame, and a channel's bytes of a packet
+      const size_t seg[2] = {q[0]->wire_row() / pk, q[1]->wire_row() / pk}, pkt = seg[0] + seg[1];
+      const size_t k = at / pkt, in_pkt = at % pkt;
+      const int c = in_pkt >= seg[0];
+      const size_t in_seg = in_pkt - (c ? seg[0] : 0), room = seg[c] - in_seg;   // wire bytes to the end of this channel's part of the packet
+      uint8_t* row = st + (c ? q[0]->row_bytes() : 0);
+      if (q[c]->fmt) {                                                         // raw: bytes as they are (a split s16 sample is just two copies)
+        took = std::min(room, left);
+        memcpy(row + k * seg[c] + in_seg, src, took);
       } else {
-        for (size_t i = 0; i < pairs; ++i) {
-          double v[2];
-          memcpy(v, q + i * PAIR_BYTES, PAIR_BYTES);
-          d[i] = v[0]; d[hop + i] = v[1];
-          f[i] = (float)v[0]; f[hop + i] = (float)v[1];       // == torch.tensor(float64).float() (vap_main.py:266-270)
-        }
+        double* d[1] = {e + (c ? g->echo_ch2(s.cls, s.cls2) : 0)};
+        float* f[1] = {(float*)row};
+        took = take_f64<1>(s, k * seg[c] + in_seg, room, src, left, gain, d, f);
       }
-      s.fill += (int)pairs;
-      used += pairs * PAIR_BYTES;
     }
-    if (s.fill == hop) frame_complete(g, slot, s);   // -> tick thread
+    used += took; s.fill += (int)took;
+    if ((size_t)s.fill == total) frame_complete(g, slot, s);   // -> tick thread
   }
   return used;
 }
@@ -679,9 +621,7 @@ size_t feed(vapx_ingest* g, int slot, const uint8_t* p, size_t n) {
 // runs there (round 5: on a box with load average 60 from other tenants every front-end thread was losing ~10 ms slices).  Re-armed only
 // when the value changes: a sender that delivers whole frames never causes a setsockopt.
 void arm_lowat(vapx_ingest* g, Slot& s) {
-  const InGeo& q = g->geo[s.cls];
-  long need = s.planar ? (long)planar_frame_bytes(g, s) - (s.wbuf >= 0 ? s.fill : 0) - s.npartial
-                       : (long)(q.hop - (s.wbuf >= 0 ? s.fill : 0)) * (long)q.pair_bytes - s.npartial;
+  long need = (long)frame_wire_bytes(g, s) - (s.wbuf >= 0 ? s.fill : 0);
   if (need < 1) need = 1;
   if (need > 65536) need = 65536;           // (5 Hz frames are 51 KB; stay well inside the receive buffer)
   if ((int)need == s.lowat || s.fd_in < 0 || g->no_lowat) return;
@@ -746,7 +686,7 @@ void do_resume(vapx_ingest* g, int r, int slot) {
     std::lock_guard<std::mutex> lk(g->resume_mu[r]);
     s.paused = false;
   }
-  // The backlog moved `fill` / `npartial`: the socket's SO_RCVLOWAT still holds what the frame open BEFORE the pause lacked, and the rest
+  // The backlog moved `fill`: the socket's SO_RCVLOWAT still holds what the frame open BEFORE the pause lacked, and the rest
   // of the frame open NOW may be fewer bytes than that - they would sit in the socket unread (a finite stream lost its last frame, a
   // live one got it a frame period late).  Set the threshold first, then re-enable EPOLLIN: EPOLL_CTL_MOD polls the socket against it.
   arm_lowat(g, s);
@@ -771,47 +711,47 @@ int lowest_free_slot(vapx_ingest* g) {
   return -1;
 }
 
-// take over an accepted input connection: the lowest free stream slot gets it; false = every slot is taken (fd untouched)
-bool adopt_in(vapx_ingest* g, int fd, int cls = -1, int cls2 = -1) {
-  int slot = -1;
+// Take over an accepted input connection that came in on input port `via`: the lowest free stream slot gets it, or, `at` >= 0, the slot a
+// front door in another process names (its mirror of this shard is the allocator).  false = no slot for it (fd untouched)
+bool adopt_in(vapx_ingest* g, int fd, int via = 0, int at = -1) {
+  int slot = at;
   {
     // (round 4: this was a scan from slot 0 — 4096 dialogues connecting at once cost the accept thread ~S^2 / 2 slot visits, the output
     // connections queued behind them were attached after the first frames had been answered, and those answers went to nobody)
     std::lock_guard<std::mutex> lk(g->slots_mu);
-    for (int i = g->free_hint; i < g->S; ++i)
-      if (g->slots[i].fd_in < 0) { slot = i; break; }
-    g->free_hint = slot >= 0 ? slot + 1 : g->S;
+    if (at < 0) {
+      for (int i = g->free_hint; i < g->S && slot < 0; ++i)
+        if (g->slots[i].fd_in < 0) slot = i;
+      g->free_hint = slot >= 0 ? slot + 1 : g->S;
+    } else if (at >= g->S || g->slots[at].fd_in >= 0) slot = -1;
     if (slot >= 0) g->slots[slot].fd_in = fd;
   }
   if (slot < 0) return false;
   int one = 1;
   setsockopt(fd, IPPROTO_TCP, TCP_NODELAY, &one, sizeof one);
+  const InPort& ip = g->in_ports[via];
   Slot& s = g->slots[slot];
-  s.wbuf = -1; s.fill = 0; s.npartial = 0; s.backlog.clear(); s.paused = false; s.lowat = 0;
-  s.cls = cls >= 0 ? cls : 0;   // frames of the slot's previous connection that are still queued or being sent carry their own class (Ready::cls)
-  s.planar = cls2 >= 0;         // a pair port
-  s.cls2 = cls2 >= 0 ? cls2 : s.cls;
+  s.wbuf = -1; s.fill = 0; s.backlog.clear(); s.paused = false; s.lowat = 0;
+  // frames of the slot's previous connection that are still queued or being sent carry their own classes (Ready::cls)
+  s.cls = ip.cls; s.cls2 = ip.cls2; s.planar = ip.planar;
   {
     // the carry restarts from zeros for every connection (vap_main.py:368-369); reset_on_connect also clears the
     // model state, which the reference keeps.  Applied by the tick thread before its next step.
     std::lock_guard<std::mutex> lk(g->ready_mu);
-    g->resets.push_back({slot, g->cfg.reset_on_connect ? 0 : 1, cls, s.cls2});   // with a table: the tick thread tells the engine the stream's classes first
+    g->resets.push_back({slot, g->cfg.reset_on_connect ? 0 : 1, g->cls_table ? ip.cls : -1, ip.cls2});   // with a table: the tick thread tells the engine the stream's classes first
   }
   g->in_conns.fetch_add(1);
-  { const double t = mono_now(); if (g->dbg_t_in_first == 0) g->dbg_t_in_first = t; g->dbg_t_in_last = t; }
+  if (at < 0) { const double t = mono_now(); if (g->dbg_t_in_first == 0) g->dbg_t_in_first = t; g->dbg_t_in_last = t; }   // (the accept thread's stamps: VAPX_INGEST_DEBUG)
   ep_add(g->ep[slot % g->R], fd, K_DATA | (uint32_t)slot);
   return true;
 }
 
-// cls: the input class whose port became readable (a front-end with a table), kPairKey + p: pair port p, or -1: the one input port
-constexpr int kPairKey = 0x100;
-void accept_in(vapx_ingest* g, int cls = -1) {
-  const int pair = cls >= kPairKey ? cls - kPairKey : -1;
+// input port `via` became readable
+void accept_in(vapx_ingest* g, int via) {
   for (;;) {
-    int fd = accept4(pair >= 0 ? g->pair_lsock[pair] : cls >= 0 ? g->cls_lsock[cls] : g->lin, nullptr, nullptr, SOCK_NONBLOCK);
+    int fd = accept4(g->in_ports[via].lsock, nullptr, nullptr, SOCK_NONBLOCK);
     if (fd < 0) { accept_failed_for_fds(g); return; }
-    const bool ok = pair >= 0 ? adopt_in(g, fd, g->pair_cls[pair][0], g->pair_cls[pair][1]) : adopt_in(g, fd, cls);
-    if (!ok) close(fd);   // every stream slot is taken
+    if (!adopt_in(g, fd, via)) close(fd);   // every stream slot is taken
   }
 }
 
@@ -828,21 +768,22 @@ std::pair<int, int> next_listener_slot(vapx_ingest* g, int m = 0) {
   return {o.lmin, 0};
 }
 
-// take over an accepted output connection (non-blocking like vap_main.py:346-347): the k-th output connection hears the k-th stream
-void adopt_out(vapx_ingest* g, int fd, int m = 0) {
+// Take over an accepted output connection (non-blocking like vap_main.py:346-347): the k-th output connection hears the k-th stream,
+// or, `at` >= 0, the stream a front door in another process names
+void adopt_out(vapx_ingest* g, int fd, int m = 0, int at = -1) {
   OutPort& o = g->ports[m];
   int one = 1;
   setsockopt(fd, IPPROTO_TCP, TCP_NODELAY, &one, sizeof one);
   g->out_conns.fetch_add(1);
-  { const double t = mono_now(); if (g->dbg_t_out_first == 0) g->dbg_t_out_first = t; g->dbg_t_out_last = t; }
+  if (at < 0) { const double t = mono_now(); if (g->dbg_t_out_first == 0) g->dbg_t_out_first = t; g->dbg_t_out_last = t; }
   if (g->broadcast) { std::lock_guard<std::mutex> lk(g->slots_mu); o.out_all.push_back(fd); return; }
-  const int best = next_listener_slot(g, m).second;
+  const int slot = at >= 0 ? at : next_listener_slot(g, m).second;
   std::lock_guard<std::mutex> lk(g->slots_mu);
-  o.lcursor = best + 1;
-  ++o.lcount[best];
-  std::lock_guard<std::mutex> l2(g->slots[best].lmu);
-  g->slots[best].listeners[m].push_back(fd);
-  if (g->slots[best].dbg_t_attach == 0) g->slots[best].dbg_t_attach = mono_now();
+  if (at < 0) o.lcursor = slot + 1;
+  ++o.lcount[slot];
+  std::lock_guard<std::mutex> l2(g->slots[slot].lmu);
+  g->slots[slot].listeners[m].push_back(fd);
+  if (at < 0 && g->slots[slot].dbg_t_attach == 0) g->slots[slot].dbg_t_attach = mono_now();
 }
 
 void accept_out(vapx_ingest* g, int m) {
@@ -864,41 +805,10 @@ void listener_dropped(vapx_ingest* g, int slot, int m = 0) {
   link_event(g, LK_OUT_CLOSED, slot);
 }
 
-// the same adoptions with the slot named by a front door in another process (its mirror of this shard is the allocator)
-bool adopt_in_at(vapx_ingest* g, int fd, int slot) {
-  if (slot < 0 || slot >= g->S) return false;
-  {
-    std::lock_guard<std::mutex> lk(g->slots_mu);
-    if (g->slots[slot].fd_in >= 0) return false;
-    g->slots[slot].fd_in = fd;
-  }
-  int one = 1;
-  setsockopt(fd, IPPROTO_TCP, TCP_NODELAY, &one, sizeof one);
+// a descriptor that arrived over the link is whatever the door's accept made it: the receive and sender threads need it non-blocking
+void set_nonblocking(int fd) {
   const int fl = fcntl(fd, F_GETFL, 0);
   if (fl >= 0) fcntl(fd, F_SETFL, fl | O_NONBLOCK);
-  Slot& s = g->slots[slot];
-  s.wbuf = -1; s.fill = 0; s.npartial = 0; s.backlog.clear(); s.paused = false; s.lowat = 0;
-  {
-    std::lock_guard<std::mutex> lk(g->ready_mu);
-    g->resets.push_back({slot, g->cfg.reset_on_connect ? 0 : 1, -1});
-  }
-  g->in_conns.fetch_add(1);
-  ep_add(g->ep[slot % g->R], fd, K_DATA | (uint32_t)slot);
-  return true;
-}
-
-void adopt_out_at(vapx_ingest* g, int fd, int slot) {
-  int one = 1;
-  setsockopt(fd, IPPROTO_TCP, TCP_NODELAY, &one, sizeof one);
-  const int fl = fcntl(fd, F_GETFL, 0);
-  if (fl >= 0) fcntl(fd, F_SETFL, fl | O_NONBLOCK);
-  g->out_conns.fetch_add(1);
-  if (g->broadcast) { std::lock_guard<std::mutex> lk(g->slots_mu); g->ports[0].out_all.push_back(fd); return; }
-  if (slot < 0 || slot >= g->S) slot = 0;
-  std::lock_guard<std::mutex> lk(g->slots_mu);
-  ++g->ports[0].lcount[slot];
-  std::lock_guard<std::mutex> l2(g->slots[slot].lmu);
-  g->slots[slot].listeners[0].push_back(fd);
 }
 
 void link_main(vapx_ingest* g) {
@@ -908,10 +818,11 @@ void link_main(vapx_ingest* g) {
     const int rc = link_recv(g->link_fd, &m, &fd, 100);
     if (rc == 0) continue;
     if (rc < 0) break;                       // the front door is gone: keep serving the dialogues we have, take no new ones
+    if (fd >= 0 && (m.kind == LK_ADOPT_IN || m.kind == LK_ADOPT_OUT)) set_nonblocking(fd);
     if (m.kind == LK_ADOPT_IN) {
-      if (fd >= 0 && !adopt_in_at(g, fd, m.a)) { close(fd); link_event(g, LK_IN_CLOSED, m.a); }   // (cannot happen while the door's mirror is right)
+      if (fd >= 0 && (m.a < 0 || !adopt_in(g, fd, 0, m.a))) { close(fd); link_event(g, LK_IN_CLOSED, m.a); }   // (cannot happen while the door's mirror is right)
     } else if (m.kind == LK_ADOPT_OUT) {
-      if (fd >= 0) adopt_out_at(g, fd, m.a);
+      if (fd >= 0) adopt_out(g, fd, 0, m.a >= 0 && m.a < g->S ? m.a : 0);
     } else if (fd >= 0) close(fd);
   }
 }
@@ -922,7 +833,7 @@ void accept_main(vapx_ingest* g) {
     int n = epoll_wait(g->ep_accept, evs, 8, 100);
     for (int i = 0; i < n; ++i) {
       const uint64_t kind = evs[i].data.u64 & ~0xffffffffull;
-      if (kind == K_LISTEN_IN) accept_in(g, g->n_cls ? (int)(evs[i].data.u64 & 0xffffffffu) : -1);
+      if (kind == K_LISTEN_IN) accept_in(g, (int)(evs[i].data.u64 & 0xffffffffu));
       else if (kind == K_LISTEN_OUT) accept_out(g, (int)(evs[i].data.u64 & 0xffffffffu));
     }
   }
@@ -973,7 +884,7 @@ bool send_packet(int fd, iovec* iov, int niov, size_t total) {
 void tx_main(vapx_ingest* g, int x) {
   std::vector<uint8_t> tail(64 + 8 * 256);
   size_t raw_hop = 0;
-  for (int c = 0; c < std::max(g->n_cls, 1); ++c)
+  for (int c = 0; c < g->n_cls; ++c)
     if (g->geo[c].fmt) raw_hop = std::max(raw_hop, (size_t)g->geo[c].hop);
   std::vector<double> expanded(2 * raw_hop);   // a raw format: the echo of a row's channels, decoded from the staging by the table
   constexpr int MAX_R = 10;                  // 50 Hz -> 5 Hz
@@ -1215,7 +1126,7 @@ void tick_main(vapx_ingest* g) {
 
 int engine_step(void* user, int32_t n, const int32_t* ids, const float* audio, float* out) {
   vapx_ingest* g = (vapx_ingest*)user;
-  return vapx_step(g->engine, n, ids, audio, g->n_cls ? 0 : g->hop, out, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);   // a table: the classes size the slots
+  return vapx_step(g->engine, n, ids, audio, g->cls_table ? 0 : g->geo[0].hop, out, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);   // a table: the classes size the slots
 }
 void engine_set_class(void* user, int32_t sid, int32_t cls, int32_t cls2) {
   vapx_ingest* g = (vapx_ingest*)user;
@@ -1277,16 +1188,15 @@ int check_format(const vapx_ingest_config* cfg, int engine_fmt) {
   return VAPX_OK;
 }
 
-InGeo make_geo(int fmt, int in_hz, int frame_hz) {
-  InGeo q;
-  q.fmt = fmt; q.in_hz = in_hz; q.hop = in_hz / frame_hz;
-  q.bps = fmt == VAPX_PCM_F32 ? 4 : fmt == VAPX_PCM_S16 ? 2 : 1;
-  q.pair_bytes = fmt ? 2 * q.bps : PAIR_BYTES;
-  return q;
-}
+// What the engine behind a front-end says of its input (vapx_get_input_rate, _format, _classes).  Over a step function there is none to
+// ask: 16 kHz, and the format and the table are the config's (fmt and n_cls stay -1)
+struct EngineInput {
+  int hz = 16000, fmt = -1, n_cls = -1;
+  vapx_input_class tab[VAPX_MAX_INPUT_CLASSES];
+};
 
 // the class table a front-end serves: the engine's (n_engine > 0; the config's must then be empty or equal to it) or, over a step function
-// (n_engine < 0), the config's.  Sets g->n_cls / cls_pub; VAPX_OK or the refusal, with its message
+// (n_engine < 0), the config's.  Sets g->cls_table / n_cls / cls_pub (the pair ports stay in the config); VAPX_OK or the refusal, with its message
 int check_classes(vapx_ingest* g, const vapx_ingest_config* cfg, int n_engine, const vapx_input_class* engine_tab) {
   const int nc = cfg->n_input_classes;
   if (nc < 0 || nc > VAPX_MAX_INPUT_CLASSES) return open_refused("n_input_classes: the table holds 0 (no classes) .. 16 entries");
@@ -1306,19 +1216,19 @@ int check_classes(vapx_ingest* g, const vapx_ingest_config* cfg, int n_engine, c
       if (cfg->input_classes[i].input_hz != engine_tab[i].input_hz || cfg->input_classes[i].format != engine_tab[i].format)
         return open_refused("vapx_ingest_config.input_classes differs from the engine's table (vapx_set_input_classes): leave it empty or make them equal");
   }
-  g->n_cls = n_engine >= 0 ? n_engine : nc;
-  for (int i = 0; i < g->n_cls; ++i) g->cls_pub[i] = n_engine >= 0 ? engine_tab[i] : cfg->input_classes[i];
+  const int n_tab = n_engine >= 0 ? n_engine : nc;
+  g->cls_table = n_tab > 0;
+  if (g->cls_table) g->n_cls = n_tab;
+  for (int i = 0; i < n_tab; ++i) g->cls_pub[i] = n_engine >= 0 ? engine_tab[i] : cfg->input_classes[i];
   const int np = cfg->n_pair_ports;
   if (np < 0 || np > VAPX_MAX_PAIR_PORTS) return open_refused("n_pair_ports: 0 (no pair ports) .. 16 entries");
-  if (np && !g->n_cls) return open_refused("pair_ports without input classes: a pair port names two classes of the table (vapx_set_input_classes, or input_classes here)");
+  if (np && !g->cls_table) return open_refused("pair_ports without input classes: a pair port names two classes of the table (vapx_set_input_classes, or input_classes here)");
   for (int i = 0; i < np; ++i) {
     if (cfg->pair_ports[i].cls_ch1 < 0 || cfg->pair_ports[i].cls_ch1 >= g->n_cls || cfg->pair_ports[i].cls_ch2 < 0 || cfg->pair_ports[i].cls_ch2 >= g->n_cls)
       return open_refused("pair_ports: a channel's class is not an index into the table of input classes");
     if (cfg->pair_ports[i].port_in < 0) return open_refused("pair_ports: a pair port's input port must be >= 0 (0 = ephemeral)");
   }
-  g->n_pair = np;
-  for (int i = 0; i < np; ++i) { g->pair_cls[i][0] = cfg->pair_ports[i].cls_ch1; g->pair_cls[i][1] = cfg->pair_ports[i].cls_ch2; }
-  if (!g->n_cls) return VAPX_OK;
+  if (!g->cls_table) return VAPX_OK;
   if (cfg->input_format) return open_refused("input_format together with input classes: the format is each class's own");
   if (cfg->port_in < 0 || cfg->port_out < 0)
     return open_refused("a front-end with input classes cannot be a passive shard (port_in = -1): the front door has one input port, a class is known by its port");
@@ -1330,28 +1240,50 @@ int check_classes(vapx_ingest* g, const vapx_ingest_config* cfg, int n_engine, c
   return VAPX_OK;
 }
 
-int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt = -1, int n_engine_cls = -1,
-                const vapx_input_class* engine_tab = nullptr) {
+// The first half of every open: the config against what the engine says of its input, and the one description of the input that follows
+// from the two - classes, geometries, strides, input ports.  g->S, max_batch, hz and the output ports are set.  Touches nothing outside
+// *g: a refusal here leaves the engine as it was
+int configure(vapx_ingest* g, const vapx_ingest_config* cfg_in, const EngineInput& e = EngineInput()) {
   if (!read_config(cfg_in, &g->cfg)) return VAPX_E_INVAL;
   const vapx_ingest_config* cfg = &g->cfg;
   g->debug = getenv("VAPX_INGEST_DEBUG") != nullptr;
   g->no_lowat = getenv("VAPX_INGEST_NO_LOWAT") != nullptr;
-  { const int rc = check_classes(g, cfg, n_engine_cls, engine_tab); if (rc) return rc; }
+  { const int rc = check_classes(g, cfg, e.n_cls, e.tab); if (rc) return rc; }
   if (g->cfg.gain == 0.0) g->cfg.gain = 1.0;
-  { const int rc = check_format(cfg, engine_fmt); if (rc) return rc; }
-  g->fmt = engine_fmt >= 0 ? engine_fmt : cfg->input_format;
-  g->bps = g->fmt == VAPX_PCM_F32 ? 4 : g->fmt == VAPX_PCM_S16 ? 2 : 1;
-  g->pair_bytes = g->fmt ? 2 * g->bps : PAIR_BYTES;
+  { const int rc = check_format(cfg, e.fmt); if (rc) return rc; }
   g->R = cfg->rx_threads > 0 ? std::min(cfg->rx_threads, 16) : 2;
   g->X = cfg->tx_threads > 0 ? std::min(cfg->tx_threads, 16) : 2;
   g->broadcast = cfg->broadcast < 0 ? (g->S == 1) : (cfg->broadcast != 0);
-  g->hop = g->in_hz / g->hz;
-  g->geo[0] = make_geo(g->fmt, g->in_hz, g->hz);   // no table: the one geometry, every slot's
-  for (int c = 0; c < g->n_cls; ++c) g->geo[c] = make_geo(g->cls_pub[c].format, g->cls_pub[c].input_hz, g->hz);
+  g->n_in = 0;
+  if (!g->cls_table) {   // the one-class case: the engine's rate and format (or the config's format), one input port
+    g->cls_pub[0] = {e.hz, e.fmt >= 0 ? e.fmt : cfg->input_format};
+    g->in_ports[g->n_in++].port = cfg->port_in;
+  } else {               // one input port per class (port_in is ignored), then the pair ports
+    for (int c = 0; c < g->n_cls; ++c) { InPort& ip = g->in_ports[g->n_in++]; ip.port = cfg->class_ports_in[c]; ip.cls = ip.cls2 = c; }
+    for (int p = 0; p < cfg->n_pair_ports; ++p) {
+      InPort& ip = g->in_ports[g->n_in++];
+      ip.port = cfg->pair_ports[p].port_in; ip.cls = cfg->pair_ports[p].cls_ch1; ip.cls2 = cfg->pair_ports[p].cls_ch2; ip.planar = true;
+    }
+  }
   g->frame_stride = g->echo_stride = 0;
-  for (int c = 0; c < std::max(g->n_cls, 1); ++c) {
-    g->frame_stride = std::max(g->frame_stride, g->geo[c].frame_bytes());
-    if (!g->geo[c].fmt) g->echo_stride = std::max(g->echo_stride, (size_t)2 * g->geo[c].hop);   // a raw format keeps no f64 echo
+  for (int c = 0; c < g->n_cls; ++c) {
+    InGeo& q = g->geo[c];
+    q.fmt = g->cls_pub[c].format; q.in_hz = g->cls_pub[c].input_hz; q.hop = q.in_hz / g->hz;
+    g->frame_stride = std::max(g->frame_stride, q.frame_bytes());
+    if (!q.fmt) g->echo_stride = std::max(g->echo_stride, (size_t)2 * q.hop);   // a raw format keeps no f64 echo
+  }
+  return VAPX_OK;
+}
+
+// The second half: staging, sockets, threads
+int start(vapx_ingest* g) {
+  const vapx_ingest_config* cfg = &g->cfg;
+  for (int m = 0; m < g->M; ++m) {
+    OutPort& o = g->ports[m];
+    if (o.R <= 1) continue;   // input framing, ticks and batching stay the leader's; this model's packets echo R leader hops as received
+    o.hist.assign((size_t)g->S * (o.R - 1) * 2 * g->geo[0].hop, 0.0);
+    o.hist_n.assign(g->S, 0);
+    o.hist_gen.assign(g->S, 0u);
   }
   g->tick_cls.assign((size_t)g->S * 2, 0);
   g->slots.reset(new Slot[g->S]);
@@ -1392,23 +1324,17 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt
   // port_in < 0: a PASSIVE shard of a multi-GPU front door (vapx_frontdoor_open): it listens on nothing, connections are handed to it
   const bool passive = cfg->port_in < 0;
   if (passive != (cfg->port_out < 0)) return VAPX_E_INVAL;   // a shard is passive on BOTH ports or on none (-1 / >= 0 mixed is a configuration error)
-  if (!passive) {
-    if (g->n_cls) {   // one input port per class; port_in is ignored
-      for (int c = 0; c < g->n_cls; ++c) {
-        g->cls_lsock[c] = listen_on(cfg->class_ports_in[c], cfg->bind_any != 0, &g->cls_port[c]);
-        if (g->cls_lsock[c] < 0) return VAPX_E_INVAL;
-      }
-      for (int p = 0; p < g->n_pair; ++p) {
-        g->pair_lsock[p] = listen_on(cfg->pair_ports[p].port_in, cfg->bind_any != 0, &g->pair_port[p]);
-        if (g->pair_lsock[p] < 0) return VAPX_E_INVAL;
-      }
-      g->port_in = g->cls_port[0];
-    } else g->lin = listen_on(cfg->port_in, cfg->bind_any != 0, &g->port_in);
+  if (passive) g->in_ports[0].port = 0;
+  else {
+    for (int i = 0; i < g->n_in; ++i) {
+      InPort& ip = g->in_ports[i];
+      ip.lsock = listen_on(ip.port, cfg->bind_any != 0, &ip.port);
+      if (ip.lsock < 0) return VAPX_E_INVAL;
+    }
     for (int m = 0; m < g->M; ++m) {
       g->ports[m].lsock = listen_on(m ? g->cfg_ports_out[m] : cfg->port_out, cfg->bind_any != 0, &g->ports[m].port);
       if (g->ports[m].lsock < 0) return VAPX_E_INVAL;
     }
-    if (!g->n_cls && g->lin < 0) return VAPX_E_INVAL;
   }
   g->resume_mu = std::vector<std::mutex>(g->R);
   g->resume.assign(g->R, {});
@@ -1420,9 +1346,7 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt
   for (int m = 0; m < g->M; ++m) g->ports[m].lcount.assign(g->S, 0);
   if (!passive) {
     g->ep_accept = epoll_create1(0);          // own thread: a connect storm must not starve the streams of a receive thread
-    if (!g->n_cls) ep_add(g->ep_accept, g->lin, K_LISTEN_IN);
-    for (int c = 0; c < g->n_cls; ++c) ep_add(g->ep_accept, g->cls_lsock[c], K_LISTEN_IN | (uint32_t)c);
-    for (int p = 0; p < g->n_pair; ++p) ep_add(g->ep_accept, g->pair_lsock[p], K_LISTEN_IN | (uint32_t)(kPairKey + p));
+    for (int i = 0; i < g->n_in; ++i) ep_add(g->ep_accept, g->in_ports[i].lsock, K_LISTEN_IN | (uint32_t)i);
     for (int m = 0; m < g->M; ++m) ep_add(g->ep_accept, g->ports[m].lsock, K_LISTEN_OUT | (uint32_t)m);
     g->accept_thread = std::thread(accept_main, g);
   }
@@ -1439,37 +1363,52 @@ int open_common(vapx_ingest* g, const vapx_ingest_config* cfg_in, int engine_fmt
 
 int engine_group_step(void* user, int32_t n, const int32_t* ids, const float* audio, float* wire_out) {
   vapx_ingest* g = (vapx_ingest*)user;
-  return vapx_step_group(g->engine, n, ids, audio, g->hop, wire_out, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
+  return vapx_step_group(g->engine, n, ids, audio, g->geo[0].hop, wire_out, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
 }
 
-// sample format of the audio the engine takes: fp32 unless vapx_set_input_format said otherwise
-int engine_input_format(vapx_handle engine) {
-  const int32_t f = vapx_get_input_format ? vapx_get_input_format(engine) : VAPX_PCM_F32;
-  return f > 0 ? f : VAPX_PCM_F32;
+// what the engine says of its input: 16 kHz, fp32 and no table unless vapx_set_input_rate / _format / _classes said otherwise (or the
+// program has no such call: the weak symbols above)
+EngineInput engine_input(vapx_handle engine) {
+  EngineInput e;
+  const int32_t hz = vapx_get_input_rate ? vapx_get_input_rate(engine) : 16000;
+  const int32_t fmt = vapx_get_input_format ? vapx_get_input_format(engine) : VAPX_PCM_F32;
+  const int32_t n = vapx_get_input_classes ? vapx_get_input_classes(engine, e.tab, VAPX_MAX_INPUT_CLASSES) : 0;
+  e.hz = hz > 0 ? hz : 16000; e.fmt = fmt > 0 ? fmt : VAPX_PCM_F32; e.n_cls = n > 0 ? n : 0;
+  return e;
 }
 
 // silence in a raw format, for the warm-up: the code of the smallest magnitude (0.0 for s16 and mulaw, 8 * 2^-15 for alaw)
 int silence_byte(int fmt) { return fmt == VAPX_PCM_MULAW ? 0xFF : fmt == VAPX_PCM_ALAW ? 0xD5 : 0; }
 
-// sample rate of the audio the engine takes: 16000 unless vapx_set_input_rate said otherwise
-int engine_input_hz(vapx_handle engine) {
-  const int32_t r = vapx_get_input_rate ? vapx_get_input_rate(engine) : 16000;
-  return r > 0 ? r : 16000;
+// Warm the engine up before the first client connects: the first step of a process loads the code objects and sizes the runtime's pools
+// (hundreds of ms) - paid here, `ticks` times `step` (vapx_step, or vapx_step_group: the whole group per tick) on max_batch slots of silence
+// in class 0's geometry, rows of `out_floats`; then every touched stream is reset (a leader cascades).  Skipped under
+// VAPX_INGEST_KEEP_STATE: the streams hold imported state and the caller has warmed the engine up before importing.  With a table every
+// stream is of class 0 still and the classes size the slots (samples_per_ch = 0)
+void warm_up(const vapx_ingest* g, decltype(&vapx_step) step, size_t out_floats, int ticks) {
+  if (g->cfg.flags & VAPX_INGEST_KEEP_STATE) return;
+  const InGeo& q = g->geo[0];
+  const size_t nw = (size_t)g->max_batch;
+  float* a = (float*)vapx_host_alloc(nw * q.frame_bytes());
+  float* o = (float*)vapx_host_alloc(nw * out_floats * sizeof(float));
+  if (a && o) {
+    memset(a, silence_byte(q.fmt), nw * q.frame_bytes());
+    for (int k = 0; k < ticks; ++k) (void)step(g->engine, (int32_t)nw, nullptr, a, g->cls_table ? 0 : q.hop, o, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
+    for (size_t i = 0; i < nw; ++i) (void)vapx_reset_stream(g->engine, (int32_t)i);
+  }
+  vapx_host_free(a);
+  vapx_host_free(o);
 }
 
-// the engine's class table (vapx_set_input_classes): its length, 0 without one
-int engine_input_classes(vapx_handle engine, vapx_input_class* tab) {
-  const int32_t n = vapx_get_input_classes ? vapx_get_input_classes(engine, tab, VAPX_MAX_INPUT_CLASSES) : 0;
-  return n > 0 ? n : 0;
-}
+bool known_frame_hz(int hz) { return hz == 5 || hz == 10 || hz == 20 || hz == 50; }
 
 // a trunk group's ports: model m's framing, the geometry of its rows in the tick's wire block (vapx_step_group) and its requested port
-int setup_group(vapx_ingest* g, int n_streams, const int32_t* frame_hzs, const int32_t* ctx_frames, const int32_t* modes, int n_models,
-                const vapx_ingest_config& cfg, const int32_t* follower_ports_out, int in_hz = 16000) {
+int setup_group(vapx_ingest* g, const int32_t* frame_hzs, const int32_t* ctx_frames, const int32_t* modes, int n_models,
+                const vapx_ingest_config& cfg, const int32_t* follower_ports_out) {
   if (n_models < 1 || n_models > MAX_MODELS) return open_refused("a group serves one to three models");
   for (int m = 0; m < n_models; ++m) {
     const int hz = frame_hzs[m];
-    if (hz != 5 && hz != 10 && hz != 20 && hz != 50) return open_refused("frame_hz must be 5, 10, 20 or 50");
+    if (!known_frame_hz(hz)) return open_refused("frame_hz must be 5, 10, 20 or 50");
     if (hz > frame_hzs[0]) return open_refused("model 0 leads the group and must be its fastest model: a follower's frame_hz exceeds it");
     if (frame_hzs[0] % hz) return open_refused("the leader's frame_hz must be an integer multiple of every follower's");
   }
@@ -1485,13 +1424,7 @@ int setup_group(vapx_ingest* g, int n_streams, const int32_t* frame_hzs, const i
     g->ports[m].mode = modes[m];
     g->ports[m].wf = wf;
     g->ports[m].off = acc;
-    g->ports[m].R = frame_hzs[0] / frame_hzs[m];
-    if (g->ports[m].R > 1) {   // input framing, ticks and batching stay the leader's; this model's packets echo R leader hops
-      const size_t hop = (size_t)(in_hz / frame_hzs[0]);   // the leader's hop as received
-      g->ports[m].hist.assign((size_t)n_streams * (g->ports[m].R - 1) * 2 * hop, 0.0);
-      g->ports[m].hist_n.assign(n_streams, 0);
-      g->ports[m].hist_gen.assign(n_streams, 0u);
-    }
+    g->ports[m].R = frame_hzs[0] / frame_hzs[m];   // > 1: its echo history is sized with the staging (start)
     g->cfg_ports_out[m] = (m && follower_ports_out) ? follower_ports_out[m - 1] : 0;
     acc += (size_t)wf;
   }
@@ -1500,88 +1433,68 @@ int setup_group(vapx_ingest* g, int n_streams, const int32_t* frame_hzs, const i
   return VAPX_OK;
 }
 
+// The head and the tail every open call shares.  open_begin: the last open error is cleared and the caller's config, whatever its vintage,
+// is read into *probe; false = a null argument (`args`) or a config of unknown size.  open_end: a front-end that did not come up is taken
+// down again; a group's open always says why
+bool open_begin(bool args, const vapx_ingest_config* cfg, vapx_ingest_config* probe) {
+  g_open_error.clear();
+  return args && read_config(cfg, probe);
+}
+int open_end(vapx_ingest* g, int rc, vapx_ingest_handle* out, bool group = false) {
+  if (rc != VAPX_OK) {
+    vapx_ingest_close(g);
+    return group && g_open_error.empty() ? open_refused("could not allocate the staging blocks or bind the ports") : rc;
+  }
+  *out = g;
+  return VAPX_OK;
+}
 }  // namespace
 
 extern "C" {
 
 int vapx_ingest_open_fn(vapx_ingest_step_fn step, vapx_ingest_reset_fn reset, void* user, int32_t n_streams, int32_t max_batch,
                         int32_t frame_hz, int32_t mode, const vapx_ingest_config* cfg, vapx_ingest_handle* out) {
-  g_open_error.clear();
   vapx_ingest_config probe;
-  if (!step || !out || !read_config(cfg, &probe)) return VAPX_E_INVAL;
+  if (!open_begin(step && out, cfg, &probe)) return VAPX_E_INVAL;
   if (n_streams < 1 || max_batch < 1 || max_batch > n_streams) return VAPX_E_INVAL;
-  if (frame_hz != 5 && frame_hz != 10 && frame_hz != 20 && frame_hz != 50) return VAPX_E_INVAL;
+  if (!known_frame_hz(frame_hz)) return VAPX_E_INVAL;
   if (mode < 0 || mode > 2) return VAPX_E_INVAL;
   vapx_ingest* g = new vapx_ingest();
   g->step = step; g->reset = reset; g->user = user;
   g->S = n_streams; g->max_batch = max_batch; g->hz = frame_hz; g->ports[0].mode = mode;
-  int rc = open_common(g, cfg);
-  if (rc != VAPX_OK) { vapx_ingest_close(g); return rc; }
-  *out = g;
-  return VAPX_OK;
+  int rc = configure(g, cfg);
+  if (rc == VAPX_OK) rc = start(g);
+  return open_end(g, rc, out);
 }
 
 int vapx_ingest_open(vapx_handle engine, const vapx_ingest_config* cfg, vapx_ingest_handle* out) {
-  g_open_error.clear();
   vapx_ingest_config probe;
-  if (!engine || !out || !read_config(cfg, &probe)) return VAPX_E_INVAL;
+  if (!open_begin(engine && out, cfg, &probe)) return VAPX_E_INVAL;
   vapx_config ec;
   int rc = vapx_get_config(engine, &ec);
   if (rc != VAPX_OK) return rc;
+  const EngineInput e = engine_input(engine);
   vapx_ingest* g = new vapx_ingest();
   g->engine = engine;
   g->step = engine_step; g->reset = engine_reset; g->user = g;
   g->S = ec.max_streams; g->max_batch = ec.max_batch; g->hz = ec.frame_hz; g->ports[0].mode = ec.mode;
-  g->in_hz = engine_input_hz(engine);
-  const int efmt = engine_input_format(engine);
-  vapx_input_class etab[VAPX_MAX_INPUT_CLASSES];
-  const int ncls = engine_input_classes(engine, etab);
-  if (ncls) g->set_class = engine_set_class;
-  rc = check_classes(g, &probe, ncls, etab);   // before the warm-up: a refused open leaves the engine untouched
-  if (rc == VAPX_OK) rc = check_format(&probe, efmt);
-  if (rc != VAPX_OK) { delete g; return rc; }
-  if (ncls && !(probe.flags & VAPX_INGEST_KEEP_STATE)) {
-    // the warm-up of an engine with a table: every stream is of class 0 still, so the packed block is max_batch slots of class 0
-    const InGeo q = make_geo(etab[0].format, etab[0].input_hz, ec.frame_hz);
-    const int nw = ec.max_batch;
-    float* a = (float*)vapx_host_alloc((size_t)nw * q.frame_bytes());
-    float* o = (float*)vapx_host_alloc((size_t)nw * VAPX_OUT_STRIDE * sizeof(float));
-    if (a && o) {
-      memset(a, silence_byte(q.fmt), (size_t)nw * q.frame_bytes());
-      for (int k = 0; k < 3; ++k) (void)vapx_step(engine, nw, nullptr, a, 0, o, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
-      for (int i = 0; i < nw; ++i) (void)vapx_reset_stream(engine, i);
-    }
-    vapx_host_free(a);
-    vapx_host_free(o);
-  } else if (!(probe.flags & VAPX_INGEST_KEEP_STATE)) {
-     // warm the engine up before the first client connects: the first vapx_step of a process loads the code objects and sizes
-     // the runtime's pools (hundreds of ms) — paid here on silence, then every touched stream is reset (VAPX_INGEST_KEEP_STATE: the
-     // streams hold imported state and the caller has warmed the engine up before importing)
-    const int nw = ec.max_batch, hop = g->in_hz / ec.frame_hz;
-    float* a = (float*)vapx_host_alloc((size_t)nw * 2 * hop * sizeof(float));
-    float* o = (float*)vapx_host_alloc((size_t)nw * VAPX_OUT_STRIDE * sizeof(float));
-    if (a && o) {
-      memset(a, silence_byte(efmt), (size_t)nw * 2 * hop * sizeof(float));   // (a raw format reads the front of the block)
-      for (int k = 0; k < 3; ++k) (void)vapx_step(engine, nw, nullptr, a, hop, o, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
-      for (int i = 0; i < nw; ++i) (void)vapx_reset_stream(engine, i);
-    }
-    vapx_host_free(a);
-    vapx_host_free(o);
+  if (e.n_cls) g->set_class = engine_set_class;
+  rc = configure(g, cfg, e);   // before the warm-up: a refused open leaves the engine untouched
+  if (rc == VAPX_OK) {
+    warm_up(g, vapx_step, VAPX_OUT_STRIDE, 3);
+    rc = start(g);
   }
-  rc = open_common(g, cfg, efmt, ncls, etab);
-  if (rc != VAPX_OK) { vapx_ingest_close(g); return rc; }
-  *out = g;
-  return VAPX_OK;
+  return open_end(g, rc, out);
 }
 
 int32_t vapx_ingest_class_ports(vapx_ingest_handle g, int32_t* ports, int32_t max) {
   if (!g) return VAPX_E_INVAL;
-  for (int c = 0; ports && c < g->n_cls && c < max; ++c) ports[c] = g->cls_port[c];
-  return g->n_cls;
+  for (int c = 0; ports && c < g->tab_cls() && c < max; ++c) ports[c] = g->in_ports[c].port;
+  return g->tab_cls();
 }
 
 int32_t vapx_ingest_stream_class(vapx_ingest_handle g, int32_t stream_id) {
-  if (!g || !g->n_cls) return VAPX_E_INVAL;
+  if (!g || !g->cls_table) return VAPX_E_INVAL;
   if (stream_id < 0 || stream_id >= g->S) return VAPX_E_RANGE;
   const int32_t* c = &g->tick_cls[(size_t)2 * stream_id];
   return c[0] == c[1] ? c[0] : VAPX_E_INVAL;   // a pair port's stream: vapx_ingest_stream_channel_classes
@@ -1589,12 +1502,13 @@ int32_t vapx_ingest_stream_class(vapx_ingest_handle g, int32_t stream_id) {
 
 int32_t vapx_ingest_pair_ports(vapx_ingest_handle g, int32_t* ports, int32_t max) {
   if (!g) return VAPX_E_INVAL;
-  for (int p = 0; ports && p < g->n_pair && p < max; ++p) ports[p] = g->pair_port[p];
-  return g->n_pair;
+  const int n_pair = g->n_in - g->n_cls;      // the input ports behind the classes' own (none without a table)
+  for (int p = 0; ports && p < n_pair && p < max; ++p) ports[p] = g->in_ports[g->n_cls + p].port;
+  return n_pair;
 }
 
 int vapx_ingest_stream_channel_classes(vapx_ingest_handle g, int32_t stream_id, int32_t out[2]) {
-  if (!g || !g->n_cls || !out) return VAPX_E_INVAL;
+  if (!g || !g->cls_table || !out) return VAPX_E_INVAL;
   if (stream_id < 0 || stream_id >= g->S) return VAPX_E_RANGE;
   out[0] = g->tick_cls[(size_t)2 * stream_id];
   out[1] = g->tick_cls[(size_t)2 * stream_id + 1];
@@ -1603,14 +1517,14 @@ int vapx_ingest_stream_channel_classes(vapx_ingest_handle g, int32_t stream_id, 
 
 int vapx_ingest_ports(vapx_ingest_handle g, int32_t* port_in, int32_t* port_out) {
   if (!g) return VAPX_E_INVAL;
-  if (port_in) *port_in = g->port_in;
+  if (port_in) *port_in = g->in_ports[0].port;
   if (port_out) *port_out = g->ports[0].port;
   return VAPX_OK;
 }
 
 int vapx_ingest_group_ports(vapx_ingest_handle g, int32_t* port_in, int32_t* ports_out, int32_t max_ports) {
   if (!g) return VAPX_E_INVAL;
-  if (port_in) *port_in = g->port_in;
+  if (port_in) *port_in = g->in_ports[0].port;
   for (int m = 0; m < g->M && m < max_ports && ports_out; ++m) ports_out[m] = g->ports[m].port;
   return g->M;
 }
@@ -1633,32 +1547,27 @@ int vapx_ingest_open_group_fn(vapx_ingest_group_step_fn step, vapx_ingest_reset_
 int vapx_ingest_open_group_fn2(vapx_ingest_group_step_fn step, vapx_ingest_reset_fn reset, void* user, int32_t n_streams, int32_t max_batch,
                                const int32_t* frame_hzs, const int32_t* ctx_frames, const int32_t* modes, int32_t n_models,
                                const vapx_ingest_config* cfg, const int32_t* follower_ports_out, vapx_ingest_handle* out) {
-  g_open_error.clear();
   vapx_ingest_config probe;
-  if (!step || !out || !modes || !frame_hzs || !ctx_frames || !read_config(cfg, &probe))
+  if (!open_begin(step && out && modes && frame_hzs && ctx_frames, cfg, &probe))
     return open_refused("null argument or a vapx_ingest_config of unknown size");
   if (n_streams < 1 || max_batch < 1 || max_batch > n_streams) return open_refused("need 1 <= max_batch <= n_streams");
   if (n_models < 1 || n_models > MAX_MODELS) return open_refused("a group serves one to three models");
   if (probe.n_input_classes)
     return open_refused("a trunk group's front-end takes no input classes: multi-port groups are not part of the class ports yet");
-  const int32_t frame_hz = frame_hzs[0];
-  if (frame_hz != 5 && frame_hz != 10 && frame_hz != 20 && frame_hz != 50) return open_refused("frame_hz must be 5, 10, 20 or 50");
+  if (!known_frame_hz(frame_hzs[0])) return open_refused("frame_hz must be 5, 10, 20 or 50");
   vapx_ingest* g = new vapx_ingest();
-  int rc = setup_group(g, n_streams, frame_hzs, ctx_frames, modes, n_models, probe, follower_ports_out);
-  if (rc != VAPX_OK) { delete g; return rc; }
   g->step = step; g->reset = reset; g->user = user;
-  g->S = n_streams; g->max_batch = max_batch; g->hz = frame_hz;
-  rc = open_common(g, cfg);
-  if (rc != VAPX_OK) { vapx_ingest_close(g); return g_open_error.empty() ? open_refused("could not allocate the staging blocks or bind the ports") : rc; }
-  *out = g;
-  return VAPX_OK;
+  g->S = n_streams; g->max_batch = max_batch; g->hz = frame_hzs[0];
+  int rc = setup_group(g, frame_hzs, ctx_frames, modes, n_models, probe, follower_ports_out);
+  if (rc == VAPX_OK) rc = configure(g, cfg);
+  if (rc == VAPX_OK) rc = start(g);
+  return open_end(g, rc, out, true);
 }
 
 int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int32_t n_followers, const vapx_ingest_config* cfg,
                            const int32_t* follower_ports_out, vapx_ingest_handle* out) {
-  g_open_error.clear();
   vapx_ingest_config probe;
-  if (!leader || !out || n_followers < 0 || (n_followers && !followers) || !read_config(cfg, &probe))
+  if (!open_begin(leader && out && n_followers >= 0 && (!n_followers || followers), cfg, &probe))
     return open_refused("null argument or a vapx_ingest_config of unknown size");
   if (!vapx_step_group || !vapx_group_wire_floats) return open_refused("this build has no vapx_step_group");
   if (n_followers + 1 > MAX_MODELS) return open_refused("a group serves at most three models (vap, bc, nod)");
@@ -1671,42 +1580,26 @@ int vapx_ingest_open_group(vapx_handle leader, const vapx_handle* followers, int
     if (!followers[i] || vapx_get_config(followers[i], &fc) != VAPX_OK) return open_refused("null follower");
     modes[i + 1] = fc.mode; hzs[i + 1] = fc.frame_hz; ctxs[i + 1] = fc.ctx_frames;
   }
-  {
-    vapx_input_class etab[VAPX_MAX_INPUT_CLASSES];
-    if (engine_input_classes(leader, etab) || probe.n_input_classes)
-      return open_refused("a trunk group's front-end takes no input classes (the leader has a table, or the config names one): multi-port "
-                          "groups are not part of the class ports yet; serve the leader alone, or the group without a table");
-  }
+  const EngineInput e = engine_input(leader);
+  if (e.n_cls || probe.n_input_classes)
+    return open_refused("a trunk group's front-end takes no input classes (the leader has a table, or the config names one): multi-port "
+                        "groups are not part of the class ports yet; serve the leader alone, or the group without a table");
   vapx_ingest* g = new vapx_ingest();
-  g->in_hz = engine_input_hz(leader);
-  const int efmt = engine_input_format(leader);
-  rc = check_format(&probe, efmt);
-  if (rc == VAPX_OK) rc = setup_group(g, ec.max_streams, hzs, ctxs, modes, n_followers + 1, probe, follower_ports_out, g->in_hz);
-  if (rc == VAPX_OK && g->row_floats != vapx_group_wire_floats(leader)) {
-    rc = open_refused("`followers` are not the leader's attached followers (vapx_attach_trunk) in attach order");
-  }
-  if (rc != VAPX_OK) { delete g; return rc; }
   g->engine = leader;
   g->step = engine_group_step; g->reset = engine_reset; g->user = g;
   g->S = ec.max_streams; g->max_batch = ec.max_batch; g->hz = ec.frame_hz;
-  if (!(probe.flags & VAPX_INGEST_KEEP_STATE)) {  // warm-up on silence as in vapx_ingest_open, the whole group per tick; every touched stream is reset (the leader cascades)
-    const int nw = ec.max_batch, hop = g->in_hz / ec.frame_hz;
-    float* a = (float*)vapx_host_alloc((size_t)nw * 2 * hop * sizeof(float));
-    float* o = (float*)vapx_host_alloc((size_t)nw * g->row_floats * sizeof(float));
-    if (a && o) {
-      memset(a, silence_byte(efmt), (size_t)nw * 2 * hop * sizeof(float));   // (a raw format reads the front of the block)
-      int nwarm = 3;   // every model's chain at least once: a slower follower's runs on every R-th tick
-      for (int m = 0; m <= n_followers; ++m) nwarm = std::max(nwarm, g->ports[m].R);
-      for (int k = 0; k < nwarm; ++k) (void)vapx_step_group(leader, nw, nullptr, a, hop, o, VAPX_AUDIO_HOST | VAPX_OUT_HOST, nullptr);
-      for (int i = 0; i < nw; ++i) (void)vapx_reset_stream(leader, i);
-    }
-    vapx_host_free(a);
-    vapx_host_free(o);
+  rc = check_format(&probe, e.fmt);   // (ahead of the group's own refusals, as ever; configure finds nothing more in it)
+  if (rc == VAPX_OK) rc = setup_group(g, hzs, ctxs, modes, n_followers + 1, probe, follower_ports_out);
+  if (rc == VAPX_OK && g->row_floats != vapx_group_wire_floats(leader))
+    rc = open_refused("`followers` are not the leader's attached followers (vapx_attach_trunk) in attach order");
+  if (rc == VAPX_OK) rc = configure(g, cfg, e);
+  if (rc == VAPX_OK) {
+    int ticks = 3;   // every model's chain at least once: a slower follower's runs on every R-th tick
+    for (int m = 0; m < g->M; ++m) ticks = std::max(ticks, g->ports[m].R);
+    warm_up(g, vapx_step_group, g->row_floats, ticks);
+    rc = start(g);
   }
-  rc = open_common(g, cfg, efmt);
-  if (rc != VAPX_OK) { vapx_ingest_close(g); return g_open_error.empty() ? open_refused("could not allocate the staging blocks or bind the ports") : rc; }
-  *out = g;
-  return VAPX_OK;
+  return open_end(g, rc, out, true);
 }
 
 int vapx_ingest_stats_read(vapx_ingest_handle g, vapx_ingest_stats* st, int32_t reset_latency_window) {
@@ -1783,9 +1676,7 @@ void vapx_ingest_close(vapx_ingest_handle g) {
     }
   }
   for (auto& o : g->ports) { for (int fd : o.out_all) close(fd); if (o.lsock >= 0) close(o.lsock); }
-  if (g->lin >= 0) close(g->lin);
-  for (int fd : g->cls_lsock) if (fd >= 0) close(fd);
-  for (int fd : g->pair_lsock) if (fd >= 0) close(fd);
+  for (const InPort& ip : g->in_ports) if (ip.lsock >= 0) close(ip.lsock);
   for (int fd : g->ep) close(fd);
   for (int fd : g->wake) close(fd);
   auto drop = [&](void* p) {
@@ -1964,7 +1855,7 @@ extern "C" {
 
 int vapx_ingest_attach_link(vapx_ingest_handle g, int32_t link_fd) {
   if (!g || link_fd < 0 || g->link_fd >= 0) return VAPX_E_INVAL;
-  if (g->lin >= 0 || g->ports[0].lsock >= 0) return VAPX_E_INVAL;           // only a passive shard takes its connections from a door
+  if (g->in_ports[0].lsock >= 0 || g->ports[0].lsock >= 0) return VAPX_E_INVAL;   // only a passive shard takes its connections from a door
   g->link_fd = link_fd;
   if (!link_send(link_fd, &g->link_mu, LinkMsg{LK_HELLO, g->S, g->hz, g->ports[0].mode | (g->broadcast ? 256 : 0)})) { g->link_fd = -1; return VAPX_E_INVAL; }
   g->link_thread = std::thread(link_main, g);
@@ -2002,7 +1893,7 @@ int vapx_frontdoor_open(vapx_ingest_handle* shards, int32_t n_shards, int32_t po
                         vapx_frontdoor_handle* out) {
   if (!shards || n_shards < 1 || !out || port_in < 0 || port_out < 0) return VAPX_E_INVAL;
   for (int k = 0; k < n_shards; ++k) {
-    if (!shards[k] || shards[k]->lin >= 0 || shards[k]->ports[0].lsock >= 0 || shards[k]->M != 1) return VAPX_E_INVAL;   // shards must be passive (port_in = port_out = -1)
+    if (!shards[k] || shards[k]->in_ports[0].lsock >= 0 || shards[k]->ports[0].lsock >= 0 || shards[k]->M != 1) return VAPX_E_INVAL;   // shards must be passive (port_in = port_out = -1)
     if (shards[k]->hz != shards[0]->hz || shards[k]->ports[0].mode != shards[0]->ports[0].mode) return VAPX_E_INVAL;
   }
   vapx_frontdoor* d = new vapx_frontdoor();
@@ -2047,14 +1938,13 @@ int64_t vapx_wire_decode_input(const uint8_t* bytes, size_t n_bytes, double gain
                                double* x2_f64) {
   if (!bytes || n_bytes % PAIR_BYTES) return VAPX_E_INVAL;   // util.conv_bytearray_2_2floatarray needs whole f64 pairs
   const size_t n = n_bytes / PAIR_BYTES;
-  for (size_t i = 0; i < n; ++i) {
-    double v[2];
-    memcpy(v, bytes + i * PAIR_BYTES, PAIR_BYTES);
-    const double a = gain != 1.0 ? v[0] * gain : v[0], b = gain != 1.0 ? v[1] * gain : v[1];
-    if (x1_f64) x1_f64[i] = a;
-    if (x2_f64) x2_f64[i] = b;
-    if (x1_f32) x1_f32[i] = (float)a;
-    if (x2_f32) x2_f32[i] = (float)b;
+  constexpr size_t CH = 256;   // pairs per pass: an output the caller left out is written to a scratch on the stack, and dropped
+  double no_d[CH];
+  float no_f[CH];
+  for (size_t i = 0; i < n; i += CH) {
+    double* d[2] = {x1_f64 ? x1_f64 + i : no_d, x2_f64 ? x2_f64 + i : no_d};
+    float* f[2] = {x1_f32 ? x1_f32 + i : no_f, x2_f32 ? x2_f32 + i : no_f};
+    move_f64<2>(bytes + i * PAIR_BYTES, std::min(CH, n - i), gain, d, f);
   }
   return (int64_t)n;
 }
