@@ -2,6 +2,7 @@
 // for every geometry, window, batch and number of overlap groups, group g's slice of every buffer starts b0 x (elements per slot) into
 // it, consecutive groups abut and the last one ends exactly at the allocated size.  Plain C++, built with ASan + UBSan by
 // tests/test_engine_buffers.py.  The buffers are address space only (PROT_NONE mappings of the largest size): nothing is read or written.
+// Then vapx_peek's refusal rules (peek_refusal, ring_direct_for, prune_last_for of the same header) against a table written out by hand.
 #include <sys/mman.h>
 
 #include <algorithm>
@@ -34,6 +35,63 @@ static std::map<std::string, size_t> expected_sizes(const int* P, int ncpc, int 
   for (const char* n : {"last[0]", "last[1]", "last[2]", "last[3]", "last[4]", "last[5]"}) m[n] = 512;
   m["qkv_new"] = m["lffn"] = 1536;
   return m;
+}
+
+// vapx_peek's rules (peek_refusal and the two create-time decisions it is given) against the answers written out by hand.  0 = readable
+static void check_peek_rules() {
+  const char* const OK = nullptr;
+  const char *PRE = kPeekNotInPrefill, *LDS = kPeekInLds, *X0 = kPeekX0InRing, *S2 = kPeekStereo2Pruned, *LAST = kPeekLastEveryRow,
+             *NOD = kPeekCombNotNod, *SPLIT = kPeekCombSplit;
+  // every peek name after a step, after a prefill chunk and after either with the fused conv tail: a default engine (vap, the rings read
+  // in place, the last layer on the newest row), one group
+  const PassRecord step{64, 1, false, false}, prefill{40, 1, true, false}, step_tail{64, 1, false, true}, prefill_tail{40, 1, true, true};
+  const struct { const char* name; const char *step, *prefill, *step_tail, *prefill_tail; } by_pass[] = {
+      {"h0", OK, OK, OK, OK},         {"h1", OK, OK, OK, OK},         {"h2", OK, OK, LDS, LDS},       {"h3", OK, OK, LDS, LDS},
+      {"z", OK, OK, OK, OK},          {"lstm_out", OK, PRE, OK, PRE}, {"e", OK, OK, OK, OK},          {"x0", X0, PRE, X0, PRE},
+      {"o", OK, PRE, OK, PRE},        {"stereo0", OK, PRE, OK, PRE},  {"stereo1", OK, PRE, OK, PRE},  {"stereo2", S2, PRE, S2, PRE},
+      {"last", OK, PRE, OK, PRE},     {"comb", NOD, PRE, NOD, PRE},
+  };
+  size_t named = 0;
+  for (const ScratchRow& r : kScratchTable) named += r.peek != nullptr;
+  CHECK(named == sizeof by_pass / sizeof by_pass[0], "%zu peek names in the table, %zu in the hand-written list", named, sizeof by_pass / sizeof by_pass[0]);
+  for (const auto& c : by_pass) {
+    CHECK(scratch_row_by_peek(c.name) != nullptr, "%s is no peek name", c.name);
+    CHECK(peek_refusal(step, VAPX_MODE_VAP, true, true, false, c.name) == c.step, "%s after a step", c.name);
+    CHECK(peek_refusal(prefill, VAPX_MODE_VAP, true, true, false, c.name) == c.prefill, "%s after a prefill", c.name);
+    CHECK(peek_refusal(step_tail, VAPX_MODE_VAP, true, true, false, c.name) == c.step_tail, "%s after a step with the fused tail", c.name);
+    CHECK(peek_refusal(prefill_tail, VAPX_MODE_VAP, true, true, false, c.name) == c.prefill_tail, "%s after a prefill with the fused tail", c.name);
+  }
+  // "x0": the window either side of the short-window block's limit x the two flags that decide
+  const struct { int T, flags; bool ring_direct; } x0s[] = {
+      {64, 0, true},  {64, VAPX_FLAG_UNFUSED_PROJ, true},  {64, VAPX_FLAG_MATERIALIZE_X0, false},
+      {65, 0, true},  {65, VAPX_FLAG_UNFUSED_PROJ, false}, {65, VAPX_FLAG_MATERIALIZE_X0, false},
+  };
+  for (const auto& c : x0s) {
+    CHECK(ring_direct_for(c.flags, c.T) == c.ring_direct, "ring_direct at T = %d, flags 0x%x", c.T, c.flags);
+    CHECK(peek_refusal(step, VAPX_MODE_VAP, ring_direct_for(c.flags, c.T), true, false, "x0") == (c.ring_direct ? X0 : OK), "x0 at T = %d, flags 0x%x", c.T, c.flags);
+  }
+  // the last layer: vap / nod x VAPX_FLAG_FULL_LAST_LAYER
+  const struct { int mode, flags; bool prune; const char *stereo2, *last, *comb; } lasts[] = {
+      {VAPX_MODE_VAP, 0, true, S2, OK, NOD},  {VAPX_MODE_VAP, VAPX_FLAG_FULL_LAST_LAYER, false, OK, LAST, NOD},
+      {VAPX_MODE_NOD, 0, false, OK, LAST, OK}, {VAPX_MODE_NOD, VAPX_FLAG_FULL_LAST_LAYER, false, OK, LAST, OK},
+  };
+  for (const auto& c : lasts) {
+    const bool prune = prune_last_for(c.flags, c.mode);
+    CHECK(prune == c.prune, "prune_last in mode %d, flags 0x%x", c.mode, c.flags);
+    CHECK(peek_refusal(step, c.mode, true, prune, false, "stereo2") == c.stereo2, "stereo2 in mode %d, flags 0x%x", c.mode, c.flags);
+    CHECK(peek_refusal(step, c.mode, true, prune, false, "last") == c.last, "last in mode %d, flags 0x%x", c.mode, c.flags);
+    CHECK(peek_refusal(step, c.mode, true, prune, false, "comb") == c.comb, "comb in mode %d, flags 0x%x", c.mode, c.flags);
+  }
+  CHECK(prune_last_for(0, VAPX_MODE_BC), "bc prunes the last layer");
+  // "comb" in one and in two overlap groups; a released encoder buffer; a name the table does not have
+  const PassRecord two_groups{64, 2, false, false};
+  CHECK(peek_refusal(step, VAPX_MODE_NOD, true, false, false, "comb") == OK, "comb in one group");
+  CHECK(peek_refusal(two_groups, VAPX_MODE_NOD, true, false, false, "comb") == SPLIT, "comb in two groups");
+  CHECK(peek_refusal(two_groups, VAPX_MODE_NOD, true, false, false, "o") == OK, "o in two groups");
+  CHECK(peek_refusal(step, VAPX_MODE_VAP, true, true, true, "h0") == kPeekReleased, "a released h0");
+  CHECK(peek_refusal(prefill, VAPX_MODE_VAP, true, true, true, "lstm_out") == PRE, "a released lstm_out after a prefill: the prefill's rule comes first");
+  CHECK(peek_refusal(step, VAPX_MODE_VAP, true, true, false, "qkv") == kPeekUnknown, "a buffer without a peek name");
+  CHECK(strstr(kPeekCombSplit, "%d") && !strstr(kPeekCombSplit, "%s"), "the one format that takes the group count");
 }
 
 int main() {
@@ -113,6 +171,7 @@ int main() {
   rel.h2 = nullptr; rel.bn = nullptr;
   const Scratch rs = rel.slice(5, geometry(20, 50));
   CHECK(rs.h2 == nullptr && rs.bn == nullptr && rs.h1 == base.h1 + (size_t)5 * 2 * (56 + 2) * 256, "slice of a released buffer");
+  check_peek_rules();
   if (g_fail) { printf("%d checks failed\n", g_fail); return 1; }
   printf("ok: %zu buffers, %ld slices\n", sizeof kScratchTable / sizeof kScratchTable[0], shapes);
   return 0;

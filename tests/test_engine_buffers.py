@@ -1,7 +1,9 @@
 """The engine's buffer table (csrc/engine_buffers.h) tiles every scratch buffer: tests/native/engine_buffers_check.cpp includes
 only that header and holds its per-slot sizes, its poison / follower-release / peek sets and Scratch::slice against figures written
 out by hand, for frame_hz in {5, 10, 20, 50}, T in {1, 64, 65, 250, 512}, B in {1, 77, 1000} and 1 .. 8 overlap groups, under
-Address + UndefinedBehaviour sanitizers.  No GPU involved."""
+Address + UndefinedBehaviour sanitizers.  The same program holds vapx_peek's refusal rules (peek_refusal) against a hand-written table:
+every peek name after a step, a prefill and the fused conv tail, "x0" either side of T = 64, the last layer's buffers in vap / nod mode
+with and without VAPX_FLAG_FULL_LAST_LAYER, "comb" in one and two groups, a released buffer.  No GPU involved."""
 import os
 import shutil
 import subprocess

@@ -52,164 +52,6 @@ struct Weights {
   const float *head_w, *head_wT, *head_b, *vad_w, *vad_b, *aux_w, *aux_b;
 };
 
-// host -> pinned -> device behind an event: the pinned block is reused by the next upload only after the copy out of it has completed
-template <typename T>
-struct Staged {
-  T *dev = nullptr, *pin = nullptr;
-  hipEvent_t evt = nullptr;   // the latest copy out of `pin` has completed
-  hipError_t create_pinned(size_t n) {
-    hipError_t e = hipHostMalloc((void**)&pin, n * sizeof(T), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&evt, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(evt, nullptr);
-    return e;
-  }
-  hipError_t upload(const T* src, size_t n, hipStream_t st) {
-    hipError_t e = hipEventSynchronize(evt);
-    if (e != hipSuccess) return e;
-    memcpy(pin, src, n * sizeof(T));
-    if ((e = hipMemcpyAsync(dev, pin, n * sizeof(T), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-    return hipEventRecord(evt, st);
-  }
-};
-
-}  // namespace
-
-// per-stream state bases; for identity stream ids of a sub-batch starting at slot b0 the bases are
-// simply advanced by b0 streams
-struct StateView {
-  float *ring, *ring_qkv, *h_state, *c_state, *carry;
-  int* frames_seen;
-};
-
-struct vapx_engine : Geometry {
-  vapx_config cfg;
-  std::string err;
-
-  float* w = nullptr;  // weight blob
-  const vapx_layout::Entry* lay = nullptr;
-  size_t lay_n = 0;
-  Layer layer[4];
-  Weights wt = {};
-
-  // per-stream state
-  float *ring = nullptr, *ring_qkv = nullptr, *h_state = nullptr, *c_state = nullptr, *carry = nullptr;
-  int* frames_seen = nullptr;
-
-  // scratch (max_batch); every buffer is linear in the batch index, so a sub-batch starting at
-  // stream slot b0 is just the same struct with offset pointers (Scratch::slice, engine_buffers.h)
-  Scratch sc;
-  Staged<float> audio;   // host audio: device block of the step; pageable memory is staged through the pinned one (vapx_host_alloc memory skips it)
-  Staged<int> ids;       // host stream ids of a step
-  // intra-tick overlap: the batch is split into groups that run on their own HIP streams
-  static constexpr int kMaxGroups = 8;
-  hipStream_t gstream[kMaxGroups] = {};
-  hipEvent_t gdone[kMaxGroups] = {};
-  hipEvent_t gstart = nullptr;
-  int n_groups = 1;
-  // debug knob (env VAPX_POISON_SCRATCH): every scratch buffer the table marks is refilled with NaN bit patterns before each step and the
-  // rings start as NaNs, so a kernel that consumes anything it (or an earlier kernel of the same tick) did not write shows up as a non-finite output
-  bool poison = false;
-  // debug knob (env VAPX_FORCE_ATTENTION_XL, read once per engine in vapx_create): every long window of the fp32 path runs
-  // attention_xl_kernel, so tests can hold it against attention_long2_kernel on windows both kernels take
-  bool force_xl = false;
-#ifdef VAPX_TRACE   // debug build only (make trace -> libvapx_trace.so): per-workgroup phase stamps, tools/ffn_trace.py / tools/attn_trace.py
-  unsigned long long* ffn_trace = nullptr;   // env VAPX_FFN_TRACE=<file>: phase stamps of the layer-0 FFN block's workgroups
-  unsigned long long* attn_trace = nullptr;  // env VAPX_ATTN_TRACE=<file>: phase stamps of the layer-1 self-attention block's workgroups
-  size_t ffn_trace_wgs = 0, attn_trace_wgs = 0;
-  std::string ffn_trace_path, attn_trace_path;
-#endif
-  // the engine's input (input_classes.hip): n_cls = 0, the caller's audio is 16 kHz fp32 and goes to conv0 as it is, nothing below exists.
-  // Otherwise ONE launch of input_classes_kernel turns the tick's block into rs_out, which takes the place of the caller's audio in front of
-  // conv0.  A uniform engine (vapx_set_input_rate and / or vapx_set_input_format) is the one class cls[0]; an engine with a table
-  // (vapx_set_input_classes, cls_table) gives every stream a class of its own
-  int n_cls = 0;
-  bool cls_table = false;
-  InputClassGeom cls[VAPX_MAX_INPUT_CLASSES] = {};
-  int tab_cls() const { return cls_table ? n_cls : 0; }               // what the public class calls see: a uniform engine has no classes
-  int in_fmt() const { return n_cls && !cls_table ? cls[0].fmt : VAPX_PCM_F32; }
-  int in_hz() const {                                                 // 0: no rate of the engine's own (16 kHz, or each class's)
-    static const int hz[4] = {0, 8000, 32000, 48000};                 // by ResampleGeom::orig
-    return n_cls && !cls_table ? hz[cls[0].orig] : 0;
-  }
-  int hop_in() const { return cls[0].hop_in; }                        // a uniform engine's samples per channel and tick
-  size_t cls_lds = 0;                     // floats of dynamic LDS: the largest window of cls[]
-  int rs_rec = 0;                         // floats of a stream's history [2][largest H of cls[]], padded to a multiple of 4; 0: every class is 16 kHz.
-                                          // Channel 2 starts H floats in on a uniform engine and at half the record with a table (input_classes.h)
-  float* rs_hist = nullptr;               // [max_streams][rs_rec], null with rs_rec = 0
-  int* rs_started = nullptr;              // [max_streams * 2] the (stream, channel) has consumed a tick since its reset
-  int rs_row = 0;                         // floats of a row of rs_out: hop; L on a uniform 16 kHz engine, which may be stepped with full frames
-  float* rs_out = nullptr;                // [max_batch][2][rs_row]
-  size_t audio_floats = 0;                // what `audio` (device and pinned) holds: [max_batch][2][L], more where the largest slot needs it
-  vapx_input_class cls_pub[VAPX_MAX_INPUT_CLASSES] = {};   // a table as the caller gave it
-  std::vector<int32_t> stream_cls;        // a table: [max_streams][2] a (stream, channel)'s class; the host builds the slot descriptors from it
-  Staged<int> cls_slots;                  // a table: [max_batch] InputSlot {byte_off, cls} of a step
-  std::vector<InputSlot> cls_slots_host;
-  size_t cls_row_bytes(int c) const { return (size_t)cls[c].hop_in * (size_t)pcm_bytes_per_sample(cls[c].fmt); }   // one channel's row
-  size_t cls_slot_bytes(int c) const { return 2 * cls_row_bytes(c); }
-  float* out_pinned = nullptr;
-  int last_B = 0, last_G = 1;
-  bool last_tail_fused = false;           // some overlap group of the latest encoder pass ran conv_tail_kernel: h2 / h3 were not written
-  bool last_prefill = false;              // the latest encoder pass was a vapx_prefill chunk: last_B (frame, stream) entries, frame-major; no
-                                          // lstm_out, no transformer buffer (vapx_peek refuses them)
-  bool deferred_pending = false;          // the latest step left its overlap groups un-joined (VAPX_DEFER_JOIN)
-  std::vector<int32_t> pending_resets;    // vapx_reset_stream requests, applied stream-ordered by the next step
-  std::vector<uint32_t> id_stamp;         // duplicate-id check: id_stamp[sid] == id_gen <=> sid already in this batch
-  uint32_t id_gen = 0;
-  std::vector<int32_t> bad_slots;         // batch slots of the latest host-output step whose results were not finite
-
-  // shared trunk (vapx_attach_trunk): followers take the leader's LSTM outputs instead of running the CPC encoder
-  vapx_engine* trunk = nullptr;           // set on a follower
-  std::vector<vapx_engine*> followers;    // set on the leader
-  bool orphaned = false;                  // follower whose leader was destroyed
-  uint64_t tick = 0, followed_tick = 0;
-  const int* last_ids = nullptr;          // device ids of the latest step (null = identity)
-  // a follower at its own window and / or at 1/R of the leader's rate (mixed trunk groups)
-  int R = 1;                              // leader ticks per frame of this follower
-  bool own_window = false;                // R == 1, ctx_frames differs from the leader's: bn / bhead from this engine's frames_seen
-  std::vector<int32_t> last_ids_host;     // leader: host copy of the latest step's ids (identity spelled out) ...
-  bool last_ids_known = false;            // ... unless they were device ids
-  std::vector<int32_t> phase;             // R > 1: leader ticks since the stream's last follower frame, per stream
-  float *acc = nullptr, *mixA = nullptr, *out_c = nullptr;   // R > 1: TrunkCollectArgs acc / A, compact output rows [max_batch][784]
-  Staged<int> mix;                        // R > 1: [3][max_batch] stream id | leader slot | pos of this tick's entries
-  std::vector<int> mix_host;              // ... as the host sorts them
-  // vapx_step_group (leader only): the tick's wire rows, model-major, on the device and in page-locked host memory
-  float *gw_dev = nullptr, *gw_pinned = nullptr;
-  size_t gw_cap = 0;                      // floats either block holds
-  std::vector<std::pair<int32_t, int32_t>> group_bad;   // (batch slot, model index) pairs of the latest host-output vapx_step_group
-  // vapx_export_streams / vapx_import_streams: ids of up to max_streams streams; bounded staging blocks for host records (allocated
-  // on the first host-buffer call; the pinned one only for pageable memory)
-  Staged<int> sio_ids;
-  hipEvent_t sio_evt = nullptr;           // the copy out of sio_pin has completed
-  float *sio_dev = nullptr, *sio_pin = nullptr;
-  size_t sio_dev_cap = 0, sio_pin_cap = 0;               // floats
-
-  // optional per-kernel-class HIP-event timing (vapx_profile_*): events are recorded on the launch
-  // stream around the launches whose class bit is set in prof_mask
-  uint32_t prof_mask = 0;
-  struct ProfRec { hipEvent_t a, b; int cls; };
-  std::vector<ProfRec> prof_recs;
-  std::vector<hipEvent_t> prof_pool;
-};
-
-namespace {
-
-int fail(vapx_engine* h, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  if (h) h->err = buf;
-  else g_create_error = buf;
-  return code;
-}
-
-#define HIPCHK(h, expr)                                                                          \
-  do {                                                                                           \
-    hipError_t _e = (expr);                                                                      \
-    if (_e != hipSuccess) return fail(h, VAPX_E_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-
 // debug knob (env VAPX_GUARD_ZONES): every device allocation of the engine gets a 4 KiB canary zone on both sides; vapx_peek("guard_violations")
 // counts the canary bytes that changed, i.e. out-of-bounds writes just past (or before) a buffer
 constexpr size_t kGuardBytes = 4096;
@@ -270,23 +112,196 @@ bool is_pinned_host(const void* p) {
   return at.type == hipMemoryTypeHost;
 }
 
-// device -> host: straight into the caller's block when it is page-locked (the copy is then still in flight on return), else through
-// `pinned`, synchronised and copied on
-hipError_t download(void* dst, const void* src_dev, size_t bytes, void* pinned, hipStream_t st) {
-  if (is_pinned_host(dst)) return hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, st);
-  hipError_t e = hipMemcpyAsync(pinned, src_dev, bytes, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e == hipSuccess) memcpy(dst, pinned, bytes);
-  return e;
+// A device block and the page-locked host block that pageable memory travels through, either way.  The pinned block is behind an event:
+// the next upload reuses it only after the copy out of it has completed
+template <typename T>
+struct Staged {
+  T *dev = nullptr, *pin = nullptr;
+  size_t cap = 0, pin_cap = 0;   // elements the two blocks hold
+  hipEvent_t evt = nullptr;      // the latest copy out of `pin` has completed
+  // reserve: at least n elements in the device block (new ones zero-filled) and, on request, in the pinned one.  Contents are not kept, so
+  // only while no copy is in flight; on failure the old blocks stay as they were
+  hipError_t reserve_pinned(size_t n) {
+    if (!evt) {
+      hipError_t e = hipEventCreateWithFlags(&evt, hipEventDisableTiming);
+      if (e == hipSuccess) e = hipEventRecord(evt, nullptr);
+      if (e != hipSuccess) return e;
+    }
+    if (n <= pin_cap) return hipSuccess;
+    T* np = nullptr;
+    const hipError_t e = hipHostMalloc((void**)&np, n * sizeof(T), hipHostMallocDefault);
+    if (e != hipSuccess) return e;
+    if (pin) (void)hipHostFree(pin);
+    pin = np; pin_cap = n;
+    return hipSuccess;
+  }
+  hipError_t reserve(size_t n, bool with_pinned) {
+    T* nd = nullptr;
+    hipError_t e = n > cap ? dalloc(&nd, n) : hipSuccess;
+    if (e == hipSuccess && with_pinned) e = reserve_pinned(n);
+    if (e != hipSuccess) { dfree(nd); return e; }
+    if (nd) { dfree(dev); dev = nd; cap = n; }
+    return hipSuccess;
+  }
+  // host -> device: straight from a page-locked source (`direct`), else through `pin`
+  hipError_t upload(const T* src, size_t n, hipStream_t st, bool direct = false) {
+    if (direct) return hipMemcpyAsync(dev, src, n * sizeof(T), hipMemcpyHostToDevice, st);
+    hipError_t e = hipEventSynchronize(evt);
+    if (e != hipSuccess) return e;
+    memcpy(pin, src, n * sizeof(T));
+    if ((e = hipMemcpyAsync(dev, pin, n * sizeof(T), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+    return hipEventRecord(evt, st);
+  }
+  // device (`src`, or this block) -> host: straight into the caller's block when it is page-locked (the copy is then still in flight on
+  // return), else through `pin`, synchronised and copied on
+  hipError_t download(void* dst, size_t bytes, hipStream_t st, const T* src = nullptr) {
+    if (!src) src = dev;
+    if (is_pinned_host(dst)) return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(pin, src, bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) memcpy(dst, pin, bytes);
+    return e;
+  }
+  void release() {
+    dfree(dev);
+    if (pin) (void)hipHostFree(pin);
+    if (evt) (void)hipEventDestroy(evt);
+    *this = Staged();
+  }
+};
+
+}  // namespace
+
+// per-stream state bases; for identity stream ids of a sub-batch starting at slot b0 the bases are
+// simply advanced by b0 streams
+struct StateView {
+  float *ring, *ring_qkv, *h_state, *c_state, *carry;
+  int* frames_seen;
+};
+
+struct vapx_engine : Geometry {
+  vapx_config cfg;
+  std::string err;
+
+  float* w = nullptr;  // weight blob
+  const vapx_layout::Entry* lay = nullptr;
+  size_t lay_n = 0;
+  Layer layer[4];
+  Weights wt = {};
+
+  // per-stream state
+  float *ring = nullptr, *ring_qkv = nullptr, *h_state = nullptr, *c_state = nullptr, *carry = nullptr;
+  int* frames_seen = nullptr;
+
+  // scratch (max_batch); every buffer is linear in the batch index, so a sub-batch starting at
+  // stream slot b0 is just the same struct with offset pointers (Scratch::slice, engine_buffers.h)
+  Scratch sc;
+  Staged<float> audio;   // host audio: device block of the step, [max_batch][2][L] floats, more where an input class's largest slot needs it;
+                         // pageable memory is staged through the pinned one (vapx_host_alloc memory skips it)
+  Staged<int> ids;       // host stream ids of a step
+  Staged<float> out;     // pinned block only: a step's output rows (sc.out_dev) on their way to pageable memory
+  bool ring_direct = false, prune_last = false;   // decided once, in vapx_create (engine_buffers.h)
+  PassRecord pass;       // the latest pass through the scratch buffers
+  // intra-tick overlap: the batch is split into groups that run on their own HIP streams
+  static constexpr int kMaxGroups = 8;
+  hipStream_t gstream[kMaxGroups] = {};
+  hipEvent_t gdone[kMaxGroups] = {};
+  hipEvent_t gstart = nullptr;
+  int n_groups = 1;
+  // debug knob (env VAPX_POISON_SCRATCH): every scratch buffer the table marks is refilled with NaN bit patterns before each step and the
+  // rings start as NaNs, so a kernel that consumes anything it (or an earlier kernel of the same tick) did not write shows up as a non-finite output
+  bool poison = false;
+  // debug knob (env VAPX_FORCE_ATTENTION_XL, read once per engine in vapx_create): every long window of the fp32 path runs
+  // attention_xl_kernel, so tests can hold it against attention_long2_kernel on windows both kernels take
+  bool force_xl = false;
+#ifdef VAPX_TRACE   // debug build only (make trace -> libvapx_trace.so): per-workgroup phase stamps, tools/ffn_trace.py / tools/attn_trace.py
+  unsigned long long* ffn_trace = nullptr;   // env VAPX_FFN_TRACE=<file>: phase stamps of the layer-0 FFN block's workgroups
+  unsigned long long* attn_trace = nullptr;  // env VAPX_ATTN_TRACE=<file>: phase stamps of the layer-1 self-attention block's workgroups
+  size_t ffn_trace_wgs = 0, attn_trace_wgs = 0;
+  std::string ffn_trace_path, attn_trace_path;
+#endif
+  // the engine's input (input_classes.hip): n_cls = 0, the caller's audio is 16 kHz fp32 and goes to conv0 as it is, nothing below exists.
+  // Otherwise ONE launch of input_classes_kernel turns the tick's block into rs_out, which takes the place of the caller's audio in front of
+  // conv0.  A uniform engine (vapx_set_input_rate and / or vapx_set_input_format) is the one class cls[0]; an engine with a table
+  // (vapx_set_input_classes, cls_table) gives every stream a class of its own
+  int n_cls = 0;
+  bool cls_table = false;
+  InputClassGeom cls[VAPX_MAX_INPUT_CLASSES] = {};
+  int tab_cls() const { return cls_table ? n_cls : 0; }               // what the public class calls see: a uniform engine has no classes
+  int in_fmt() const { return n_cls && !cls_table ? cls[0].fmt : VAPX_PCM_F32; }
+  int in_hz() const {                                                 // 0: no rate of the engine's own (16 kHz, or each class's)
+    static const int hz[4] = {0, 8000, 32000, 48000};                 // by ResampleGeom::orig
+    return n_cls && !cls_table ? hz[cls[0].orig] : 0;
+  }
+  int hop_in() const { return cls[0].hop_in; }                        // a uniform engine's samples per channel and tick
+  size_t cls_lds = 0;                     // floats of dynamic LDS: the largest window of cls[]
+  int rs_rec = 0;                         // floats of a stream's history [2][largest H of cls[]], padded to a multiple of 4; 0: every class is 16 kHz.
+                                          // Channel 2 starts H floats in on a uniform engine and at half the record with a table (input_classes.h)
+  float* rs_hist = nullptr;               // [max_streams][rs_rec], null with rs_rec = 0
+  int* rs_started = nullptr;              // [max_streams * 2] the (stream, channel) has consumed a tick since its reset
+  int rs_row = 0;                         // floats of a row of rs_out: hop; L on a uniform 16 kHz engine, which may be stepped with full frames
+  float* rs_out = nullptr;                // [max_batch][2][rs_row]
+  vapx_input_class cls_pub[VAPX_MAX_INPUT_CLASSES] = {};   // a table as the caller gave it
+  std::vector<int32_t> stream_cls;        // a table: [max_streams][2] a (stream, channel)'s class; the host builds the slot descriptors from it
+  Staged<int> cls_slots;                  // a table: [max_batch] InputSlot {byte_off, cls} of a step
+  std::vector<InputSlot> cls_slots_host;
+  size_t cls_row_bytes(int c) const { return (size_t)cls[c].hop_in * (size_t)pcm_bytes_per_sample(cls[c].fmt); }   // one channel's row
+  size_t cls_slot_bytes(int c) const { return 2 * cls_row_bytes(c); }
+  bool deferred_pending = false;          // the latest step left its overlap groups un-joined (VAPX_DEFER_JOIN)
+  std::vector<int32_t> pending_resets;    // vapx_reset_stream requests, applied stream-ordered by the next step
+  std::vector<uint32_t> id_stamp;         // duplicate-id check: id_stamp[sid] == id_gen <=> sid already in this batch
+  uint32_t id_gen = 0;
+  std::vector<int32_t> bad_slots;         // batch slots of the latest host-output step whose results were not finite
+
+  // shared trunk (vapx_attach_trunk): followers take the leader's LSTM outputs instead of running the CPC encoder
+  vapx_engine* trunk = nullptr;           // set on a follower
+  std::vector<vapx_engine*> followers;    // set on the leader
+  bool orphaned = false;                  // follower whose leader was destroyed
+  uint64_t tick = 0, followed_tick = 0;
+  const int* last_ids = nullptr;          // device ids of the latest step (null = identity)
+  // a follower at its own window and / or at 1/R of the leader's rate (mixed trunk groups)
+  int R = 1;                              // leader ticks per frame of this follower
+  bool own_window = false;                // R == 1, ctx_frames differs from the leader's: bn / bhead from this engine's frames_seen
+  std::vector<int32_t> last_ids_host;     // leader: host copy of the latest step's ids (identity spelled out) ...
+  bool last_ids_known = false;            // ... unless they were device ids
+  std::vector<int32_t> phase;             // R > 1: leader ticks since the stream's last follower frame, per stream
+  float *acc = nullptr, *mixA = nullptr, *out_c = nullptr;   // R > 1: TrunkCollectArgs acc / A, compact output rows [max_batch][784]
+  Staged<int> mix;                        // R > 1: [3][max_batch] stream id | leader slot | pos of this tick's entries
+  std::vector<int> mix_host;              // ... as the host sorts them
+  // vapx_step_group (leader only): the tick's wire rows, model-major, on the device and in page-locked host memory
+  Staged<float> gw;                       // allocated by the first host-output group step (the follower set is fixed once anyone has stepped)
+  std::vector<std::pair<int32_t, int32_t>> group_bad;   // (batch slot, model index) pairs of the latest host-output vapx_step_group
+  // vapx_export_streams / vapx_import_streams: ids of up to max_streams streams; bounded staging blocks for host records (allocated
+  // on the first host-buffer call; the pinned one only for pageable memory)
+  Staged<int> sio_ids;
+  Staged<float> sio;
+
+  // optional per-kernel-class HIP-event timing (vapx_profile_*): events are recorded on the launch
+  // stream around the launches whose class bit is set in prof_mask
+  uint32_t prof_mask = 0;
+  struct ProfRec { hipEvent_t a, b; int cls; };
+  std::vector<ProfRec> prof_recs;
+  std::vector<hipEvent_t> prof_pool;
+};
+
+namespace {
+
+int fail(vapx_engine* h, int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  if (h) h->err = buf;
+  else g_create_error = buf;
+  return code;
 }
 
-template <typename T>
-void release(Staged<T>& s) {
-  dfree(s.dev);
-  if (s.pin) (void)hipHostFree(s.pin);
-  if (s.evt) (void)hipEventDestroy(s.evt);
-  s = Staged<T>();
-}
+#define HIPCHK(h, expr)                                                                          \
+  do {                                                                                           \
+    hipError_t _e = (expr);                                                                      \
+    if (_e != hipSuccess) return fail(h, VAPX_E_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+  } while (0)
 
 // free (and null) the buffers of the scratch table: all of them, or the encoder's (what a trunk follower never uses)
 void release_scratch(Scratch& sc, bool encoder_only) {
@@ -366,7 +381,7 @@ int run_conv_chain(vapx_engine* h, const Scratch& sc, int B, hipStream_t st) {
   // (on the split-precision path the three GEMMs are 2x cheaper and beat the fp32 fused tail even at 256 streams)
   const bool fused_tail = conv_tail_supported(P[1], h->ncpc) && !(h->cfg.flags & VAPX_FLAG_UNFUSED_CONV) &&
                           !(h->cfg.flags & VAPX_FLAG_SPLIT_F16) && B <= 512;
-  if (fused_tail) h->last_tail_fused = true;   // B is this group's batch: vapx_peek must not re-derive the decision from last_B
+  if (fused_tail) h->pass.tail_fused = true;   // B is this group's batch: vapx_peek must not re-derive the decision from the pass's entries
   for (int i = 0; i < (fused_tail ? 1 : 3); ++i) {
     const ConvSpec& c = cs[i];
     const ConvW& cw = w.conv[i + 1];
@@ -804,12 +819,12 @@ int check_ids(vapx_engine* h, int n, const int32_t* ids) {
   return VAPX_OK;
 }
 
-int upload_ids(vapx_engine* h, int n, const int32_t* ids, int flags, hipStream_t st, const int** out) {
-  if (!ids) { *out = nullptr; return VAPX_OK; }
-  if (flags & VAPX_IDS_DEVICE) { *out = ids; return VAPX_OK; }
-  { int rc = check_ids(h, n, ids); if (rc) return rc; }
-  HIPCHK(h, h->ids.upload(ids, n, st));
-  *out = h->ids.dev;
+// a call's stream ids on the device: host ids (check_ids has passed them) travel through `buf`; device ids and none (identity) stay
+int upload_ids(vapx_engine* h, Staged<int>& buf, int n, const int32_t* ids, int flags, hipStream_t st, const int** out) {
+  *out = ids;
+  if (!ids || (flags & VAPX_IDS_DEVICE)) return VAPX_OK;
+  HIPCHK(h, buf.upload(ids, n, st));
+  *out = buf.dev;
   return VAPX_OK;
 }
 
@@ -839,10 +854,45 @@ int flush_resets(vapx_engine* h, hipStream_t st) {
   return VAPX_OK;
 }
 
-// quiesce the device and apply queued resets (state import / export, peeks)
-int quiesce(vapx_engine* h) {
-  (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
+// Every call that takes an engine runs in one order: its argument checks (host stream ids among them: check_ids) before anything is
+// enqueued, then enter(), then - where it touches stream state or the scratch buffers - settle() or, synchronising, quiesce().
+//
+// enter: a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's, and the device is the engine's
+int enter(vapx_engine* h) {
+  (void)hipGetLastError();
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  return VAPX_OK;
+}
+
+// make `st` wait for overlap groups a VAPX_DEFER_JOIN step left running
+int join_deferred(vapx_engine* h, hipStream_t st) {
+  if (!h->deferred_pending) return VAPX_OK;
+  for (int g = 0; g < h->pass.groups; ++g) HIPCHK(h, hipStreamWaitEvent(st, h->gdone[g], 0));
+  h->deferred_pending = false;
+  return VAPX_OK;
+}
+
+// settle: order `st` behind this engine's un-joined overlap groups and apply the queued resets.  They live in the trunk leader and touch
+// every engine of its group (a follower's head_kernel writes the frame counter the reset zeroes), so with resets queued the leader's and
+// every follower's groups are joined before the leader's reset kernel goes to `st`
+int settle(vapx_engine* h, hipStream_t st) {
+  int rc = join_deferred(h, st);
+  vapx_engine* lead = h->trunk ? h->trunk : h;
+  if (rc || lead->pending_resets.empty()) return rc;
+  if ((rc = join_deferred(lead, st))) return rc;
+  for (vapx_engine* f : lead->followers)
+    if ((rc = join_deferred(f, st))) return rc;
+  rc = flush_resets(lead, st);
+  return rc == VAPX_OK || h == lead ? rc : fail(h, rc, "trunk leader: %s", lead->err.c_str());
+}
+int enter_settled(vapx_engine* h, hipStream_t st) {
+  const int rc = enter(h);
+  return rc ? rc : settle(h, st);
+}
+
+// the synchronising form (vapx_get_state / vapx_set_state, peeks): the device idle, the queued resets applied
+int quiesce(vapx_engine* h) {
+  if (int rc = enter(h)) return rc;
   HIPCHK(h, hipDeviceSynchronize());
   vapx_engine* lead = h->trunk ? h->trunk : h;
   if (!lead->pending_resets.empty()) {
@@ -850,14 +900,6 @@ int quiesce(vapx_engine* h) {
     if (rc) return rc;
     HIPCHK(h, hipDeviceSynchronize());
   }
-  h->deferred_pending = false;
-  return VAPX_OK;
-}
-
-// make `st` wait for overlap groups a VAPX_DEFER_JOIN step left running
-int join_deferred(vapx_engine* h, hipStream_t st) {
-  if (!h->deferred_pending) return VAPX_OK;
-  for (int g = 0; g < h->last_G; ++g) HIPCHK(h, hipStreamWaitEvent(st, h->gdone[g], 0));
   h->deferred_pending = false;
   return VAPX_OK;
 }
@@ -914,15 +956,9 @@ int step_group(vapx_engine* h, const Scratch& sc_own, int nb, int b0, const int*
   ga.e = sc.e; ga.xin = nullptr; ga.ids = ids; ga.bn = sc.bn; ga.bhead = sc.bhead;
   ga.x0 = sc.xl[0]; ga.xn = sc.xn; ga.gamma = h->layer[0].ln_self_g; ga.beta = h->layer[0].ln_self_b;
   ga.B = nb; ga.T = h->T; ga.rows_in = 0;
-  // layer 0 reads the rings in place (no chronological copy): always for the fused short-window block, and for long windows
-  // when they run the fused long-window chain (the GEMM-chain variants need x0 as a plain buffer)
-  const bool ring_direct = !(h->cfg.flags & VAPX_FLAG_MATERIALIZE_X0) &&
-                           (h->T <= 64 || !(h->cfg.flags & VAPX_FLAG_UNFUSED_PROJ));
+  const bool ring_direct = h->ring_direct, prune = h->prune_last;
   ga.rot = sc.rot;
-  if (ring_direct) { ProfScope ps(h, CLS_GATHER, st); HIPCHK(h, launch_ring_append(ga, st)); }
-  else { ProfScope ps(h, CLS_GATHER, st); HIPCHK(h, launch_gather_ln(ga, st)); }
-  // the nod variant emits p_bc for every row of the window, which needs the whole last layer
-  const bool prune = !(h->cfg.flags & VAPX_FLAG_FULL_LAST_LAYER) && h->cfg.mode != VAPX_MODE_NOD;
+  { ProfScope ps(h, CLS_GATHER, st); HIPCHK(h, ring_direct ? launch_ring_append(ga, st) : launch_gather_ln(ga, st)); }
   RingView rv{ring_direct ? sv.ring : nullptr, sv.ring_qkv, ids};
   rc = run_layers(h, sc, nb, st, 0, 4, prune, /*qkv0_ready=*/true, ring_direct ? &rv : nullptr);
   if (rc) return rc;
@@ -985,15 +1021,9 @@ void vapx_destroy(vapx_handle h) {
 #endif
   for (void* p : {(void*)h->w, (void*)h->ring, (void*)h->ring_qkv, (void*)h->h_state, (void*)h->c_state, (void*)h->carry, (void*)h->frames_seen}) dfree(p);
   release_scratch(h->sc, /*encoder_only=*/false);
-  release(h->audio); release(h->ids); release(h->mix); release(h->sio_ids); release(h->cls_slots);
-  dfree(h->rs_hist); dfree(h->rs_out); dfree(h->rs_started);
-  dfree(h->gw_dev);
-  dfree(h->acc); dfree(h->mixA); dfree(h->out_c);
-  dfree(h->sio_dev);
-  if (h->sio_pin) (void)hipHostFree(h->sio_pin);
-  if (h->sio_evt) (void)hipEventDestroy(h->sio_evt);
-  if (h->gw_pinned) (void)hipHostFree(h->gw_pinned);
-  if (h->out_pinned) (void)hipHostFree(h->out_pinned);
+  for (Staged<float>* s : {&h->audio, &h->out, &h->gw, &h->sio}) s->release();
+  for (Staged<int>* s : {&h->ids, &h->mix, &h->sio_ids, &h->cls_slots}) s->release();
+  for (void* p : {(void*)h->rs_hist, (void*)h->rs_out, (void*)h->rs_started, (void*)h->acc, (void*)h->mixA, (void*)h->out_c}) dfree(p);
   if (h->gstart) (void)hipEventDestroy(h->gstart);
   for (int g = 0; g < vapx_engine::kMaxGroups; ++g) {
     if (h->gdone[g]) (void)hipEventDestroy(h->gdone[g]);
@@ -1137,20 +1167,18 @@ int vapx_create(const vapx_config* cfg, const float* blob, size_t n_floats, vapx
   CR(dalloc(&h->c_state, S * 2 * 256));
   CR(dalloc(&h->carry, S * 2 * VAPX_PAD));
   CR(dalloc(&h->frames_seen, S));
-  CR(dalloc(&h->audio.dev, B * 2 * h->L));
-  CR(dalloc(&h->ids.dev, B));
+  CR(h->audio.reserve(B * 2 * h->L, true));
+  CR(h->ids.reserve(B, true));
+  CR(h->sio_ids.reserve(S, true));
+  CR(h->out.reserve_pinned(B * VAPX_OUT_STRIDE));
   for (const ScratchRow& r : kScratchTable) {   // zero-filled: the guard rows of h0 .. h3 stay zero forever
     const ScratchSlot p = r.slot(h->sc);
     if (p.f) CR(dalloc(p.f, B * r.per_slot(*h)));
     else CR(dalloc(p.i, B * r.per_slot(*h)));
   }
-  CR(hipHostMalloc((void**)&h->out_pinned, B * VAPX_OUT_STRIDE * sizeof(float), hipHostMallocDefault));
-  CR(h->ids.create_pinned(B));
-  CR(h->audio.create_pinned(B * 2 * h->L));
-  h->audio_floats = B * 2 * h->L;
-  CR(dalloc(&h->sio_ids.dev, S));
-  CR(h->sio_ids.create_pinned(S));
   h->id_stamp.assign(S, 0u);
+  h->ring_direct = ring_direct_for(cfg->flags, h->T);
+  h->prune_last = prune_last_for(cfg->flags, cfg->mode);
   h->force_xl = getenv("VAPX_FORCE_ATTENTION_XL") != nullptr;
   if (getenv("VAPX_POISON_SCRATCH")) {
     CR(hipMemset(h->ring, 0xFF, S * 2 * T * 256 * sizeof(float)));          // rows beyond frames_seen are never read: prove it
@@ -1175,8 +1203,7 @@ int vapx_create(const vapx_config* cfg, const float* blob, size_t n_floats, vapx
     CR(hipEventCreateWithFlags(&h->gdone[g], hipEventDisableTiming));
   }
   CR(hipEventCreateWithFlags(&h->gstart, hipEventDisableTiming));
-  CR(hipEventCreateWithFlags(&h->sio_evt, hipEventDisableTiming));
-  CR(hipEventRecord(h->sio_evt, nullptr));
+  CR(h->sio.reserve_pinned(0));   // its event, before the synchronisation below: the blocks come with the first host-buffer state call
   CR(hipDeviceSynchronize());
 #undef CR
   *out = h;
@@ -1206,179 +1233,241 @@ static int check_audio(vapx_engine* h, const int32_t* stream_ids, const void* au
   return VAPX_OK;
 }
 
-int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* audio, int32_t spc, float* out,
-              int32_t flags, void* hip_stream) {
-  if (!h) return VAPX_E_INVAL;
-  if (n < 1 || n > h->cfg.max_batch) return fail(h, VAPX_E_RANGE, "n=%d outside [1,%d]", n, h->cfg.max_batch);
-  if (!out) return fail(h, VAPX_E_INVAL, "null out");
-  vapx_engine* lead = h->trunk;
-  if (h->orphaned) return fail(h, VAPX_E_INVAL, "the trunk leader of this engine was destroyed");
-  if (lead) {
-    if (audio) return fail(h, VAPX_E_INVAL, "a trunk follower takes no audio (pass NULL): it consumes its leader's encoder output");
-    if (lead->tick == 0 || lead->tick == h->followed_tick)
-      return fail(h, VAPX_E_INVAL, "step the trunk leader first: no new encoder output since this follower's last step");
-    if (n != lead->last_B) return fail(h, VAPX_E_INVAL, "n=%d differs from the leader's latest step (%d streams)", n, lead->last_B);
-    if (h->R > 1 && !lead->last_ids_known)
-      return fail(h, VAPX_E_INVAL, "the leader's latest step took device stream ids (VAPX_IDS_DEVICE): a follower at 1/%d of the leader's rate "
-                  "needs host ids (or none), the host decides which streams have a frame due", h->R);
-  } else {
-    if (!audio) return fail(h, VAPX_E_INVAL, "null audio");
-    const int rc0 = check_audio(h, stream_ids, audio, spc, flags);
-    if (rc0) return rc0;
-  }
-  if (!stream_ids && n > h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "n exceeds max_streams");
-  hipStream_t st = (hipStream_t)hip_stream;
-  (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  // split the batch into groups on separate HIP streams: streams are independent, and a second
-  // group's kernels fill the prologue / epilogue / tail bubbles of the first group's kernels
-  const bool slower = lead && h->R > 1;
-  int n_run = n;   // rows this engine's chain runs on: a slower follower's streams with a frame due this tick
-  if (slower) {
-    const int32_t* lid = lead->last_ids_host.data();
-    n_run = 0;
-    for (int i = 0; i < n; ++i) n_run += h->phase[lid[i]] + 1 == h->R;
-  }
+// ---- vapx_step in pieces, each straight-line for the role it serves: the leader (or a stand-alone engine), a follower at the leader's
+// rate, a follower at 1/R of it ------------------------------------------------------------------------------------------------------
+
+// overlap groups of a tick on n_run rows: streams are independent, and a second group's kernels fill the prologue / epilogue / tail bubbles
+// of the first group's kernels; a group keeps at least 32 rows
+static int overlap_groups(const vapx_engine* h, int n_run) {
   int G = h->n_groups;
   while (G > 1 && n_run / G < 32) --G;
-  // free-running groups are only safe when nothing of this step is staged through engine-owned buffers on `st`
-  // (host audio / host ids would be overwritten under a still-running group of the previous tick)
-  const bool all_device = (flags & VAPX_OUT_DEVICE) && (lead || (flags & VAPX_AUDIO_DEVICE)) && (!stream_ids || (flags & VAPX_IDS_DEVICE));
-  const bool defer_join = G > 1 && (flags & VAPX_DEFER_JOIN) && all_device && !slower && !h->n_cls;   // rs_out is one buffer: the next tick's input launch must not overtake a running group
-  int rc = VAPX_OK;
-  // a different batch split re-slices the shared scratch, and a reset touches state a running group may still use:
-  // in both cases the previous tick's groups are joined first
-  if (h->deferred_pending && (!defer_join || n != h->last_B || G != h->last_G || !h->pending_resets.empty())) {
-    rc = join_deferred(h, st);
-    if (rc) return rc;
+  return G;
+}
+
+// May the previous tick's un-joined groups keep running under this one?  Only if this one defers too and splits the batch the same way (a
+// different split re-slices the shared scratch); the leader adds: and no reset is queued (it touches state a running group may still use)
+static bool same_split(const vapx_engine* h, int n, int G, bool defer_join) {
+  return defer_join && n == h->pass.entries && G == h->pass.groups && !h->poison;
+}
+
+// VAPX_POISON_SCRATCH: refill what the table marks (a follower's released encoder scratch is null) and the input kernel's rows
+static int poison_scratch(vapx_engine* h, hipStream_t st) {
+  for (const ScratchRow& r : kScratchTable)
+    if (r.poison && scratch_ptr(r, h->sc))
+      HIPCHK(h, hipMemsetAsync(scratch_ptr(r, h->sc), 0xFF, (size_t)h->cfg.max_batch * r.per_slot(*h) * sizeof(float), st));
+  if (h->n_cls) HIPCHK(h, hipMemsetAsync(h->rs_out, 0xFF, (size_t)h->cfg.max_batch * 2 * h->rs_row * sizeof(float), st));
+  return VAPX_OK;
+}
+
+// a follower's admission: it consumes the encoder output of its leader's latest step, once
+static int admit_follower(vapx_engine* h, int n, const float* audio) {
+  const vapx_engine* lead = h->trunk;
+  if (audio) return fail(h, VAPX_E_INVAL, "a trunk follower takes no audio (pass NULL): it consumes its leader's encoder output");
+  if (lead->tick == 0 || lead->tick == h->followed_tick)
+    return fail(h, VAPX_E_INVAL, "step the trunk leader first: no new encoder output since this follower's last step");
+  if (n != lead->pass.entries) return fail(h, VAPX_E_INVAL, "n=%d differs from the leader's latest step (%d streams)", n, lead->pass.entries);
+  if (h->R > 1 && !lead->last_ids_known)
+    return fail(h, VAPX_E_INVAL, "the leader's latest step took device stream ids (VAPX_IDS_DEVICE): a follower at 1/%d of the leader's rate "
+                "needs host ids (or none), the host decides which streams have a frame due", h->R);
+  return VAPX_OK;
+}
+
+// A slower follower's due-plan.  The host advances every stream's phase and sorts the batch into due entries (compact slots 0 .. n_due-1 of
+// this engine's chain) and collecting ones; trunk_collect_kernel does the rest, keyed by stream id.  The plan stays in h->mix.dev as
+// [stream id | leader slot | pos][n]: its first n_due ids are the due streams', in compact order
+static int count_due(const vapx_engine* h, int n) {
+  const int32_t* lid = h->trunk->last_ids_host.data();
+  int n_due = 0;
+  for (int i = 0; i < n; ++i) n_due += h->phase[lid[i]] + 1 == h->R;
+  return n_due;
+}
+static int plan_due(vapx_engine* h, int n, int n_due, hipStream_t st) {
+  const vapx_engine* lead = h->trunk;
+  if (lead->deferred_pending)   // the collect reads every overlap group's LSTM rows (the leader's own flag stays: only `st` waits)
+    for (int g = 0; g < lead->pass.groups; ++g) HIPCHK(h, hipStreamWaitEvent(st, lead->gdone[g], 0));
+  const int32_t* lid = lead->last_ids_host.data();
+  int *e_sid = h->mix_host.data(), *e_slot = e_sid + n, *e_pos = e_sid + 2 * n;
+  int kd = 0, kn = n_due;
+  for (int i = 0; i < n; ++i) {
+    const int sid = lid[i], ph = h->phase[sid];
+    const bool due = ph + 1 == h->R;
+    const int k = due ? kd++ : kn++;
+    e_sid[k] = sid; e_slot[k] = i; e_pos[k] = ph;
+    h->phase[sid] = due ? 0 : ph + 1;
   }
-  if (h->poison) {
-    rc = join_deferred(h, st);
-    if (rc) return rc;
-    for (const ScratchRow& r : kScratchTable)
-      if (r.poison && !(r.encoder && lead))   // a follower has released its encoder scratch
-        HIPCHK(h, hipMemsetAsync(scratch_ptr(r, h->sc), 0xFF, (size_t)h->cfg.max_batch * r.per_slot(*h) * sizeof(float), st));
-    if (h->n_cls) HIPCHK(h, hipMemsetAsync(h->rs_out, 0xFF, (size_t)h->cfg.max_batch * 2 * h->rs_row * sizeof(float), st));
-  }
-  if (!lead) { rc = flush_resets(h, st); if (rc) return rc; }
-  const int* ids = nullptr;
-  if (lead) ids = lead->last_ids;   // same streams, same order as the leader's step (stream_ids is ignored)
-  else rc = upload_ids(h, n, stream_ids, flags, st, &ids);
-  if (rc) return rc;
-  if (!lead) {   // what a slower follower walks: this step's stream ids on the host
-    h->last_ids_known = !(stream_ids && (flags & VAPX_IDS_DEVICE));
-    if (h->last_ids_known && !h->followers.empty()) {
-      h->last_ids_host.resize(n);
-      for (int i = 0; i < n; ++i) h->last_ids_host[i] = stream_ids ? stream_ids[i] : i;
-    }
-  }
-  if (slower) {
-    // the host advances every stream's phase and sorts the batch into due entries (compact slots 0 .. n_run-1 of this engine's
-    // chain) and collecting ones; trunk_collect_kernel does the rest, keyed by stream id
-    if (lead->deferred_pending)   // the collect reads every overlap group's LSTM rows (the leader's own flag stays: only `st` waits)
-      for (int g = 0; g < lead->last_G; ++g) HIPCHK(h, hipStreamWaitEvent(st, lead->gdone[g], 0));
-    const int32_t* lid = lead->last_ids_host.data();
-    int *e_sid = h->mix_host.data(), *e_slot = e_sid + n, *e_pos = e_sid + 2 * n;
-    int kd = 0, kn = n_run;
+  HIPCHK(h, h->mix.upload(e_sid, (size_t)3 * n, st));
+  TrunkCollectArgs ca;
+  ca.lstm_out = lead->sc.lstm_out; ca.acc = h->acc; ca.A = h->mixA; ca.sid = h->mix.dev; ca.slot = h->mix.dev + n; ca.pos = h->mix.dev + 2 * n;
+  ca.frames_seen = h->frames_seen; ca.bn = h->sc.bn; ca.bhead = h->sc.bhead;
+  ca.n = n; ca.n_due = n_due; ca.ncpc_l = lead->ncpc; ca.R = h->R; ca.T = h->T;
+  ProfScope ps(h, CLS_TRUNK_COLLECT, st);
+  HIPCHK(h, launch_trunk_collect(ca, st));
+  return VAPX_OK;
+}
+
+// The leader's input of one batch, on `st`: the caller's block - [n][2][spc] samples of the engine's format, or a table's packed slots,
+// whose descriptors the host builds - goes to the device (unless it is there) and, on an engine with input classes, through ONE launch of
+// the input kernel.  What conv0 and its carry see afterwards is plain rows: [n][2][spc] fp32 at 16 kHz.  Nothing here knows of a step
+struct InputRows { const float* rows; int spc; };
+static int stage_input(vapx_engine* h, int n, const int32_t* stream_ids, const int* ids_dev, const float* audio, int spc, int flags,
+                       hipStream_t st, InputRows* out) {
+  size_t bytes = (size_t)n * 2 * spc * (size_t)pcm_bytes_per_sample(h->in_fmt());
+  if (h->cls_table) {
+    bytes = 0;
     for (int i = 0; i < n; ++i) {
-      const int sid = lid[i], ph = h->phase[sid];
-      const bool due = ph + 1 == h->R;
-      const int k = due ? kd++ : kn++;
-      e_sid[k] = sid; e_slot[k] = i; e_pos[k] = ph;
-      h->phase[sid] = due ? 0 : ph + 1;
+      const int32_t* c = &h->stream_cls[(size_t)2 * (stream_ids ? stream_ids[i] : i)];
+      h->cls_slots_host[i] = {(uint32_t)bytes, input_slot_classes(c[0], c[1])};
+      // channel 1's row, then channel 2's.  Below 2^32: vapx_set_input_classes refused a table whose largest same-class slot x max_batch
+      // is not, and row(c1) + row(c2) <= 2 max(row) = the largest same-class slot
+      bytes += h->cls_row_bytes(c[0]) + h->cls_row_bytes(c[1]);
     }
-    HIPCHK(h, h->mix.upload(e_sid, (size_t)3 * n, st));
-    TrunkCollectArgs ca;
-    ca.lstm_out = lead->sc.lstm_out; ca.acc = h->acc; ca.A = h->mixA; ca.sid = h->mix.dev; ca.slot = h->mix.dev + n; ca.pos = h->mix.dev + 2 * n;
-    ca.frames_seen = h->frames_seen; ca.bn = h->sc.bn; ca.bhead = h->sc.bhead;
-    ca.n = n; ca.n_due = n_run; ca.ncpc_l = lead->ncpc; ca.R = h->R; ca.T = h->T;
-    { ProfScope ps(h, CLS_TRUNK_COLLECT, st); HIPCHK(h, launch_trunk_collect(ca, st)); }
-    ids = h->mix.dev;   // the due streams' ids, in compact order
+    HIPCHK(h, h->cls_slots.upload((const int*)h->cls_slots_host.data(), (size_t)2 * n, st));
   }
   const float* ad = audio;
-  if (!lead) {
-    // bytes of the tick's block: [n][2][spc] samples of the engine's format, or a table's packed slots, whose descriptors the host builds
-    size_t bytes = (size_t)n * 2 * spc * (size_t)pcm_bytes_per_sample(h->in_fmt());
-    if (h->cls_table) {
-      bytes = 0;
-      for (int i = 0; i < n; ++i) {
-        const int32_t* c = &h->stream_cls[(size_t)2 * (stream_ids ? stream_ids[i] : i)];
-        h->cls_slots_host[i] = {(uint32_t)bytes, input_slot_classes(c[0], c[1])};
-        // channel 1's row, then channel 2's.  Below 2^32: vapx_set_input_classes refused a table whose largest same-class slot x max_batch
-        // is not, and row(c1) + row(c2) <= 2 max(row) = the largest same-class slot
-        bytes += h->cls_row_bytes(c[0]) + h->cls_row_bytes(c[1]);
-      }
-      HIPCHK(h, h->cls_slots.upload((const int*)h->cls_slots_host.data(), (size_t)2 * n, st));
-    }
-    if (!(flags & VAPX_AUDIO_DEVICE)) {
-      // pageable memory: stage through the engine's pinned buffer (an async copy from pageable memory is a hidden synchronous staging
-      // copy inside the runtime); vapx_host_alloc memory: copy straight from the caller.  `bytes` is a whole number of dwords
-      // (check_audio; a table's slots are multiples of 16) and never more than `audio` holds (build_input)
-      if (is_pinned_host(audio)) HIPCHK(h, hipMemcpyAsync(h->audio.dev, audio, bytes, hipMemcpyHostToDevice, st));
-      else HIPCHK(h, h->audio.upload(audio, bytes / sizeof(float), st));
-      ad = h->audio.dev;
-    }
-    if (h->n_cls) {   // the block -> 16 kHz fp32 rows, one launch for the whole batch before the overlap groups fork; conv0 and its carry see plain rows
-      if (h->rs_row == h->hop) spc = h->hop;   // else a uniform 16 kHz engine: hop or full frame, as stepped
-      InputClassesArgs ia;
-      ia.in = (const unsigned char*)ad; ia.slots = h->cls_table ? (const InputSlot*)h->cls_slots.dev : nullptr; ia.ids = ids;
-      ia.hist = h->rs_hist; ia.started = h->rs_started; ia.out = h->rs_out; ia.rec = h->rs_rec; ia.out_row = spc;
-      memcpy(ia.cls, h->cls, sizeof ia.cls);
-      HIPCHK(h, launch_input_classes(ia, n, h->cls_lds, st));
-      ad = h->rs_out;
-    }
+  if (!(flags & VAPX_AUDIO_DEVICE)) {
+    // pageable memory: stage through the engine's pinned buffer (an async copy from pageable memory is a hidden synchronous staging
+    // copy inside the runtime); vapx_host_alloc memory: copy straight from the caller.  `bytes` is a whole number of dwords
+    // (check_audio; a table's slots are multiples of 16) and never more than `audio` holds (build_input)
+    HIPCHK(h, h->audio.upload(audio, bytes / sizeof(float), st, is_pinned_host(audio)));
+    ad = h->audio.dev;
   }
-  float* od = (flags & VAPX_OUT_DEVICE) ? out : h->sc.out_dev;
-  float* orows = slower ? h->out_c : od;   // a slower follower's kernels write compact rows; one scatter places them in `od`
+  if (h->n_cls) {   // the block -> 16 kHz fp32 rows, one launch for the whole batch before the overlap groups fork
+    if (h->rs_row == h->hop) spc = h->hop;   // else a uniform 16 kHz engine: hop or full frame, as stepped
+    InputClassesArgs ia;
+    ia.in = (const unsigned char*)ad; ia.slots = h->cls_table ? (const InputSlot*)h->cls_slots.dev : nullptr; ia.ids = ids_dev;
+    ia.hist = h->rs_hist; ia.started = h->rs_started; ia.out = h->rs_out; ia.rec = h->rs_rec; ia.out_row = spc;
+    memcpy(ia.cls, h->cls, sizeof ia.cls);
+    HIPCHK(h, launch_input_classes(ia, n, h->cls_lds, st));
+    ad = h->rs_out;
+  }
+  *out = {ad, spc};
+  return VAPX_OK;
+}
+
+// where a group's encoder output comes from: the engine's own encoder on `audio` (rows of `spc` samples), or - a follower - LSTM rows
+// that exist already in `trunk`, a Scratch sliced by `trunk_geo`
+struct GroupFeed { const float* audio; int spc; const Scratch* trunk; const Geometry* trunk_geo; };
+
+// fork, run, join: the tick's rows [0, n_run) in G groups on HIP streams of their own (G = 1: on `st` itself); with defer_join the groups
+// are left running and `st` does not wait
+static int run_groups(vapx_engine* h, int n_run, int G, const int* ids, const GroupFeed& in, float* orows, hipStream_t st, bool defer_join) {
   if (G > 1) {
     HIPCHK(h, hipEventRecord(h->gstart, st));
     for (int g = 0; g < G; ++g) HIPCHK(h, hipStreamWaitEvent(h->gstream[g], h->gstart, 0));
   }
-  if (!lead) h->last_tail_fused = false;   // run_encoder sets it per group
   for (int g = 0; g < G && n_run > 0; ++g) {
-    int b0 = (int)((long)n_run * g / G), b1 = (int)((long)n_run * (g + 1) / G);
-    const int nb = b1 - b0;
+    const int b0 = (int)((long)n_run * g / G), nb = (int)((long)n_run * (g + 1) / G) - b0;
     hipStream_t gs = G > 1 ? h->gstream[g] : st;
-    const Scratch sc = h->sc.slice(b0, *h);
-    const int* gids = ids ? ids + b0 : nullptr;
-    Scratch lsc;
-    if (slower) lsc.lstm_out = h->mixA + (size_t)b0 * 2 * h->ncpc * 256;   // the collected operand: this engine's own n_cpc rows per frame
-    else if (lead) lsc = lead->sc.slice(b0, *lead);
-    rc = step_group(h, sc, nb, b0, gids, lead ? nullptr : ad + (size_t)b0 * 2 * spc, spc, orows + (size_t)b0 * VAPX_OUT_STRIDE, gs,
-                    lead ? &lsc : nullptr);
+    Scratch trunk;
+    if (in.trunk) trunk = in.trunk->slice(b0, *in.trunk_geo);
+    const int rc = step_group(h, h->sc.slice(b0, *h), nb, b0, ids ? ids + b0 : nullptr, in.audio ? in.audio + (size_t)b0 * 2 * in.spc : nullptr,
+                              in.spc, orows + (size_t)b0 * VAPX_OUT_STRIDE, gs, in.trunk ? &trunk : nullptr);
     if (rc) return rc;
     if (G > 1) HIPCHK(h, hipEventRecord(h->gdone[g], gs));
   }
   if (G > 1 && !defer_join)
     for (int g = 0; g < G; ++g) HIPCHK(h, hipStreamWaitEvent(st, h->gdone[g], 0));
-  if (slower) {
-    OutScatterArgs oa{h->out_c, od, h->mix.dev + n, n, n_run, VAPX_OUT_STRIDE};
+  return VAPX_OK;
+}
+
+// The end of a host-output call.  With `from`: its device block (or `src`) first travels to `rows`, the caller's memory (vapx_host_alloc
+// memory: the copy lands there directly), and `st` is synchronised.  Then e->bad_slots lists the rows - n of them, `stride` floats apart -
+// that carry VAPX_OUT_STATUS = 1, non-finite results (VAPX_STATUS_NO_FRAME, 2, is no fault)
+static int finish_host_rows(vapx_engine* e, Staged<float>* from, const float* src, size_t bytes, float* rows, int n, size_t stride, hipStream_t st) {
+  if (from) {
+    HIPCHK(e, from->download(rows, bytes, st, src));
+    HIPCHK(e, hipStreamSynchronize(st));
+  }
+  e->bad_slots.clear();
+  for (int i = 0; i < n; ++i)
+    if (rows[(size_t)i * stride + VAPX_OUT_STATUS] == 1.f) e->bad_slots.push_back(i);
+  return VAPX_OK;
+}
+
+// the tick is enqueued: what the next call, vapx_peek and vapx_join find; then the output rows of a host-output step
+static int finish_step(vapx_engine* h, int n, int G, const int* ids, bool defer_join, const int32_t* host_ids, float* out, int flags, hipStream_t st) {
+  h->deferred_pending = defer_join;
+  h->pass.groups = G; h->pass.entries = n; h->pass.prefill = false;
+  h->last_ids = ids;
+  if (h->trunk) h->followed_tick = h->trunk->tick; else ++h->tick;
+  if (flags & VAPX_OUT_DEVICE) return VAPX_OK;
+  const int rc = finish_host_rows(h, &h->out, h->sc.out_dev, (size_t)n * VAPX_OUT_STRIDE * sizeof(float), out, n, VAPX_OUT_STRIDE, st);
+  if (rc || h->bad_slots.empty()) return rc;
+  // Fail loudly rather than hand NaNs to a dialogue system — but per stream: the out block is complete, the healthy rows
+  // are valid, the offending batch slots carry VAPX_OUT_STATUS = 1 and are listed by vapx_bad_slots().
+  const int i = h->bad_slots[0];
+  return fail(h, VAPX_E_NUMERIC, "non-finite outputs for batch slot %d (stream %d) and %zu more; the other rows are valid; these streams' state is "
+              "poisoned: reset them (vapx_bad_slots lists the slots)", i, host_ids ? host_ids[i] : i, h->bad_slots.size() - 1);
+}
+
+static int step_leader(vapx_engine* h, int n, const int32_t* stream_ids, const float* audio, int spc, float* out, int flags, hipStream_t st) {
+  const int32_t* host_ids = stream_ids && !(flags & VAPX_IDS_DEVICE) ? stream_ids : nullptr;
+  if (!audio) return fail(h, VAPX_E_INVAL, "null audio");
+  int rc = check_audio(h, stream_ids, audio, spc, flags);
+  if (rc || (host_ids && (rc = check_ids(h, n, host_ids))) || (rc = enter(h))) return rc;
+  const int G = overlap_groups(h, n);
+  // free-running groups are only safe when nothing of this step is staged through engine-owned buffers on `st` (host audio / host ids
+  // would be overwritten under a still-running group of the previous tick); rs_out is one buffer: the next tick's input launch must not
+  // overtake a running group
+  const bool defer_join = G > 1 && (flags & VAPX_DEFER_JOIN) && (flags & VAPX_OUT_DEVICE) && (flags & VAPX_AUDIO_DEVICE) && !host_ids && !h->n_cls;
+  if (!(same_split(h, n, G, defer_join) && h->pending_resets.empty()) && (rc = settle(h, st))) return rc;   // the fast path: nothing is joined
+  if (h->poison && (rc = poison_scratch(h, st))) return rc;
+  const int* ids = nullptr;
+  if ((rc = upload_ids(h, h->ids, n, stream_ids, flags, st, &ids))) return rc;
+  h->last_ids_known = !(stream_ids && (flags & VAPX_IDS_DEVICE));   // what a slower follower walks: this step's stream ids on the host
+  if (h->last_ids_known && !h->followers.empty()) {
+    h->last_ids_host.resize(n);
+    for (int i = 0; i < n; ++i) h->last_ids_host[i] = stream_ids ? stream_ids[i] : i;
+  }
+  InputRows in;
+  if ((rc = stage_input(h, n, stream_ids, ids, audio, spc, flags, st, &in))) return rc;
+  h->pass.tail_fused = false;   // run_conv_chain sets it per group
+  rc = run_groups(h, n, G, ids, GroupFeed{in.rows, in.spc, nullptr, nullptr}, (flags & VAPX_OUT_DEVICE) ? out : h->sc.out_dev, st, defer_join);
+  return rc ? rc : finish_step(h, n, G, ids, defer_join, host_ids, out, flags, st);
+}
+
+// a follower at its leader's rate: the same streams in the same order as the leader's step, the leader's LSTM rows group by group
+static int step_same_rate(vapx_engine* h, int n, const int32_t* host_ids, float* out, int flags, hipStream_t st) {
+  const vapx_engine* lead = h->trunk;
+  const int G = overlap_groups(h, n);
+  const bool defer_join = G > 1 && (flags & VAPX_DEFER_JOIN) && (flags & VAPX_OUT_DEVICE) && !host_ids;
+  int rc = VAPX_OK;
+  if (!same_split(h, n, G, defer_join) && (rc = join_deferred(h, st))) return rc;
+  if (h->poison && (rc = poison_scratch(h, st))) return rc;
+  rc = run_groups(h, n, G, lead->last_ids, GroupFeed{nullptr, 0, &lead->sc, lead}, (flags & VAPX_OUT_DEVICE) ? out : h->sc.out_dev, st, defer_join);
+  return rc ? rc : finish_step(h, n, G, lead->last_ids, defer_join, host_ids, out, flags, st);
+}
+
+// a follower at 1/R of its leader's rate: its chain runs on the streams with a frame due this tick, compact; one scatter places their rows
+// (and the others' VAPX_STATUS_NO_FRAME rows) in the caller's block.  It never defers: its groups split the due streams
+static int step_slower(vapx_engine* h, int n, const int32_t* host_ids, float* out, int flags, hipStream_t st) {
+  const int n_due = count_due(h, n), G = overlap_groups(h, n_due);
+  int rc = VAPX_OK;
+  if ((h->poison && (rc = poison_scratch(h, st))) || (rc = plan_due(h, n, n_due, st))) return rc;
+  Scratch collected;   // the collected operand: this engine's own n_cpc rows per frame
+  collected.lstm_out = h->mixA;
+  if ((rc = run_groups(h, n_due, G, h->mix.dev, GroupFeed{nullptr, 0, &collected, h}, h->out_c, st, false))) return rc;
+  {
+    OutScatterArgs oa{h->out_c, (flags & VAPX_OUT_DEVICE) ? out : h->sc.out_dev, h->mix.dev + n, n, n_due, VAPX_OUT_STRIDE};
     ProfScope ps(h, CLS_TRUNK_COLLECT, st);
     HIPCHK(h, launch_out_scatter(oa, st));
   }
-  h->deferred_pending = defer_join;
-  h->last_G = G;
-  h->last_B = n;
-  h->last_prefill = false;
-  h->last_ids = ids;
-  if (lead) h->followed_tick = lead->tick; else ++h->tick;
-  if (!(flags & VAPX_OUT_DEVICE)) {
-    const size_t bytes = (size_t)n * VAPX_OUT_STRIDE * sizeof(float);
-    HIPCHK(h, download(out, h->sc.out_dev, bytes, h->out_pinned, st));   // vapx_host_alloc memory: lands in the caller's buffer directly
-    HIPCHK(h, hipStreamSynchronize(st));
-    // Fail loudly rather than hand NaNs to a dialogue system — but per stream: the out block is complete, the healthy rows
-    // are valid, the offending batch slots carry VAPX_OUT_STATUS = 1 and are listed by vapx_bad_slots().
-    h->bad_slots.clear();
-    for (int i = 0; i < n; ++i)
-      if (out[(size_t)i * VAPX_OUT_STRIDE + VAPX_OUT_STATUS] == 1.f) h->bad_slots.push_back(i);   // VAPX_STATUS_NO_FRAME (2) is no fault
-    if (!h->bad_slots.empty()) {
-      const int i = h->bad_slots[0];
-      return fail(h, VAPX_E_NUMERIC, "non-finite outputs for batch slot %d (stream %d) and %zu more; the other rows are valid; these streams' state is "
-                  "poisoned: reset them (vapx_bad_slots lists the slots)", i,
-                  (stream_ids && !(flags & VAPX_IDS_DEVICE)) ? stream_ids[i] : i, h->bad_slots.size() - 1);
-    }
-  }
-  return VAPX_OK;
+  return finish_step(h, n, G, h->mix.dev, false, host_ids, out, flags, st);
+}
+
+int vapx_step(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* audio, int32_t spc, float* out,
+              int32_t flags, void* hip_stream) {
+  if (!h) return VAPX_E_INVAL;
+  if (n < 1 || n > h->cfg.max_batch) return fail(h, VAPX_E_RANGE, "n=%d outside [1,%d]", n, h->cfg.max_batch);
+  if (!out) return fail(h, VAPX_E_INVAL, "null out");
+  if (h->orphaned) return fail(h, VAPX_E_INVAL, "the trunk leader of this engine was destroyed");
+  if (!stream_ids && n > h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "n exceeds max_streams");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (!h->trunk) return step_leader(h, n, stream_ids, audio, spc, out, flags, st);
+  const int32_t* host_ids = stream_ids && !(flags & VAPX_IDS_DEVICE) ? stream_ids : nullptr;   // ignored, but for what may be deferred
+  int rc = admit_follower(h, n, audio);
+  if (rc || (rc = enter(h))) return rc;
+  return h->R > 1 ? step_slower(h, n, host_ids, out, flags, st) : step_same_rate(h, n, host_ids, out, flags, st);
 }
 
 int32_t vapx_bad_slots(vapx_handle h, int32_t* slots, int32_t max_slots) {
@@ -1408,16 +1497,8 @@ int vapx_step_group(vapx_handle h, int32_t n, const int32_t* stream_ids, const f
   hipStream_t st = (hipStream_t)hip_stream;
   const bool to_host = !(flags & VAPX_OUT_DEVICE);
   const size_t per = vapx_group_wire_floats(h);
-  (void)hipGetLastError();
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (to_host && h->gw_cap < per * (size_t)h->cfg.max_batch) {   // first group step (the follower set is fixed once anyone has stepped)
-    dfree(h->gw_dev); h->gw_dev = nullptr;
-    if (h->gw_pinned) (void)hipHostFree(h->gw_pinned);
-    h->gw_pinned = nullptr; h->gw_cap = 0;
-    HIPCHK(h, dalloc(&h->gw_dev, per * (size_t)h->cfg.max_batch));
-    HIPCHK(h, hipHostMalloc((void**)&h->gw_pinned, per * (size_t)h->cfg.max_batch * sizeof(float), hipHostMallocDefault));
-    h->gw_cap = per * (size_t)h->cfg.max_batch;
-  }
+  if (int rc = enter(h)) return rc;
+  if (to_host) HIPCHK(h, h->gw.reserve(per * (size_t)h->cfg.max_batch, true));
   // every model device-resident, on the one stream: exactly the vapx_step(.., VAPX_OUT_DEVICE, ..) path (VAPX_DEFER_JOIN is dropped:
   // the pack kernel below consumes every overlap group's rows)
   int rc = vapx_step(h, n, stream_ids, audio, spc, h->sc.out_dev, (flags & (VAPX_AUDIO_DEVICE | VAPX_IDS_DEVICE)) | VAPX_OUT_DEVICE, hip_stream);
@@ -1427,7 +1508,7 @@ int vapx_step_group(vapx_handle h, int32_t n, const int32_t* stream_ids, const f
     rc = vapx_step(f, n, nullptr, nullptr, 0, f->sc.out_dev, VAPX_OUT_DEVICE, hip_stream);
     if (rc) return fail(h, rc, "follower %zu: %s", i, f->err.c_str());
   }
-  float* wd = to_host ? h->gw_dev : wire_out;
+  float* wd = to_host ? h->gw.dev : wire_out;
   const int M = 1 + (int)h->followers.size();
   std::vector<int> wf(M);
   std::vector<size_t> off(M);
@@ -1451,15 +1532,13 @@ int vapx_step_group(vapx_handle h, int32_t n, const int32_t* stream_ids, const f
   }
   h->group_bad.clear();
   if (!to_host) return VAPX_OK;
-  const size_t bytes = (size_t)n * per * sizeof(float);
-  HIPCHK(h, download(wire_out, h->gw_dev, bytes, h->gw_pinned, st));   // vapx_host_alloc memory: the one D2H copy of the tick lands in the caller's block
-  HIPCHK(h, hipStreamSynchronize(st));
-  // per stream and per model, as vapx_step: the block is complete, the offending rows carry VAPX_OUT_STATUS = 1
+  // per stream and per model, as vapx_step: the block is complete, the offending rows carry VAPX_OUT_STATUS = 1.  The leader's call
+  // brings the whole block: the one D2H copy of the tick
   for (int m = 0; m < M; ++m) {
     vapx_engine* e = m ? h->followers[m - 1] : h;
-    e->bad_slots.clear();
-    for (int i = 0; i < n; ++i)
-      if (wire_out[off[m] + (size_t)i * wf[m] + VAPX_OUT_STATUS] == 1.f) { e->bad_slots.push_back(i); h->group_bad.push_back({i, m}); }
+    rc = finish_host_rows(e, m ? nullptr : &h->gw, nullptr, (size_t)n * per * sizeof(float), wire_out + off[m], n, (size_t)wf[m], st);
+    if (rc) return rc;
+    for (int i : e->bad_slots) h->group_bad.push_back({i, m});
   }
   if (!h->group_bad.empty())
     return fail(h, VAPX_E_NUMERIC, "non-finite outputs for batch slot %d in model %d and %zu more (slot, model) pairs; the other rows are valid; "
@@ -1490,9 +1569,8 @@ void vapx_host_free(void* p) {
 
 int vapx_join(vapx_handle h, void* hip_stream) {
   if (!h) return VAPX_E_INVAL;
-  (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  for (int g = 0; g < h->last_G && h->last_G > 1; ++g) HIPCHK(h, hipStreamWaitEvent((hipStream_t)hip_stream, h->gdone[g], 0));
+  if (int rc = enter(h)) return rc;
+  for (int g = 0; g < h->pass.groups && h->pass.groups > 1; ++g) HIPCHK(h, hipStreamWaitEvent((hipStream_t)hip_stream, h->gdone[g], 0));
   return VAPX_OK;   // deferred_pending stays set: only `hip_stream` waited, a later step on another stream still has to
 }
 
@@ -1534,8 +1612,7 @@ int vapx_attach_trunk(vapx_handle f, vapx_handle lead) {
     hipError_t e = dalloc(&f->acc, S * 2 * (size_t)(R - 1) * lead->ncpc * 256);
     if (e == hipSuccess) e = dalloc(&f->mixA, B * 2 * (size_t)f->ncpc * 256);
     if (e == hipSuccess) e = dalloc(&f->out_c, B * VAPX_OUT_STRIDE);
-    if (e == hipSuccess) e = dalloc(&f->mix.dev, 3 * B);
-    if (e == hipSuccess) e = f->mix.create_pinned(3 * B);
+    if (e == hipSuccess) e = f->mix.reserve(3 * B, true);
     if (e != hipSuccess) {   // nothing of the engine is released yet: it stays a stand-alone engine
       (void)hipGetLastError();
       return fail(f, e == hipErrorOutOfMemory ? VAPX_E_NOMEM : VAPX_E_HIP, "state of a 1/%d-rate follower: %s", R, hipGetErrorString(e));
@@ -1545,7 +1622,8 @@ int vapx_attach_trunk(vapx_handle f, vapx_handle lead) {
   }
   // a follower never runs the encoder: release its encoder scratch and LSTM / carry state
   release_scratch(f->sc, /*encoder_only=*/true);
-  for (float** p : {&f->audio.dev, &f->h_state, &f->c_state, &f->carry}) { dfree(*p); *p = nullptr; }
+  f->audio.release();
+  for (float** p : {&f->h_state, &f->c_state, &f->carry}) { dfree(*p); *p = nullptr; }
   f->R = R;
   f->own_window = R == 1 && f->T != lead->T;
   f->trunk = lead;
@@ -1664,24 +1742,6 @@ size_t state_floats(const vapx_engine* h, int flags) {
          ((flags & VAPX_STATE_CACHE) ? (size_t)2 * h->T * 768 : 0);
 }
 
-// what every state call does first: order `st` behind un-joined overlap groups and apply the queued resets (they live in the leader and
-// touch every engine of its trunk group, so with resets pending every engine's groups are joined first)
-int sio_begin(vapx_engine* h, hipStream_t st) {
-  (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  int rc = join_deferred(h, st);
-  if (rc) return rc;
-  vapx_engine* lead = h->trunk ? h->trunk : h;
-  if (!lead->pending_resets.empty()) {
-    if ((rc = join_deferred(lead, st))) return rc;
-    for (vapx_engine* f : lead->followers)
-      if ((rc = join_deferred(f, st))) return rc;
-    rc = flush_resets(lead, st);
-    if (rc) return h == lead ? rc : fail(h, rc, "trunk leader: %s", lead->err.c_str());
-  }
-  return VAPX_OK;
-}
-
 // common argument checks; host ids are validated here, before anything is enqueued
 int sio_check(vapx_engine* h, const char* what, int n, const int32_t* ids, const void* buf, int flags) {
   if (h->R > 1)   // the record has no place yet for the leader rows of a frame in the making (acc) and the stream's phase
@@ -1695,16 +1755,8 @@ int sio_check(vapx_engine* h, const char* what, int n, const int32_t* ids, const
   return VAPX_OK;
 }
 
-// device copy of host ids (up to max_streams of them: the step's id buffers hold max_batch)
-int sio_ids(vapx_engine* h, int n, const int32_t* ids, int flags, hipStream_t st, const int** out) {
-  if (!ids || (flags & VAPX_IDS_DEVICE)) { *out = ids; return VAPX_OK; }
-  HIPCHK(h, h->sio_ids.upload(ids, n, st));
-  *out = h->sio_ids.dev;
-  return VAPX_OK;
-}
-
 // staging blocks for host records: streams per block (>= 1).  Every host-buffer call ends with the stream synchronised, so a block that
-// has to grow is idle.
+// has to grow is idle.  (The ids of a state call, up to max_streams of them, travel through sio_ids: the step's id buffers hold max_batch)
 int sio_stage(vapx_engine* h, size_t rec, int n, bool need_pinned, int* per_block) {
   size_t cap = kStateStageFloats;
   if (const char* ev = getenv("VAPX_STATE_STAGE_FLOATS")) {   // debug knob: small blocks, so that a test with a handful of streams takes the multi-block path
@@ -1715,18 +1767,11 @@ int sio_stage(vapx_engine* h, size_t rec, int n, bool need_pinned, int* per_bloc
   if (per < 1) per = 1;
   if (per > (size_t)n) per = (size_t)n;
   const size_t want = per * rec;
-  if (h->sio_dev_cap < want) {
-    dfree(h->sio_dev); h->sio_dev = nullptr; h->sio_dev_cap = 0;
-    hipError_t e = dalloc(&h->sio_dev, want, false);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, VAPX_E_NOMEM, "state staging block (%zu bytes, device): %s", want * 4, hipGetErrorString(e)); }
-    h->sio_dev_cap = want;
-  }
-  if (need_pinned && h->sio_pin_cap < want) {
-    if (h->sio_pin) (void)hipHostFree(h->sio_pin);
-    h->sio_pin = nullptr; h->sio_pin_cap = 0;
-    hipError_t e = hipHostMalloc((void**)&h->sio_pin, want * sizeof(float), hipHostMallocDefault);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, VAPX_E_NOMEM, "state staging block (%zu bytes, pinned): %s", want * 4, hipGetErrorString(e)); }
-    h->sio_pin_cap = want;
+  hipError_t e = h->sio.reserve(want, false);
+  if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, VAPX_E_NOMEM, "state staging block (%zu bytes, device): %s", want * 4, hipGetErrorString(e)); }
+  if (need_pinned && (e = h->sio.reserve_pinned(want)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(h, VAPX_E_NOMEM, "state staging block (%zu bytes, pinned): %s", want * 4, hipGetErrorString(e));
   }
   *per_block = (int)per;
   return VAPX_OK;
@@ -1757,10 +1802,9 @@ int vapx_export_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, flo
                             "records with per-stream history sizes do not exist yet (vapx_get_state / vapx_set_state work)", "vapx_export_streams");
   { int rc = sio_check(h, "vapx_export_streams", n, stream_ids, dst, flags); if (rc) return rc; }
   hipStream_t st = (hipStream_t)hip_stream;
-  int rc = sio_begin(h, st);
-  if (rc) return rc;
   const int* ids = nullptr;
-  if ((rc = sio_ids(h, n, stream_ids, flags, st, &ids))) return rc;
+  int rc = enter_settled(h, st);
+  if (rc || (rc = upload_ids(h, h->sio_ids, n, stream_ids, flags, st, &ids))) return rc;
   if (flags & VAPX_OUT_DEVICE) {   // one gather kernel, no synchronisation
     HIPCHK(h, launch_state_export(sio_args(h, flags, dst, ids, n), st));
     return VAPX_OK;
@@ -1771,12 +1815,10 @@ int vapx_export_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, flo
   if ((rc = sio_stage(h, rec, n, !direct, &per))) return rc;
   for (int k0 = 0; k0 < n; k0 += per) {
     const int nb = std::min(per, n - k0);
-    StateIoArgs a = sio_args(h, flags, h->sio_dev, ids ? ids + k0 : nullptr, nb);
+    StateIoArgs a = sio_args(h, flags, h->sio.dev, ids ? ids + k0 : nullptr, nb);
     a.id0 = k0;
     HIPCHK(h, launch_state_export(a, st));
-    const size_t bytes = (size_t)nb * rec * sizeof(float);
-    float* to = dst + (size_t)k0 * rec;
-    HIPCHK(h, download(to, h->sio_dev, bytes, h->sio_pin, st));   // pageable: block by block through the pinned buffer
+    HIPCHK(h, h->sio.download(dst + (size_t)k0 * rec, (size_t)nb * rec * sizeof(float), st));   // pageable: block by block through the pinned buffer
   }
   HIPCHK(h, hipStreamSynchronize(st));
   return VAPX_OK;
@@ -1818,10 +1860,9 @@ int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, con
     }
   }
   hipStream_t st = (hipStream_t)hip_stream;
-  int rc = sio_begin(h, st);
-  if (rc) return rc;
   const int* ids = nullptr;
-  if ((rc = sio_ids(h, n, stream_ids, flags, st, &ids))) return rc;
+  int rc = enter_settled(h, st);
+  if (rc || (rc = upload_ids(h, h->sio_ids, n, stream_ids, flags, st, &ids))) return rc;
   if (!on_host) {   // one scatter kernel, no synchronisation
     HIPCHK(h, launch_state_import(sio_args(h, flags, const_cast<float*>(src), ids, n), st));
   } else {
@@ -1830,16 +1871,8 @@ int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, con
     if ((rc = sio_stage(h, rec, n, !direct, &per))) return rc;
     for (int k0 = 0; k0 < n; k0 += per) {
       const int nb = std::min(per, n - k0);
-      const size_t bytes = (size_t)nb * rec * sizeof(float);
-      const float* from = src + (size_t)k0 * rec;
-      if (!direct) {
-        HIPCHK(h, hipEventSynchronize(h->sio_evt));   // the previous block has left the pinned buffer
-        memcpy(h->sio_pin, from, bytes);
-        from = h->sio_pin;
-      }
-      HIPCHK(h, hipMemcpyAsync(h->sio_dev, from, bytes, hipMemcpyHostToDevice, st));
-      if (!direct) HIPCHK(h, hipEventRecord(h->sio_evt, st));
-      StateIoArgs a = sio_args(h, flags, h->sio_dev, ids ? ids + k0 : nullptr, nb);
+      HIPCHK(h, h->sio.upload(src + (size_t)k0 * rec, (size_t)nb * rec, st, direct));   // pageable: once the previous block has left the pinned buffer
+      StateIoArgs a = sio_args(h, flags, h->sio.dev, ids ? ids + k0 : nullptr, nb);
       a.id0 = k0;
       HIPCHK(h, launch_state_import(a, st));
     }
@@ -1890,16 +1923,10 @@ int vapx_prefill(vapx_handle h, int32_t n, const int32_t* stream_ids, const floa
   if ((uintptr_t)audio & 15) return fail(h, VAPX_E_INVAL, "vapx_prefill: the audio block must be 16-byte aligned");
   if (flags & ~(VAPX_AUDIO_DEVICE | VAPX_IDS_DEVICE)) return fail(h, VAPX_E_INVAL, "vapx_prefill: unknown flag bits 0x%x", flags);
   if (!stream_ids && n > h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "vapx_prefill: n exceeds max_streams");
-  const bool host_ids = stream_ids && !(flags & VAPX_IDS_DEVICE);
-  if (host_ids) { int rc = check_ids(h, n, stream_ids); if (rc) return rc; }   // before anything is enqueued
   hipStream_t st = (hipStream_t)hip_stream;
-  (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  int rc = join_deferred(h, st);
-  if (rc) return rc;
-  if ((rc = flush_resets(h, st))) return rc;
-  const int* ids = stream_ids;
-  if (host_ids) { HIPCHK(h, h->ids.upload(stream_ids, n, st)); ids = h->ids.dev; }
+  const int* ids = nullptr;
+  int rc = stream_ids && !(flags & VAPX_IDS_DEVICE) ? check_ids(h, n, stream_ids) : VAPX_OK;
+  if (rc || (rc = enter_settled(h, st)) || (rc = upload_ids(h, h->ids, n, stream_ids, flags, st, &ids))) return rc;
 
   const int hop = h->hop, T = h->T, Fc = prefill_chunk_frames(h->cfg.max_batch, n);
   const bool on_dev = (flags & VAPX_AUDIO_DEVICE) != 0, direct = !on_dev && is_pinned_host(audio);
@@ -1937,8 +1964,7 @@ int vapx_prefill(vapx_handle h, int32_t n, const int32_t* stream_ids, const floa
     c0.frames_seen = sv.frames_seen; c0.bhead = f0 ? nullptr : sc.bhead; c0.L = h->L; c0.n = n; c0.T = T;
     { ProfScope ps(h, CLS_CONV0, st); HIPCHK(h, launch_conv0_prefill(c0, V, st)); }
     // what vapx_peek finds afterwards is this chunk: V entries in one group, h2 / h3 only where the chain ran
-    h->last_tail_fused = false;
-    h->last_B = V; h->last_G = 1; h->last_prefill = true;
+    h->pass = {V, 1, true, false};
     if ((rc = run_conv_chain(h, sc, V, st))) return rc;
     LstmPrefillArgs la;
     lstm_args(h, sc, sv, la);
@@ -1968,22 +1994,16 @@ int vapx_encode_audio(vapx_handle h, int32_t n, const int32_t* stream_ids, const
   if (h->cls_table) return fail(h, VAPX_E_INVAL, "vapx_encode_audio takes complete 16 kHz fp32 frames that carry their own carry; this engine has input classes");
   if (h->in_hz()) return fail(h, VAPX_E_INVAL, "vapx_encode_audio takes complete 16 kHz frames that carry their own carry; this engine's input rate is %d Hz", h->in_hz());
   hipStream_t st = (hipStream_t)hip_stream;
-  (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const int* ids = nullptr;
-  int rc = join_deferred(h, st);
-  if (rc) return rc;
-  rc = flush_resets(h, st);
-  if (rc) return rc;
-  rc = upload_ids(h, n, stream_ids, 0, st, &ids);
-  if (rc) return rc;
+  int rc = stream_ids ? check_ids(h, n, stream_ids) : VAPX_OK;
+  if (rc || (rc = enter_settled(h, st)) || (rc = upload_ids(h, h->ids, n, stream_ids, 0, st, &ids))) return rc;
   const StateView sv{h->ring, h->ring_qkv, h->h_state, h->c_state, h->carry, h->frames_seen};
-  h->last_tail_fused = false;
+  h->pass.tail_fused = false;
   rc = run_encoder(h, h->sc, sv, n, ids, frames, h->L, false, st);
   if (rc) return rc;
   HIPCHK(h, hipMemcpyAsync(e, h->sc.e, (size_t)n * 2 * 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
-  h->last_B = n;
-  h->last_prefill = false;
+  h->pass.entries = n;
+  h->pass.prefill = false;
   return VAPX_OK;
 }
 
@@ -2004,11 +2024,10 @@ int vapx_transformer_maps(vapx_handle h, int32_t n, int32_t rows, const float* x
   if (stage == 2 && attn) return fail(h, VAPX_E_INVAL, "stage 2 does not run ar_channel: no attn map");
   if (stage == 1 && (self_attn || cross_attn)) return fail(h, VAPX_E_INVAL, "stage 1 does not run ar: no self_attn / cross_attn maps");
   hipStream_t st = (hipStream_t)hip_stream;
-  (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const int T = h->T;
   const int l_begin = stage == 2 ? 1 : 0, l_end = stage == 1 ? 1 : 4;
-  { int rc0 = join_deferred(h, st); if (rc0) return rc0; }   // the stage API shares the step's scratch
+  int rc = enter(h);
+  if (rc || (rc = join_deferred(h, st))) return rc;   // the stage API shares the step's scratch, and touches no stream state
   hipLaunchKernelGGL(fill_int_kernel, dim3((n + 255) / 256), dim3(256), 0, st, h->sc.bn, rows, n);
   GatherArgs ga;
   memset(&ga, 0, sizeof ga);
@@ -2018,8 +2037,7 @@ int vapx_transformer_maps(vapx_handle h, int32_t n, int32_t rows, const float* x
   { ProfScope ps(h, CLS_GATHER, st); HIPCHK(h, launch_gather_ln(ga, st)); }
   const MapOut maps{attn, self_attn, cross_attn, rows};
   const bool want_maps = attn || self_attn || cross_attn;
-  int rc = run_layers(h, h->sc, n, st, l_begin, l_end, false, false, nullptr, want_maps ? &maps : nullptr);
-  if (rc) return rc;
+  if ((rc = run_layers(h, h->sc, n, st, l_begin, l_end, false, false, nullptr, want_maps ? &maps : nullptr))) return rc;
   const long nro = (long)n * 2 * rows;
   const unsigned cgrid = (unsigned)((nro * 64 + 255) / 256);
   if (o) hipLaunchKernelGGL(compact_rows_kernel, dim3(cgrid), dim3(256), 0, st, o, h->sc.xl[1], T, rows, nro);
@@ -2032,8 +2050,8 @@ int vapx_transformer_maps(vapx_handle h, int32_t n, int32_t rows, const float* x
     hipLaunchKernelGGL(compact_rows_kernel, dim3((unsigned)((nrc * 64 + 255) / 256)), dim3(256), 0, st, comb, h->sc.xmid, T, rows, nrc);
   }
   HIPCHK(h, hipGetLastError());
-  h->last_B = n;
-  h->last_prefill = false;
+  h->pass.entries = n;
+  h->pass.prefill = false;
   return VAPX_OK;
 }
 
@@ -2059,34 +2077,12 @@ int64_t vapx_peek(vapx_handle h, const char* name, float* dst, size_t max_floats
     dst[0] = (float)seen;
     return 1;
   }
-  // what exists after the latest step depends on the path it took: refuse what was not written
-  if (h->last_prefill && strcmp(name, "h0") && strcmp(name, "h1") && strcmp(name, "h2") && strcmp(name, "h3") && strcmp(name, "z") &&
-      strcmp(name, "e"))
-    return fail(h, VAPX_E_INVAL, "\"%s\" is not written by vapx_prefill (its LSTM launch keeps lstm_out to itself and no transformer layer runs): "
-                "after a prefill only h0 .. h3, z and e of its last chunk exist; step to peek \"%s\"", name, name);
-  const bool full_last = (h->cfg.flags & VAPX_FLAG_FULL_LAST_LAYER) || h->cfg.mode == VAPX_MODE_NOD;
-  if ((!strcmp(name, "h2") || !strcmp(name, "h3")) && h->last_tail_fused)
-    // what run_encoder ran for the latest step, not a guess from last_B: the 512-stream limit holds per overlap group, so a batch of
-    // 1000 in two groups runs the fused tail twice and leaves h2 / h3 stale
-    return fail(h, VAPX_E_INVAL, "\"%s\" stays in LDS in the fused conv tail; create the engine with VAPX_FLAG_UNFUSED_CONV to peek it", name);
-  if (!strcmp(name, "x0") && !(h->cfg.flags & VAPX_FLAG_MATERIALIZE_X0) && (h->T <= 64 || !(h->cfg.flags & VAPX_FLAG_UNFUSED_PROJ)))
-    return fail(h, VAPX_E_INVAL, "\"x0\" is read straight from the ring; create the engine with VAPX_FLAG_MATERIALIZE_X0 to peek it");
-  if (!strcmp(name, "stereo2") && !full_last)
-    return fail(h, VAPX_E_INVAL, "\"stereo2\" is only materialised with VAPX_FLAG_FULL_LAST_LAYER (default: last layer runs on the newest row only)");
-  if (!strcmp(name, "last") && full_last)   // the last layer's newest row of every (stream, channel): fused block and the ten-launch path alike
-    return fail(h, VAPX_E_INVAL, "\"last\" exists only where the last layer runs on the newest row alone; this engine (VAPX_FLAG_FULL_LAST_LAYER "
-                "or nod mode) computes every row: peek \"stereo2\" and take row n - 1");
-  const bool comb = !strcmp(name, "comb");   // the all-rows combinator of the nod variant, [n][T][256] of xmid
-  if (comb && h->cfg.mode != VAPX_MODE_NOD)
-    return fail(h, VAPX_E_INVAL, "\"comb\" is only materialised in nod mode (vap / bc: the combinator of the newest row stays inside head_kernel)");
-  if (comb && h->last_G > 1)   // a group's block starts at its first row of the [B*2*T]-row scratch, twice the stride of the [nb*T] rows it holds
-    return fail(h, VAPX_E_INVAL, "\"comb\" is not contiguous when the latest step ran in %d overlap groups; step with groups = 1 to peek it", h->last_G);
   const ScratchRow* row = scratch_row_by_peek(name);
-  if (!row) return fail(h, VAPX_E_INVAL, "unknown buffer '%s'", name);
-  const float* src = (const float*)scratch_ptr(*row, h->sc);   // overlap groups slice every buffer by batch row, so one copy spans them
-  size_t n = (size_t)h->last_B * (comb ? (size_t)h->T * 256 : row->per_slot(*h));
-  if (!src)   // vapx_attach_trunk freed the follower's encoder scratch
-    return fail(h, VAPX_E_INVAL, "\"%s\" is released: this engine is a trunk follower, peek its leader", name);
+  const float* src = row ? (const float*)scratch_ptr(*row, h->sc) : nullptr;   // overlap groups slice every buffer by batch row, so one copy spans them
+  if (const char* why = peek_refusal(h->pass, h->cfg.mode, h->ring_direct, h->prune_last, row && !src, name))
+    return why == kPeekCombSplit ? fail(h, VAPX_E_INVAL, why, h->pass.groups) : fail(h, VAPX_E_INVAL, why, name, name);
+  // "comb": the all-rows combinator of the nod variant, [n][T][256] of xmid
+  size_t n = (size_t)h->pass.entries * (!strcmp(name, "comb") ? (size_t)h->T * 256 : row->per_slot(*h));
   if (n > max_floats) n = max_floats;
   HIPCHK(h, hipMemcpy(dst, src, n * sizeof(float), hipMemcpyDeviceToHost));
   return (int64_t)n;
@@ -2100,8 +2096,7 @@ int vapx_profile_enable(vapx_handle h, uint32_t class_mask) {
 
 int vapx_profile_read(vapx_handle h, double* total_ms, int64_t* launches, int32_t n_classes) {
   if (!h || !total_ms || !launches) return VAPX_E_INVAL;
-  (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (int rc = enter(h)) return rc;
   HIPCHK(h, hipDeviceSynchronize());
   for (int i = 0; i < n_classes; ++i) { total_ms[i] = 0.0; launches[i] = 0; }
   for (auto& r : h->prof_recs) {
@@ -2117,8 +2112,7 @@ int vapx_profile_read(vapx_handle h, double* total_ms, int64_t* launches, int32_
 int vapx_vap_head(vapx_handle h, int64_t rows, const float* x, float* logits, void* hip_stream) {
   if (!h || !x || !logits || rows < 1) return VAPX_E_INVAL;
   if (h->cfg.mode != VAPX_MODE_VAP) return fail(h, VAPX_E_INVAL, "this weight set has no vap_head (bc / nod variant)");
-  (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (int rc = enter(h)) return rc;
   GemmArgs g = gemm_args(x, contiguous_rows(256), h->wt.head_w, (int)rows, 256, 256, logits, contiguous_rows(256));
   g.bias = h->wt.head_b;
   HIPCHK(h, launch_gemm_f32(g, EPI_STORE, 0, (hipStream_t)hip_stream));
@@ -2127,8 +2121,7 @@ int vapx_vap_head(vapx_handle h, int64_t rows, const float* x, float* logits, vo
 
 int vapx_va_classifier(vapx_handle h, int64_t rows, const float* x, float* y, void* hip_stream) {
   if (!h || !x || !y || rows < 1) return VAPX_E_INVAL;
-  (void)hipGetLastError();   // a stale error of an earlier, unrelated HIP call (this library's or anyone's) is not this call's
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (int rc = enter(h)) return rc;
   hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, x, h->wt.vad_w, h->wt.vad_b, y, (long)rows);
   HIPCHK(h, hipGetLastError());
   return VAPX_OK;
@@ -2142,8 +2135,7 @@ int vapx_aux_head(vapx_handle h, int32_t which, int64_t rows, const float* x, fl
   else if (h->cfg.mode == VAPX_MODE_NOD && which == VAPX_AUX_BC_HEAD) { row0 = 4; nout = 1; }
   else if (h->cfg.mode == VAPX_MODE_NOD && which == VAPX_AUX_NOD_HEAD) { row0 = 0; nout = 4; }
   else return fail(h, VAPX_E_INVAL, "this weight set has no such head (bc_head: bc / nod variants, nod_head: nod variant)");
-  (void)hipGetLastError();
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (int rc = enter(h)) return rc;
   hipLaunchKernelGGL(rowheads_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, x, h->wt.aux_w + row0 * 256,
                      h->wt.aux_b + row0, y, (long)rows, nout);
   HIPCHK(h, hipGetLastError());
@@ -2170,8 +2162,7 @@ static bool input_class_geom(vapx_engine* h, int hz, int fmt, const char* who, I
 // size does not change is kept with its contents: a format set after a rate keeps the history.  On an allocation failure the engine stays
 // as it was and nothing leaks.  `what` names the state in the error text.
 static int build_input(vapx_engine* h, const InputClassGeom* tab, int n, bool table, const char* what) {
-  (void)hipGetLastError();
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (int rc = enter(h)) return rc;
   HIPCHK(h, hipDeviceSynchronize());
   const size_t S = h->cfg.max_streams, B = h->cfg.max_batch;
   int Hmax = 0;
@@ -2183,7 +2174,7 @@ static int build_input(vapx_engine* h, const InputClassGeom* tab, int n, bool ta
   const int rec = (2 * Hmax + 3) & ~3;
   const int row = !table && tab[0].orig == 0 ? h->L : h->hop;   // a uniform 16 kHz engine may be stepped with full frames (never a larger block than `audio` holds)
   const size_t stage_floats = B * slot_max / sizeof(float);     // staging for host audio: the largest slot in every batch slot
-  float *hist = nullptr, *rout = nullptr, *adev = nullptr, *apin = nullptr;
+  float *hist = nullptr, *rout = nullptr;
   int* started = nullptr;
   Staged<int> slots;
   hipError_t e = hipSuccess;
@@ -2192,28 +2183,16 @@ static int build_input(vapx_engine* h, const InputClassGeom* tab, int n, bool ta
     if (e == hipSuccess) e = dalloc(&started, S * 2);
   }
   if (e == hipSuccess && row != h->rs_row) e = dalloc(&rout, B * 2 * (size_t)row);
-  if (e == hipSuccess && stage_floats > h->audio_floats) {
-    e = dalloc(&adev, stage_floats);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&apin, stage_floats * sizeof(float), hipHostMallocDefault);
-  }
-  if (e == hipSuccess && table) {
-    e = dalloc(&slots.dev, B * 2);
-    if (e == hipSuccess) e = slots.create_pinned(B * 2);
-  }
+  if (e == hipSuccess && table) e = slots.reserve(B * 2, true);
+  if (e == hipSuccess) e = h->audio.reserve(stage_floats, true);   // the last that can fail: a larger block alone changes nothing
   if (e != hipSuccess) {   // the engine stays as it was
     (void)hipGetLastError();
-    dfree(hist); dfree(started); dfree(rout); dfree(adev);
-    if (apin) (void)hipHostFree(apin);
-    release(slots);
+    dfree(hist); dfree(started); dfree(rout);
+    slots.release();
     return fail(h, e == hipErrorOutOfMemory ? VAPX_E_NOMEM : VAPX_E_HIP, "%s: %s", what, hipGetErrorString(e));
   }
   if (hist) { dfree(h->rs_hist); dfree(h->rs_started); h->rs_hist = hist; h->rs_started = started; h->rs_rec = rec; }
   if (rout) { dfree(h->rs_out); h->rs_out = rout; h->rs_row = row; }
-  if (adev) {
-    dfree(h->audio.dev); h->audio.dev = adev;
-    (void)hipHostFree(h->audio.pin); h->audio.pin = apin;
-    h->audio_floats = stage_floats;
-  }
   if (table) {
     h->cls_slots = slots;
     h->cls_slots_host.assign(B, InputSlot{0, 0});

@@ -127,3 +127,59 @@ inline const ScratchRow* scratch_row_by_peek(const char* name) {
     if (r.peek && !strcmp(r.peek, name)) return &r;
   return nullptr;
 }
+
+// Two decisions an engine makes once, at vapx_create, from its flags, mode and window.
+// Layer 0 reads the rings in place (no chronological copy, so no x0): always for the fused short-window block, and for long windows when
+// they run the fused long-window chain (the GEMM-chain variants need x0 as a plain buffer)
+inline bool ring_direct_for(int flags, int T) {
+  return !(flags & VAPX_FLAG_MATERIALIZE_X0) && (T <= 64 || !(flags & VAPX_FLAG_UNFUSED_PROJ));
+}
+// The last layer runs on the newest row alone (the nod variant emits p_bc for every row of the window, which needs the whole last layer)
+inline bool prune_last_for(int flags, int mode) { return !(flags & VAPX_FLAG_FULL_LAST_LAYER) && mode != VAPX_MODE_NOD; }
+
+// The latest pass through the scratch buffers, as vapx_peek and vapx_join find it.  Who writes what:
+//   vapx_step, leader      entries = n, groups, prefill = false; tail_fused = false, then true if a group's encoder ran conv_tail_kernel
+//   vapx_step, follower    entries = n, groups, prefill = false (tail_fused stays: it has no encoder)
+//   vapx_prefill           per chunk: entries = (frame, stream) pairs, frame-major, groups = 1, prefill = true, tail_fused as a leader step
+//   vapx_encode_audio      entries = n, prefill = false, tail_fused as a leader step (groups stays)
+//   vapx_transformer_maps  entries = n, prefill = false (groups and tail_fused stay)
+struct PassRecord {
+  int entries = 0, groups = 1;
+  bool prefill = false;      // no lstm_out (the prefill's LSTM launch keeps it to itself) and no transformer buffer
+  bool tail_fused = false;   // h2 / h3 were not written
+};
+
+// vapx_peek's refusals: each is a printf format of the arguments (name, name), but kPeekCombSplit, which takes the number of groups
+inline constexpr char kPeekNotInPrefill[] =
+    "\"%s\" is not written by vapx_prefill (its LSTM launch keeps lstm_out to itself and no transformer layer runs): "
+    "after a prefill only h0 .. h3, z and e of its last chunk exist; step to peek \"%s\"";
+inline constexpr char kPeekInLds[] = "\"%s\" stays in LDS in the fused conv tail; create the engine with VAPX_FLAG_UNFUSED_CONV to peek it";
+inline constexpr char kPeekX0InRing[] = "\"x0\" is read straight from the ring; create the engine with VAPX_FLAG_MATERIALIZE_X0 to peek it";
+inline constexpr char kPeekStereo2Pruned[] =
+    "\"stereo2\" is only materialised with VAPX_FLAG_FULL_LAST_LAYER (default: last layer runs on the newest row only)";
+inline constexpr char kPeekLastEveryRow[] =
+    "\"last\" exists only where the last layer runs on the newest row alone; this engine (VAPX_FLAG_FULL_LAST_LAYER "
+    "or nod mode) computes every row: peek \"stereo2\" and take row n - 1";
+inline constexpr char kPeekCombNotNod[] =
+    "\"comb\" is only materialised in nod mode (vap / bc: the combinator of the newest row stays inside head_kernel)";
+inline constexpr char kPeekCombSplit[] =
+    "\"comb\" is not contiguous when the latest step ran in %d overlap groups; step with groups = 1 to peek it";
+inline constexpr char kPeekUnknown[] = "unknown buffer '%s'";
+inline constexpr char kPeekReleased[] = "\"%s\" is released: this engine is a trunk follower, peek its leader";
+
+// What exists after the latest pass depends on the path it took: null, or why buffer `name` cannot be read (one of the formats above).
+// `released`: the engine has freed the buffer of that name (vapx_attach_trunk, a follower's encoder scratch)
+inline const char* peek_refusal(const PassRecord& pass, int mode, bool ring_direct, bool prune_last, bool released, const char* name) {
+  const auto is = [name](const char* s) { return !strcmp(name, s); };
+  if (pass.prefill && !(is("h0") || is("h1") || is("h2") || is("h3") || is("z") || is("e"))) return kPeekNotInPrefill;
+  if ((is("h2") || is("h3")) && pass.tail_fused) return kPeekInLds;   // what the encoder ran, not a guess from the batch: the fused tail's
+                                                                      // 512-stream limit holds per overlap group
+  if (is("x0") && ring_direct) return kPeekX0InRing;
+  if (is("stereo2") && prune_last) return kPeekStereo2Pruned;
+  if (is("last") && !prune_last) return kPeekLastEveryRow;   // the newest row of every (stream, channel): fused block and ten-launch path alike
+  if (is("comb") && mode != VAPX_MODE_NOD) return kPeekCombNotNod;
+  if (is("comb") && pass.groups > 1) return kPeekCombSplit;   // a group's block starts at its first row of the [B*2*T]-row scratch, twice
+                                                              // the stride of the [nb*T] rows it holds
+  if (!scratch_row_by_peek(name)) return kPeekUnknown;
+  return released ? kPeekReleased : nullptr;
+}

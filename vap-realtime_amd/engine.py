@@ -32,23 +32,6 @@ STATE_HEADER_FLOATS = 8
 STATE_LSTM_FLOATS, STATE_CARRY_FLOATS = 2 * 2 * 256, 2 * 320
 MODE = {"vap": 0, "bc": 1, "nod": 2}
 
-EXPORTS = ("vapx_abi_version", "vapx_blob_floats", "vapx_create", "vapx_destroy", "vapx_step",
-           "vapx_attach_trunk", "vapx_join", "vapx_reset_stream", "vapx_get_state", "vapx_set_state", "vapx_encode_audio",
-           "vapx_transformer", "vapx_transformer_maps", "vapx_peek", "vapx_gemm", "vapx_last_error", "vapx_profile_enable",
-           "vapx_profile_read", "vapx_bad_slots", "vapx_host_alloc", "vapx_host_free", "vapx_reset_carry", "vapx_get_config",
-           "vapx_ingest_open", "vapx_ingest_open_fn", "vapx_ingest_ports", "vapx_ingest_stats_read", "vapx_ingest_late_read", "vapx_ingest_close",
-           "vapx_wire_decode_input", "vapx_wire_encode_result", "vapx_vap_head", "vapx_va_classifier", "vapx_softmax256",
-           "vapx_aggregate", "vapx_aux_head", "vapx_frontdoor_open", "vapx_frontdoor_open_links", "vapx_ingest_attach_link", "vapx_frontdoor_ports", "vapx_frontdoor_counts", "vapx_frontdoor_close",
-           "vapx_wire_floats", "vapx_group_wire_floats", "vapx_step_group", "vapx_group_bad", "vapx_ingest_open_group",
-           "vapx_ingest_open_group_fn", "vapx_ingest_open_group_fn2", "vapx_ingest_group_ports", "vapx_ingest_last_open_error",
-           "vapx_state_floats", "vapx_export_streams", "vapx_import_streams",
-           "vapx_set_input_rate", "vapx_get_input_rate", "vapx_resample",
-           "vapx_set_input_format", "vapx_get_input_format", "vapx_pcm_decode",
-           "vapx_set_input_classes", "vapx_get_input_classes", "vapx_set_stream_class", "vapx_get_stream_class", "vapx_input_slot_bytes",
-           "vapx_ingest_class_ports", "vapx_ingest_stream_class",
-           "vapx_set_stream_channel_classes", "vapx_get_stream_channel_classes", "vapx_input_row_bytes",
-           "vapx_ingest_pair_ports", "vapx_ingest_stream_channel_classes",
-           "vapx_prefill", "vapx_gemm_tile_rows")
 MAX_INPUT_CLASSES = 16
 PROF_CLASSES = {0: "gemm_store", 1: "gemm_gelu", 2: "gemm_resid", 3: "gemm_resid_ln", 4: "gemm_cn_relu",
                 5: "conv_tail", 6: "ffn_block", 7: "last_row", 8: "conv0", 9: "lstm", 10: "gather_ln", 11: "attention", 12: "head",
@@ -67,6 +50,96 @@ class _Config(C.Structure):
 
 class _InputClass(C.Structure):
     _fields_ = [("input_hz", C.c_int32), ("format", C.c_int32)]
+
+
+def _prototypes() -> dict:
+    """Every export of include/vapx.h: ``name -> (restype, argtypes)`` or ``(restype, argtypes, True)`` for one that an older build
+    may lack (``load_library`` then leaves it undeclared)."""
+    P, vp, i32, i64, sz, dbl, text = C.POINTER, C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_double, C.c_char_p
+    f32p = i32p = vp                     # device or host blocks, passed as raw addresses
+    step = [vp, i32, i32p, f32p, i32, f32p, i32, vp]
+    state_io = [vp, i32, i32p, f32p, i32, vp]
+    rows = [vp, i64, f32p, f32p, vp]
+    return {
+        "vapx_abi_version": (i32, []),
+        "vapx_blob_floats": (sz, [i32]),
+        "vapx_create": (i32, [P(_Config), f32p, sz, P(vp)]),
+        "vapx_destroy": (None, [vp]),
+        "vapx_last_error": (text, [vp]),
+        "vapx_get_config": (i32, [vp, P(_Config)]),
+        "vapx_step": (i32, step),
+        "vapx_join": (i32, [vp, vp]),
+        "vapx_bad_slots": (i32, [vp, i32p, i32]),
+        "vapx_attach_trunk": (i32, [vp, vp]),
+        "vapx_wire_floats": (i32, [i32, i32]),
+        "vapx_group_wire_floats": (sz, [vp]),
+        "vapx_step_group": (i32, step),
+        "vapx_group_bad": (i32, [vp, i32p, i32p, i32]),
+        "vapx_reset_stream": (i32, [vp, i32]),
+        "vapx_reset_carry": (i32, [vp, i32]),
+        "vapx_get_state": (i32, [vp, i32, f32p, P(i32), f32p, f32p]),
+        "vapx_set_state": (i32, [vp, i32, f32p, i32, f32p, f32p]),
+        "vapx_state_floats": (sz, [vp, i32]),
+        "vapx_export_streams": (i32, state_io),
+        "vapx_import_streams": (i32, state_io),
+        "vapx_prefill": (i32, [vp, i32, i32p, f32p, i32, i32, vp], True),
+        "vapx_set_input_rate": (i32, [vp, i32]),
+        "vapx_get_input_rate": (i32, [vp]),
+        "vapx_resample": (i32, [i32, i64, i64, f32p, f32p, vp]),
+        "vapx_set_input_format": (i32, [vp, i32]),
+        "vapx_get_input_format": (i32, [vp]),
+        "vapx_pcm_decode": (i32, [i32, i64, vp, f32p, vp]),
+        "vapx_set_input_classes": (i32, [vp, i32, vp]),
+        "vapx_get_input_classes": (i32, [vp, vp, i32]),
+        "vapx_set_stream_class": (i32, [vp, i32, i32]),
+        "vapx_get_stream_class": (i32, [vp, i32]),
+        "vapx_input_slot_bytes": (i64, [vp, i32]),
+        "vapx_set_stream_channel_classes": (i32, [vp, i32, i32, i32]),
+        "vapx_get_stream_channel_classes": (i32, [vp, i32, vp]),
+        "vapx_input_row_bytes": (i64, [vp, i32]),
+        "vapx_encode_audio": (i32, [vp, i32, i32p, f32p, f32p, vp]),
+        "vapx_transformer": (i32, [vp, i32, i32, f32p, f32p, f32p, f32p, i32, vp]),
+        "vapx_transformer_maps": (i32, [vp, i32, i32, f32p, f32p, f32p, f32p, i32, f32p, f32p, f32p, vp]),
+        "vapx_peek": (i64, [vp, text, f32p, sz]),
+        "vapx_profile_enable": (i32, [vp, C.c_uint32]),
+        "vapx_profile_read": (i32, [vp, P(dbl), P(i64), i32]),
+        "vapx_host_alloc": (vp, [sz]),
+        "vapx_host_free": (None, [vp]),
+        "vapx_vap_head": (i32, rows),
+        "vapx_va_classifier": (i32, rows),
+        "vapx_aux_head": (i32, [vp, i32, i64, f32p, f32p, vp]),
+        "vapx_softmax256": (i32, [i64, f32p, f32p, vp]),
+        "vapx_aggregate": (i32, [i64, f32p, i32, i32, f32p, vp]),
+        "vapx_gemm": (i32, [vp, i32, i32, i32, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, f32p, i32]),
+        "vapx_gemm_tile_rows": (i32, [i32, i32, i32, i32], True),
+        "vapx_ingest_open": (i32, [vp, vp, P(vp)]),
+        "vapx_ingest_open_fn": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, P(vp)]),
+        "vapx_ingest_open_group": (i32, [vp, P(vp), i32, vp, P(i32), P(vp)]),
+        "vapx_ingest_open_group_fn": (i32, [vp, vp, vp, i32, i32, i32, i32, P(i32), i32, vp, P(i32), P(vp)]),
+        "vapx_ingest_open_group_fn2": (i32, [vp, vp, vp, i32, i32, P(i32), P(i32), P(i32), i32, vp, P(i32), P(vp)]),
+        "vapx_ingest_last_open_error": (text, []),
+        "vapx_ingest_ports": (i32, [vp, P(i32), P(i32)]),
+        "vapx_ingest_group_ports": (i32, [vp, P(i32), P(i32), i32]),
+        "vapx_ingest_class_ports": (i32, [vp, vp, i32]),
+        "vapx_ingest_pair_ports": (i32, [vp, vp, i32]),
+        "vapx_ingest_stream_class": (i32, [vp, i32]),
+        "vapx_ingest_stream_channel_classes": (i32, [vp, i32, vp]),
+        "vapx_ingest_attach_link": (i32, [vp, i32]),
+        "vapx_ingest_stats_read": (i32, [vp, vp, i32]),
+        "vapx_ingest_late_read": (i32, [vp, vp, vp]),
+        "vapx_ingest_close": (None, [vp]),
+        "vapx_frontdoor_open": (i32, [vp, i32, i32, i32, i32, P(vp)]),
+        "vapx_frontdoor_open_links": (i32, [P(i32), i32, i32, i32, i32, P(vp)]),
+        "vapx_frontdoor_ports": (i32, [vp, P(i32), P(i32)]),
+        "vapx_frontdoor_counts": (i32, [vp, P(i64), P(i64), P(i64)]),
+        "vapx_frontdoor_close": (None, [vp]),
+        "vapx_wire_decode_input": (i64, [vp, sz, dbl, vp, vp, vp, vp]),
+        "vapx_wire_encode_result": (i64, [i32, dbl, vp, vp, i32, vp, vp, sz]),
+    }
+
+
+PROTOTYPES = _prototypes()
+EXPORTS = tuple(PROTOTYPES)
 
 
 def input_class_table(classes) -> list:
@@ -187,157 +260,11 @@ def load_library(path: Optional[str] = None):
     except Exception:  # pragma: no cover
         pass
     lib = C.CDLL(p, mode=C.RTLD_GLOBAL)
-    vp, i32, f32p, i32p = C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p
-    lib.vapx_abi_version.restype = i32
-    lib.vapx_blob_floats.restype = C.c_size_t
-    lib.vapx_blob_floats.argtypes = [i32]
-    lib.vapx_create.restype = i32
-    lib.vapx_create.argtypes = [C.POINTER(_Config), f32p, C.c_size_t, C.POINTER(vp)]
-    lib.vapx_destroy.restype = None
-    lib.vapx_destroy.argtypes = [vp]
-    lib.vapx_step.restype = i32
-    lib.vapx_step.argtypes = [vp, i32, i32p, f32p, i32, f32p, i32, vp]
-    lib.vapx_join.restype = i32
-    lib.vapx_join.argtypes = [vp, vp]
-    lib.vapx_attach_trunk.restype = i32
-    lib.vapx_attach_trunk.argtypes = [vp, vp]
-    lib.vapx_reset_stream.restype = i32
-    lib.vapx_reset_stream.argtypes = [vp, i32]
-    lib.vapx_get_state.restype = i32
-    lib.vapx_get_state.argtypes = [vp, i32, f32p, C.POINTER(i32), f32p, f32p]
-    lib.vapx_set_state.restype = i32
-    lib.vapx_set_state.argtypes = [vp, i32, f32p, i32, f32p, f32p]
-    lib.vapx_state_floats.restype = C.c_size_t
-    lib.vapx_state_floats.argtypes = [vp, i32]
-    lib.vapx_export_streams.restype = i32
-    lib.vapx_export_streams.argtypes = [vp, i32, i32p, f32p, i32, vp]
-    lib.vapx_import_streams.restype = i32
-    lib.vapx_import_streams.argtypes = [vp, i32, i32p, f32p, i32, vp]
-    if hasattr(lib, "vapx_prefill"):   # absent from an older build named by VAPX_LIBRARY for an A/B run (tools/ab_lib.sh); build() checks EXPORTS
-        lib.vapx_prefill.restype = i32
-        lib.vapx_prefill.argtypes = [vp, i32, i32p, f32p, i32, i32, vp]
-    lib.vapx_set_input_rate.restype = i32
-    lib.vapx_set_input_rate.argtypes = [vp, i32]
-    lib.vapx_get_input_rate.restype = i32
-    lib.vapx_get_input_rate.argtypes = [vp]
-    lib.vapx_resample.restype = i32
-    lib.vapx_resample.argtypes = [i32, C.c_int64, C.c_int64, f32p, f32p, vp]
-    lib.vapx_set_input_format.restype = i32
-    lib.vapx_set_input_format.argtypes = [vp, i32]
-    lib.vapx_get_input_format.restype = i32
-    lib.vapx_get_input_format.argtypes = [vp]
-    lib.vapx_pcm_decode.restype = i32
-    lib.vapx_pcm_decode.argtypes = [i32, C.c_int64, vp, f32p, vp]
-    lib.vapx_set_input_classes.restype = i32
-    lib.vapx_set_input_classes.argtypes = [vp, i32, vp]
-    lib.vapx_get_input_classes.restype = i32
-    lib.vapx_get_input_classes.argtypes = [vp, vp, i32]
-    lib.vapx_set_stream_class.restype = i32
-    lib.vapx_set_stream_class.argtypes = [vp, i32, i32]
-    lib.vapx_get_stream_class.restype = i32
-    lib.vapx_get_stream_class.argtypes = [vp, i32]
-    lib.vapx_input_slot_bytes.restype = C.c_int64
-    lib.vapx_input_slot_bytes.argtypes = [vp, i32]
-    lib.vapx_set_stream_channel_classes.restype = i32
-    lib.vapx_set_stream_channel_classes.argtypes = [vp, i32, i32, i32]
-    lib.vapx_get_stream_channel_classes.restype = i32
-    lib.vapx_get_stream_channel_classes.argtypes = [vp, i32, vp]
-    lib.vapx_input_row_bytes.restype = C.c_int64
-    lib.vapx_input_row_bytes.argtypes = [vp, i32]
-    lib.vapx_encode_audio.restype = i32
-    lib.vapx_encode_audio.argtypes = [vp, i32, i32p, f32p, f32p, vp]
-    lib.vapx_transformer.restype = i32
-    lib.vapx_transformer.argtypes = [vp, i32, i32, f32p, f32p, f32p, f32p, i32, vp]
-    lib.vapx_transformer_maps.restype = i32
-    lib.vapx_transformer_maps.argtypes = [vp, i32, i32, f32p, f32p, f32p, f32p, i32, f32p, f32p, f32p, vp]
-    lib.vapx_peek.restype = C.c_int64
-    lib.vapx_peek.argtypes = [vp, C.c_char_p, f32p, C.c_size_t]
-    lib.vapx_gemm.restype = i32
-    lib.vapx_gemm.argtypes = [vp, i32, i32, i32, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, f32p, i32]
-    if hasattr(lib, "vapx_gemm_tile_rows"):   # absent from an older build named by VAPX_LIBRARY, as vapx_prefill below
-        lib.vapx_gemm_tile_rows.restype = i32
-        lib.vapx_gemm_tile_rows.argtypes = [i32, i32, i32, i32]
-    lib.vapx_profile_enable.restype = i32
-    lib.vapx_profile_enable.argtypes = [vp, C.c_uint32]
-    lib.vapx_profile_read.restype = i32
-    lib.vapx_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), i32]
-    lib.vapx_last_error.restype = C.c_char_p
-    lib.vapx_last_error.argtypes = [vp]
-    lib.vapx_bad_slots.restype = i32
-    lib.vapx_bad_slots.argtypes = [vp, i32p, i32]
-    lib.vapx_host_alloc.restype = vp
-    lib.vapx_host_alloc.argtypes = [C.c_size_t]
-    lib.vapx_host_free.restype = None
-    lib.vapx_host_free.argtypes = [vp]
-    lib.vapx_reset_carry.restype = i32
-    lib.vapx_reset_carry.argtypes = [vp, i32]
-    lib.vapx_get_config.restype = i32
-    lib.vapx_get_config.argtypes = [vp, C.POINTER(_Config)]
-    lib.vapx_ingest_open.restype = i32
-    lib.vapx_ingest_open.argtypes = [vp, vp, C.POINTER(vp)]
-    lib.vapx_ingest_open_fn.restype = i32
-    lib.vapx_ingest_open_fn.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, C.POINTER(vp)]
-    lib.vapx_ingest_ports.restype = i32
-    lib.vapx_ingest_ports.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-    lib.vapx_ingest_class_ports.restype = i32
-    lib.vapx_ingest_class_ports.argtypes = [vp, vp, i32]
-    lib.vapx_ingest_stream_class.restype = i32
-    lib.vapx_ingest_stream_class.argtypes = [vp, i32]
-    lib.vapx_ingest_pair_ports.restype = i32
-    lib.vapx_ingest_pair_ports.argtypes = [vp, vp, i32]
-    lib.vapx_ingest_stream_channel_classes.restype = i32
-    lib.vapx_ingest_stream_channel_classes.argtypes = [vp, i32, vp]
-    lib.vapx_ingest_stats_read.restype = i32
-    lib.vapx_ingest_stats_read.argtypes = [vp, vp, i32]
-    lib.vapx_ingest_late_read.restype = i32
-    lib.vapx_ingest_late_read.argtypes = [vp, vp, vp]
-    lib.vapx_ingest_close.restype = None
-    lib.vapx_ingest_close.argtypes = [vp]
-    lib.vapx_frontdoor_open.restype = i32
-    lib.vapx_frontdoor_open.argtypes = [vp, i32, i32, i32, i32, C.POINTER(vp)]
-    lib.vapx_frontdoor_open_links.restype = i32
-    lib.vapx_frontdoor_open_links.argtypes = [C.POINTER(i32), i32, i32, i32, i32, C.POINTER(vp)]
-    lib.vapx_ingest_attach_link.restype = i32
-    lib.vapx_ingest_attach_link.argtypes = [vp, i32]
-    lib.vapx_frontdoor_ports.restype = i32
-    lib.vapx_frontdoor_ports.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-    lib.vapx_frontdoor_counts.restype = i32
-    lib.vapx_frontdoor_counts.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.vapx_frontdoor_close.restype = None
-    lib.vapx_frontdoor_close.argtypes = [vp]
-    lib.vapx_vap_head.restype = i32
-    lib.vapx_vap_head.argtypes = [vp, C.c_int64, f32p, f32p, vp]
-    lib.vapx_va_classifier.restype = i32
-    lib.vapx_va_classifier.argtypes = [vp, C.c_int64, f32p, f32p, vp]
-    lib.vapx_aux_head.restype = i32
-    lib.vapx_aux_head.argtypes = [vp, i32, C.c_int64, f32p, f32p, vp]
-    lib.vapx_softmax256.restype = i32
-    lib.vapx_softmax256.argtypes = [C.c_int64, f32p, f32p, vp]
-    lib.vapx_aggregate.restype = i32
-    lib.vapx_aggregate.argtypes = [C.c_int64, f32p, i32, i32, f32p, vp]
-    lib.vapx_wire_floats.restype = i32
-    lib.vapx_wire_floats.argtypes = [i32, i32]
-    lib.vapx_group_wire_floats.restype = C.c_size_t
-    lib.vapx_group_wire_floats.argtypes = [vp]
-    lib.vapx_step_group.restype = i32
-    lib.vapx_step_group.argtypes = [vp, i32, i32p, f32p, i32, f32p, i32, vp]
-    lib.vapx_group_bad.restype = i32
-    lib.vapx_group_bad.argtypes = [vp, i32p, i32p, i32]
-    lib.vapx_ingest_open_group.restype = i32
-    lib.vapx_ingest_open_group.argtypes = [vp, C.POINTER(vp), i32, vp, C.POINTER(i32), C.POINTER(vp)]
-    lib.vapx_ingest_open_group_fn.restype = i32
-    lib.vapx_ingest_open_group_fn.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), i32, vp, C.POINTER(i32), C.POINTER(vp)]
-    lib.vapx_ingest_open_group_fn2.restype = i32
-    lib.vapx_ingest_open_group_fn2.argtypes = [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, vp, C.POINTER(i32),
-                                               C.POINTER(vp)]
-    lib.vapx_ingest_group_ports.restype = i32
-    lib.vapx_ingest_group_ports.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), i32]
-    lib.vapx_ingest_last_open_error.restype = C.c_char_p
-    lib.vapx_ingest_last_open_error.argtypes = []
-    lib.vapx_wire_decode_input.restype = C.c_int64
-    lib.vapx_wire_decode_input.argtypes = [vp, C.c_size_t, C.c_double, vp, vp, vp, vp]
-    lib.vapx_wire_encode_result.restype = C.c_int64
-    lib.vapx_wire_encode_result.argtypes = [i32, C.c_double, vp, vp, i32, vp, vp, C.c_size_t]
+    for name, (restype, argtypes, *optional) in PROTOTYPES.items():
+        if optional and not hasattr(lib, name):   # an older build named by VAPX_LIBRARY for an A/B run (tools/ab_lib.sh); build() checks EXPORTS
+            continue
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if path is None:
         _lib = lib
     return lib
