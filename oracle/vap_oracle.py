@@ -80,6 +80,18 @@ class VapOracle:
         bits = ((idx[:, None] >> torch.arange(8)[None, :]) & 1).to(dtype).view(256, 2, 4)
         self.abp_now = bits[:, :, 0:2].sum(-1)                   # BINS_P_NOW = [0,1]  vap_main.py:187
         self.abp_fut = bits[:, :, 2:4].sum(-1)                   # BINS_PFUTURE = [2,3]
+        self._sink: Optional[dict] = None
+
+    def _collect_pre(self, collect: Optional[dict]) -> None:
+        """``collect["pre"]`` (a dict the caller put there, else nothing is kept) receives the INPUT of every non-linearity that
+        ``encode`` / ``transformer`` / ``step`` evaluate: one list per name, one entry per evaluation.  ``gates`` [B, 1024] (i, f, g, o)
+        and ``cell`` [B, 256] per LSTM step, ``gelu.downsample``, ``gelu.<layer>`` (FFN hidden), ``gelu.combinator``,
+        ``att.<layer>.mha`` / ``.mha_cross`` [B, 4, n, n] (causal entries are -inf), ``head`` [S, 256], ``aux``, ``vad`` [S, 2]."""
+        self._sink = None if collect is None else collect.get("pre")
+
+    def _pre(self, name: str, x: torch.Tensor) -> None:
+        if self._sink is not None:
+            self._sink.setdefault(name, []).append(x)
 
     def new_state(self, n_streams: int) -> OracleState:
         return OracleState(n_streams, self.T)
@@ -109,6 +121,8 @@ class VapOracle:
             g = z[:, t] @ wih.T + h @ whh.T + b
             i, f, gg, o = g.split(DIM, dim=1)
             c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
+            self._pre("gates", g)
+            self._pre("cell", c)
             h = torch.sigmoid(o) * torch.tanh(c)
             outs.append(h)
         return torch.stack(outs, dim=1), h, c
@@ -119,12 +133,14 @@ class VapOracle:
         wd = v["encoder.downsample.1.weight"]                    # [256,256,K]
         out = torch.einsum("bkc,ock->bo", y, wd) + v["encoder.downsample.1.bias"]
         out = F.layer_norm(out, (DIM,), v["encoder.downsample.2.ln.weight"], v["encoder.downsample.2.ln.bias"], 1e-5)
+        self._pre("gelu.downsample", out)
         return F.gelu(out)
 
     def encode(self, audio: torch.Tensor, st: OracleState, collect: Optional[dict] = None) -> torch.Tensor:
         """audio [S,2,L] -> e [S,2,256]; the two channels share weights but own (h,c)
         (vap_main.py:144-169: encoder1/encoder2 built from the same checkpoint)."""
         S = audio.shape[0]
+        self._collect_pre(collect)
         x = audio.reshape(S * 2, 1, self.L)
         z = self.cnn(x, collect)                                  # [S*2,256,P4]
         z = z.transpose(1, 2)[:, 1:-1, :]                         # encoder.py:75-76
@@ -138,6 +154,7 @@ class VapOracle:
             collect["z"] = z.reshape(S, 2, -1, DIM)
             collect["lstm_out"] = y.reshape(S, 2, -1, DIM)
             collect["e"] = e
+        self._sink = None                                         # the sink lives for one call
         return e
 
     # ---- transformer --------------------------------------------------------------------------
@@ -153,6 +170,7 @@ class VapOracle:
         j = torch.arange(n, dtype=self.dtype).view(1, 1, 1, n)
         causal = torch.full((n, n), float("-inf")).triu(1)
         att = att + (m * j + causal)
+        self._pre(f"att.{pre}", att)
         att = att.softmax(dim=-1)
         y = (att @ val).transpose(1, 2).reshape(B, n, DIM)
         return y @ v[f"{pre}.proj.weight"].T
@@ -169,11 +187,14 @@ class VapOracle:
             z = self._ln(x, f"{pre}.ln_src_attn")
             x = x + self._mha(f"{pre}.mha_cross", z, src)         # src NOT normalised, :276-283
         z = self._ln(x, f"{pre}.ln_ffnetwork")
-        x = x + F.gelu(z @ v[f"{pre}.ffnetwork.0.weight"].T) @ v[f"{pre}.ffnetwork.3.weight"].T
+        hid = z @ v[f"{pre}.ffnetwork.0.weight"].T
+        self._pre(f"gelu.{pre}", hid)
+        x = x + F.gelu(hid) @ v[f"{pre}.ffnetwork.3.weight"].T
         return x
 
     def transformer(self, x1: torch.Tensor, x2: torch.Tensor, collect: Optional[dict] = None):
         """x1,x2 [S,n,256] -> (o1,o2,a,b,h)."""
+        self._collect_pre(collect)
         o1 = self.layer("ar_channel.layers.0", x1, None)          # vap_main.py:285-286
         o2 = self.layer("ar_channel.layers.0", x2, None)
         a, b = o1, o2
@@ -184,11 +205,15 @@ class VapOracle:
             if collect is not None:
                 collect[f"stereo{l}"] = torch.stack([a, b], 1)
         v = self.v
-        ha = F.gelu(self._ln(a @ v["ar.combinator.h0_a.weight"].T, "ar.combinator.ln"))
-        hb = F.gelu(self._ln(b @ v["ar.combinator.h0_b.weight"].T, "ar.combinator.ln"))
+        ya = self._ln(a @ v["ar.combinator.h0_a.weight"].T, "ar.combinator.ln")
+        yb = self._ln(b @ v["ar.combinator.h0_b.weight"].T, "ar.combinator.ln")
+        self._pre("gelu.combinator", ya)
+        self._pre("gelu.combinator", yb)
+        ha, hb = F.gelu(ya), F.gelu(yb)
         h = ha + hb                                               # modules.py:449-464
         if collect is not None:
             collect["comb"] = h
+        self._sink = None
         return o1, o2, a, b, h
 
     # ---- window only (per-layer row tests) ----------------------------------------------------
@@ -222,6 +247,7 @@ class VapOracle:
                 st.ring = st.ring[-self.T:]                       # vap_main.py:277-280
             X = torch.stack(st.ring, dim=2)                       # [S,2,n,256]
             o1, o2, a, b, h = self.transformer(X[:, 0], X[:, 1], collect)
+            self._collect_pre(collect)                            # the heads below record too
             v = self.v
             out: Dict[str, np.ndarray] = {}
             vad_logit = torch.stack([(o1[:, -1] @ v["va_classifier.weight"].T + v["va_classifier.bias"])[:, 0],
@@ -229,8 +255,10 @@ class VapOracle:
             out["vad"] = torch.sigmoid(vad_logit).numpy()         # vap_main.py:292-293,313-314
             if collect is not None:
                 collect["vad_logit"] = vad_logit                  # [S,2], before the sigmoid
+            self._pre("vad", vad_logit)
             if "vap_head.weight" in v:
                 logits = h[:, -1] @ v["vap_head.weight"].T + v["vap_head.bias"]
+                self._pre("head", logits)
                 probs = logits.softmax(dim=-1)
                 pn = probs @ self.abp_now
                 pf = probs @ self.abp_fut
@@ -251,11 +279,18 @@ class VapOracle:
                 out["p_nod_long"] = nod[:, 2].numpy()
                 out["p_nod_long_p"] = nod[:, 3].numpy()
                 # quirk: `p_bc.sigmoid()[-1]` indexes the batch dim -> all n rows are emitted
-                out["p_bc"] = torch.sigmoid(h @ v["bc_head.weight"].T + v["bc_head.bias"])[..., 0].numpy()  # [S,n]
+                pbc_logit = (h @ v["bc_head.weight"].T + v["bc_head.bias"])[..., 0]
+                self._pre("p_bc", pbc_logit)
+                if collect is not None:
+                    collect["p_bc_logit"] = pbc_logit             # [S,n], before the sigmoid
+                out["p_bc"] = torch.sigmoid(pbc_logit).numpy()    # [S,n]
+            if self.mode in ("bc", "nod"):
+                self._pre("aux", aux)
             if collect is not None and self.mode in ("bc", "nod"):
                 collect["aux_logit"] = aux                        # [S,3] / [S,4], before the softmax
                 collect["aux"] = aux.softmax(-1)                  # every column, also the one the reference drops
             out["e"] = e.numpy()
+        self._sink = None
         return out
 
 

@@ -34,11 +34,12 @@ def row_bound(want64: np.ndarray, want32: np.ndarray):
 
 
 def check_rows(buf: str, got: np.ndarray, ns: Sequence[int], want64: Sequence[np.ndarray], want32: Sequence[np.ndarray],
-               streams: Optional[Sequence] = None, what: str = "") -> float:
+               streams: Optional[Sequence] = None, what: str = "", excess: Optional[dict] = None) -> float:
     """Check one peeked buffer.  ``got``: [B, 2, T, 256] as ``Engine.peek`` returns it (batch rows in the step's order,
     window rows chronological, rows t >= n undefined); ``ns[b]``: valid rows of batch row b; ``want64[b]`` / ``want32[b]``:
     the oracles' rows [2, ns[b], 256] of that stream.  Returns the worst err / E32 over the batch.  Fails on the first
-    batch row with a non-finite valid row or a valid row beyond the bound, naming stream, channel, row, tile and layer."""
+    batch row with a non-finite valid row or a valid row beyond the bound, naming stream, channel, row, tile and layer.
+    ``excess[buf]``, if given, collects the worst err / bound (the asserted figure: it cannot pass 1)."""
     streams = list(range(len(ns))) if streams is None else list(streams)
     worst = 0.0
     for b, n in enumerate(ns):
@@ -59,6 +60,8 @@ def check_rows(buf: str, got: np.ndarray, ns: Sequence[int], want64: Sequence[np
             raise AssertionError(f"{where}: channel {c} row {t} (tile {t // TILE}) of {buf} ({LAYER[buf]}) is off by "
                                  f"{err[c, t]:.3e} > bound {bound:.3e} (E32 {e32:.3e}, worst {err.max():.3e}), n = {n}")
         worst = max(worst, float(err.max()) / max(e32, 1e-30))
+        if excess is not None:
+            excess[buf] = max(excess.get(buf, 0.0), float(err.max()) / bound)
     return worst
 
 

@@ -134,9 +134,9 @@ class Cast:
     """The dialogues of a case on the CPU.  Dialogues that start on the same tick share one oracle call per tick (S > 1), which is
     what keeps a 137-tick case at a few seconds; per oracle key the float64 and the fp32 oracle keep their own state."""
 
-    def __init__(self, oracles, audio, hop, starts):
+    def __init__(self, oracles, audio, hop, starts, pre_hook=None):
         from oracle.vap_oracle import ServerFramer
-        self.oracles, self.audio, self.hop = oracles, audio, hop
+        self.oracles, self.audio, self.hop, self.pre_hook = oracles, audio, hop, pre_hook
         self.dlg = [Dialogue(s) for s in starts]
         self.troupes = []
         for s in sorted(set(starts)):
@@ -160,7 +160,10 @@ class Cast:
                     o64.advance(frame, s64)
                     o32.advance(frame, s32)
                     continue
-                r64, r32 = HS.collect_heads(o64, frame, s64), HS.collect_heads(o32, frame, s32)
+                pre = {} if self.pre_hook else None
+                r64, r32 = HS.collect_heads(o64, frame, s64, pre), HS.collect_heads(o32, frame, s32)
+                if pre is not None:                          # the inputs of the float64 oracle's non-linearities at this checkpoint
+                    self.pre_hook(pre)
                 for j, d in enumerate(tr["idx"]):
                     self.dlg[d].r64[k], self.dlg[d].r32[k] = HS.row_of(r64, j), HS.row_of(r32, j)
 
@@ -174,15 +177,15 @@ def oracle_pair(cpc, vap, hz, T, mode):
     return o64, o32
 
 
-def make_cast(oracles, hz, n, frames, seed, late):
+def make_cast(oracles, hz, n, frames, seed, late, pre_hook=None):
     from vap_realtime_amd import synth
     hop = 16000 // hz
     audio = synth.dialogue_batch([seed + 100 * k for k in range(n)], hop * frames)
     audio = audio * np.asarray([AMPS[k % len(AMPS)] for k in range(n)], np.float32)[:, None, None]
-    return Cast(oracles, audio, hop, [LATE if late and n > 1 and k == n - 1 else 0 for k in range(n)])
+    return Cast(oracles, audio, hop, [LATE if late and n > 1 and k == n - 1 else 0 for k in range(n)], pre_hook)
 
 
-def check_engine(eng, var, key, out, batch, dlg, slot, T, what):
+def check_engine(eng, var, key, out, batch, dlg, slot, T, what, propagate=False):
     """Every stage and every exact field of one engine after a step of ``batch`` = [(dialogue index, copy index)]."""
     from vap_realtime_amd import engine
     B, mode = len(batch), var.mode
@@ -208,25 +211,30 @@ def check_engine(eng, var, key, out, batch, dlg, slot, T, what):
         if mode != "vap":
             row["aux"] = o["aux"][r, :HS.AUX_COLS[mode]]
         got.append(row)
-    HS.check_tick(mode, got, w64, w32, path=var.path, streams=names, what=what, worst=var.worst, excess=var.excess)
+    HS.check_tick(mode, got, w64, w32, path=var.path, streams=names, what=what, worst=var.worst, excess=var.excess, propagate=propagate)
     HS.check_own(got, streams=names, what=what, excess=var.excess)
 
 
 def run_case(hz, T, variants, *, label, seed=61, n_dialogues=3, copies=3, slots=7, frames=None, cps=SMALL_CP, late=True,
-             engine_kw=None, group=None):
+             engine_kw=None, group=None, weights=None, propagate=False, pre_hook=None):
     """Steps every engine variant and the oracles over ``frames`` ticks; ``copies`` engine streams tile the ``n_dialogues`` dialogues
     (copy i plays dialogue i % n_dialogues).  ``group``: {mode: vap state dict} of a TrunkGroup (the first leads); then ``variants``
-    holds one entry per mode and they are the group's engines."""
+    holds one entry per mode and they are the group's engines.  ``weights``: (cpc, vap) -> (cpc, vap), applied to the synthetic weights
+    of every mode (tests/weight_regimes.py); ``propagate``: ``head_stages.check_tick``'s, for head weights scaled up; ``pre_hook``: called at
+    every checkpoint with the inputs of the float64 oracle's non-linearities (``VapOracle._collect_pre``), so that a case can assert what it reached."""
     from vap_realtime_amd import engine, weights as W
     frames = max(cps) if frames is None else frames
     modes = list(group) if group else sorted({v.mode for v in variants})
     cpc = W.synthetic_weights(seed, hz, "vap")[0]
     sd = group or {m: W.synthetic_weights(seed, hz, m)[1] for m in modes}
+    if weights is not None:
+        sd = {m: weights(cpc, v)[1] for m, v in sd.items()}
+        cpc = weights(cpc, sd[modes[0]])[0]
     oracles = {m: oracle_pair(cpc, sd[m], hz, T, m) for m in modes}
     blobs = {m: W.pack_blob(cpc, sd[m], m) for m in modes}
     import torch
     torch.set_num_threads(min(4, torch.get_num_threads()))     # the oracles' per-tick tensors are small
-    cast = make_cast(oracles, hz, n_dialogues, frames, seed, late)
+    cast = make_cast(oracles, hz, n_dialogues, frames, seed, late, pre_hook)
     dlg = cast.dlg
     owner = [i % n_dialogues for i in range(copies)]
     rng = np.random.default_rng(seed + hz + copies)
@@ -263,7 +271,8 @@ def run_case(hz, T, variants, *, label, seed=61, n_dialogues=3, copies=3, slots=
                 if v.label in failed:
                     continue
                 try:                                         # one variant's first failure does not hide the other variants'
-                    check_engine(e, v, v.mode, out, batch, dlg, slot, T, f"{label} {hz} Hz {v.label} tick {f + 1} (B = {len(batch)})")
+                    check_engine(e, v, v.mode, out, batch, dlg, slot, T, f"{label} {hz} Hz {v.label} tick {f + 1} (B = {len(batch)})",
+                                 propagate)
                 except AssertionError as ex:
                     failed[v.label] = str(ex)
     finally:

@@ -232,16 +232,18 @@ def layers_by_n(orc, windows: Sequence[np.ndarray], layers=None) -> List[Dict[st
     return ref
 
 
-def check(cap: Capture, tr: Truth, buffers: Sequence[str], T: int, what: str = "", path: str = "", at: Optional[dict] = None) -> Dict[str, float]:
+def check(cap: Capture, tr: Truth, buffers: Sequence[str], T: int, what: str = "", path: str = "", at: Optional[dict] = None,
+          excess: Optional[dict] = None) -> Dict[str, float]:
     """``check_rows`` on every buffer of ``buffers``, stream by stream, and, where the capture has it, ``head_stages.check_tick`` on
     ``last`` against row n - 1 of the oracle's stereo2.  Returns the worst err / E32 per buffer (per-stream E32; ``last``: the tick's
-    pooled E32, as head_stages defines that check); ``at[buffer]`` receives the state (n, rot) of the stream that gave it."""
+    pooled E32, as head_stages defines that check); ``at[buffer]`` receives the state (n, rot) of the stream that gave it, ``excess[buffer]``
+    the worst err / bound."""
     states = [cap.prog.states[i] for i in cap.order]
     names = [f"{i} (slot {cap.prog.slot[i]}, n = {n}, rot = {r}, {tiles(n)} tiles)" for i, (n, r) in zip(cap.order, states)]
     worst = {}
     for buf in buffers:
         ratios = [check_rows(buf, cap.peeks[buf][b:b + 1], [cap.ns[b]], [tr.ref64[b][buf]], [tr.ref32[b][buf]], streams=[names[b]],
-                             what=f"{what} T={T}") for b in range(len(cap.ns))]
+                             what=f"{what} T={T}", excess=excess) for b in range(len(cap.ns))]
         worst[buf] = max(ratios)
         if at is not None:
             at[buf] = states[int(np.argmax(ratios))]
@@ -249,6 +251,6 @@ def check(cap: Capture, tr: Truth, buffers: Sequence[str], T: int, what: str = "
         w: dict = {}
         head_stages.check_tick("vap", [{"last": cap.peeks["last"][b]} for b in range(len(cap.ns))],
                                [{"last": r["stereo2"][:, -1]} for r in tr.ref64], [{"last": r["stereo2"][:, -1]} for r in tr.ref32],
-                               path=path, streams=names, what=f"{what} T={T}", stages=("last",), worst=w)
+                               path=path, streams=names, what=f"{what} T={T}", stages=("last",), worst=w, excess=excess)
         worst["last"] = w["last"]
     return worst

@@ -1133,6 +1133,38 @@ int vapx_create(const vapx_config* cfg, const float* blob, size_t n_floats, vapx
               vapx_destroy(h);
               return rc;
             }
+    //  * every ChannelNorm / LayerNorm whose output is an A operand converted to f16 WITHOUT a scale (gemm() with bounded_A: cn0 .. cn3 ->
+    //    conv1 .. conv4, cn4 -> lstm.wih, ln_self -> wqkv, ln_src -> wq_x; the flat-row blocks: ln_self, ln_src, ln_ffn) obeys
+    //    16 |gamma_k| + |beta_k| < 65504 in every channel k (a normalised row of 256 values has |xhat| <= sqrt(255) < 16)
+    {
+      auto entry = [&](const std::string& name) -> const vapx_layout::Entry* {
+        for (size_t i = 0; i < h->lay_n; ++i)
+          if (name == h->lay[i].name) return &h->lay[i];
+        return nullptr;
+      };
+      std::vector<std::string> norms;
+      for (int i = 0; i < 5; ++i) norms.push_back("cn" + std::to_string(i));
+      for (int l = 0; l < 4; ++l)
+        for (const char* s : {".ln_self", ".ln_src", ".ln_ffn"}) norms.push_back("L" + std::to_string(l) + s);
+      for (const std::string& nm : norms) {
+        const auto *g = entry(nm + ".g"), *b = entry(nm + ".b");
+        if (nm == "L0.ln_src") continue;   // layer 0 has no cross-attention: the only norm the layout may lack
+        if (!g || !b) {
+          int rc = fail(nullptr, VAPX_E_INVAL, "the weights layout for %d Hz has no entry \"%s.g\" / \"%s.b\"", cfg->frame_hz, nm.c_str(), nm.c_str());
+          vapx_destroy(h);
+          return rc;
+        }
+        for (size_t k = 0; k < g->n && k < b->n; ++k) {
+          const double bound = 16.0 * fabs((double)blob[g->off + k]) + fabs((double)blob[b->off + k]);
+          if (!(bound < 65504.0)) {
+            int rc = fail(nullptr, VAPX_E_INVAL, "VAPX_FLAG_SPLIT_F16: the norm %s has 16 |gamma| + |beta| = %g >= 65504 (or not finite) in channel %zu: "
+                          "its output is an unscaled f16 operand; use the fp32 path", nm.c_str(), bound, k);
+            vapx_destroy(h);
+            return rc;
+          }
+        }
+      }
+    }
     for (int l = 0; l < 4; ++l) {
       Layer& Lw = h->layer[l];
       auto host = [&](const float* dev) { return blob + (dev - h->w); };
