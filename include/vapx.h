@@ -376,7 +376,17 @@ int vapx_get_config(vapx_handle h, vapx_config* out);
 /* State export / import for one stream (tests, migration between GPUs).  Host pointers, any may
  * be NULL to skip.  ring: [2][T][256] oldest->newest, rows >= n_frames undefined;
  * lstm: [2 ch][2 (h,c)][256]; carry: [2][320].  The resampler history of an engine with an input rate has no place in these calls:
- * vapx_set_state ZEROES it (the stream's input continues as a new signal); vapx_export_streams / vapx_import_streams carry it. */
+ * vapx_set_state ZEROES it (the stream's input continues as a new signal); vapx_export_streams / vapx_import_streams carry it.
+ * They work on every engine, input classes and trunk followers at any rate included.
+ *
+ * Ordering: synchronising.  Argument checks first - a refused call reads and writes nothing: a vapx_get_state refused for a follower's
+ * lstm / carry leaves ring and n_frames as the caller had them, and a follower whose leader was destroyed is refused the same way
+ * (VAPX_E_INVAL; its LSTM / carry buffers went with the attach).  Then the device is made idle and queued resets are applied (as vapx_peek
+ * does), and the call moves the stream with the bulk calls' kernels on the NULL stream - ordered against a caller's blocking streams as a
+ * null-stream call is - through one copy, and returns after one synchronisation of that stream; host buffers are valid / reusable on
+ * return.  vapx_set_state with a ring rebuilds the layer-0 Q|K|V cache of rows t < n_frames as an import without VAPX_STATE_CACHE does (one
+ * LayerNorm, one GEMM, one scatter); cache rows t >= n_frames stay as they were: nothing reads them before the step that appends row t
+ * rewrites them. */
 int vapx_get_state(vapx_handle h, int32_t stream_id, float* ring, int32_t* n_frames, float* lstm, float* carry);
 int vapx_set_state(vapx_handle h, int32_t stream_id, const float* ring, int32_t n_frames, const float* lstm,
                    const float* carry);

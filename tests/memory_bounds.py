@@ -438,7 +438,7 @@ scenario("state_long_window_T70", "state", STATE_KERNELS, proofs=("records_round
     _state_scenario("host", False, fr=50, T=70))
 
 
-@scenario("state_get_set_last_slot", "state", (), proofs=("state_moves",))
+@scenario("state_get_set_last_slot", "state", STATE_KERNELS, proofs=("state_moves",))
 def _get_set(run):
     fr = 20
     a = run.engine(blob(fr), fr, ctx_sec(T8, fr), max_streams=S7)

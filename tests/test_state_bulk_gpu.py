@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-5          # the bar tests/test_engine_gpu.py::test_state_roundtrip_and_reset sets for a migrated stream
 SLOTS = [9, 2, 6, 0, 10, 4, 7]           # source slots of the seven streams (max_streams = 11)
 SLOTS_B = [3, 15, 0, 8, 12, 1, 6]        # their slots in the target engine (max_streams = 16)
-CTX = {50: 2.5, 70: 3.5}
+CTX = {1: 0.05, 50: 2.5, 70: 3.5}
 _CACHE = {}
 
 
@@ -203,6 +203,87 @@ def test_import_without_cache_equals_the_per_stream_path(T):
             for key in ("p_now", "p_future", "vad", "logits", "e"):
                 np.testing.assert_allclose(ox[key], oy[key], rtol=0, atol=TOL, err_msg=f"tick {f} stream {k} {key}")
     a.close(); x.close(); y.close()
+
+
+@pytest.mark.parametrize("T", [50, 70])
+@pytest.mark.parametrize("split", [False, True], ids=["fp32", "split"])
+def test_set_state_is_the_one_record_import(split, T):
+    """vapx_set_state moves a stream through the kernels of the bulk import and rebuilds its cache with the import's helper: one record
+    per vapx_import_streams call has the GEMM shape (M = 2T) of a vapx_set_state, so the two engines end up BIT-equal - ring, LSTM, carry,
+    n_frames and every cache row of the export - and stay so for three more ticks."""
+    a, F, _ = _populate(T, split_f16=split)
+    x, y = _engine(T, split_f16=split), _engine(T, split_f16=split)
+    rec = a.export_streams(SLOTS)
+    for k, sid in enumerate(SLOTS):
+        x.import_streams([sid], rec[k:k + 1])
+        y.set_state(sid, a.get_state(sid))
+    np.testing.assert_array_equal(y.export_streams(SLOTS, cache=True), x.export_streams(SLOTS, cache=True))
+    for f in range(F, F + 3):
+        rx, ry = _tick(x, T, f, list(range(7)), SLOTS), _tick(y, T, f, list(range(7)), SLOTS)
+        for k in range(7):
+            np.testing.assert_array_equal(ry[k], rx[k], err_msg=f"tick {f} stream {k}: not bit-identical")
+    a.close(); x.close(); y.close()
+
+
+@pytest.mark.parametrize("T", [1, 50])
+def test_partial_set_state_touches_only_what_it_names(T):
+    """vapx_set_state with the ring alone, the LSTM alone, the carry alone and the ring with n_frames = 0, on every stream of the
+    population in turn: after each call the export (with cache) of ALL seven streams is held against the export before it - what the call
+    did not name is bit-equal, n_frames and cache rows included, what it named is what was given."""
+    from vap_realtime_amd import engine
+    eng, _, fills = _populate(T)
+    rng = np.random.default_rng(T)
+    want = eng.export_streams(SLOTS, cache=True).copy()
+    w = engine.split_state(want, T)                                   # views into `want`
+
+    def held(what):
+        np.testing.assert_array_equal(eng.export_streams(SLOTS, cache=True), want, err_msg=what)
+
+    for k, sid in enumerate(SLOTS):
+        lstm = rng.standard_normal((2, 2, 256)).astype(np.float32)
+        eng.set_state(sid, {"lstm": lstm, "n_frames": T})             # n_frames without a ring says nothing
+        w["lstm"][k] = lstm
+        held(f"stream {k}: lstm alone")
+        carry = rng.standard_normal((2, 320)).astype(np.float32)
+        eng.set_state(sid, {"carry": carry})
+        w["carry"][k] = carry
+        held(f"stream {k}: carry alone")
+        n = [T, max(T - 3, 1), 1][k % 3]
+        ring = rng.standard_normal((2, T, 256)).astype(np.float32)
+        eng.set_state(sid, {"ring": ring, "n_frames": n})
+        got = engine.split_state(eng.export_streams(SLOTS, cache=True), T)
+        assert got["n_frames"][k] == n
+        np.testing.assert_array_equal(got["ring"][k][:, :n], ring[:, :n])
+        assert not got["ring"][k][:, n:].any() and not got["cache"][k][:, n:].any()
+        assert np.isfinite(got["cache"][k]).all() and all(got["cache"][k][c, t].any() for c in range(2) for t in range(n))
+        w["n_frames"][k], w["ring"][k], w["cache"][k] = n, got["ring"][k], got["cache"][k]      # the named sections move on ...
+        held(f"stream {k}: ring alone")                                                         # ... and nothing else has
+        eng.set_state(sid, {"ring": ring, "n_frames": 0})
+        w["n_frames"][k], w["ring"][k], w["cache"][k] = 0, 0, 0
+        held(f"stream {k}: ring with n_frames = 0")
+    eng.close()
+
+
+def test_refused_follower_read_writes_nothing():
+    """vapx_get_state on a same-rate follower with a non-NULL lstm is refused before anything is written: the caller's ring and n_frames
+    keep the pattern they held (argument checks before anything)."""
+    import ctypes as C
+    c, g = _trunk_group()
+    for f in range(3):
+        g.step_wire(c.new_samples(f), [3, 1])
+    fol = g.engines["nod"]
+    assert fol.get_state(3)["n_frames"] == 3
+    ring = np.full((2, c.T, 256), np.nan, np.float32)
+    ring.view(np.uint32)[:] = 0x7FC0BEEF
+    lstm, n = np.zeros((2, 2, 256), np.float32), C.c_int32(-77)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    for args in ((ptr(lstm), None), (None, ptr(np.zeros((2, 320), np.float32))), (ptr(lstm), ptr(np.zeros((2, 320), np.float32)))):
+        rc = fol.lib.vapx_get_state(fol._h, 3, ptr(ring), C.byref(n), *args)
+        assert rc == -1 and "lives in the trunk leader" in fol.lib.vapx_last_error(fol._h).decode()
+        assert n.value == -77 and (ring.view(np.uint32) == 0x7FC0BEEF).all() and not lstm.any()
+    assert fol.lib.vapx_get_state(fol._h, 3, ptr(ring), C.byref(n), None, None) == 0 and n.value == 3
+    assert np.isfinite(ring[:, :3]).all() and (ring.view(np.uint32)[:, 3:] == 0x7FC0BEEF).all()      # rows beyond n_frames stay the caller's
+    g.close()
 
 
 def test_records_without_cache_move_between_the_precision_paths():

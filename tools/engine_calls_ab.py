@@ -5,10 +5,13 @@
 
 1. One seeded program through each build - host and device steps at 1, 8 and 64 streams, a prefill of 40 entries, export and import of
    64 streams with and without the Q|K|V cache, a two-model vapx_step_group - and every output block and every exported record must be
-   bit-identical.
+   bit-identical.  Then the per-stream state calls (state_program): on an fp32 and a split engine at T = 50 and T = 70, an 8 kHz engine, a
+   two-class engine and a vap 20 Hz + nod 10 Hz trunk group, four streams with window fills 0, 3, T and T + 7: every vapx_get_state
+   array, then vapx_set_state into a fresh engine, its vapx_export_streams with the cache (vapx_get_state where the bulk calls are
+   refused) and three more ticks (four in the group).
 2. The two builds timed alternately, `--pairs` pairs per leg (a sample is the median of `--iters` calls, of `--iters` / 5 for the two
    bulk legs): the host-inclusive step at 1, 8 and 64 streams ending in a synchronise (what tools/latency_small_batches.py measures),
-   export + import of 64 streams through pageable memory, and the prefill.  Gate per leg: median(new) <= median(parent) + (max(parent)
+   export + import of 64 streams through pageable memory, the prefill, and vapx_get_state + vapx_set_state over 64 streams.  Gate per leg: median(new) <= median(parent) + (max(parent)
    - min(parent)).  A leg whose parent samples disagree by more than the two medians differ says so: lengthen it (--iters) and repeat.
 
 Both builds export the same symbols, and a build calls some of its own functions (the vapx_engine constructor among them) through the
@@ -91,6 +94,62 @@ def program(b):
     return res
 
 
+def state_program(b):
+    """vapx_get_state / vapx_set_state on every kind of engine that moves state through them; returns {name: array}."""
+    res = {}
+    cpc20 = W.synthetic_weights(0, HZ, "vap")[0]
+    nod10 = W.pack_blob(cpc20, W.synthetic_weights(0, 10, "nod")[1], "nod")
+    rng = np.random.default_rng(77)
+    mulaw = rng.integers(0, 256, (4, 2, 400 * 80), dtype=np.uint8)
+    wide, narrow = synth.noise_batch(4, HOP * 80, seed=51), synth.noise_batch(4, 400 * 80, seed=52)
+
+    def plain(T, **kw):
+        return lambda: b.make(engine.Engine, b.blob, HZ, T / HZ, max_streams=4, **kw)
+
+    def classes2():
+        e = plain(50, input_classes=[("f32", 16000), ("mulaw", 8000)])()
+        for s in (1, 3):
+            e.set_stream_class(s, 1)
+        return e
+
+    def group():
+        return b.make(engine.TrunkGroup, {"vap": b.blobs["vap"], "nod": nod10}, {"vap": 20, "nod": 10}, {"vap": 2.5, "nod": 3.0}, max_streams=4)
+
+    hop16 = lambda t, ids: wide[ids, :, t * HOP:(t + 1) * HOP]
+    kinds = {f"{name}_T{T}": (plain(T, split_f16=name == "split"), T, hop16) for T in (50, 70) for name in ("fp32", "split")}
+    kinds["in8k_T50"] = (plain(50, input_hz=8000), 50, lambda t, ids: narrow[ids, :, t * 400:(t + 1) * 400])
+    kinds["classes2_T50"] = (classes2, 50, lambda t, ids: [(mulaw[s, :, t * 400:(t + 1) * 400] if s % 2 else wide[s, :, t * HOP:(t + 1) * HOP]).copy()
+                                                           for s in ids])
+    kinds["follow_20_10"] = (group, 50, hop16)
+    for kind, (make, T, block) in kinds.items():
+        fills = [0, 3, T, T + 7]
+        engines = lambda o: list(o.engines.items()) if isinstance(o, engine.TrunkGroup) else [("", o)]
+        src = make()
+        for t in range(T + 7):
+            ids = [s for s in range(4) if t >= T + 7 - fills[s]]
+            if ids:
+                src.step(block(t, ids), ids)
+        dst = make()
+        grouped = isinstance(dst, engine.TrunkGroup)
+        for (m, a), (_, d) in zip(engines(src), engines(dst)):
+            got = []
+            for s in range(4):
+                st = a.get_state(s)
+                got += [np.float32([st["n_frames"]])] + [st[k].ravel() for k in ("ring", "lstm", "carry") if st[k] is not None]
+                d.set_state(s, st)
+            res[f"{kind}{m}_get"] = np.concatenate(got)
+            bulk = not d.input_classes and not (grouped and dst.R[m] > 1)       # else vapx_export_streams is refused
+            res[f"{kind}{m}_after_set"] = d.export_streams(cache=True) if bulk else np.concatenate([d.get_state(s)["ring"].ravel() for s in range(4)])
+        ticks = []
+        for t in range(T + 7, T + 7 + (4 if grouped else 3)):
+            o = dst.step(block(t, [0, 1, 2, 3]), [0, 1, 2, 3])
+            ticks.append({m: o[m].copy() for m in o} if grouped else {"": o.copy()})
+        for m in ticks[0]:
+            res[f"{kind}{m}_ticks"] = np.stack([o[m] for o in ticks])
+        src.close(); dst.close()
+    return res
+
+
 def stepper(eng, audio):
     """One host step per call, walking the eight hops of `audio` round and round."""
     k = [0]
@@ -128,6 +187,11 @@ def legs(b, iters):
     out["export_import_64"] = lambda: median_ms(lambda: eng.import_streams(None, eng.export_streams(out=rec), False), max(iters // 5, 5))
     history, ids = synth.noise_batch(8, HOP * 5, seed=31), np.arange(8, 16)
     out["prefill_40"] = lambda: median_ms(lambda: eng.prefill(history, ids), max(iters // 5, 5))
+
+    def get_set_64():
+        for s in range(64):
+            eng.set_state(s, eng.get_state(s))
+    out["get_set_state_64"] = lambda: median_ms(get_set_64, max(iters // 5, 5))
     return out, keep
 
 
@@ -142,7 +206,7 @@ def main():
     assert args.pairs >= 5, "at least five pairs per leg"
     builds = [Build("parent", open_build(args.parent)), Build("new", open_build(args.new))]
 
-    got = [program(b) for b in builds]
+    got = [{**program(b), **state_program(b)} for b in builds]
     assert sorted(got[0]) == sorted(got[1])
     differ = [k for k in sorted(got[0]) if got[0][k].shape != got[1][k].shape or got[0][k].tobytes() != got[1][k].tobytes()]
     dead = [k for k in sorted(got[0]) if not np.isfinite(got[0][k]).all() or not np.abs(got[0][k]).max() > 0]

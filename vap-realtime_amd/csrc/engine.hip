@@ -143,12 +143,14 @@ struct Staged {
     if (nd) { dfree(dev); dev = nd; cap = n; }
     return hipSuccess;
   }
-  // host -> device: straight from a page-locked source (`direct`), else through `pin`
+  // `pin`, for a caller that assembles its block there and then calls upload(pin, n, st): idle once the latest copy out of it is done
+  hipError_t acquire_pinned() { return hipEventSynchronize(evt); }
+  // host -> device: straight from a page-locked source (`direct`), else through `pin` (src == pin: assembled in place)
   hipError_t upload(const T* src, size_t n, hipStream_t st, bool direct = false) {
     if (direct) return hipMemcpyAsync(dev, src, n * sizeof(T), hipMemcpyHostToDevice, st);
-    hipError_t e = hipEventSynchronize(evt);
+    hipError_t e = src == pin ? hipSuccess : hipEventSynchronize(evt);
     if (e != hipSuccess) return e;
-    memcpy(pin, src, n * sizeof(T));
+    if (src != pin) memcpy(pin, src, n * sizeof(T));
     if ((e = hipMemcpyAsync(dev, pin, n * sizeof(T), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
     return hipEventRecord(evt, st);
   }
@@ -272,7 +274,8 @@ struct vapx_engine : Geometry {
   Staged<float> gw;                       // allocated by the first host-output group step (the follower set is fixed once anyone has stepped)
   std::vector<std::pair<int32_t, int32_t>> group_bad;   // (batch slot, model index) pairs of the latest host-output vapx_step_group
   // vapx_export_streams / vapx_import_streams: ids of up to max_streams streams; bounded staging blocks for host records (allocated
-  // on the first host-buffer call; the pinned one only for pageable memory)
+  // on the first host-buffer call; the pinned one only for pageable memory).  vapx_get_state / vapx_set_state move their one record
+  // through the same blocks
   Staged<int> sio_ids;
   Staged<float> sio;
 
@@ -1693,89 +1696,22 @@ int vapx_get_config(vapx_handle h, vapx_config* out) {
   return VAPX_OK;
 }
 
-int vapx_get_state(vapx_handle h, int32_t sid, float* ring, int32_t* n_frames, float* lstm, float* carry) {
-  if (!h) return VAPX_E_INVAL;
-  if (sid < 0 || sid >= h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "stream id out of range");
-  { int rc = quiesce(h); if (rc) return rc; }
-  int fs = 0;
-  HIPCHK(h, hipMemcpy(&fs, h->frames_seen + sid, sizeof(int), hipMemcpyDeviceToHost));
-  const int T = h->T, n = fs < T ? fs : T;
-  if (n_frames) *n_frames = n;
-  if (ring) {
-    std::vector<float> tmp((size_t)2 * T * 256);
-    HIPCHK(h, hipMemcpy(tmp.data(), h->ring + (size_t)sid * 2 * T * 256, tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (int c = 0; c < 2; ++c)
-      for (int t = 0; t < n; ++t) {
-        int slot = ((fs - n + t) % T + T) % T;
-        memcpy(ring + ((size_t)c * T + t) * 256, tmp.data() + ((size_t)c * T + slot) * 256, 256 * sizeof(float));
-      }
-  }
-  if (h->trunk && (lstm || carry)) return fail(h, VAPX_E_INVAL, "LSTM / carry state lives in the trunk leader");
-  if (lstm) {
-    for (int c = 0; c < 2; ++c) {
-      HIPCHK(h, hipMemcpy(lstm + (c * 2 + 0) * 256, h->h_state + ((size_t)sid * 2 + c) * 256, 256 * sizeof(float), hipMemcpyDeviceToHost));
-      HIPCHK(h, hipMemcpy(lstm + (c * 2 + 1) * 256, h->c_state + ((size_t)sid * 2 + c) * 256, 256 * sizeof(float), hipMemcpyDeviceToHost));
-    }
-  }
-  if (carry) HIPCHK(h, hipMemcpy(carry, h->carry + (size_t)sid * 2 * VAPX_PAD, 2 * VAPX_PAD * sizeof(float), hipMemcpyDeviceToHost));
-  return VAPX_OK;
-}
-
-int vapx_set_state(vapx_handle h, int32_t sid, const float* ring, int32_t n_frames, const float* lstm, const float* carry) {
-  if (!h) return VAPX_E_INVAL;
-  if (sid < 0 || sid >= h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "stream id out of range");
-  if (n_frames < 0 || n_frames > h->T) return fail(h, VAPX_E_INVAL, "n_frames outside [0,T]");
-  if (h->trunk && (lstm || carry)) return fail(h, VAPX_E_INVAL, "LSTM / carry state lives in the trunk leader");
-  { int rc = quiesce(h); if (rc) return rc; }
-  const int T = h->T;
-  if (h->rs_hist) {   // the call has no place for the resampler history: the stream's input starts as a new signal
-    HIPCHK(h, hipMemset(h->rs_hist + (size_t)sid * h->rs_rec, 0, (size_t)h->rs_rec * sizeof(float)));
-    HIPCHK(h, hipMemset(h->rs_started + (size_t)sid * 2, 0, 2 * sizeof(int)));
-  }
-  if (ring) {
-    // chronological rows land in slots 0..n-1 and frames_seen = n, so the next append goes to slot n % T
-    for (int c = 0; c < 2; ++c)
-      HIPCHK(h, hipMemcpy(h->ring + ((size_t)sid * 2 + c) * T * 256, ring + (size_t)c * T * 256, (size_t)n_frames * 256 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->frames_seen + sid, &n_frames, sizeof(int), hipMemcpyHostToDevice));
-    if (n_frames > 0) {
-      // rebuild the layer-0 Q|K|V cache of the imported rows: LN(ring rows) . Wqkv^T (slots 0..n-1)
-      hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, nullptr, h->sc.bn, T, 1);
-      GatherArgs ga;
-      memset(&ga, 0, sizeof ga);
-      ga.xin = h->ring + (size_t)sid * 2 * T * 256; ga.bn = h->sc.bn; ga.bhead = h->sc.bhead;
-      ga.x0 = h->sc.xl[0]; ga.xn = h->sc.xn; ga.gamma = h->layer[0].ln_self_g; ga.beta = h->layer[0].ln_self_b;
-      ga.B = 1; ga.T = T; ga.rows_in = T;
-      HIPCHK(h, launch_gather_ln(ga, nullptr));
-      GemmArgs g = gemm_args(h->sc.xn, contiguous_rows(256), h->layer[0].wqkv, 2 * T, 768, 256,
-                             h->ring_qkv + (size_t)sid * 2 * T * 768, contiguous_rows(768));
-      HIPCHK(h, launch_gemm_f32(g, EPI_STORE, 0, nullptr));
-      HIPCHK(h, hipDeviceSynchronize());
-    }
-  }
-  if (lstm) {
-    for (int c = 0; c < 2; ++c) {
-      HIPCHK(h, hipMemcpy(h->h_state + ((size_t)sid * 2 + c) * 256, lstm + (c * 2 + 0) * 256, 256 * sizeof(float), hipMemcpyHostToDevice));
-      HIPCHK(h, hipMemcpy(h->c_state + ((size_t)sid * 2 + c) * 256, lstm + (c * 2 + 1) * 256, 256 * sizeof(float), hipMemcpyHostToDevice));
-    }
-  }
-  if (carry) HIPCHK(h, hipMemcpy(h->carry + (size_t)sid * 2 * VAPX_PAD, carry, 2 * VAPX_PAD * sizeof(float), hipMemcpyHostToDevice));
-  return VAPX_OK;
-}
-
-// ---- bulk state export / import (vapx.h "Bulk state export / import"; kernels in state_io.hip) ----------------------------------------
+// ---- stream state in and out: vapx_get_state / vapx_set_state and the bulk calls (vapx.h "Bulk state export / import") -----------------
+// One mover: the gather / scatter kernels of state_io.hip on a record laid out by state_record.h.  The bulk calls move the public record,
+// stream-ordered; the per-stream calls move one engine-internal record (no resampler history, no cache) on the null stream.
 namespace {
 
 constexpr size_t kStateStageFloats = (size_t)8 << 20;   // 32 MiB: host records travel through device / pinned blocks of at most this size
 
 bool sio_follower(const vapx_engine* h) { return h->trunk != nullptr || h->orphaned; }
 
-size_t state_floats(const vapx_engine* h, int flags) {
-  return VAPX_STATE_HEADER_FLOATS + (sio_follower(h) ? 0 : (size_t)(1024 + 2 * VAPX_PAD)) + (size_t)h->rs_rec + (size_t)2 * h->T * 256 +
-         ((flags & VAPX_STATE_CACHE) ? (size_t)2 * h->T * 768 : 0);
-}
+StateLayout sio_layout(const vapx_engine* h, int flags) { return state_layout(h->T, !sio_follower(h), h->rs_rec, (flags & VAPX_STATE_CACHE) != 0); }
+size_t state_floats(const vapx_engine* h, int flags) { return (size_t)sio_layout(h, flags).total; }
 
-// common argument checks; host ids are validated here, before anything is enqueued
+// argument checks of the bulk calls; host ids are validated here, before anything is enqueued
 int sio_check(vapx_engine* h, const char* what, int n, const int32_t* ids, const void* buf, int flags) {
+  if (h->cls_table) return fail(h, VAPX_E_INVAL, "%s is refused on an engine with input classes: a state record has one resampler history size per engine, "
+                            "records with per-stream history sizes do not exist yet (vapx_get_state / vapx_set_state work)", what);
   if (h->R > 1)   // the record has no place yet for the leader rows of a frame in the making (acc) and the stream's phase
     return fail(h, VAPX_E_INVAL, "%s: refused on a trunk follower at 1/%d of its leader's rate: a state record does not carry the stream's "
                 "half-collected frame and phase yet (vapx_get_state / vapx_set_state move its ring)", what, h->R);
@@ -1787,8 +1723,19 @@ int sio_check(vapx_engine* h, const char* what, int n, const int32_t* ids, const
   return VAPX_OK;
 }
 
-// staging blocks for host records: streams per block (>= 1).  Every host-buffer call ends with the stream synchronised, so a block that
-// has to grow is idle.  (The ids of a state call, up to max_streams of them, travel through sio_ids: the step's id buffers hold max_batch)
+// the staging blocks at `want` floats.  Every host-buffer call ends with the stream synchronised, so a block that has to grow is idle
+int sio_reserve(vapx_engine* h, size_t want, bool need_pinned) {
+  hipError_t e = h->sio.reserve(want, false);
+  if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, VAPX_E_NOMEM, "state staging block (%zu bytes, device): %s", want * 4, hipGetErrorString(e)); }
+  if (need_pinned && (e = h->sio.reserve_pinned(want)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(h, VAPX_E_NOMEM, "state staging block (%zu bytes, pinned): %s", want * 4, hipGetErrorString(e));
+  }
+  return VAPX_OK;
+}
+
+// staging blocks for the bulk calls' host records: streams per block (>= 1).  (The ids of a state call, up to max_streams of them, travel
+// through sio_ids: the step's id buffers hold max_batch)
 int sio_stage(vapx_engine* h, size_t rec, int n, bool need_pinned, int* per_block) {
   size_t cap = kStateStageFloats;
   if (const char* ev = getenv("VAPX_STATE_STAGE_FLOATS")) {   // debug knob: small blocks, so that a test with a handful of streams takes the multi-block path
@@ -1798,56 +1745,129 @@ int sio_stage(vapx_engine* h, size_t rec, int n, bool need_pinned, int* per_bloc
   size_t per = cap / rec;
   if (per < 1) per = 1;
   if (per > (size_t)n) per = (size_t)n;
-  const size_t want = per * rec;
-  hipError_t e = h->sio.reserve(want, false);
-  if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, VAPX_E_NOMEM, "state staging block (%zu bytes, device): %s", want * 4, hipGetErrorString(e)); }
-  if (need_pinned && (e = h->sio.reserve_pinned(want)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(h, VAPX_E_NOMEM, "state staging block (%zu bytes, pinned): %s", want * 4, hipGetErrorString(e));
-  }
   *per_block = (int)per;
-  return VAPX_OK;
+  return sio_reserve(h, per * rec, need_pinned);
 }
 
-StateIoArgs sio_args(vapx_engine* h, int flags, float* rec, const int* ids, int n) {
+// kernel arguments for n records of layout L at `rec`, every section of the layout named; the header words say what the record holds
+StateIoArgs sio_args(vapx_engine* h, const StateLayout& L, float* rec, const int* ids, int n) {
   StateIoArgs a;
   memset(&a, 0, sizeof a);
-  a.rec = rec; a.rec_floats = (long)state_floats(h, flags); a.ids = ids; a.id0 = 0;
+  a.rec = rec; a.lay = L; a.sections = L.sections(); a.ids = ids; a.id0 = 0;
   a.ring = h->ring; a.ring_qkv = h->ring_qkv; a.h_state = h->h_state; a.c_state = h->c_state; a.carry = h->carry;
   a.frames_seen = h->frames_seen; a.T = h->T; a.n = n;
-  a.with_state = sio_follower(h) ? 0 : 1; a.with_cache = (flags & VAPX_STATE_CACHE) ? 1 : 0;
-  a.hdr[0] = VAPX_STATE_MAGIC; a.hdr[1] = h->T; a.hdr[2] = h->cfg.frame_hz;
-  a.rs_hist = h->rs_hist; a.rs_started = h->rs_started; a.rs_rec = h->rs_rec; a.hdr[6] = h->in_hz();
-  a.hdr[3] = (a.with_state ? VAPX_STATE_HAS_LSTM : 0) | (h->in_hz() ? VAPX_STATE_HAS_RESAMPLE : 0) |
-             (a.with_cache ? VAPX_STATE_HAS_CACHE | ((h->cfg.flags & VAPX_FLAG_SPLIT_F16) ? VAPX_STATE_CACHE_SPLIT : 0) : 0);
-  a.hdr[5] = h->cfg.mode;
+  const bool history = L.history >= 0;   // of the bulk calls' record, on an engine with an input rate
+  a.rs_hist = history ? h->rs_hist : nullptr; a.rs_started = history ? h->rs_started : nullptr; a.rs_rec = history ? h->rs_rec : 0;
+  a.hdr[SH_MAGIC] = VAPX_STATE_MAGIC; a.hdr[SH_CTX_FRAMES] = h->T; a.hdr[SH_FRAME_HZ] = h->cfg.frame_hz;
+  a.hdr[SH_BITS] = (L.lstm >= 0 ? VAPX_STATE_HAS_LSTM : 0) | (history ? VAPX_STATE_HAS_RESAMPLE : 0) |
+                   (L.cache >= 0 ? VAPX_STATE_HAS_CACHE | ((h->cfg.flags & VAPX_FLAG_SPLIT_F16) ? VAPX_STATE_CACHE_SPLIT : 0) : 0);
+  a.hdr[SH_MODE] = h->cfg.mode; a.hdr[SH_INPUT_HZ] = history ? h->in_hz() : 0;
   return a;
 }
 
+// rebuild the layer-0 Q|K|V cache of n streams (ids, or id0 + k) from their ring rows: LN(ring rows) . Wqkv^T (fp32 path), for up to
+// max_batch streams per pass through the step's scratch: LN, one GEMM, one scatter of the rows below the window fill - whatever the
+// number of streams in the pass
+int rebuild_cache(vapx_engine* h, const int* ids, int id0, int n, hipStream_t st) {
+  const int B = h->cfg.max_batch, T = h->T;
+  for (int k0 = 0; k0 < n; k0 += B) {
+    const int nb = std::min(B, n - k0);
+    const int* cids = ids ? ids + k0 : nullptr;
+    { ProfScope ps(h, CLS_GATHER, st);
+      HIPCHK(h, launch_state_ln(h->ring, cids, id0 + k0, h->sc.xn, h->layer[0].ln_self_g, h->layer[0].ln_self_b, T, nb, st)); }
+    GemmArgs g = gemm_args(h->sc.xn, contiguous_rows(256), h->layer[0].wqkv, nb * 2 * T, 768, 256, h->sc.qkv, contiguous_rows(768));
+    { ProfScope ps(h, gemm_class(EPI_STORE), st); HIPCHK(h, launch_gemm_f32(g, EPI_STORE, 0, st)); }
+    HIPCHK(h, launch_state_cache_scatter(h->sc.qkv, cids, id0 + k0, h->ring_qkv, h->frames_seen, T, nb, st));
+  }
+  return VAPX_OK;
+}
+
+// the per-stream calls, once their arguments are checked: the device idle, then kernel arguments for stream `sid` and an engine-internal
+// record - its ring and, unless this is a follower, LSTM + carry - in the staging blocks.  Not the public format's business: no sio_check,
+// no staging bound
+int sio_one(vapx_engine* h, int sid, StateIoArgs* a) {
+  if (int rc = quiesce(h)) return rc;
+  const StateLayout L = state_layout(h->T, !sio_follower(h), 0, false);
+  if (int rc = sio_reserve(h, (size_t)L.total, true)) return rc;
+  *a = sio_args(h, L, h->sio.dev, nullptr, 1);
+  a->id0 = sid;
+  return VAPX_OK;
+}
+
 }  // namespace
+
+int vapx_get_state(vapx_handle h, int32_t sid, float* ring, int32_t* n_frames, float* lstm, float* carry) {
+  if (!h) return VAPX_E_INVAL;
+  if (sid < 0 || sid >= h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "stream id out of range");
+  if (sio_follower(h) && (lstm || carry)) return fail(h, VAPX_E_INVAL, "LSTM / carry state lives in the trunk leader");
+  StateIoArgs a;
+  if (int rc = sio_one(h, sid, &a)) return rc;
+  const StateLayout& L = a.lay;
+  HIPCHK(h, launch_state_export(a, nullptr));
+  const float* r = h->sio.pin;
+  HIPCHK(h, h->sio.download(h->sio.pin, (size_t)L.total * sizeof(float), nullptr));   // page-locked: one asynchronous copy
+  HIPCHK(h, hipStreamSynchronize(nullptr));
+  int32_t n = 0;
+  memcpy(&n, r + L.header + SH_N_FRAMES, sizeof n);
+  if (n_frames) *n_frames = n;
+  if (ring)   // rows t < n_frames; the caller's rows beyond stay as they are
+    for (int c = 0; c < 2; ++c) memcpy(ring + (size_t)c * h->T * 256, r + L.ring + (size_t)c * h->T * 256, (size_t)n * 256 * sizeof(float));
+  if (lstm) memcpy(lstm, r + L.lstm, kStateLstmFloats * sizeof(float));
+  if (carry) memcpy(carry, r + L.carry, kStateCarryFloats * sizeof(float));
+  return VAPX_OK;
+}
+
+int vapx_set_state(vapx_handle h, int32_t sid, const float* ring, int32_t n_frames, const float* lstm, const float* carry) {
+  if (!h) return VAPX_E_INVAL;
+  if (sid < 0 || sid >= h->cfg.max_streams) return fail(h, VAPX_E_RANGE, "stream id out of range");
+  if (n_frames < 0 || n_frames > h->T) return fail(h, VAPX_E_INVAL, "n_frames outside [0,T]");
+  if (sio_follower(h) && (lstm || carry)) return fail(h, VAPX_E_INVAL, "LSTM / carry state lives in the trunk leader");
+  StateIoArgs a;
+  if (int rc = sio_one(h, sid, &a)) return rc;
+  const StateLayout& L = a.lay;
+  a.sections = (ring ? SEC_RING : 0) | (lstm ? SEC_LSTM : 0) | (carry ? SEC_CARRY : 0);
+  HIPCHK(h, h->sio.acquire_pinned());
+  float* r = h->sio.pin;
+  a.hdr[SH_N_FRAMES] = n_frames;
+  memcpy(r + L.header, a.hdr, sizeof a.hdr);
+  // chronological rows land in slots 0..n-1 and frames_seen = n, so the next append goes to slot n % T
+  if (ring)
+    for (int c = 0; c < 2; ++c) memcpy(r + L.ring + (size_t)c * h->T * 256, ring + (size_t)c * h->T * 256, (size_t)n_frames * 256 * sizeof(float));
+  if (lstm) memcpy(r + L.lstm, lstm, kStateLstmFloats * sizeof(float));
+  if (carry) memcpy(r + L.carry, carry, kStateCarryFloats * sizeof(float));
+  HIPCHK(h, h->sio.upload(r, (size_t)(ring ? L.total : L.ring), nullptr));   // without a ring: the header and the small sections
+  HIPCHK(h, launch_state_import(a, nullptr));
+  if (ring && n_frames > 0)
+    if (int rc = rebuild_cache(h, nullptr, sid, 1, nullptr)) return rc;
+  if (h->rs_hist) {   // the call has no place for the resampler history: the stream's input starts as a new signal
+    HIPCHK(h, hipMemsetAsync(h->rs_hist + (size_t)sid * h->rs_rec, 0, (size_t)h->rs_rec * sizeof(float), nullptr));
+    HIPCHK(h, hipMemsetAsync(h->rs_started + (size_t)sid * 2, 0, 2 * sizeof(int), nullptr));
+  }
+  HIPCHK(h, hipStreamSynchronize(nullptr));
+  return VAPX_OK;
+}
 
 size_t vapx_state_floats(vapx_handle h, int32_t flags) { return h ? state_floats(h, flags) : 0; }
 
 int vapx_export_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, float* dst, int32_t flags, void* hip_stream) {
   if (!h) return VAPX_E_INVAL;
-  if (h->cls_table) return fail(h, VAPX_E_INVAL, "%s is refused on an engine with input classes: a state record has one resampler history size per engine, "
-                            "records with per-stream history sizes do not exist yet (vapx_get_state / vapx_set_state work)", "vapx_export_streams");
   { int rc = sio_check(h, "vapx_export_streams", n, stream_ids, dst, flags); if (rc) return rc; }
   hipStream_t st = (hipStream_t)hip_stream;
   const int* ids = nullptr;
   int rc = enter_settled(h, st);
   if (rc || (rc = upload_ids(h, h->sio_ids, n, stream_ids, flags, st, &ids))) return rc;
+  const StateLayout L = sio_layout(h, flags);
   if (flags & VAPX_OUT_DEVICE) {   // one gather kernel, no synchronisation
-    HIPCHK(h, launch_state_export(sio_args(h, flags, dst, ids, n), st));
+    HIPCHK(h, launch_state_export(sio_args(h, L, dst, ids, n), st));
     return VAPX_OK;
   }
-  const size_t rec = state_floats(h, flags);
+  const size_t rec = (size_t)L.total;
   const bool direct = is_pinned_host(dst);   // vapx_host_alloc memory: the copies land in the caller's block
   int per = 1;
   if ((rc = sio_stage(h, rec, n, !direct, &per))) return rc;
   for (int k0 = 0; k0 < n; k0 += per) {
     const int nb = std::min(per, n - k0);
-    StateIoArgs a = sio_args(h, flags, h->sio.dev, ids ? ids + k0 : nullptr, nb);
+    StateIoArgs a = sio_args(h, L, h->sio.dev, ids ? ids + k0 : nullptr, nb);
     a.id0 = k0;
     HIPCHK(h, launch_state_export(a, st));
     HIPCHK(h, h->sio.download(dst + (size_t)k0 * rec, (size_t)nb * rec * sizeof(float), st));   // pageable: block by block through the pinned buffer
@@ -1858,37 +1878,40 @@ int vapx_export_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, flo
 
 int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, const float* src, int32_t flags, void* hip_stream) {
   if (!h) return VAPX_E_INVAL;
-  if (h->cls_table) return fail(h, VAPX_E_INVAL, "%s is refused on an engine with input classes: a state record has one resampler history size per engine, "
-                            "records with per-stream history sizes do not exist yet (vapx_get_state / vapx_set_state work)", "vapx_import_streams");
   { int rc = sio_check(h, "vapx_import_streams", n, stream_ids, src, flags); if (rc) return rc; }
-  const size_t rec = state_floats(h, flags);
+  const StateLayout L = sio_layout(h, flags);
+  const size_t rec = (size_t)L.total;
   const bool with_cache = (flags & VAPX_STATE_CACHE) != 0, on_host = !(flags & VAPX_OUT_DEVICE);
-  const int T = h->T;
   if (on_host) {   // every header, before any stream is touched
-    const int want_bits = (sio_follower(h) ? 0 : VAPX_STATE_HAS_LSTM) | (with_cache ? VAPX_STATE_HAS_CACHE : 0);
-    const int split_bit = (h->cfg.flags & VAPX_FLAG_SPLIT_F16) ? VAPX_STATE_CACHE_SPLIT : 0;
+    const int T = h->T, in_hz = h->in_hz();
+    const bool split = (h->cfg.flags & VAPX_FLAG_SPLIT_F16) != 0;
+    const StateExpect want{T, h->cfg.frame_hz, in_hz, sio_follower(h), with_cache, split};
     for (int k = 0; k < n; ++k) {
-      int32_t hd[8];
-      memcpy(hd, src + (size_t)k * rec, sizeof hd);
-      if (hd[0] != VAPX_STATE_MAGIC) return fail(h, VAPX_E_INVAL, "record %d: magic 0x%08x is not a state record (0x%08x)", k, hd[0], VAPX_STATE_MAGIC);
-      if (hd[1] != T) return fail(h, VAPX_E_INVAL, "record %d: ctx_frames %d differs from this engine's %d", k, hd[1], T);
-      if (hd[2] != h->cfg.frame_hz) return fail(h, VAPX_E_INVAL, "record %d: frame_hz %d differs from this engine's %d", k, hd[2], h->cfg.frame_hz);
-      if ((hd[3] & VAPX_STATE_HAS_LSTM) != (want_bits & VAPX_STATE_HAS_LSTM))
-        return fail(h, VAPX_E_INVAL, "record %d: content bits 0x%x: %s", k, hd[3],
-                    sio_follower(h) ? "a leader / stand-alone record (LSTM + carry) offered to a trunk follower"
-                                    : "a trunk follower's record (no LSTM + carry) offered to a leader / stand-alone engine");
-      if (((hd[3] & VAPX_STATE_HAS_RESAMPLE) != 0) != (h->in_hz() != 0) || hd[6] != h->in_hz())
-        return fail(h, VAPX_E_INVAL, "record %d: input_hz %d (content bits 0x%x) differs from this engine's %d: the record %s a resampler history, "
-                    "this engine %s", k, hd[6] ? hd[6] : 16000, hd[3], h->in_hz() ? h->in_hz() : 16000,
-                    (hd[3] & VAPX_STATE_HAS_RESAMPLE) ? "carries" : "carries no", h->in_hz() ? "keeps one" : "keeps none");
-      if ((hd[3] & VAPX_STATE_HAS_CACHE) != (want_bits & VAPX_STATE_HAS_CACHE))
-        return fail(h, VAPX_E_INVAL, "record %d: content bits 0x%x: the record %s a Q|K|V cache, the call's flags say it %s", k, hd[3],
-                    (hd[3] & VAPX_STATE_HAS_CACHE) ? "carries" : "carries no", with_cache ? "does" : "does not");
-      if (with_cache && (hd[3] & VAPX_STATE_CACHE_SPLIT) != split_bit)
-        return fail(h, VAPX_E_INVAL, "record %d: content bits 0x%x: the Q|K|V cache was made on the %s path, this engine runs the %s path "
-                    "(import without VAPX_STATE_CACHE: records without a cache are portable)", k, hd[3],
-                    (hd[3] & VAPX_STATE_CACHE_SPLIT) ? "split-precision" : "fp32", split_bit ? "split-precision" : "fp32");
-      if (hd[4] < 0 || hd[4] > T) return fail(h, VAPX_E_RANGE, "record %d: n_frames %d outside [0,%d]", k, hd[4], T);
+      int32_t hd[SH_WORDS];
+      memcpy(hd, src + (size_t)k * rec + L.header, sizeof hd);
+      const int bits = hd[SH_BITS];
+      switch (state_header_check(hd, want)) {
+        case SHF_NONE: break;
+        case SHF_MAGIC: return fail(h, VAPX_E_INVAL, "record %d: magic 0x%08x is not a state record (0x%08x)", k, hd[SH_MAGIC], VAPX_STATE_MAGIC);
+        case SHF_CTX_FRAMES: return fail(h, VAPX_E_INVAL, "record %d: ctx_frames %d differs from this engine's %d", k, hd[SH_CTX_FRAMES], T);
+        case SHF_FRAME_HZ: return fail(h, VAPX_E_INVAL, "record %d: frame_hz %d differs from this engine's %d", k, hd[SH_FRAME_HZ], h->cfg.frame_hz);
+        case SHF_ROLE:
+          return fail(h, VAPX_E_INVAL, "record %d: content bits 0x%x: %s", k, bits,
+                      sio_follower(h) ? "a leader / stand-alone record (LSTM + carry) offered to a trunk follower"
+                                      : "a trunk follower's record (no LSTM + carry) offered to a leader / stand-alone engine");
+        case SHF_INPUT_RATE:
+          return fail(h, VAPX_E_INVAL, "record %d: input_hz %d (content bits 0x%x) differs from this engine's %d: the record %s a resampler history, "
+                      "this engine %s", k, hd[SH_INPUT_HZ] ? hd[SH_INPUT_HZ] : 16000, bits, in_hz ? in_hz : 16000,
+                      (bits & VAPX_STATE_HAS_RESAMPLE) ? "carries" : "carries no", in_hz ? "keeps one" : "keeps none");
+        case SHF_CACHE:
+          return fail(h, VAPX_E_INVAL, "record %d: content bits 0x%x: the record %s a Q|K|V cache, the call's flags say it %s", k, bits,
+                      (bits & VAPX_STATE_HAS_CACHE) ? "carries" : "carries no", with_cache ? "does" : "does not");
+        case SHF_CACHE_PATH:
+          return fail(h, VAPX_E_INVAL, "record %d: content bits 0x%x: the Q|K|V cache was made on the %s path, this engine runs the %s path "
+                      "(import without VAPX_STATE_CACHE: records without a cache are portable)", k, bits,
+                      (bits & VAPX_STATE_CACHE_SPLIT) ? "split-precision" : "fp32", split ? "split-precision" : "fp32");
+        case SHF_N_FRAMES: return fail(h, VAPX_E_RANGE, "record %d: n_frames %d outside [0,%d]", k, hd[SH_N_FRAMES], T);
+      }
     }
   }
   hipStream_t st = (hipStream_t)hip_stream;
@@ -1896,7 +1919,7 @@ int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, con
   int rc = enter_settled(h, st);
   if (rc || (rc = upload_ids(h, h->sio_ids, n, stream_ids, flags, st, &ids))) return rc;
   if (!on_host) {   // one scatter kernel, no synchronisation
-    HIPCHK(h, launch_state_import(sio_args(h, flags, const_cast<float*>(src), ids, n), st));
+    HIPCHK(h, launch_state_import(sio_args(h, L, const_cast<float*>(src), ids, n), st));
   } else {
     const bool direct = is_pinned_host(src);
     int per = 1;
@@ -1904,25 +1927,12 @@ int vapx_import_streams(vapx_handle h, int32_t n, const int32_t* stream_ids, con
     for (int k0 = 0; k0 < n; k0 += per) {
       const int nb = std::min(per, n - k0);
       HIPCHK(h, h->sio.upload(src + (size_t)k0 * rec, (size_t)nb * rec, st, direct));   // pageable: once the previous block has left the pinned buffer
-      StateIoArgs a = sio_args(h, flags, h->sio.dev, ids ? ids + k0 : nullptr, nb);
+      StateIoArgs a = sio_args(h, L, h->sio.dev, ids ? ids + k0 : nullptr, nb);
       a.id0 = k0;
       HIPCHK(h, launch_state_import(a, st));
     }
   }
-  if (!with_cache) {
-    // rebuild the layer-0 Q|K|V cache of the imported rows as vapx_set_state does, LN(ring rows) . Wqkv^T (fp32 path), for up to
-    // max_batch streams per pass through the step's scratch: LN, one GEMM, one scatter - whatever the number of streams in the pass
-    const int B = h->cfg.max_batch;
-    for (int k0 = 0; k0 < n; k0 += B) {
-      const int nb = std::min(B, n - k0);
-      const int* cids = ids ? ids + k0 : nullptr;
-      { ProfScope ps(h, CLS_GATHER, st);
-        HIPCHK(h, launch_state_ln(h->ring, cids, k0, h->sc.xn, h->layer[0].ln_self_g, h->layer[0].ln_self_b, T, nb, st)); }
-      GemmArgs g = gemm_args(h->sc.xn, contiguous_rows(256), h->layer[0].wqkv, nb * 2 * T, 768, 256, h->sc.qkv, contiguous_rows(768));
-      { ProfScope ps(h, gemm_class(EPI_STORE), st); HIPCHK(h, launch_gemm_f32(g, EPI_STORE, 0, st)); }
-      HIPCHK(h, launch_state_cache_scatter(h->sc.qkv, cids, k0, h->ring_qkv, h->frames_seen, T, nb, st));
-    }
-  }
+  if (!with_cache && (rc = rebuild_cache(h, ids, 0, n, st))) return rc;
   if (on_host) HIPCHK(h, hipStreamSynchronize(st));
   return VAPX_OK;
 }

@@ -1,4 +1,5 @@
-// Bulk stream-state export / import (vapx_export_streams / vapx_import_streams, include/vapx.h "Bulk state export / import").
+// Stream-state export / import: vapx_export_streams / vapx_import_streams (include/vapx.h "Bulk state export / import") and, one stream
+// at a time through an engine-internal record, vapx_get_state / vapx_set_state.  The record's layout is state_record.h's.
 // Pure data movement: no LDS, no atomics, every access a plain 16-byte vector load / store.  One wave moves one 256-float ring row
 // (64 lanes x 16 bytes, coalesced on both sides) and, when the cache travels, the row's three 256-float Q | K | V segments with it: four
 // independent 16-byte loads in flight per lane before the first store.  A workgroup is four such waves; the grid is
@@ -12,11 +13,10 @@ namespace {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kStateFloats = 2 * 2 * 256 + 2 * VAPX_PAD;   // lstm [2][2][256] + carry [2][320]
-constexpr int kHeaderFloats = 8;
-constexpr int kSmallItems = 9;                             // 4 LSTM rows, 3 carry chunks (640 floats = 2.5 rows), 1 header, 1 resampler history
 constexpr int kHeaderItem = 7, kResampleItem = 8;
+constexpr int kSmallItems = 9;                              // 4 LSTM rows, 3 carry chunks (640 floats = 2.5 rows), 1 header, 1 resampler history
 constexpr int kMaxGridY = 32768;
+static_assert(kStateLstmFloats == 4 * 256 && kStateCarryFloats == 2 * VAPX_PAD, "state_record.h against the small items and common.h");
 
 // export: ring slot ((fs - n + t) mod T) -> chronological row t, zero rows beyond n = min(fs, T)
 __global__ __launch_bounds__(256) void state_export_kernel(StateIoArgs a) {
@@ -27,9 +27,11 @@ __global__ __launch_bounds__(256) void state_export_kernel(StateIoArgs a) {
   const int sid = a.ids ? a.ids[k] : a.id0 + k;
   const int fs = a.frames_seen[sid];
   const int nn = fs < 0 ? 0 : (fs < T ? fs : T);
-  float* r = a.rec + (long)k * a.rec_floats;
-  const long o_ring = kHeaderFloats + (a.with_state ? kStateFloats : 0) + a.rs_rec;
+  const StateLayout& L = a.lay;
+  float* r = a.rec + (long)k * L.total;
   if (item < 2 * T) {
+    if (!(a.sections & SEC_RING)) return;
+    const bool cache = a.sections & SEC_CACHE;
     const int c = item >= T ? 1 : 0, t = item - c * T;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     f32x4 q0 = v, q1 = v, q2 = v;
@@ -37,61 +39,58 @@ __global__ __launch_bounds__(256) void state_export_kernel(StateIoArgs a) {
       const int slot = (fs - nn + t) % T;
       const long srow = ((long)sid * 2 + c) * T + slot;
       v = *(const f32x4*)(a.ring + srow * 256 + lane * 4);
-      if (a.with_cache) {
+      if (cache) {
         const float* qs = a.ring_qkv + srow * 768 + lane * 4;
         q0 = *(const f32x4*)(qs); q1 = *(const f32x4*)(qs + 256); q2 = *(const f32x4*)(qs + 512);
       }
     }
-    *(f32x4*)(r + o_ring + (long)item * 256 + lane * 4) = v;
-    if (a.with_cache) {
-      float* qd = r + o_ring + (long)2 * T * 256 + (long)item * 768 + lane * 4;
+    *(f32x4*)(r + L.ring + (long)item * 256 + lane * 4) = v;
+    if (cache) {
+      float* qd = r + L.cache + (long)item * 768 + lane * 4;
       *(f32x4*)(qd) = q0; *(f32x4*)(qd + 256) = q1; *(f32x4*)(qd + 512) = q2;
     }
     return;
   }
   const int j = item - 2 * T;
   if (j == kHeaderItem) {
-    if (lane == 0) *(i32x4*)(r) = i32x4{a.hdr[0], a.hdr[1], a.hdr[2], a.hdr[3]};
+    if (lane == 0) *(i32x4*)(r + L.header) = i32x4{a.hdr[SH_MAGIC], a.hdr[SH_CTX_FRAMES], a.hdr[SH_FRAME_HZ], a.hdr[SH_BITS]};
     if (lane == 1) {
       const int st = a.rs_started ? (a.rs_started[sid * 2] != 0) | ((a.rs_started[sid * 2 + 1] != 0) << 1) : 0;
-      *(i32x4*)(r + 4) = i32x4{nn, a.hdr[5], a.hdr[6], st};
+      *(i32x4*)(r + L.header + SH_N_FRAMES) = i32x4{nn, a.hdr[SH_MODE], a.hdr[SH_INPUT_HZ], st};
     }
-    return;
-  }
-  if (!a.with_state) return;
-  if (j == kResampleItem) {     // history [2][H] + padding, after the carry
-    if (a.rs_hist && lane * 4 < a.rs_rec)
-      *(f32x4*)(r + kHeaderFloats + kStateFloats + lane * 4) = *(const f32x4*)(a.rs_hist + (long)sid * a.rs_rec + lane * 4);
-    return;
-  }
-  if (j < 4) {                  // record lstm [ch][(h, c)][256]  <-  h_state / c_state [S*2][256]
+  } else if (j == kResampleItem) {     // history [2][H] + padding
+    if ((a.sections & SEC_HISTORY) && lane * 4 < a.rs_rec)
+      *(f32x4*)(r + L.history + lane * 4) = *(const f32x4*)(a.rs_hist + (long)sid * a.rs_rec + lane * 4);
+  } else if (j < 4) {         // record lstm [ch][(h, c)][256]  <-  h_state / c_state [S*2][256]
+    if (!(a.sections & SEC_LSTM)) return;
     const float* src = ((j & 1) ? a.c_state : a.h_state) + ((long)sid * 2 + (j >> 1)) * 256;
-    *(f32x4*)(r + kHeaderFloats + j * 256 + lane * 4) = *(const f32x4*)(src + lane * 4);
-  } else {                      // carry [2][320]: 160 16-byte pieces over three waves
+    *(f32x4*)(r + L.lstm + j * 256 + lane * 4) = *(const f32x4*)(src + lane * 4);
+  } else {                             // carry [2][320]: 160 16-byte pieces over three waves
     const int q = (j - 4) * 64 + lane;
-    if (q < 2 * VAPX_PAD / 4)
-      *(f32x4*)(r + kHeaderFloats + 1024 + q * 4) = *(const f32x4*)(a.carry + (long)sid * 2 * VAPX_PAD + q * 4);
+    if ((a.sections & SEC_CARRY) && q < kStateCarryFloats / 4)
+      *(f32x4*)(r + L.carry + q * 4) = *(const f32x4*)(a.carry + (long)sid * kStateCarryFloats + q * 4);
   }
 }
 
-// import: chronological row t -> ring slot t (t < n_frames, clamped into [0, T]); frames_seen = n_frames
+// import: chronological row t -> ring slot t (t < n_frames, clamped into [0, T]); frames_seen = n_frames.  Only what a.sections names
 __global__ __launch_bounds__(256) void state_import_kernel(StateIoArgs a) {
   const int lane = threadIdx.x & 63;
   const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int T = a.T, k = blockIdx.y;
   if (item >= 2 * T + kSmallItems) return;
   const int sid = a.ids ? a.ids[k] : a.id0 + k;
-  const float* r = a.rec + (long)k * a.rec_floats;
-  int nn = ((const int*)r)[4];
+  const StateLayout& L = a.lay;
+  const float* r = a.rec + (long)k * L.total;
+  const int* hd = (const int*)(r + L.header);
+  int nn = hd[SH_N_FRAMES];
   nn = nn < 0 ? 0 : (nn < T ? nn : T);
-  const long o_ring = kHeaderFloats + (a.with_state ? kStateFloats : 0) + a.rs_rec;
   if (item < 2 * T) {
     const int c = item >= T ? 1 : 0, t = item - c * T;
-    if (t >= nn) return;
+    if (!(a.sections & SEC_RING) || t >= nn) return;
     const long drow = ((long)sid * 2 + c) * T + t;
-    const f32x4 v = *(const f32x4*)(r + o_ring + (long)item * 256 + lane * 4);
-    if (a.with_cache) {
-      const float* qs = r + o_ring + (long)2 * T * 256 + (long)item * 768 + lane * 4;
+    const f32x4 v = *(const f32x4*)(r + L.ring + (long)item * 256 + lane * 4);
+    if (a.sections & SEC_CACHE) {
+      const float* qs = r + L.cache + (long)item * 768 + lane * 4;
       const f32x4 q0 = *(const f32x4*)(qs), q1 = *(const f32x4*)(qs + 256), q2 = *(const f32x4*)(qs + 512);
       float* qd = a.ring_qkv + drow * 768 + lane * 4;
       *(f32x4*)(qd) = q0; *(f32x4*)(qd + 256) = q1; *(f32x4*)(qd + 512) = q2;
@@ -101,23 +100,19 @@ __global__ __launch_bounds__(256) void state_import_kernel(StateIoArgs a) {
   }
   const int j = item - 2 * T;
   if (j == kHeaderItem) {
-    if (lane == 0) a.frames_seen[sid] = nn;
-    if (lane < 2 && a.rs_started) a.rs_started[sid * 2 + lane] = (((const int*)r)[7] >> lane) & 1;
-    return;
-  }
-  if (!a.with_state) return;
-  if (j == kResampleItem) {
-    if (a.rs_hist && lane * 4 < a.rs_rec)
-      *(f32x4*)(a.rs_hist + (long)sid * a.rs_rec + lane * 4) = *(const f32x4*)(r + kHeaderFloats + kStateFloats + lane * 4);
-    return;
-  }
-  if (j < 4) {
+    if (lane == 0 && (a.sections & SEC_RING)) a.frames_seen[sid] = nn;
+    if (lane < 2 && a.rs_started) a.rs_started[sid * 2 + lane] = (hd[SH_STARTED] >> lane) & 1;
+  } else if (j == kResampleItem) {
+    if ((a.sections & SEC_HISTORY) && lane * 4 < a.rs_rec)
+      *(f32x4*)(a.rs_hist + (long)sid * a.rs_rec + lane * 4) = *(const f32x4*)(r + L.history + lane * 4);
+  } else if (j < 4) {
+    if (!(a.sections & SEC_LSTM)) return;
     float* dst = ((j & 1) ? a.c_state : a.h_state) + ((long)sid * 2 + (j >> 1)) * 256;
-    *(f32x4*)(dst + lane * 4) = *(const f32x4*)(r + kHeaderFloats + j * 256 + lane * 4);
+    *(f32x4*)(dst + lane * 4) = *(const f32x4*)(r + L.lstm + j * 256 + lane * 4);
   } else {
     const int q = (j - 4) * 64 + lane;
-    if (q < 2 * VAPX_PAD / 4)
-      *(f32x4*)(a.carry + (long)sid * 2 * VAPX_PAD + q * 4) = *(const f32x4*)(r + kHeaderFloats + 1024 + q * 4);
+    if ((a.sections & SEC_CARRY) && q < kStateCarryFloats / 4)
+      *(f32x4*)(a.carry + (long)sid * kStateCarryFloats + q * 4) = *(const f32x4*)(r + L.carry + q * 4);
   }
 }
 
@@ -163,7 +158,7 @@ hipError_t launch_per_stream(K kernel, StateIoArgs a, hipStream_t st) {
   for (int k0 = 0; k0 < n; k0 += kMaxGridY) {   // gridDim.y is a 16-bit quantity
     StateIoArgs c = a;
     c.n = n - k0 < kMaxGridY ? n - k0 : kMaxGridY;
-    c.rec = a.rec + (long)k0 * a.rec_floats;
+    c.rec = a.rec + (long)k0 * a.lay.total;
     if (a.ids) c.ids = a.ids + k0; else c.id0 = a.id0 + k0;
     hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)c.n), dim3(256), 0, st, c);
   }

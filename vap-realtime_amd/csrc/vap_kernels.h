@@ -1,6 +1,7 @@
 // Argument blocks + launchers of the non-GEMM kernels (see vap_kernels.hip).
 #pragma once
 #include "common.h"
+#include "state_record.h"
 
 struct Conv0Args {
   const float* audio;   // [B][2][spc]
@@ -190,17 +191,19 @@ hipError_t launch_out_scatter(const OutScatterArgs& a, hipStream_t st);
 // bn / bhead of a same-rate follower with a window of its own: bn[i] = min(fs + 1, T), bhead[i] = fs % T, fs = frames_seen[ids ? ids[i] : i]
 hipError_t launch_window_meta(const int* ids, const int* frames_seen, int T, int* bn, int* bhead, int n, hipStream_t st);
 
-struct StateIoArgs {    // state_io.hip: bulk stream-state export / import (vapx_export_streams / vapx_import_streams)
-  float* rec;           // [n][rec_floats] records (device): header | lstm + carry (with_state) | ring [2][T][256] | cache [2][T][768] (with_cache)
-  long rec_floats;
+struct StateIoArgs {    // state_io.hip: stream-state export / import, the bulk calls' records and the per-stream calls' internal one
+  float* rec;           // [n][lay.total] records (device), sections where `lay` (state_record.h) puts them
+  StateLayout lay;
+  int sections;         // SEC_* mask: export writes and import applies the ring rows, frames_seen and the small sections named here
+                        // (the header is always written); a section the layout lacks must not be named
   const int* ids;       // [n] stream slots (device) or null: slot = id0 + k
   int id0;
-  float *ring, *ring_qkv, *h_state, *c_state, *carry;   // per-stream state bases (h_state / c_state / carry unused without with_state)
+  float *ring, *ring_qkv, *h_state, *c_state, *carry;   // per-stream state bases (h_state / c_state / carry unused without their sections)
   int* frames_seen;
-  int T, n, with_state, with_cache;
-  int hdr[8];           // export: the header words as they are written, [4] (n_frames) filled in per stream
-  float* rs_hist;       // engines with an input rate: [S][rs_rec] resampler history, travels after the carry (null: none, rs_rec = 0)
-  int* rs_started;      // [S*2], travels as bits 0-1 of header word [7]
+  int T, n;
+  int hdr[8];           // export: the header words (StateHeaderWord) as they are written, SH_N_FRAMES and SH_STARTED filled in per stream
+  float* rs_hist;       // engines with an input rate: [S][rs_rec] resampler history, the SEC_HISTORY section (null: none)
+  int* rs_started;      // [S*2], travels as bits 0-1 of header word SH_STARTED; null: not read, not applied
   int rs_rec;           // floats per stream, a multiple of 4, at most 256
 };
 

@@ -664,10 +664,11 @@ class Engine:
         return {"ring": ring, "n_frames": n.value, "lstm": lstm, "carry": carry}
 
     def set_state(self, sid: int, state: dict):
-        ring = np.ascontiguousarray(state["ring"], np.float32)
+        """``ring`` [2,T,256] with ``n_frames``, ``lstm`` and ``carry``: a section that is missing or None is left as it is."""
+        ring = None if state.get("ring") is None else np.ascontiguousarray(state["ring"], np.float32)
         lstm = None if state.get("lstm") is None else np.ascontiguousarray(state["lstm"], np.float32)
         carry = None if state.get("carry") is None else np.ascontiguousarray(state["carry"], np.float32)
-        self._check(self.lib.vapx_set_state(self._h, sid, _np_ptr(ring), int(state["n_frames"]), _np_ptr(lstm), _np_ptr(carry)), "vapx_set_state")
+        self._check(self.lib.vapx_set_state(self._h, sid, _np_ptr(ring), int(state.get("n_frames", 0)), _np_ptr(lstm), _np_ptr(carry)), "vapx_set_state")
 
     # -- bulk state export / import (snapshot, restore, migrate) -----------------------------------------
     def state_floats(self, cache: bool = False) -> int:
